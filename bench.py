@@ -374,6 +374,31 @@ def fit_line(line):
     return txt
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much in all
+
+
+def write_outputs(dirpath, per_cell, scalars, suffix="", limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: `per_cell` (name -> array with one row per cell) and `scalars` (name -> small array) as DIR/<name><suffix>.npy,
+    float32 where given as float32, float64 otherwise.  Should the per-cell arrays exceed `limit`, one fixed, seeded sample of cells is
+    written for all of them, with the indices of the sampled cells as `cell_index`.  -> {file name: shape}"""
+    per_cell = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in per_cell.items()}
+    scalars = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in scalars.items()}
+    ncell = len(next(iter(per_cell.values())))
+    assert all(len(v) == ncell for v in per_cell.values()), {k: v.shape for k, v in per_cell.items()}
+    fixed = sum(v.nbytes for v in scalars.values())
+    per_row = sum(v.nbytes for v in per_cell.values()) // max(ncell, 1)
+    if ncell * per_row + fixed > limit:
+        keep = (limit - fixed) // (per_row + 8)    # + the float64 index of each sampled cell
+        idx = np.sort(np.random.default_rng(seed).choice(ncell, keep, replace=False))
+        per_cell = dict({k: v[idx] for k, v in per_cell.items()}, cell_index=idx.astype(np.float64))
+    os.makedirs(dirpath, exist_ok=True)
+    written = {}
+    for k, v in list(per_cell.items()) + list(scalars.items()):
+        np.save(os.path.join(dirpath, k + suffix + ".npy"), np.ascontiguousarray(v))
+        written[k + suffix + ".npy"] = list(v.shape)
+    return written
+
+
 def launch_plan(gpus, env, device_count):
     """What `python bench.py --gpus N` has to do before any GPU call: ("inline", world) - run in this process (N = 1, or
     a rank started by torch.distributed.run) - or ("spawn", N) - start N ranks as children.  Raises SystemExit on a
@@ -443,7 +468,12 @@ def main():
                          "on for --gpus N > 1 with ILU0, where every reduction is an all-reduce over xGMI (two per iteration instead of four); --no-fused-reductions: off")
     ap.add_argument("--no-fused-reductions", dest="fused_reductions", action="store_false")
     ap.add_argument("--no-cpr-side-run", action="store_true", help="skip the side runs with the CPR preconditioners (extra keys `cpr`, `cpr_quasiimpes`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (state, Newton update, CNV norms, time-stepping position) as DIR/<name>.npy, "
+                         "at most 64 MB in all (a fixed, seeded sample of cells beyond that; N > 1: one set per rank, <name>_rank<r>.npy)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
     plan, world = launch_plan(a.gpus, os.environ, torch.cuda.device_count())  # device_count() does not initialise the GPU
@@ -594,6 +624,18 @@ def main():
         sim.next_newton_iteration()
     W = timed_window(a.steps)
     elapsed, kernels = W["elapsed"], W["kernels"]
+    dumped = None
+    if a.dump_outputs:
+        # what the timed path handed back after its last Newton iteration, fetched after the window: the state the update left, the
+        # update itself (the linear solve's result), the CNV norms of that iteration's convergence check, where the time stepping stands
+        pv, meaning = model.get_state()
+        nm = sim.model
+        dumped = write_outputs(a.dump_outputs,
+                               {"primary_variables": pv.reshape(-1, 3)[:Nb], "primary_variable_meaning": meaning[:Nb].astype(np.float32),
+                                "newton_update": model.get_result().reshape(-1, 3)},
+                               {"cnv_residual_norms": np.array(nm.residual_norms_history[-1], np.float64),
+                                "time_stepping": np.array([sim.time, sim.dt, sim.iteration, nm.last_linear_iterations], np.float64)},
+                               suffix="" if world == 1 else "_rank%d" % rank, limit=DUMP_LIMIT_BYTES // world)
     steady = None
     def guarded(what, fn):
         """the extra windows must not cost the run its line: a failure in one of them is reported in its place (all ranks
@@ -766,6 +808,7 @@ def main():
                            "avg_launch_ms": round(stream_ms, 5) if stream_ms else None, "error": stream.get("error"),
                            "kernel": "k_stream_read: the Jacobian's value array read once, 16-B loads, nothing else (back to back, 20 launches)"},
         "product_form": product_form,
+        "dumped_outputs": None if dumped is None else {"dir": a.dump_outputs, "arrays": dumped},
         "roofline": {"bound": "hbm", "kernel": ("k_spmv_pipe_st<UADD>: the block-CSR product in its half-product form - the matrix without its U part "
                                                 "(%d of %d blocks) + the backward sweep's row sums" % (product_form["rest_blocks"], nnzb))
                                                if product_form["half_product"] else "k_spmv (block-CSR SpMV, 3x3 double blocks)",

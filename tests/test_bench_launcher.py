@@ -124,3 +124,30 @@ def test_single_domain_comparator_comes_from_a_measurement_or_not_at_all(bench, 
     f.write_text("not json")
     assert bench.single_domain_comparator(str(f), 100, 20, 3, "ilu0", True) is None
     assert not hasattr(bench, "SINGLE_DOMAIN_LIN_ITS")
+
+
+def test_write_outputs_stays_under_its_limit_with_one_seeded_sample(bench, tmp_path):
+    """--dump-outputs: float64 / float32 as given, every file named; beyond the limit the same seeded cells of every per-cell array,
+    their indices beside them - the same files from call to call"""
+    import numpy as np
+    n = 5000
+    pv = np.arange(3 * n, dtype=np.float64).reshape(n, 3)
+    meaning = (np.arange(n) % 3).astype(np.float32)
+    scal = {"cnv_residual_norms": np.array([1e-3, 2e-3, 3e-3])}
+    full = bench.write_outputs(str(tmp_path / "full"), {"pv": pv, "meaning": meaning}, scal)
+    assert full == {"pv.npy": [n, 3], "meaning.npy": [n], "cnv_residual_norms.npy": [3]}
+    assert np.array_equal(np.load(tmp_path / "full" / "pv.npy"), pv) and np.load(tmp_path / "full" / "meaning.npy").dtype == np.float32
+    limit = 40000
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("cut%d" % k)
+        w = bench.write_outputs(str(d), {"pv": pv, "meaning": meaning}, scal, limit=limit)
+        assert set(w) == {"pv.npy", "meaning.npy", "cell_index.npy", "cnv_residual_norms.npy"}
+        arrays = {f: np.load(d / f) for f in w}
+        assert sum(a.nbytes for a in arrays.values()) <= limit
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        idx = arrays["cell_index.npy"].astype(np.int64)
+        assert len(idx) > 0 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(arrays["pv.npy"], pv[idx]) and np.array_equal(arrays["meaning.npy"], meaning[idx])
+        runs.append(arrays)
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])

@@ -46,3 +46,46 @@ def test_bench_line_contract(tmp_path):
     # Flow's "cpr" (true-IMPES weights) and the quasi-IMPES variant, side by side under their reference names
     assert d["cpr"]["value"] > 0 and d["cpr_quasiimpes"]["value"] > 0 and d["cpr_reuse_setup_2"]["value"] > 0 and "rccl" not in d
     assert full["cpr"]["kernels"]["cpr_amg"]["launches"] > 0 and full["kernels"]["spmv"]["launches"] > 0
+
+
+def test_dump_outputs_are_the_last_timed_newton_iteration(tmp_path, pkg):
+    """--dump-outputs: two runs with the same arguments write the same arrays bit for bit, and they are what the simulation holds after
+    exactly --warmup + --steps Newton iterations (the state, the last linear solve's update, that iteration's CNV norms)"""
+    import importlib.util
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    n, steps, warmup = 16, 3, 2
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", str(steps), "--warmup", str(warmup),
+                            "--steady-after", "0", "--no-cpr-side-run", "--no-cpu-baseline", "--detail", str(tmp_path / ("detail%d.json" % k)),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        names = sorted(os.listdir(d))
+        assert names == ["cnv_residual_norms.npy", "newton_update.npy", "primary_variable_meaning.npy", "primary_variables.npy", "time_stepping.npy"]
+        runs.append({f: np.load(d / f) for f in names})
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
+    assert all(a.dtype in (np.float32, np.float64) for a in runs[0].values())
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    case = pkg.decks.cartesian_case(n, n, n, state="mixed", heterogeneous=False)
+    src = pkg.decks.five_spot_source(case, rate_sm3_per_day=pkg.decks.BENCH_RATE_SM3_PER_DAY * (n / 100.0) ** 2)
+    model = pkg.capi.HipModel(case, device_id=0, tolerance=1e-2, maxit=200, ilu_relaxation=0.9, fused_reductions=0)
+    model.set_state(case["pv"], case["meaning"])
+    model.set_source(src)
+    sim = bench.make_simulation(pkg, model)
+    for _ in range(warmup + steps):
+        sim.next_newton_iteration()
+    pv, meaning = model.get_state()
+    d = runs[0]
+    assert np.array_equal(d["primary_variables.npy"], pv.reshape(-1, 3))
+    assert np.array_equal(d["primary_variable_meaning.npy"], meaning.astype(np.float32))
+    assert np.array_equal(d["newton_update.npy"], model.get_result().reshape(-1, 3))
+    assert np.array_equal(d["cnv_residual_norms.npy"], np.array(sim.model.residual_norms_history[-1]))
+    assert np.array_equal(d["time_stepping.npy"], np.array([sim.time, sim.dt, sim.iteration, sim.model.last_linear_iterations], np.float64))
