@@ -58,11 +58,15 @@ typedef enum opmhip_reorder {
                                         neighbour (the vertical one in CpGrid's natural order), chains coloured greedily:
                                         an exact ILU0 of that ordering, near the natural order's strength at colouring's
                                         parallelism (no counterpart in the reference) */
-    OPMHIP_REORDER_AUTO = 5          /* line colouring where it pays - a structured grid in its natural order of at least 30 000 rows,
+    OPMHIP_REORDER_AUTO = 5,         /* line colouring where it pays - a structured grid in its natural order of at least 30 000 rows,
                                         chains of 4 below 200 000 rows, of 8 below 700 000, of 10 above (chain_length = 0; a non-zero
                                         chain_length is taken as given) - and the greedy colouring elsewhere: the chain sweeps walk their
                                         steps one after the other, which a small or irregular system cannot hide (a 44 777-cell
-                                        corner-point grid: 31 Newton its/s with chains of 10, 259 greedy).  ABI 7 */
+                                        corner-point grid: 31 Newton its/s with chains of 10, 259 greedy).  ABI 7.  With
+                                        opmhip_set_ilu_fillin_level n >= 1: see there */
+    OPMHIP_REORDER_DISTANCE2_COLORING = 6 /* first-fit colouring of the graph of A^2 (no two rows of one colour share a neighbour):
+                                        the colours stay independent under level-1 fill, so ILU(1) sweeps one launch per colour
+                                        (13 on a 7-point grid); for ILU0 one more colouring */
 } opmhip_reorder;
 
 /* --linear-solver-configuration (linalg/setupPropertyTree.cpp:62-76).  The CPR variants: pressure system solved by one AMG
@@ -335,6 +339,24 @@ int opmhip_get_ordering(opmhip_ctx* ctx, int* toOrder, int* fromOrder, int* rows
  * cpr_amg_ilu_levels in force (0 without a CPR preconditioner).  The reference prints the same kind of line at set-up
  * (bda/openclSolverBackend.cpp:229-246, BILU0.cpp:106-108).  ABI 8 */
 int opmhip_get_ordering_info(opmhip_ctx* ctx, int info[4]);
+/* --ilu-fillin-level (setupPropertyTree.cpp: preconditioner.ilulevel): the block ILU(n) of the reference's ParOverILU0 with ilulevel n
+ * (level-of-fill rule of milun_decomposition, MILU variant ILU) in place of ILU0.  Call after opmhip_create and before opmhip_set_pattern
+ * / the first opmhip_solve_system; later calls return OPMHIP_INVALID_ARGUMENT, as do n < 0 and n >= 1 on a decomposed context
+ * (opmhip_comm_init_*).  n = 0 is ILU0, the default.  With a CPR preconditioner the level is ignored: its fine smoother is ILU0
+ * (setupPropertyTree.cpp:109-110).  n >= 1: the fill is computed in the ordering's elimination order (OPMHIP_REORDER_LEVEL_SCHEDULING:
+ * the natural order, the reference's preconditioner) and the sweeps run by the levels of the filled factors (opmhip_get_ordering_info
+ * info[2]); OPMHIP_REORDER_AUTO resolves to OPMHIP_REORDER_DISTANCE2_COLORING (measured: DESIGN.md section 5).  A pattern
+ * whose factors would hold more than 8 x nnzb blocks is refused at set_pattern with OPMHIP_INVALID_ARGUMENT.  The half-product form
+ * is off (U != upper(A)).  Additive to ABI 11 */
+int opmhip_set_ilu_fillin_level(opmhip_ctx* ctx, int n);
+/* after set_pattern: info[0] the fill level in force (0 with a CPR preconditioner), info[1] blocks in L, info[2] blocks in U (strict parts),
+ * info[3] levels (colours) per sweep */
+int opmhip_get_ilu_info(opmhip_ctx* ctx, int info[4]);
+/* the factors of the last factorisation in the internal order, for tests: toOrder [Nb] (natural row -> internal row), lrowptr / urowptr
+ * [Nb + 1], lcol [nl], ucol [nu] (internal column numbers, ascending), L [nl * 9], U [nu * 9], invD [Nb * 9] (the inverted diagonal blocks),
+ * nl / nu as opmhip_get_ilu_info reports them.  Any pointer may be NULL (size query: opmhip_get_ilu_info).  Works for n = 0 as well (then
+ * the pattern is the matrix's own).  Needs a factorisation for L, U, invD */
+int opmhip_get_ilu_factors(opmhip_ctx* ctx, int* toOrder, int* lrowptr, int* lcol, int* urowptr, int* ucol, double* L, double* U, double* invD);
 /* what opmhip_config.half_product resolved to at set_pattern: info[0] 1 if ILU0-BiCGStab forms the product after M^-1 from the backward
  * sweep's row sums, else 0; info[1] 1 if the pattern has the property it rests on (no elimination step touches an entry right of the
  * diagonal: U == upper(A)); info[2] the blocks that product streams: the matrix beside its U part (a subdomain with ghost columns: its interior tiles' rows beside

@@ -16,7 +16,7 @@ HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "opmhip.h")
 SUCCESS = 0
 ANALYSIS_FAILED, CREATE_PRECONDITIONER_FAILED, UNKNOWN_ERROR = -1, -2, -3
 INVALID_ARGUMENT, NOT_READY, DEVICE_ERROR, NO_DEVICE = -4, -5, -6, -7
-REORDER = {"level_scheduling": 1, "graph_coloring": 2, "graph_coloring_greedy": 3, "line_coloring": 4, "auto": 5}
+REORDER = {"level_scheduling": 1, "graph_coloring": 2, "graph_coloring_greedy": 3, "line_coloring": 4, "auto": 5, "distance2": 6}
 RELAX = {"post_scale": 0, "in_sweep": 1}
 PRECONDITIONER = {"ilu0": 0, "cpr_quasiimpes": 1, "cpr": 2, "cpr_trueimpes": 2}   # opmhip_preconditioner
 
@@ -119,6 +119,9 @@ def lib():
         L.opmhip_get_ordering.argtypes = [vp, ip, ip, ip]
         L.opmhip_get_ordering_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_get_product_form.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.opmhip_set_ilu_fillin_level.argtypes = [vp, C.c_int]
+        L.opmhip_get_ilu_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.opmhip_get_ilu_factors.argtypes = [vp, ip, ip, ip, ip, ip, dp, dp, dp]
         L.opmhip_time_kernel.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.opmhip_cpr_levels.argtypes = [vp, ip, ip, C.c_int]
         L.opmhip_profile_enable.argtypes = [vp, C.c_int]
@@ -173,10 +176,12 @@ class HipSolver:
 
     def __init__(self, verbosity=0, maxit=200, tolerance=1e-2, device_id=0, ilu_relaxation=0.9,
                  relax_mode="post_scale", reorder=None, zero_diag_fix=True, chain_length=0, spmv_pipe_wgs=0,
-                 preconditioner="ilu0", cpr_reuse_setup=3, cpr_async_setup=0, cpr_amg_ilu_levels=None, cpr_gather_rows=None, half_product=0, pin_host_arrays=0, fused_reductions=0):
+                 preconditioner="ilu0", cpr_reuse_setup=3, cpr_async_setup=0, cpr_amg_ilu_levels=None, cpr_gather_rows=None, half_product=0, pin_host_arrays=0, fused_reductions=0,
+                 ilu_fillin_level=0):
         """reorder / cpr_amg_ilu_levels / cpr_gather_rows = None: what opmhip_default_config says (reorder "auto", the library's choice of
         the AMG smoother, the pressure stage across the ranks as the communicator's kind allows).  half_product: ILU0-BiCGStab forms the
-        product after M^-1 from the backward sweep's row sums (0 the library's choice, > 0 wherever the pattern allows, < 0 never)"""
+        product after M^-1 from the backward sweep's row sums (0 the library's choice, > 0 wherever the pattern allows, < 0 never).
+        ilu_fillin_level: --ilu-fillin-level, the n of the block ILU(n) preconditioner (opmhip_set_ilu_fillin_level; ignored with CPR)"""
         L = lib()
         cfg = Config()
         L.opmhip_default_config(C.byref(cfg))
@@ -205,6 +210,8 @@ class HipSolver:
         if rc != SUCCESS:
             raise OpmHipError(rc, L.opmhip_last_error(None).decode())
         self.Nb = self.nnzb = 0
+        if ilu_fillin_level:
+            self._check(L.opmhip_set_ilu_fillin_level(self._h, int(ilu_fillin_level)))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -334,6 +341,29 @@ class HipSolver:
         self._check(lib().opmhip_get_ordering_info(self._h, C.byref(info)))
         names = {v: k for k, v in REORDER.items()}
         return {"ilu_ordering": names[info[0]], "chain_length": int(info[1]), "colors": int(info[2]), "cpr_amg_ilu_levels": int(info[3])}
+
+    def set_ilu_fillin_level(self, n):
+        self._check(lib().opmhip_set_ilu_fillin_level(self._h, int(n)))
+
+    def ilu_info(self):
+        """opmhip_get_ilu_info: fill level in force, blocks of L and U, levels (colours) per sweep"""
+        info = (C.c_int * 4)()
+        self._check(lib().opmhip_get_ilu_info(self._h, C.byref(info)))
+        return {"fill_level": int(info[0]), "nl": int(info[1]), "nu": int(info[2]), "levels": int(info[3])}
+
+    def ilu_factors(self, values=True):
+        """opmhip_get_ilu_factors: dict(to, lrowptr, lcol, urowptr, ucol[, L, U, invD]) - internal order, blocks [n, 3, 3]"""
+        inf = self.ilu_info()
+        Nb, nl, nu = self.Nb, inf["nl"], inf["nu"]
+        out = {"to": np.empty(Nb, np.int32), "lrowptr": np.empty(Nb + 1, np.int32), "lcol": np.empty(nl, np.int32),
+               "urowptr": np.empty(Nb + 1, np.int32), "ucol": np.empty(nu, np.int32)}
+        vals = [None, None, None]
+        if values:
+            vals = [np.empty((nl, 3, 3)), np.empty((nu, 3, 3)), np.empty((Nb, 3, 3))]
+            out.update(L=vals[0], U=vals[1], invD=vals[2])
+        self._check(lib().opmhip_get_ilu_factors(self._h, *[_ptr(out[k]) for k in ("to", "lrowptr", "lcol", "urowptr", "ucol")],
+                                                 *[_ptr(v) for v in vals]))
+        return out
 
     def product_form(self):
         """what opmhip_config.half_product resolved to (opmhip_get_product_form)"""

@@ -33,6 +33,12 @@ int alloc_system(opmhip_ctx* c) {
     OPMHIP_HIP(c, hipMemsetAsync(c->d_L + (size_t)P.nl * BB, 0, SLACK * sizeof(double), c->stream));
     OPMHIP_HIP(c, hipMemsetAsync(c->d_U + (size_t)P.nu * BB, 0, SLACK * sizeof(double), c->stream));
     if ((rc = dev_alloc(c, &c->d_invD, (size_t)P.Nb * BB))) return rc;
+    if (P.fillLevel > 0) {   // ILU(n): the filled factors (the tile sweeps read them with the same slack as d_L / d_U)
+        if ((rc = dev_alloc(c, &c->d_fL, (size_t)P.fnl * BB + SLACK))) return rc;
+        if ((rc = dev_alloc(c, &c->d_fU, (size_t)P.fnu * BB + SLACK))) return rc;
+        OPMHIP_HIP(c, hipMemsetAsync(c->d_fL, 0, ((size_t)P.fnl * BB + SLACK) * sizeof(double), c->stream));
+        OPMHIP_HIP(c, hipMemsetAsync(c->d_fU, 0, ((size_t)P.fnu * BB + SLACK) * sizeof(double), c->stream));
+    }
     c->half_product = half_product_wanted(c);
     if (c->half_product) {   // the matrix beside its U part (written by the factorisation) and the backward sweeps' row sums
         if ((rc = dev_alloc(c, &c->d_R, (size_t)P.nr * BB + SLACK))) return rc;
@@ -599,6 +605,8 @@ int opmhip_ilu0_factor(opmhip_ctx* c, double* lu_out) {
     if (!c) return OPMHIP_INVALID_ARGUMENT;
     return guarded(c, [&]() -> int {
         if (!c->system_loaded) return fail(c, OPMHIP_NOT_READY, "ilu0_factor before a matrix was uploaded");
+        if (lu_out && c->pat.fillLevel > 0)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "ilu0_factor: the matrix's layout cannot carry the fill of ILU(%d); opmhip_get_ilu_factors returns the factors", c->pat.fillLevel);
         OPMHIP_HIP(c, hipSetDevice(c->device));
         launch_ilu_factor(c);
         OPMHIP_HIP(c, hipGetLastError());
@@ -717,6 +725,53 @@ int opmhip_get_ordering_info(opmhip_ctx* c, int info[4]) {
     info[2] = P.numColors;
     info[3] = cpr_ilu_levels_in_force(c);
     return OPMHIP_SUCCESS;
+}
+
+int opmhip_set_ilu_fillin_level(opmhip_ctx* c, int n) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    if (n < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ilu_fillin_level: n = %d < 0", n);
+    if (c->pattern_set) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ilu_fillin_level: the pattern is set already; call it before set_pattern / the first solve");
+    if (n > 0 && c->comm.kind != COMM_NONE)
+        return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ilu_fillin_level: ILU(%d) on a decomposed context is not supported", n);
+    c->ilu_fillin = n;
+    return OPMHIP_SUCCESS;
+}
+
+int opmhip_get_ilu_info(opmhip_ctx* c, int info[4]) {
+    if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
+    if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_ilu_info before set_pattern");
+    const Pattern& P = c->pat;
+    const bool fill = P.fillLevel > 0;
+    info[0] = P.fillLevel;
+    info[1] = fill ? P.fnl : P.nl;
+    info[2] = fill ? P.fnu : P.nu;
+    info[3] = P.numColors;
+    return OPMHIP_SUCCESS;
+}
+
+int opmhip_get_ilu_factors(opmhip_ctx* c, int* toOrder, int* lrowptr, int* lcol, int* urowptr, int* ucol, double* L, double* U, double* invD) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_ilu_factors before set_pattern");
+        if ((L || U || invD) && !c->factored) return fail(c, OPMHIP_NOT_READY, "get_ilu_factors: no factorisation yet");
+        const Pattern& P = c->pat;
+        const bool fill = P.fillLevel > 0;
+        const std::vector<int>& lrp = fill ? P.flrowptr : P.lrowptr;
+        const std::vector<int>& lcl = fill ? P.flcol : P.lcol;
+        const std::vector<int>& urp = fill ? P.furowptr : P.urowptr;
+        const std::vector<int>& ucl = fill ? P.fucol : P.ucol;
+        if (toOrder) std::memcpy(toOrder, P.toOrder.data(), P.Nb * sizeof(int));
+        if (lrowptr) std::memcpy(lrowptr, lrp.data(), (P.Nb + 1) * sizeof(int));
+        if (urowptr) std::memcpy(urowptr, urp.data(), (P.Nb + 1) * sizeof(int));
+        if (lcol && !lcl.empty()) std::memcpy(lcol, lcl.data(), lcl.size() * sizeof(int));
+        if (ucol && !ucl.empty()) std::memcpy(ucol, ucl.data(), ucl.size() * sizeof(int));
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        if (L && !lcl.empty()) OPMHIP_HIP(c, hipMemcpyAsync(L, fill ? c->d_fL : c->d_L, lcl.size() * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (U && !ucl.empty()) OPMHIP_HIP(c, hipMemcpyAsync(U, fill ? c->d_fU : c->d_U, ucl.size() * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (invD) OPMHIP_HIP(c, hipMemcpyAsync(invD, c->d_invD, (size_t)P.Nb * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        return OPMHIP_SUCCESS;
+    });
 }
 
 int opmhip_get_product_form(opmhip_ctx* c, int info[4]) {

@@ -325,6 +325,8 @@ int opmhip_comm_unique_id(char* id128) {
 
 int opmhip_comm_init_rccl(opmhip_ctx* c, int nranks, int rank, const char* id128) {
     if (!c || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return OPMHIP_INVALID_ARGUMENT;
+    if (c->ilu_fillin > 0)
+        return fail(c, OPMHIP_INVALID_ARGUMENT, "comm_init: ILU(%d) on a decomposed context is not supported", c->ilu_fillin);
     const char* e = load_rccl();
     if (e) return fail(c, OPMHIP_DEVICE_ERROR, "comm_init_rccl: %s", e);
     OPMHIP_HIP(c, hipSetDevice(c->device));
@@ -341,6 +343,8 @@ int opmhip_comm_init_rccl(opmhip_ctx* c, int nranks, int rank, const char* id128
 
 int opmhip_comm_init_loopback(opmhip_ctx* c, int nranks, int rank, const char* group_name) {
     if (!c || !group_name || nranks < 1 || rank < 0 || rank >= nranks) return OPMHIP_INVALID_ARGUMENT;
+    if (c->ilu_fillin > 0)
+        return fail(c, OPMHIP_INVALID_ARGUMENT, "comm_init: ILU(%d) on a decomposed context is not supported", c->ilu_fillin);
     std::lock_guard<std::mutex> lk(g_groups_mutex);
     LoopGroup*& G = g_groups[group_name];
     if (!G) {

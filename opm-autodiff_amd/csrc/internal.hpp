@@ -137,7 +137,19 @@ struct Pattern {
     std::vector<int> rrowptr, rcol, rdest;
     int *d_rdest = nullptr, *d_rrowptr = nullptr;
     RestSched rest;
+    // ILU(n), n >= 1 (opmhip_set_ilu_fillin_level; reorder.cpp: build_fill): the factors' own pattern - the matrix's owned pattern plus the
+    // level-of-fill entries, computed in the ordering's elimination order - split into L and U like lrowptr / lcol / urowptr / ucol.  The
+    // ordering is then a schedule of the FILLED pattern: colours (levels) are its independent sets, colorPrefix their row ranges.
+    // fillDest: per matrix entry its place in the factors (L index >= 0, -2 - U index, -1 diagonal or ghost column); fill entries start
+    // at zero.  ftiles: the sweeps' tiles over the filled rows (row0 / colorTile only).  fillLevel 0: none of this exists.
+    int fillLevel = 0, fnl = 0, fnu = 0;
+    std::vector<int> flrowptr, flcol, furowptr, fucol, fillDest;
+    std::vector<int> fillBase;   // natural row -> its place in the elimination order the fill was computed in (tests: the fill rule restated)
+    TileSet ftiles;
+    int *d_flrowptr = nullptr, *d_flcol = nullptr, *d_furowptr = nullptr, *d_fucol = nullptr, *d_fillDest = nullptr, *d_frow0 = nullptr;
 };
+// ILU(n) memory guard: the filled factors (L, U and the diagonal, in blocks) may hold at most this many times the blocks of the matrix
+constexpr int ILUN_BUDGET_FACTOR = 8;
 
 struct WellsDev {
     int num_wells = 0, nperf = 0;
@@ -372,9 +384,11 @@ struct opmhip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
     bool pattern_set = false, system_loaded = false, factored = false, have_result = false;
+    int ilu_fillin = 0;                         // opmhip_set_ilu_fillin_level (--ilu-fillin-level); ignored with a CPR preconditioner
     opmhip::Pattern pat;
     // values, internal order
     double *d_A = nullptr, *d_L = nullptr, *d_U = nullptr, *d_invD = nullptr;
+    double *d_fL = nullptr, *d_fU = nullptr;    // ILU(n), n >= 1: the filled factors (Pattern::flrowptr / furowptr); d_invD as for ILU0
     double *d_R = nullptr, *d_usum = nullptr;   // Pattern::ualias: the rest of the matrix beside U (values), the backward sweeps' row sums (3 per row)
     bool half_product = false;                  // BiCGStab forms the product after an ILU0 application from d_R and d_usum (opmhip_config.half_product)
     // vectors, internal order, 3*Nb each

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <numeric>
+#include <queue>
 
 #include "internal.hpp"
 
@@ -110,6 +111,84 @@ void color_greedy(const Pattern& P, std::vector<int>& color, int& ncol) {
         color[i] = c;
         ncol = std::max(ncol, c + 1);
     }
+}
+
+// First-fit colouring of the graph of A^2 in the natural visiting order: no two rows of one colour share a neighbour (row or column
+// couplings), so level-1 fill - (i, j) through an earlier k coupled to both - never joins two rows of one colour and the colours stay
+// a schedule of the ILU(1) factors.  For ILU0 it is one more (weaker) colouring.
+void color_distance2(const Pattern& P, std::vector<int>& color, int& ncol) {
+    std::vector<int> cptr, ridx;
+    transpose_pattern(P, cptr, ridx);
+    color.assign(P.Nb, -1);
+    ncol = 0;
+    std::vector<int> seen;   // seen[c] == i: colour c is taken near row i
+    auto each_neighbour = [&](int i, auto&& f) {
+        for (int k = P.nat_rowptr[i]; k < P.nat_rowptr[i + 1]; ++k) f(P.nat_col[k]);
+        for (int k = cptr[i]; k < cptr[i + 1]; ++k) f(ridx[k]);
+    };
+    for (int i = 0; i < P.Nb; ++i) {
+        auto mark = [&](int j) { if (j != i && color[j] >= 0) seen[color[j]] = i; };
+        seen.resize(ncol + 1, -1);
+        each_neighbour(i, [&](int j) {
+            mark(j);
+            each_neighbour(j, mark);
+        });
+        int c = 0;
+        while (seen[c] == i) ++c;
+        color[i] = c;
+        ncol = std::max(ncol, c + 1);
+    }
+}
+
+// Symbolic ILU(n) of the owned pattern (rowptr / col: rows and columns in elimination order, ascending columns, diagonal present),
+// the level-of-fill rule of the reference's ILU(n) (milun_decomposition): the entries of A have generation 0; row i walks its entries
+// left of the diagonal in ascending column order, fill made earlier in the same row included; an entry (i, k) of generation < n pivots
+// row k, whose entries (k, j), j >= k, of generation < n create (i, j) with generation gen(k, j) + 1 where row i has no entry yet (an
+// existing entry keeps its generation).  Returns false - nothing more is built - as soon as the factors would hold more than `budget`
+// blocks.  frowptr / fcol: the filled pattern, ascending columns; fdiag: the diagonal's place in every row.
+bool symbolic_fill(int Nb, const std::vector<int>& rowptr, const std::vector<int>& col, int n, long long budget, std::vector<int>& frowptr,
+                   std::vector<int>& fcol, std::vector<int>& fdiag) {
+    frowptr.assign(Nb + 1, 0);
+    fcol.clear();
+    fdiag.assign(Nb, -1);
+    std::vector<int> fgen;
+    std::vector<int> genAt(Nb, -1);      // generation of (i, j) in the row under construction, -1: no entry
+    std::vector<int> cols;
+    std::priority_queue<int, std::vector<int>, std::greater<int>> lower;   // entries left of the diagonal still to walk, smallest first
+    for (int i = 0; i < Nb; ++i) {
+        cols.clear();
+        for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+            const int j = col[k];
+            genAt[j] = 0;
+            cols.push_back(j);
+            if (j < i) lower.push(j);
+        }
+        while (!lower.empty()) {
+            const int k = lower.top();
+            lower.pop();
+            if (genAt[k] >= n) continue;
+            for (int q = fdiag[k]; q < frowptr[k + 1]; ++q) {
+                const int j = fcol[q], g = fgen[q];
+                if (g >= n || genAt[j] >= 0) continue;
+                genAt[j] = g + 1;
+                cols.push_back(j);
+                if (j < i) lower.push(j);   // j > k: it comes later in this walk
+            }
+        }
+        std::sort(cols.begin(), cols.end());
+        if ((long long)fcol.size() + (long long)cols.size() > budget) {
+            for (int j : cols) genAt[j] = -1;
+            return false;
+        }
+        for (int j : cols) {
+            if (j == i) fdiag[i] = (int)fcol.size();
+            fcol.push_back(j);
+            fgen.push_back(genAt[j]);
+            genAt[j] = -1;
+        }
+        frowptr[i + 1] = (int)fcol.size();
+    }
+    return true;
 }
 
 // Sub-tiles (<= TILE_ROWS rows, <= TILE_CAP_BLOCKS blocks) grouped into chain-tiles: the sub-tiles of one chain-tile
@@ -453,6 +532,53 @@ void build_schedules(Pattern& P, int G) {
     }
 }
 
+// ILU(n): the filled pattern (rows and columns in the fill's elimination order, ibase: that order -> natural row) renamed into the
+// internal order, split into L and U, every matrix entry's place in it, and the sweeps' tiles over the filled rows
+int build_fill_split(opmhip_ctx* c, const std::vector<int>& frp, const std::vector<int>& fcl, const std::vector<int>& ibase) {
+    Pattern& P = c->pat;
+    const int Nb = P.Nb;
+    std::vector<int> bpos(Nb), colorOf(Nb);   // natural row -> elimination-order row; internal row -> colour
+    for (int b = 0; b < Nb; ++b) bpos[ibase[b]] = b;
+    for (int cc = 0; cc < P.numColors; ++cc)
+        for (int p = P.colorPrefix[cc]; p < P.colorPrefix[cc + 1]; ++p) colorOf[p] = cc;
+    P.flrowptr.assign(Nb + 1, 0);
+    P.furowptr.assign(Nb + 1, 0);
+    P.flcol.clear();
+    P.fucol.clear();
+    std::vector<int> row;
+    for (int p = 0; p < Nb; ++p) {
+        const int b = bpos[P.fromOrder[p]];
+        row.clear();
+        for (int q = frp[b]; q < frp[b + 1]; ++q) row.push_back(P.toOrder[ibase[fcl[q]]]);
+        std::sort(row.begin(), row.end());
+        for (int j : row) {
+            if (j != p && colorOf[j] == colorOf[p])
+                return fail(c, OPMHIP_ANALYSIS_FAILED, "ILU(%d): the ordering is not a schedule of the filled pattern at row %d", P.fillLevel, p);
+            if (j < p) P.flcol.push_back(j);
+            else if (j > p) P.fucol.push_back(j);
+        }
+        P.flrowptr[p + 1] = (int)P.flcol.size();
+        P.furowptr[p + 1] = (int)P.fucol.size();
+    }
+    P.fnl = (int)P.flcol.size();
+    P.fnu = (int)P.fucol.size();
+    P.fillDest.assign(P.nnzb, -1);
+    for (int p = 0; p < Nb; ++p)
+        for (int k = P.rowptr[p]; k < P.rowptr[p + 1]; ++k) {
+            const int j = P.col[k];
+            if (j == p || j >= Nb) continue;   // diagonal; ghost columns are not part of the ILU
+            const int* b0 = j < p ? &P.flcol[P.flrowptr[p]] : &P.fucol[P.furowptr[p]];
+            const int* b1 = j < p ? &P.flcol[0] + P.flrowptr[p + 1] : &P.fucol[0] + P.furowptr[p + 1];
+            const int* f = std::lower_bound(b0, b1, j);
+            if (f == b1 || *f != j) return fail(c, OPMHIP_ANALYSIS_FAILED, "ILU(%d): entry (%d, %d) of the matrix is missing from the filled pattern", P.fillLevel, p, j);
+            P.fillDest[k] = j < p ? (int)(f - &P.flcol[0]) : -2 - (int)(f - &P.fucol[0]);
+        }
+    std::vector<int> trp(Nb + 1, 0);   // the tiles bound a row's L and U blocks together: both sweeps read the same tiles
+    for (int p = 0; p <= Nb; ++p) trp[p] = P.flrowptr[p] + P.furowptr[p];
+    build_tiles(trp, P.colorPrefix, {}, P.ftiles);
+    return OPMHIP_SUCCESS;
+}
+
 }  // namespace
 
 int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, const int* cols) {
@@ -494,7 +620,13 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
     // offsets (col - row) in the natural order - a structured grid handed over in its natural order; the chain length grows with the size.
     int kind = c->cfg.reorder;
     int autoChain = 10;
-    if (kind == OPMHIP_REORDER_AUTO) {
+    if (kind == OPMHIP_REORDER_AUTO && c->ilu_fillin > 0 && !use_cpr(c)) {
+        // ILU(n), n >= 1: the distance-2 colouring.  Measured (tools/ilun_study.py, profiles/ilun_study.json), ILU(1)
+        // Newton its/s distance-2 against level scheduling: 193 / 102 on configs[2], 99 / 25 on configs[4], 34 / 10 at 10^6 cells - the
+        // level schedule saves iterations (2 - 5 against 6 - 14 per Newton iteration) but pays 114 - 595 dependent launches per sweep
+        kind = OPMHIP_REORDER_DISTANCE2_COLORING;
+        if (c->cfg.verbosity > 0) std::fprintf(stderr, "opmhip: reorder auto (ILU(%d)) -> distance2_coloring (%d rows)\n", c->ilu_fillin, Nb);
+    } else if (kind == OPMHIP_REORDER_AUTO) {
         // structured grids (tools/chain_by_size.py, Newton its/s): 32^3 greedy 568, chains of 4: 583; 40^3 423 / 487 (chains of 3-4); 50^3
         // 267 / 361 (4); 64^3 165 / 246 (8; 239 with 4, 208 with 10); 80^3 99 / 168 (8; 153 with 10); 100^3: 10 (section 5) - the shorter
         // the chains, the fewer dependent steps a launch walks through, the more iterations
@@ -516,7 +648,7 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
         kind = regular ? OPMHIP_REORDER_LINE_COLORING : OPMHIP_REORDER_GRAPH_COLORING_GREEDY;
         if (c->cfg.verbosity > 0) std::fprintf(stderr, "opmhip: reorder auto -> %s (%d rows)\n", regular ? "line_coloring" : "graph_coloring_greedy", Nb);
     }
-    const bool chained = (kind == OPMHIP_REORDER_LINE_COLORING);
+    bool chained = (kind == OPMHIP_REORDER_LINE_COLORING);
     int maxLen = 1;
     // the ordering is computed on the owned-owned couplings only
     Pattern Q;
@@ -539,7 +671,63 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
             color.resize(Nb);
             for (int i = 0; i < Nb; ++i) color[i] = chainColor[CH.chainOf[i]];
         } break;
+        case OPMHIP_REORDER_DISTANCE2_COLORING: color_distance2(Q, color, ncol); break;
         default: return fail(c, OPMHIP_INVALID_ARGUMENT, "unknown reorder kind %d", c->cfg.reorder);
+    }
+    // ILU(n), n >= 1 (opmhip_set_ilu_fillin_level): the fill is computed in the ordering's elimination order - the natural order for level
+    // scheduling (the reference's ILU(n) runs on the natural order), colour by colour otherwise (line colouring: colour, chain, step; the
+    // chains do not survive the fill).  Where the colours are independent sets of the filled pattern too (the distance-2 colouring with
+    // n = 1) they stay the schedule; otherwise the rows are renumbered by the levels of the filled pattern - a topological order of its
+    // couplings, which leaves the fill and the factors' arithmetic as they are.
+    const int fillN = use_cpr(c) ? 0 : c->ilu_fillin;   // the CPR's fine smoother is ILU0 (setupPropertyTree.cpp:109-110)
+    P.fillLevel = fillN;
+    std::vector<int> frp, fcl, fdg, ibase;   // the filled pattern in the fill's elimination order
+    P.fillBase.clear();
+    if (fillN > 0) {
+        if (Nghost > 0 || c->comm.kind != COMM_NONE)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "ILU(%d) on a decomposed context is not supported (use --ilu-fillin-level=0)", fillN);
+        ibase.resize(Nb);
+        std::iota(ibase.begin(), ibase.end(), 0);
+        if (kind != OPMHIP_REORDER_LEVEL_SCHEDULING) {
+            if (chained) std::stable_sort(ibase.begin(), ibase.end(), [&](int a, int b) {
+                const int ca = color[a], cb = color[b];
+                if (ca != cb) return ca < cb;
+                if (CH.chainOf[a] != CH.chainOf[b]) return CH.chainOf[a] < CH.chainOf[b];
+                return CH.posIn[a] < CH.posIn[b];
+            });
+            else std::stable_sort(ibase.begin(), ibase.end(), [&](int a, int b) { return color[a] < color[b]; });
+        }
+        std::vector<int>& base = P.fillBase;
+        base.resize(Nb);
+        for (int b = 0; b < Nb; ++b) base[ibase[b]] = b;
+        std::vector<int> brp(Nb + 1, 0), bcl;
+        bcl.reserve(Q.nnzb);
+        for (int b = 0; b < Nb; ++b) {
+            const int i = ibase[b];
+            const size_t o = bcl.size();
+            for (int k = Q.nat_rowptr[i]; k < Q.nat_rowptr[i + 1]; ++k) bcl.push_back(base[Q.nat_col[k]]);
+            std::sort(bcl.begin() + o, bcl.end());
+            brp[b + 1] = (int)bcl.size();
+        }
+        const long long budget = (long long)ILUN_BUDGET_FACTOR * nnzb;
+        if (!symbolic_fill(Nb, brp, bcl, fillN, budget, frp, fcl, fdg))
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "ILU(%d): the filled factors of this %d-row pattern would hold more than %lld blocks (%d x the matrix's %d); refused",
+                        fillN, Nb, budget, ILUN_BUDGET_FACTOR, nnzb);
+        bool keep = kind != OPMHIP_REORDER_LEVEL_SCHEDULING && !chained;
+        for (int b = 0; b < Nb && keep; ++b)
+            for (int q = frp[b]; q < frp[b + 1]; ++q)
+                if (fcl[q] != b && color[ibase[fcl[q]]] == color[ibase[b]]) { keep = false; break; }
+        if (!keep) {   // levels of the filled pattern over its row AND column couplings (as levels() does for the matrix)
+            std::vector<int> lev(Nb, 0);
+            ncol = 0;
+            for (int b = 0; b < Nb; ++b) {
+                for (int q = frp[b]; q < fdg[b]; ++q) lev[b] = std::max(lev[b], lev[fcl[q]] + 1);
+                for (int q = fdg[b] + 1; q < frp[b + 1]; ++q) lev[fcl[q]] = std::max(lev[fcl[q]], lev[b] + 1);
+                color[ibase[b]] = lev[b];
+                ncol = std::max(ncol, lev[b] + 1);
+            }
+            chained = false;
+        }
     }
     P.numColors = ncol;
     P.chained = chained;
@@ -677,6 +865,11 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
             }
         }
     }
+    if (fillN > 0) {   // ILU(n): U is not upper(A) (fill right of the diagonal), the product after M^-1 streams the whole matrix
+        P.ualias = false;
+        int rc = build_fill_split(c, frp, fcl, ibase);
+        if (rc) return rc;
+    }
     // the rest of the matrix beside the U part, as a block-CSR of its own (ascending columns: the order of the full row without its U entries)
     P.rrowptr.assign(Nb + 1, 0);
     P.rcol.clear();
@@ -778,6 +971,14 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
         if ((rc = dev_upload(c, &P.rest.d_word, P.rest.word))) return rc;
         if ((rc = dev_upload(c, &P.rest.d_koff, P.rest.koff))) return rc;
         if ((rc = dev_upload(c, &P.rest.d_table, P.rest.table))) return rc;
+    }
+    if (fillN > 0) {
+        if ((rc = dev_upload(c, &P.d_flrowptr, P.flrowptr))) return rc;
+        if ((rc = dev_upload(c, &P.d_flcol, P.flcol))) return rc;
+        if ((rc = dev_upload(c, &P.d_furowptr, P.furowptr))) return rc;
+        if ((rc = dev_upload(c, &P.d_fucol, P.fucol))) return rc;
+        if ((rc = dev_upload(c, &P.d_fillDest, P.fillDest))) return rc;
+        if ((rc = dev_upload(c, &P.d_frow0, P.ftiles.row0))) return rc;
     }
     if ((rc = dev_upload(c, &P.tiles.d_row0, P.tiles.row0))) return rc;
     if ((rc = dev_upload(c, &P.tiles.d_ctFirst, P.tiles.ctFirst))) return rc;

@@ -1540,6 +1540,80 @@ __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched
     }
 }
 
+// ============================== ILU(n), n >= 1 ===========================================================
+// The factors' pattern is the matrix's plus the fill (Pattern::flrowptr / furowptr): rows hold 12 - 15 blocks on a 7-point grid with
+// n = 1, more near wells, so the factorisation works in global memory, one thread per row, one launch per level of the filled pattern.
+// Step 1: the working rows - L and U of every row zeroed, the diagonal block (in invD until it is inverted) and the matrix's entries
+// scattered in through Pattern::fillDest; zfix: the zero-diagonal fix (k_zero_diag_fix's statement) in the matrix and the working row.
+__global__ __launch_bounds__(256) void k_ilun_scatter(int Nb, const int* __restrict__ rowptr, const int* __restrict__ col, double* A,
+                                                      const int* __restrict__ fdest, const int* __restrict__ flrowptr,
+                                                      const int* __restrict__ furowptr, double* __restrict__ L, double* __restrict__ U,
+                                                      double* __restrict__ D, int zfix) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= Nb) return;
+    for (size_t e = (size_t)flrowptr[p] * BB; e < (size_t)flrowptr[p + 1] * BB; ++e) L[e] = 0.0;
+    for (size_t e = (size_t)furowptr[p] * BB; e < (size_t)furowptr[p + 1] * BB; ++e) U[e] = 0.0;
+    for (int k = rowptr[p]; k < rowptr[p + 1]; ++k) {
+        const int j = col[k], d = fdest[k];
+        double* dst = j == p ? &D[(size_t)p * BB] : d >= 0 ? &L[(size_t)d * BB] : d <= -2 ? &U[(size_t)(-2 - d) * BB] : nullptr;
+        if (!dst) continue;   // ghost column
+        double* a = &A[(size_t)k * BB];
+        if (zfix && j == p)
+#pragma unroll
+            for (int dgn = 0; dgn < BS; ++dgn)
+                if (a[dgn * 4] == 0.0) a[dgn * 4] = 1e-15;
+#pragma unroll
+        for (int q = 0; q < BB; ++q) dst[q] = a[q];
+    }
+}
+// Step 2, rows [r0, r1) of one level: Dune's bilu0_decomposition on the filled pattern (oracle: bilu0_decompose) - for every L entry (i, k)
+// in ascending column order L_ik = A_ik D_k^-1, then A_ij -= L_ik U_kj wherever row i has an entry j (its L part beyond k, its diagonal, its
+// U part); finally D_i^-1.  Rows k are finished rows of earlier levels.  The same block products as k_ilu_factor, in the same order.
+__global__ __launch_bounds__(64) void k_ilun_factor(int r0, int r1, const int* __restrict__ flrowptr, const int* __restrict__ flcol,
+                                                    const int* __restrict__ furowptr, const int* __restrict__ fucol, double* L, double* U,
+                                                    double* invD) {
+    const int i = r0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r1) return;
+    const int lb = flrowptr[i], le = flrowptr[i + 1], ub = furowptr[i], ue = furowptr[i + 1];
+    double* Di = &invD[(size_t)i * BB];
+    for (int a = lb; a < le; ++a) {
+        const int k = flcol[a];
+        double tmp[BB], Dk[BB], Lik[BB];
+#pragma unroll
+        for (int q = 0; q < BB; ++q) { tmp[q] = L[(size_t)a * BB + q]; Dk[q] = invD[(size_t)k * BB + q]; }
+        blk_mul(tmp, Dk, Lik);  // A_ik * A_kk^-1
+#pragma unroll
+        for (int q = 0; q < BB; ++q) L[(size_t)a * BB + q] = Lik[q];
+        int il = a + 1, iu = ub;   // cursors into row i's L part beyond k and its U part
+        for (int kj = furowptr[k]; kj < furowptr[k + 1]; ++kj) {
+            const int j = fucol[kj];
+            double* tgt = nullptr;
+            if (j < i) {
+                while (il < le && flcol[il] < j) ++il;
+                if (il < le && flcol[il] == j) tgt = &L[(size_t)il * BB];
+            } else if (j == i) {
+                tgt = Di;
+            } else {
+                while (iu < ue && fucol[iu] < j) ++iu;
+                if (iu < ue && fucol[iu] == j) tgt = &U[(size_t)iu * BB];
+            }
+            if (!tgt) continue;
+            double Ukj[BB], Pm[BB];
+#pragma unroll
+            for (int q = 0; q < BB; ++q) Ukj[q] = U[(size_t)kj * BB + q];
+            blk_mul(Lik, Ukj, Pm);  // L_ik * U_kj
+#pragma unroll
+            for (int q = 0; q < BB; ++q) tgt[q] -= Pm[q];
+        }
+    }
+    double dblk[BB], inv[BB];
+#pragma unroll
+    for (int q = 0; q < BB; ++q) dblk[q] = Di[q];
+    blk_invert(dblk, inv);
+#pragma unroll
+    for (int q = 0; q < BB; ++q) Di[q] = inv[q];
+}
+
 // ============================== standard wells ===========================================================
 // y -= C^T (D^-1 (B x)) per well (bda/WellContributions.cu:36-126); one wavefront per well, any number of
 // perforations (the CUDA kernel's 32-lane masks assume <= 2 blocks per warp pass, :82).
@@ -2348,6 +2422,18 @@ static int dot_count(opmhip_ctx* c) { return c->last_dot_count; }  // how many p
 void launch_ilu_factor(opmhip_ctx* c, bool fix_zero_diagonal, const FactorRider* rider) {
     const Pattern& P = c->pat;
     const int ps = prof_begin(c, PROF_ILU_FACTOR);
+    if (P.fillLevel > 0) {   // ILU(n): no rider (a CPR context factors ILU0)
+        hipLaunchKernelGGL(k_ilun_scatter, dim3((P.Nb + 255) / 256), dim3(256), 0, c->stream, P.Nb, P.d_rowptr, P.d_col, c->d_A, P.d_fillDest,
+                           P.d_flrowptr, P.d_furowptr, c->d_fL, c->d_fU, c->d_invD, fix_zero_diagonal ? 1 : 0);
+        for (int col = 0; col < P.numColors; ++col) {
+            const int r0 = P.colorPrefix[col], n = P.colorPrefix[col + 1] - r0;
+            if (n > 0)
+                hipLaunchKernelGGL(k_ilun_factor, dim3((n + 63) / 64), dim3(64), 0, c->stream, r0, r0 + n, P.d_flrowptr, P.d_flcol, P.d_furowptr,
+                                   P.d_fucol, c->d_fL, c->d_fU, c->d_invD);
+        }
+        prof_end(c, ps);
+        return;
+    }
     const FactorRider none;
     const FactorRider& R = rider ? *rider : none;
     for (int col = 0; col < P.numColors; ++col) {
@@ -2443,22 +2529,31 @@ void launch_ilu_apply(opmhip_ctx* c, const double* d, double* v, double w_overri
         prof_end(c, ps);
         return;
     }
+    // ILU(n), n >= 1: the same sweeps over the filled factors, by the levels of the filled pattern (its colours), on tiles cut for its rows.
+    // The tile kernels hold a row in LDS only where the tile fits (TileCtx::staged) and read it from memory otherwise, so rows of any
+    // length are safe.
+    const bool fill = P.fillLevel > 0;
+    const std::vector<int>& ctile = fill ? P.ftiles.colorTile : P.tiles.colorTile;
+    const int* row0 = fill ? P.d_frow0 : P.tiles.d_row0;
+    const int *lrp = fill ? P.d_flrowptr : P.d_lrowptr, *lcl = fill ? P.d_flcol : P.d_lcol;
+    const int *urp = fill ? P.d_furowptr : P.d_urowptr, *ucl = fill ? P.d_fucol : P.d_ucol;
+    const double *Lv = fill ? c->d_fL : c->d_L, *Uv = fill ? c->d_fU : c->d_U;
     for (int col = 1; col < C; ++col) {
-        const int tb = P.tiles.colorTile[col], nt = P.tiles.colorTile[col + 1] - tb;
+        const int tb = ctile[col], nt = ctile[col + 1] - tb;
         if (nt <= 0) continue;
         if (col < C - 1)
-            hipLaunchKernelGGL(k_ilu_sweep<SW_L>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, P.tiles.d_row0, P.d_lrowptr, P.d_lcol, c->d_L,
+            hipLaunchKernelGGL(k_ilu_sweep<SW_L>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, row0, lrp, lcl, Lv,
                                c->d_invD, d, vu, v, addp, mode, w, c->d_done);
         else
-            hipLaunchKernelGGL(k_ilu_sweep<SW_LF>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, P.tiles.d_row0, P.d_lrowptr, P.d_lcol, c->d_L,
+            hipLaunchKernelGGL(k_ilu_sweep<SW_LF>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, row0, lrp, lcl, Lv,
                                c->d_invD, d, vu, v, addp, mode, w, c->d_done);
     }
     for (int col = (C > 1 ? C - 2 : 0); col >= 0; --col) {
-        const int tb = P.tiles.colorTile[col], nt = P.tiles.colorTile[col + 1] - tb;
+        const int tb = ctile[col], nt = ctile[col + 1] - tb;
         if (nt <= 0) continue;
         // gathers only reach later colours (>= n0 rows in), so the d/vu split of the gather is inert here (n0 = 0)
-        hipLaunchKernelGGL(k_ilu_sweep<SW_UF>, grid(nt), dim3(64), 0, c->stream, tb, nt, 0, col == 0 ? 1 : 0, P.tiles.d_row0, P.d_urowptr, P.d_ucol,
-                           c->d_U, c->d_invD, d, vu, v, addp, mode, w, c->d_done);
+        hipLaunchKernelGGL(k_ilu_sweep<SW_UF>, grid(nt), dim3(64), 0, c->stream, tb, nt, 0, col == 0 ? 1 : 0, row0, urp, ucl,
+                           Uv, c->d_invD, d, vu, v, addp, mode, w, c->d_done);
     }
     prof_end(c, ps);
 }

@@ -45,7 +45,8 @@ public:
     /// ISTLSolverEbos::getTrueImpesWeights (ISTLSolverEbos.hpp:466-475) to setCprWeights() before each solve.
     hipSolverBackend(int linear_solver_verbosity, int maxit_, double tolerance_, unsigned int deviceID_,
                      const std::string& ilu_reorder = "auto", double ilu_relaxation = 0.9,
-                     const std::string& linsolver = "ilu0", int cpr_reuse_setup = 3, int cpr_amg_ilu_levels = -1, int cpr_gather_rows = 0)
+                     const std::string& linsolver = "ilu0", int cpr_reuse_setup = 3, int cpr_amg_ilu_levels = -1, int cpr_gather_rows = 0,
+                     int ilu_fillin_level = 0)
         : Base(linear_solver_verbosity, maxit_, tolerance_, deviceID_) {
         static_assert(block_size == 3, "libopmhip handles 3x3 blocks (three-phase black-oil)");
         opmhip_config cfg;
@@ -78,6 +79,12 @@ public:
         cfg.pin_host_arrays = 1;
         const int rc = opmhip_create(&cfg, &ctx);
         if (rc != OPMHIP_SUCCESS) throw std::logic_error(std::string("hipSolverBackend: ") + opmhip_last_error(nullptr));
+        // --ilu-fillin-level: block ILU(n) in place of ILU0 (ignored by the CPR configurations, whose fine smoother is ILU0)
+        if (ilu_fillin_level != 0 && opmhip_set_ilu_fillin_level(ctx, ilu_fillin_level) != OPMHIP_SUCCESS) {
+            const std::string msg = std::string("hipSolverBackend: ") + opmhip_last_error(ctx);
+            opmhip_destroy(ctx);
+            throw std::logic_error(msg);
+        }
     }
     ~hipSolverBackend() override { opmhip_destroy(ctx); }
     /// weights of the CPR preconditioner (3 per block row), e.g. Amg::getTrueImpesWeights; nullptr: computed by the library
