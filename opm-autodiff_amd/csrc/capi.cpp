@@ -30,15 +30,11 @@ int alloc_system(opmhip_ctx* c) {
     if ((rc = dev_alloc(c, &c->d_L, (size_t)P.nl * BB + SLACK))) return rc;
     if ((rc = dev_alloc(c, &c->d_U, (size_t)P.nu * BB + SLACK))) return rc;
     OPMHIP_HIP(c, hipMemsetAsync(c->d_A + (size_t)P.nnzb * BB, 0, SLACK * sizeof(double), c->stream));
-    OPMHIP_HIP(c, hipMemsetAsync(c->d_L + (size_t)P.nl * BB, 0, SLACK * sizeof(double), c->stream));
-    OPMHIP_HIP(c, hipMemsetAsync(c->d_U + (size_t)P.nu * BB, 0, SLACK * sizeof(double), c->stream));
+    // ILU0 writes every entry of its factors, only the slack is zeroed; ILU(n) factors (the filled pattern) are zeroed whole
+    const size_t l0 = P.fillLevel > 0 ? 0 : (size_t)P.nl * BB, u0 = P.fillLevel > 0 ? 0 : (size_t)P.nu * BB;
+    OPMHIP_HIP(c, hipMemsetAsync(c->d_L + l0, 0, ((size_t)P.nl * BB + SLACK - l0) * sizeof(double), c->stream));
+    OPMHIP_HIP(c, hipMemsetAsync(c->d_U + u0, 0, ((size_t)P.nu * BB + SLACK - u0) * sizeof(double), c->stream));
     if ((rc = dev_alloc(c, &c->d_invD, (size_t)P.Nb * BB))) return rc;
-    if (P.fillLevel > 0) {   // ILU(n): the filled factors (the tile sweeps read them with the same slack as d_L / d_U)
-        if ((rc = dev_alloc(c, &c->d_fL, (size_t)P.fnl * BB + SLACK))) return rc;
-        if ((rc = dev_alloc(c, &c->d_fU, (size_t)P.fnu * BB + SLACK))) return rc;
-        OPMHIP_HIP(c, hipMemsetAsync(c->d_fL, 0, ((size_t)P.fnl * BB + SLACK) * sizeof(double), c->stream));
-        OPMHIP_HIP(c, hipMemsetAsync(c->d_fU, 0, ((size_t)P.fnu * BB + SLACK) * sizeof(double), c->stream));
-    }
     c->half_product = half_product_wanted(c);
     if (c->half_product) {   // the matrix beside its U part (written by the factorisation) and the backward sweeps' row sums
         if ((rc = dev_alloc(c, &c->d_R, (size_t)P.nr * BB + SLACK))) return rc;
@@ -741,10 +737,9 @@ int opmhip_get_ilu_info(opmhip_ctx* c, int info[4]) {
     if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
     if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_ilu_info before set_pattern");
     const Pattern& P = c->pat;
-    const bool fill = P.fillLevel > 0;
     info[0] = P.fillLevel;
-    info[1] = fill ? P.fnl : P.nl;
-    info[2] = fill ? P.fnu : P.nu;
+    info[1] = P.nl;
+    info[2] = P.nu;
     info[3] = P.numColors;
     return OPMHIP_SUCCESS;
 }
@@ -755,19 +750,14 @@ int opmhip_get_ilu_factors(opmhip_ctx* c, int* toOrder, int* lrowptr, int* lcol,
         if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_ilu_factors before set_pattern");
         if ((L || U || invD) && !c->factored) return fail(c, OPMHIP_NOT_READY, "get_ilu_factors: no factorisation yet");
         const Pattern& P = c->pat;
-        const bool fill = P.fillLevel > 0;
-        const std::vector<int>& lrp = fill ? P.flrowptr : P.lrowptr;
-        const std::vector<int>& lcl = fill ? P.flcol : P.lcol;
-        const std::vector<int>& urp = fill ? P.furowptr : P.urowptr;
-        const std::vector<int>& ucl = fill ? P.fucol : P.ucol;
         if (toOrder) std::memcpy(toOrder, P.toOrder.data(), P.Nb * sizeof(int));
-        if (lrowptr) std::memcpy(lrowptr, lrp.data(), (P.Nb + 1) * sizeof(int));
-        if (urowptr) std::memcpy(urowptr, urp.data(), (P.Nb + 1) * sizeof(int));
-        if (lcol && !lcl.empty()) std::memcpy(lcol, lcl.data(), lcl.size() * sizeof(int));
-        if (ucol && !ucl.empty()) std::memcpy(ucol, ucl.data(), ucl.size() * sizeof(int));
+        if (lrowptr) std::memcpy(lrowptr, P.lrowptr.data(), (P.Nb + 1) * sizeof(int));
+        if (urowptr) std::memcpy(urowptr, P.urowptr.data(), (P.Nb + 1) * sizeof(int));
+        if (lcol && P.nl > 0) std::memcpy(lcol, P.lcol.data(), P.nl * sizeof(int));
+        if (ucol && P.nu > 0) std::memcpy(ucol, P.ucol.data(), P.nu * sizeof(int));
         OPMHIP_HIP(c, hipSetDevice(c->device));
-        if (L && !lcl.empty()) OPMHIP_HIP(c, hipMemcpyAsync(L, fill ? c->d_fL : c->d_L, lcl.size() * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (U && !ucl.empty()) OPMHIP_HIP(c, hipMemcpyAsync(U, fill ? c->d_fU : c->d_U, ucl.size() * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (L && P.nl > 0) OPMHIP_HIP(c, hipMemcpyAsync(L, c->d_L, (size_t)P.nl * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (U && P.nu > 0) OPMHIP_HIP(c, hipMemcpyAsync(U, c->d_U, (size_t)P.nu * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (invD) OPMHIP_HIP(c, hipMemcpyAsync(invD, c->d_invD, (size_t)P.Nb * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         return OPMHIP_SUCCESS;

@@ -35,6 +35,18 @@ struct DevBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// Stencil form of a block-CSR's index streams (reorder.cpp: encode_stencil): the rows of a tile share their column offsets, so a tile carries
+// a table of <= 15 offsets (col - row) and a row one word of eight 4-bit table indices (15 = no entry) and one byte (first entry - the
+// tile's first entry) - 5 bytes per row instead of 28 + 16 for column indices and row bounds.  Read by k_spmv_pipe_st and the chain sweeps.
+struct StencilForm {
+    std::vector<unsigned> word;        // per row
+    std::vector<unsigned char> koff;   // per row
+    std::vector<int> table;            // [16 * tiles]
+    unsigned* d_word = nullptr;
+    unsigned char* d_koff = nullptr;
+    int* d_table = nullptr;
+};
+
 struct TileSet {            // tiles over one block-CSR row-pointer array, never crossing a colour boundary
     std::vector<int> row0;  // [ntiles+1]
     std::vector<int> colorTile;  // [numColors+1] first tile of each colour
@@ -56,37 +68,24 @@ struct TileSet {            // tiles over one block-CSR row-pointer array, never
     std::vector<int> ctDesc;
     int descStride = 0, descS1 = 0;
     int* d_spmvSched = nullptr;
-    // stencil form of the SpMV's index streams (reorder.cpp: build_schedules): the rows of a tile share their column offsets, so a launch
-    // position carries a table of <= 15 offsets (col - row) and a row one word of eight 4-bit table indices (15 = no entry) and one byte
-    // (first entry - the tile's first entry) - 5 bytes per row instead of 28 + 16 for column indices and row bounds.  stencil = false: a
-    // tile needs more offsets or a row more than eight entries; the explicit index streams are used
+    // stencil form of the SpMV's index streams, one table per launch position.  stencil = false: a tile needs more than 15 offsets or a
+    // row more than eight entries; the explicit index streams are used
     bool stencil = false;           // some part of the schedule has it
     bool stencilPart[2] = {false, false};   // [0] positions [0, nschedInt), [1] the boundary tiles of a decomposed run
-    std::vector<unsigned> stWord;
-    std::vector<unsigned char> stKoff;
-    std::vector<int> stTable;   // [16 * nsched]
-    unsigned* d_stWord = nullptr;
-    unsigned char* d_stKoff = nullptr;
-    int* d_stTable = nullptr;
+    StencilForm st;
     int* d_ctSched = nullptr;
     int* d_ctDesc = nullptr;
     int ntiles() const { return (int)row0.size() - 1; }
 };
 
 // Launch schedule of the "rest product" (Pattern::ualias): the tiles of y = R x + s u over the block-CSR of the matrix entries that are NOT
-// in the factor's U part - lower entries, diagonal, ghost columns.  Same record formats as the SpMV's stencil form (TileSet::spmvSched /
-// stWord / stKoff / stTable, read by k_spmv_pipe_st); tiles hold up to 64 rows (one per lane) and TILE_CAP_BLOCKS blocks.
-struct RestSched {
+// in the factor's U part - lower entries, diagonal, ghost columns.  Same record formats as the SpMV's (TileSet::spmvSched and a stencil form
+// with one table per launch position, read by k_spmv_pipe_st); tiles hold up to 64 rows (one per lane) and TILE_CAP_BLOCKS blocks.
+struct RestSched : StencilForm {
     bool on = false;
     int nsched = 0, nschedInt = 0;            // launch positions; [0, nschedInt) interior tiles, the rest boundary tiles (decomposed runs)
     std::vector<int> sched;                   // [4 * nsched] (r0, r1, rrowptr[r0], rrowptr[r1]); r1 <= r0 = padding
-    std::vector<unsigned> word;               // per row: eight 4-bit table indices (15 = no entry)
-    std::vector<unsigned char> koff;          // per row: first entry - the tile's first entry
-    std::vector<int> table;                   // [16 * nsched]
     int* d_sched = nullptr;
-    unsigned* d_word = nullptr;
-    unsigned char* d_koff = nullptr;
-    int* d_table = nullptr;
 };
 
 struct Pattern {
@@ -104,7 +103,7 @@ struct Pattern {
     std::vector<int> toOrder, fromOrder, colorPrefix;  // colorPrefix[numColors+1] in rows
     // internal (reordered) pattern
     std::vector<int> rowptr, col, diag, nnzMap;  // nnzMap[k_internal] = k_natural
-    std::vector<int> lrowptr, lcol, urowptr, ucol;
+    std::vector<int> lrowptr, lcol, urowptr, ucol;   // the factors' L / U split (ILU(n): of the filled pattern, see fillLevel)
     std::vector<long long> gids;  // optional: global id of every local cell (decomposed runs), natural local order
     TileSet tiles;
     // device copies
@@ -113,15 +112,10 @@ struct Pattern {
     int *d_lrowptr = nullptr, *d_lcol = nullptr, *d_urowptr = nullptr, *d_ucol = nullptr;
     std::vector<int> fdest;      // per matrix entry: where the factorisation puts it - L index (>= 0), -2 - U index, -1 (diagonal / dropped ghost column)
     int* d_fdest = nullptr;
-    // stencil form of the sweeps' index streams (solver.hip: SweepStencil), per factor part: word / byte per row, table per tile;
+    // stencil form of the sweeps' index streams (solver.hip: SweepStencil), per factor part (L, U), one table per tile of `tiles`;
     // sweepStencil = false: some tile needs more than 15 offsets or a row more than CGCH entries - explicit streams
     bool sweepStencil = false;
-    std::vector<unsigned> swWord[2];
-    std::vector<unsigned char> swKoff[2];
-    std::vector<int> swTable[2];
-    unsigned* d_swWord[2] = {nullptr, nullptr};
-    unsigned char* d_swKoff[2] = {nullptr, nullptr};
-    int* d_swTable[2] = {nullptr, nullptr};
+    StencilForm sw[2];
     // per L entry (i, j) what its elimination step touches: the ONE entry of row i that meets the U part of row j (a 7-point grid has no
     // triangles: it is the diagonal) as U index * 64 + offset of the target in row i; -1: none; -2: several (the general search)
     std::vector<int> lmatch;
@@ -137,16 +131,14 @@ struct Pattern {
     std::vector<int> rrowptr, rcol, rdest;
     int *d_rdest = nullptr, *d_rrowptr = nullptr;
     RestSched rest;
-    // ILU(n), n >= 1 (opmhip_set_ilu_fillin_level; reorder.cpp: build_fill): the factors' own pattern - the matrix's owned pattern plus the
-    // level-of-fill entries, computed in the ordering's elimination order - split into L and U like lrowptr / lcol / urowptr / ucol.  The
-    // ordering is then a schedule of the FILLED pattern: colours (levels) are its independent sets, colorPrefix their row ranges.
-    // fillDest: per matrix entry its place in the factors (L index >= 0, -2 - U index, -1 diagonal or ghost column); fill entries start
-    // at zero.  ftiles: the sweeps' tiles over the filled rows (row0 / colorTile only).  fillLevel 0: none of this exists.
-    int fillLevel = 0, fnl = 0, fnu = 0;
-    std::vector<int> flrowptr, flcol, furowptr, fucol, fillDest;
+    // ILU(n), n >= 1 (opmhip_set_ilu_fillin_level; reorder.cpp: build_fill_split): lrowptr / lcol / urowptr / ucol / fdest / nl / nu describe
+    // the factors' own pattern - the matrix's owned pattern plus the level-of-fill entries, computed in the ordering's elimination order; fill
+    // entries start at zero.  The ordering is then a schedule of the FILLED pattern: colours (levels) are its independent sets, colorPrefix
+    // their row ranges.  ftiles: the sweeps' tiles over the filled rows (row0 / colorTile / d_row0 only; `tiles` still cuts the SpMV).
+    // lmatch and the chain kernels' records (TileSet::ctDesc) belong to ILU0 and are not built; ualias is false.
+    int fillLevel = 0;
     std::vector<int> fillBase;   // natural row -> its place in the elimination order the fill was computed in (tests: the fill rule restated)
     TileSet ftiles;
-    int *d_flrowptr = nullptr, *d_flcol = nullptr, *d_furowptr = nullptr, *d_fucol = nullptr, *d_fillDest = nullptr, *d_frow0 = nullptr;
 };
 // ILU(n) memory guard: the filled factors (L, U and the diagonal, in blocks) may hold at most this many times the blocks of the matrix
 constexpr int ILUN_BUDGET_FACTOR = 8;
@@ -388,7 +380,6 @@ struct opmhip_ctx {
     opmhip::Pattern pat;
     // values, internal order
     double *d_A = nullptr, *d_L = nullptr, *d_U = nullptr, *d_invD = nullptr;
-    double *d_fL = nullptr, *d_fU = nullptr;    // ILU(n), n >= 1: the filled factors (Pattern::flrowptr / furowptr); d_invD as for ILU0
     double *d_R = nullptr, *d_usum = nullptr;   // Pattern::ualias: the rest of the matrix beside U (values), the backward sweeps' row sums (3 per row)
     bool half_product = false;                  // BiCGStab forms the product after an ILU0 application from d_R and d_usum (opmhip_config.half_product)
     // vectors, internal order, 3*Nb each

@@ -282,6 +282,47 @@ void color_chains(const Pattern& P, const Chains& C, std::vector<int>& chainColo
     }
 }
 
+// The sorted, distinct column offsets (col - row) of rows [r0, r1) of a block-CSR
+void tile_offsets(const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1, std::vector<int>& offs) {
+    offs.clear();
+    for (int r = r0; r < r1; ++r)
+        for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) offs.push_back(col[k] - r);
+    std::sort(offs.begin(), offs.end());
+    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
+}
+void reset_stencil(StencilForm& S, int Nb, size_t tables) {
+    S.word.assign(Nb, 0xFFFFFFFFu);
+    S.koff.assign(Nb, 0);
+    S.table.assign(16 * tables, 0);
+}
+// Rows [r0, r1) of a block-CSR in stencil form (internal.hpp: StencilForm), their offsets in table `slot`.  False where the tile has more
+// than 15 offsets (nothing written) or a row more than 8 entries or a first entry more than 255 blocks in (the table and the rows before
+// that one are written): the form does not fit.
+bool encode_stencil(const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1, int slot, StencilForm& S) {
+    std::vector<int> offs;
+    tile_offsets(rowptr, col, r0, r1, offs);
+    if (offs.size() > 15) return false;
+    for (size_t q = 0; q < offs.size(); ++q) S.table[(size_t)16 * slot + q] = offs[q];
+    for (int r = r0; r < r1; ++r) {
+        const int len = rowptr[r + 1] - rowptr[r], ko = rowptr[r] - rowptr[r0];
+        if (len > 8 || ko > 255) return false;
+        unsigned w = 0xFFFFFFFFu;
+        for (int u = 0; u < len; ++u) {
+            const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), col[rowptr[r] + u] - r) - offs.begin());
+            w = (w & ~(0xFu << (4 * u))) | ((unsigned)idx << (4 * u));
+        }
+        S.word[r] = w;
+        S.koff[r] = (unsigned char)ko;
+    }
+    return true;
+}
+int upload_stencil(opmhip_ctx* c, StencilForm& S) {
+    int rc;
+    if ((rc = dev_upload(c, &S.d_word, S.word))) return rc;
+    if ((rc = dev_upload(c, &S.d_koff, S.koff))) return rc;
+    return dev_upload(c, &S.d_table, S.table);
+}
+
 // Launch schedules.  The hardware deals consecutive workgroups of a launch round-robin over the 8 XCDs, each with an L2 of
 // its own.  With the identity map (workgroup b = tile b) a line of the gathered vector is wanted by ~7 tiles that land
 // on ~5 different XCDs and is fetched from the fabric by each (PMC: the 24 MB input vector of the 100^3 SpMV costs
@@ -289,6 +330,14 @@ void color_chains(const Pattern& P, const Chains& C, std::vector<int>& chainColo
 // GROUPS of `G` consecutive chain-tiles of every colour at the same relative position of their colour - the same stretch
 // of the grid - so that most neighbours of a tile are gathered through the L2 that already holds them.
 // Results do not depend on the schedule (each tile's arithmetic is its own); only the order of the partial sums does.
+// deal: list k's items to launch positions k, k + 8, k + 16, ... (position % 8 = the XCD), shorter lists padded with `pad`
+template <class T>
+void deal(const std::vector<std::vector<T>>& lists, const T& pad, std::vector<T>& out) {
+    size_t L = 0;
+    for (const auto& l : lists) L = std::max(L, l.size());
+    for (size_t j = 0; j < L; ++j)
+        for (int k = 0; k < 8; ++k) out.push_back(j < lists[k].size() ? lists[k][j] : pad);
+}
 // Launch schedule of the rest product (internal.hpp: RestSched).  The tiles follow the SpMV's launch order - position b and b + 8 of it are
 // consecutive tiles of one stretch of the grid on one XCD - and consecutive tiles are merged while the rows stay contiguous, the tile holds
 // at most 64 rows (one per lane) and TILE_CAP_BLOCKS blocks and its rows share at most 15 column offsets: a row of the rest has 2 - 6 blocks
@@ -301,13 +350,6 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
     R.on = false;
     if (!P.ualias || !P.chained) return;
     struct Rt { int r0, r1; };
-    auto offsets_of = [&](int r0, int r1, std::vector<int>& offs) {
-        offs.clear();
-        for (int r = r0; r < r1; ++r)
-            for (int k = P.rrowptr[r]; k < P.rrowptr[r + 1]; ++k) offs.push_back(P.rcol[k] - r);
-        std::sort(offs.begin(), offs.end());
-        offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-    };
     std::vector<int> offs;
     static const int maxRows = [] { const char* e = tuning_env("OPMHIP_REST_ROWS"); const int v = e ? std::atoi(e) : 64; return v < 1 ? 1 : (v > 64 ? 64 : v); }();   // measurement switch: rows per tile at most
     static const int maxBlocks = [] { const char* e = tuning_env("OPMHIP_REST_BLOCKS"); const int v = e ? std::atoi(e) : TILE_CAP_BLOCKS; return v < 8 ? 8 : (v > TILE_CAP_BLOCKS ? TILE_CAP_BLOCKS : v); }();
@@ -326,7 +368,7 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
                 const int r0 = T.row0[order[b]], r1 = T.row0[order[b] + 1];
                 if (r1 <= r0) continue;
                 if (cur.r1 > cur.r0 && r0 == cur.r1 && r1 - cur.r0 <= maxRows && P.rrowptr[r1] - P.rrowptr[cur.r0] <= maxBlocks) {
-                    offsets_of(cur.r0, r1, offs);
+                    tile_offsets(P.rrowptr, P.rcol, cur.r0, r1, offs);
                     if (offs.size() <= 15) { cur.r1 = r1; continue; }
                 }
                 if (cur.r1 > cur.r0) lists[k].push_back(cur);
@@ -334,38 +376,20 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
             }
             if (cur.r1 > cur.r0) lists[k].push_back(cur);
         }
-        size_t L = 0;
-        for (const auto& l : lists) L = std::max(L, l.size());
-        for (size_t j = 0; j < L; ++j)
-            for (int k = 0; k < 8; ++k) out.push_back(j < lists[k].size() ? lists[k][j] : Rt{0, 0});
+        deal(lists, Rt{0, 0}, out);
         if (part == 0) nInt = (int)out.size();
     }
     R.nsched = (int)out.size();
     R.nschedInt = P.Nghost > 0 ? R.nsched : nInt;
     R.sched.assign((size_t)4 * R.nsched, 0);
-    R.word.assign(P.Nb, 0xFFFFFFFFu);
-    R.koff.assign(P.Nb, 0);
-    R.table.assign((size_t)16 * std::max(1, R.nsched), 0);
+    reset_stencil(R, P.Nb, std::max(1, R.nsched));
     for (int b = 0; b < R.nsched; ++b) {
         const int r0 = out[b].r0, r1 = out[b].r1;
         if (r1 <= r0) continue;
         R.sched[4 * b] = r0; R.sched[4 * b + 1] = r1;
         R.sched[4 * b + 2] = P.rrowptr[r0]; R.sched[4 * b + 3] = P.rrowptr[r1];
         if (P.rrowptr[r1] - P.rrowptr[r0] > TILE_CAP_BLOCKS || r1 - r0 > 64) return;   // a single SpMV tile too large for the form: off
-        offsets_of(r0, r1, offs);
-        if (offs.size() > 15) return;
-        for (size_t q = 0; q < offs.size(); ++q) R.table[(size_t)16 * b + q] = offs[q];
-        for (int r = r0; r < r1; ++r) {
-            const int len = P.rrowptr[r + 1] - P.rrowptr[r], ko = P.rrowptr[r] - P.rrowptr[r0];
-            if (len > 8 || ko > 255) return;
-            unsigned w = 0xFFFFFFFFu;
-            for (int u = 0; u < len; ++u) {
-                const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), P.rcol[P.rrowptr[r] + u] - r) - offs.begin());
-                w = (w & ~(0xFu << (4 * u))) | ((unsigned)idx << (4 * u));
-            }
-            R.word[r] = w;
-            R.koff[r] = (unsigned char)ko;
-        }
+        if (!encode_stencil(P.rrowptr, P.rcol, r0, r1, b, R)) return;
     }
     R.on = R.nsched > 0;
 }
@@ -374,12 +398,6 @@ void build_schedules(Pattern& P, int G) {
     TileSet& T = P.tiles;
     const int ncol = P.numColors;
     const int nt = T.ntiles();
-    auto deal = [](const std::vector<std::vector<int>>& lists, int pad, std::vector<int>& out) {
-        size_t L = 0;
-        for (const auto& l : lists) L = std::max(L, l.size());
-        for (size_t j = 0; j < L; ++j)
-            for (int k = 0; k < 8; ++k) out.push_back(j < lists[k].size() ? lists[k][j] : pad);
-    };
     T.ctSched.clear();
     T.ctSchedOff.assign(ncol + 1, 0);
     std::vector<int> order;  // SpMV: tiles in launch order (-1 = padding)
@@ -419,8 +437,8 @@ void build_schedules(Pattern& P, int G) {
             T.ctSchedOff[c + 1] = (int)T.ctSched.size();
         }
     }
-    // descriptor records of the chain kernels' launch positions
-    {
+    // descriptor records of the chain kernels' launch positions (ILU0 only: an ILU(n) context is never chained)
+    if (P.fillLevel == 0) {
         int S = 1;
         for (size_t q = 0; q + 1 < T.ctFirst.size(); ++q) S = std::max(S, T.ctFirst[q + 1] - T.ctFirst[q]);
         T.descS1 = S + 1;
@@ -468,72 +486,88 @@ void build_schedules(Pattern& P, int G) {
             T.spmvSched[4 * b] = r0; T.spmvSched[4 * b + 1] = r1;
             T.spmvSched[4 * b + 2] = P.rowptr[r0]; T.spmvSched[4 * b + 3] = P.rowptr[r1];
         }
-    // stencil form of the index streams (internal.hpp: TileSet::stWord ...), judged per part of the schedule: the interior tiles of a
+    // stencil form of the index streams, one table per launch position, judged per part of the schedule: the interior tiles of a
     // decomposed run are as regular as a single domain's, its boundary tiles (ghost columns at arbitrary offsets) usually are not
     T.stencilPart[0] = T.stencilPart[1] = true;
-    T.stWord.assign(P.Nb, 0xFFFFFFFFu);
-    T.stKoff.assign(P.Nb, 0);
-    T.stTable.assign((size_t)16 * T.nsched, 0);
+    reset_stencil(T.st, P.Nb, T.nsched);
     for (int b = 0; b < T.nsched; ++b) {
         if (order[b] < 0) continue;
-        const int part = b < T.nschedInt ? 0 : 1;
-        if (!T.stencilPart[part]) continue;
-        const int r0 = T.row0[order[b]], r1 = T.row0[order[b] + 1];
-        std::vector<int> offs;
-        for (int r = r0; r < r1; ++r)
-            for (int k = P.rowptr[r]; k < P.rowptr[r + 1]; ++k) offs.push_back(P.col[k] - r);
-        std::sort(offs.begin(), offs.end());
-        offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-        if (offs.size() > 15) { T.stencilPart[part] = false; continue; }
-        for (size_t q = 0; q < offs.size(); ++q) T.stTable[(size_t)16 * b + q] = offs[q];
-        for (int r = r0; r < r1; ++r) {
-            const int len = P.rowptr[r + 1] - P.rowptr[r], ko = P.rowptr[r] - P.rowptr[r0];
-            if (len > 8 || ko > 255) { T.stencilPart[part] = false; break; }
-            unsigned w = 0xFFFFFFFFu;
-            for (int u = 0; u < len; ++u) {
-                const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), P.col[P.rowptr[r] + u] - r) - offs.begin());
-                w = (w & ~(0xFu << (4 * u))) | ((unsigned)idx << (4 * u));
-            }
-            T.stWord[r] = w;
-            T.stKoff[r] = (unsigned char)ko;
-        }
+        bool& on = T.stencilPart[b < T.nschedInt ? 0 : 1];
+        if (on) on = encode_stencil(P.rowptr, P.col, T.row0[order[b]], T.row0[order[b] + 1], b, T.st);
     }
     T.stencil = T.stencilPart[0] || T.stencilPart[1];
     build_rest_schedule(P, order);
-    // the same for the two factor parts the sweeps stream (chained orderings only: their kernels are the ones that read it)
+    // the same for the two factor parts the sweeps stream, one table per tile (chained orderings only: their kernels are the ones that read it)
     P.sweepStencil = P.chained;
     for (int part = 0; part < 2 && P.sweepStencil; ++part) {
-        const std::vector<int>& prow = part == 0 ? P.lrowptr : P.urowptr;
-        const std::vector<int>& pcol = part == 0 ? P.lcol : P.ucol;
-        P.swWord[part].assign(P.Nb, 0xFFFFFFFFu);
-        P.swKoff[part].assign(P.Nb, 0);
-        P.swTable[part].assign((size_t)16 * nt, 0);
-        for (int t = 0; t < nt && P.sweepStencil; ++t) {
-            const int r0 = T.row0[t], r1 = T.row0[t + 1];
-            std::vector<int> offs;
-            for (int r = r0; r < r1; ++r)
-                for (int k = prow[r]; k < prow[r + 1]; ++k) offs.push_back(pcol[k] - r);
-            std::sort(offs.begin(), offs.end());
-            offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-            if (offs.size() > 15) { P.sweepStencil = false; break; }
-            for (size_t q = 0; q < offs.size(); ++q) P.swTable[part][(size_t)16 * t + q] = offs[q];
-            for (int r = r0; r < r1; ++r) {
-                const int len = prow[r + 1] - prow[r], ko = prow[r] - prow[r0];
-                if (len > 8 || ko > 255) { P.sweepStencil = false; break; }
-                unsigned w = 0xFFFFFFFFu;
-                for (int u = 0; u < len; ++u) {
-                    const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), pcol[prow[r] + u] - r) - offs.begin());
-                    w = (w & ~(0xFu << (4 * u))) | ((unsigned)idx << (4 * u));
-                }
-                P.swWord[part][r] = w;
-                P.swKoff[part][r] = (unsigned char)ko;
+        reset_stencil(P.sw[part], P.Nb, nt);
+        for (int t = 0; t < nt && P.sweepStencil; ++t)
+            P.sweepStencil = encode_stencil(part == 0 ? P.lrowptr : P.urowptr, part == 0 ? P.lcol : P.ucol, T.row0[t], T.row0[t + 1], t, P.sw[part]);
+    }
+}
+
+// ILU0: L / U split of the internal pattern (what Dune's convertToCRS produces, linalg/ParallelOverlappingILU0.hpp:497-584; here both
+// parts keep ascending columns and the sweeps choose their own direction), the elimination steps' targets (lmatch) and whether U is
+// upper(A) (ualias)
+void build_ilu0_split(Pattern& P) {
+    const int Nb = P.Nb;
+    P.lrowptr.assign(Nb + 1, 0);
+    P.urowptr.assign(Nb + 1, 0);
+    P.lcol.clear();
+    P.ucol.clear();
+    P.fdest.assign(P.nnzb, -1);
+    for (int p = 0; p < Nb; ++p) {
+        for (int k = P.rowptr[p]; k < P.rowptr[p + 1]; ++k) {
+            if (P.col[k] < p) { P.fdest[k] = (int)P.lcol.size(); P.lcol.push_back(P.col[k]); }
+            else if (P.col[k] > p && P.col[k] < Nb) { P.fdest[k] = -2 - (int)P.ucol.size(); P.ucol.push_back(P.col[k]); }  // ghost columns are not part of the ILU
+        }
+        P.lrowptr[p + 1] = (int)P.lcol.size();
+        P.urowptr[p + 1] = (int)P.ucol.size();
+    }
+    P.nl = (int)P.lcol.size();
+    P.nu = (int)P.ucol.size();
+    // symbolic elimination: which entries of row p the step against row j updates (k_ilu_factor looks them up instead of merging two
+    // column lists per L entry - three dependent rounds of loads became one)
+    P.lmatch.assign(P.nnzb, -2);
+    static const bool general = [] { const char* e = tuning_env("OPMHIP_FACTOR_GENERAL"); return e && e[0] == '1'; }();   // A/B switch: every step by the general search
+    for (int p = 0; p < Nb && !general; ++p) {
+        const int kb = P.rowptr[p], ke = P.rowptr[p + 1];
+        for (int k = kb; k < ke; ++k) {
+            const int j = P.col[k];
+            if (j >= p) break;
+            int count = 0, uidx = -1, target = -1;
+            int ik = k + 1, jk = P.urowptr[j];
+            const int jend = P.urowptr[j + 1];
+            while (ik < ke && jk < jend) {
+                if (P.col[ik] == P.ucol[jk]) { if (count++ == 0) { uidx = jk; target = ik - kb; } ++ik; ++jk; }
+                else if (P.col[ik] < P.ucol[jk]) ++ik;
+                else ++jk;
+            }
+            if (count == 0) P.lmatch[k] = -1;
+            else if (count == 1 && target < 64 && uidx < (1 << 25)) P.lmatch[k] = uidx * 64 + target;
+        }
+    }
+    // U == upper(A)?  (Pattern::ualias)  Every match of an elimination step must lie on or left of the diagonal of the row being eliminated.
+    P.ualias = true;
+    for (int p = 0; p < Nb && P.ualias; ++p) {
+        const int kb = P.rowptr[p], ke = P.rowptr[p + 1];
+        for (int k = kb; k < ke && P.ualias; ++k) {
+            const int j = P.col[k];
+            if (j >= p) break;
+            int ik = k + 1, jk = P.urowptr[j];
+            const int jend = P.urowptr[j + 1];
+            while (ik < ke && jk < jend) {
+                if (P.col[ik] == P.ucol[jk]) { if (P.col[ik] > p) { P.ualias = false; break; } ++ik; ++jk; }
+                else if (P.col[ik] < P.ucol[jk]) ++ik;
+                else ++jk;
             }
         }
     }
 }
 
 // ILU(n): the filled pattern (rows and columns in the fill's elimination order, ibase: that order -> natural row) renamed into the
-// internal order, split into L and U, every matrix entry's place in it, and the sweeps' tiles over the filled rows
+// internal order and split into L and U, every matrix entry's place in it, and the sweeps' tiles over the filled rows.  U is not upper(A)
+// (fill right of the diagonal): the product after M^-1 streams the whole matrix.
 int build_fill_split(opmhip_ctx* c, const std::vector<int>& frp, const std::vector<int>& fcl, const std::vector<int>& ibase) {
     Pattern& P = c->pat;
     const int Nb = P.Nb;
@@ -541,10 +575,10 @@ int build_fill_split(opmhip_ctx* c, const std::vector<int>& frp, const std::vect
     for (int b = 0; b < Nb; ++b) bpos[ibase[b]] = b;
     for (int cc = 0; cc < P.numColors; ++cc)
         for (int p = P.colorPrefix[cc]; p < P.colorPrefix[cc + 1]; ++p) colorOf[p] = cc;
-    P.flrowptr.assign(Nb + 1, 0);
-    P.furowptr.assign(Nb + 1, 0);
-    P.flcol.clear();
-    P.fucol.clear();
+    P.lrowptr.assign(Nb + 1, 0);
+    P.urowptr.assign(Nb + 1, 0);
+    P.lcol.clear();
+    P.ucol.clear();
     std::vector<int> row;
     for (int p = 0; p < Nb; ++p) {
         const int b = bpos[P.fromOrder[p]];
@@ -554,27 +588,28 @@ int build_fill_split(opmhip_ctx* c, const std::vector<int>& frp, const std::vect
         for (int j : row) {
             if (j != p && colorOf[j] == colorOf[p])
                 return fail(c, OPMHIP_ANALYSIS_FAILED, "ILU(%d): the ordering is not a schedule of the filled pattern at row %d", P.fillLevel, p);
-            if (j < p) P.flcol.push_back(j);
-            else if (j > p) P.fucol.push_back(j);
+            if (j < p) P.lcol.push_back(j);
+            else if (j > p) P.ucol.push_back(j);
         }
-        P.flrowptr[p + 1] = (int)P.flcol.size();
-        P.furowptr[p + 1] = (int)P.fucol.size();
+        P.lrowptr[p + 1] = (int)P.lcol.size();
+        P.urowptr[p + 1] = (int)P.ucol.size();
     }
-    P.fnl = (int)P.flcol.size();
-    P.fnu = (int)P.fucol.size();
-    P.fillDest.assign(P.nnzb, -1);
+    P.nl = (int)P.lcol.size();
+    P.nu = (int)P.ucol.size();
+    P.fdest.assign(P.nnzb, -1);
     for (int p = 0; p < Nb; ++p)
         for (int k = P.rowptr[p]; k < P.rowptr[p + 1]; ++k) {
             const int j = P.col[k];
             if (j == p || j >= Nb) continue;   // diagonal; ghost columns are not part of the ILU
-            const int* b0 = j < p ? &P.flcol[P.flrowptr[p]] : &P.fucol[P.furowptr[p]];
-            const int* b1 = j < p ? &P.flcol[0] + P.flrowptr[p + 1] : &P.fucol[0] + P.furowptr[p + 1];
+            const int* b0 = j < p ? &P.lcol[P.lrowptr[p]] : &P.ucol[P.urowptr[p]];
+            const int* b1 = j < p ? &P.lcol[0] + P.lrowptr[p + 1] : &P.ucol[0] + P.urowptr[p + 1];
             const int* f = std::lower_bound(b0, b1, j);
             if (f == b1 || *f != j) return fail(c, OPMHIP_ANALYSIS_FAILED, "ILU(%d): entry (%d, %d) of the matrix is missing from the filled pattern", P.fillLevel, p, j);
-            P.fillDest[k] = j < p ? (int)(f - &P.flcol[0]) : -2 - (int)(f - &P.fucol[0]);
+            P.fdest[k] = j < p ? (int)(f - &P.lcol[0]) : -2 - (int)(f - &P.ucol[0]);
         }
+    P.ualias = false;
     std::vector<int> trp(Nb + 1, 0);   // the tiles bound a row's L and U blocks together: both sweeps read the same tiles
-    for (int p = 0; p <= Nb; ++p) trp[p] = P.flrowptr[p] + P.furowptr[p];
+    for (int p = 0; p <= Nb; ++p) trp[p] = P.lrowptr[p] + P.urowptr[p];
     build_tiles(trp, P.colorPrefix, {}, P.ftiles);
     return OPMHIP_SUCCESS;
 }
@@ -811,65 +846,8 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
                     !(chained && CH.chainOf[P.fromOrder[P.col[k]]] == CH.chainOf[P.fromOrder[p]]))
                         return fail(c, OPMHIP_ANALYSIS_FAILED, "ordering is not a valid schedule at row %d", p);
     }
-    // L / U split (what Dune's convertToCRS produces, linalg/ParallelOverlappingILU0.hpp:497-584; here both
-    // parts keep ascending columns and the sweeps choose their own direction)
-    P.lrowptr.assign(Nb + 1, 0);
-    P.urowptr.assign(Nb + 1, 0);
-    P.lcol.clear();
-    P.ucol.clear();
-    P.fdest.assign(P.nnzb, -1);
-    for (int p = 0; p < Nb; ++p) {
-        for (int k = P.rowptr[p]; k < P.rowptr[p + 1]; ++k) {
-            if (P.col[k] < p) { P.fdest[k] = (int)P.lcol.size(); P.lcol.push_back(P.col[k]); }
-            else if (P.col[k] > p && P.col[k] < Nb) { P.fdest[k] = -2 - (int)P.ucol.size(); P.ucol.push_back(P.col[k]); }  // ghost columns are not part of the ILU
-        }
-        P.lrowptr[p + 1] = (int)P.lcol.size();
-        P.urowptr[p + 1] = (int)P.ucol.size();
-    }
-    P.nl = (int)P.lcol.size();
-    P.nu = (int)P.ucol.size();
-    // symbolic elimination: which entries of row p the step against row j updates (k_ilu_factor looks them up instead of merging two
-    // column lists per L entry - three dependent rounds of loads became one)
-    P.lmatch.assign(P.nnzb, -2);
-    static const bool general = [] { const char* e = tuning_env("OPMHIP_FACTOR_GENERAL"); return e && e[0] == '1'; }();   // A/B switch: every step by the general search
-    for (int p = 0; p < Nb && !general; ++p) {
-        const int kb = P.rowptr[p], ke = P.rowptr[p + 1];
-        for (int k = kb; k < ke; ++k) {
-            const int j = P.col[k];
-            if (j >= p) break;
-            int count = 0, uidx = -1, target = -1;
-            int ik = k + 1, jk = P.urowptr[j];
-            const int jend = P.urowptr[j + 1];
-            while (ik < ke && jk < jend) {
-                if (P.col[ik] == P.ucol[jk]) { if (count++ == 0) { uidx = jk; target = ik - kb; } ++ik; ++jk; }
-                else if (P.col[ik] < P.ucol[jk]) ++ik;
-                else ++jk;
-            }
-            if (count == 0) P.lmatch[k] = -1;
-            else if (count == 1 && target < 64 && uidx < (1 << 25)) P.lmatch[k] = uidx * 64 + target;
-        }
-    }
-    // U == upper(A)?  (Pattern::ualias)  Every match of an elimination step must lie on or left of the diagonal of the row being eliminated.
-    P.ualias = true;
-    for (int p = 0; p < Nb && P.ualias; ++p) {
-        const int kb = P.rowptr[p], ke = P.rowptr[p + 1];
-        for (int k = kb; k < ke && P.ualias; ++k) {
-            const int j = P.col[k];
-            if (j >= p) break;
-            int ik = k + 1, jk = P.urowptr[j];
-            const int jend = P.urowptr[j + 1];
-            while (ik < ke && jk < jend) {
-                if (P.col[ik] == P.ucol[jk]) { if (P.col[ik] > p) { P.ualias = false; break; } ++ik; ++jk; }
-                else if (P.col[ik] < P.ucol[jk]) ++ik;
-                else ++jk;
-            }
-        }
-    }
-    if (fillN > 0) {   // ILU(n): U is not upper(A) (fill right of the diagonal), the product after M^-1 streams the whole matrix
-        P.ualias = false;
-        int rc = build_fill_split(c, frp, fcl, ibase);
-        if (rc) return rc;
-    }
+    if (fillN == 0) build_ilu0_split(P);
+    else if (int rc = build_fill_split(c, frp, fcl, ibase)) return rc;
     // the rest of the matrix beside the U part, as a block-CSR of its own (ascending columns: the order of the full row without its U entries)
     P.rrowptr.assign(Nb + 1, 0);
     P.rcol.clear();
@@ -940,18 +918,11 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
     }
     int rc;
     if ((rc = dev_upload(c, &P.tiles.d_spmvSched, P.tiles.spmvSched))) return rc;
-    for (int part = 0; part < 2 && P.sweepStencil; ++part) {
-        if ((rc = dev_upload(c, &P.d_swWord[part], P.swWord[part]))) return rc;
-        if ((rc = dev_upload(c, &P.d_swKoff[part], P.swKoff[part]))) return rc;
-        if ((rc = dev_upload(c, &P.d_swTable[part], P.swTable[part]))) return rc;
-    }
-    if (P.tiles.stencil) {
-        if ((rc = dev_upload(c, &P.tiles.d_stWord, P.tiles.stWord))) return rc;
-        if ((rc = dev_upload(c, &P.tiles.d_stKoff, P.tiles.stKoff))) return rc;
-        if ((rc = dev_upload(c, &P.tiles.d_stTable, P.tiles.stTable))) return rc;
-    }
+    for (int part = 0; part < 2 && P.sweepStencil; ++part)
+        if ((rc = upload_stencil(c, P.sw[part]))) return rc;
+    if (P.tiles.stencil && (rc = upload_stencil(c, P.tiles.st))) return rc;
     if ((rc = dev_upload(c, &P.tiles.d_ctSched, P.tiles.ctSched))) return rc;
-    if ((rc = dev_upload(c, &P.tiles.d_ctDesc, P.tiles.ctDesc))) return rc;
+    if (fillN == 0 && (rc = dev_upload(c, &P.tiles.d_ctDesc, P.tiles.ctDesc))) return rc;
     if ((rc = dev_upload(c, &P.d_rowptr, P.rowptr))) return rc;
     if ((rc = dev_upload(c, &P.d_col, P.col))) return rc;
     if ((rc = dev_upload(c, &P.d_diag, P.diag))) return rc;
@@ -963,22 +934,13 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
     if ((rc = dev_upload(c, &P.d_urowptr, P.urowptr))) return rc;
     if ((rc = dev_upload(c, &P.d_ucol, P.ucol))) return rc;
     if ((rc = dev_upload(c, &P.d_fdest, P.fdest))) return rc;
-    if ((rc = dev_upload(c, &P.d_lmatch, P.lmatch))) return rc;
+    if (fillN == 0 && (rc = dev_upload(c, &P.d_lmatch, P.lmatch))) return rc;
+    if (fillN > 0 && (rc = dev_upload(c, &P.ftiles.d_row0, P.ftiles.row0))) return rc;
     if (P.rest.on) {
         if ((rc = dev_upload(c, &P.d_rdest, P.rdest))) return rc;
         if ((rc = dev_upload(c, &P.d_rrowptr, P.rrowptr))) return rc;
         if ((rc = dev_upload(c, &P.rest.d_sched, P.rest.sched))) return rc;
-        if ((rc = dev_upload(c, &P.rest.d_word, P.rest.word))) return rc;
-        if ((rc = dev_upload(c, &P.rest.d_koff, P.rest.koff))) return rc;
-        if ((rc = dev_upload(c, &P.rest.d_table, P.rest.table))) return rc;
-    }
-    if (fillN > 0) {
-        if ((rc = dev_upload(c, &P.d_flrowptr, P.flrowptr))) return rc;
-        if ((rc = dev_upload(c, &P.d_flcol, P.flcol))) return rc;
-        if ((rc = dev_upload(c, &P.d_furowptr, P.furowptr))) return rc;
-        if ((rc = dev_upload(c, &P.d_fucol, P.fucol))) return rc;
-        if ((rc = dev_upload(c, &P.d_fillDest, P.fillDest))) return rc;
-        if ((rc = dev_upload(c, &P.d_frow0, P.ftiles.row0))) return rc;
+        if ((rc = upload_stencil(c, P.rest))) return rc;
     }
     if ((rc = dev_upload(c, &P.tiles.d_row0, P.tiles.row0))) return rc;
     if ((rc = dev_upload(c, &P.tiles.d_ctFirst, P.tiles.ctFirst))) return rc;

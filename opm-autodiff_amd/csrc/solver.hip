@@ -594,12 +594,12 @@ __global__ __launch_bounds__(64) void k_spmv_pipe(int npos, const int4* __restri
     }
 }
 
-// The pipelined SpMV on the STENCIL form of its index streams (TileSet::stWord / stKoff / stTable): stage W (two tiles ahead)
+// The pipelined SpMV on the STENCIL form of its index streams (TileSet::st, a StencilForm): stage W (two tiles ahead)
 // fetches a row's word of eight 4-bit table indices, its first-entry byte and - lanes 0..15 - the tile's offset table; stage
 // M (one ahead) turns them into column indices (table entries travel lane to lane, no LDS, no memory) and gathers.  No row
 // bounds, no column indices: 5 bytes per row instead of 44, and the gathers wait for ONE round of loads instead of two.
 // Same tiles, same per-row arithmetic in the same order as k_spmv_pipe: the same bits.
-// UADD (the "rest product", Pattern::ualias): val / sched / stWord ... describe the matrix WITHOUT its U part and the row's sum ends with
+// UADD (the "rest product", Pattern::ualias): val / sched / stWord ... (Pattern::rest) describe the matrix WITHOUT its U part and the row's sum ends with
 // + xs * uadd_i, uadd = the row sums sum_{j>i} U_ij x_j the backward sweep of the ILU0 application left behind (U == upper(A) bit for bit):
 // y_i = (sum over the lower entries, the diagonal and the ghost columns, ascending, of A_ik (xs x_k)) + xs u_i.
 template <int NDOT, bool UADD = false>
@@ -840,7 +840,7 @@ __device__ __forceinline__ int load_desc(const int* __restrict__ desc, int dstri
     wave_sync();
     return sdesc[0];
 }
-// the stencil form of one factor part's index streams (Pattern::swL / swU, reorder.cpp: build_sweep_stencils): per tile a table of <= 15
+// the stencil form of one factor part's index streams (Pattern::sw[0] / sw[1], reorder.cpp: build_schedules): per tile a table of <= 15
 // column offsets (col - row), per row a word of eight 4-bit table indices in ascending column order (15 = no entry) and a byte (first
 // entry - the tile's first entry) - as for the SpMV (k_spmv_pipe_st)
 struct SweepStencil {
@@ -1541,10 +1541,11 @@ __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched
 }
 
 // ============================== ILU(n), n >= 1 ===========================================================
-// The factors' pattern is the matrix's plus the fill (Pattern::flrowptr / furowptr): rows hold 12 - 15 blocks on a 7-point grid with
-// n = 1, more near wells, so the factorisation works in global memory, one thread per row, one launch per level of the filled pattern.
+// The factors' pattern is the matrix's plus the fill (Pattern::lrowptr / urowptr of an ILU(n) context): rows hold 12 - 15 blocks on a
+// 7-point grid with n = 1, more near wells, so the factorisation works in global memory, one thread per row, one launch per level of the
+// filled pattern.
 // Step 1: the working rows - L and U of every row zeroed, the diagonal block (in invD until it is inverted) and the matrix's entries
-// scattered in through Pattern::fillDest; zfix: the zero-diagonal fix (k_zero_diag_fix's statement) in the matrix and the working row.
+// scattered in through Pattern::fdest; zfix: the zero-diagonal fix (k_zero_diag_fix's statement) in the matrix and the working row.
 __global__ __launch_bounds__(256) void k_ilun_scatter(int Nb, const int* __restrict__ rowptr, const int* __restrict__ col, double* A,
                                                       const int* __restrict__ fdest, const int* __restrict__ flrowptr,
                                                       const int* __restrict__ furowptr, double* __restrict__ L, double* __restrict__ U,
@@ -2313,15 +2314,16 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
         static const bool explicitIdx = [] { const char* e = tuning_env("OPMHIP_SPMV_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch: the explicit index streams
         const bool inInt = p0 < P.tiles.nschedInt, inBnd = p0 + np > P.tiles.nschedInt;   // which parts of the schedule this launch covers
         if ((!inInt || P.tiles.stencilPart[0]) && (!inBnd || P.tiles.stencilPart[1]) && !explicitIdx) {
-            const int* tab = P.tiles.d_stTable + (size_t)p0 * 16;
+            const StencilForm& S = P.tiles.st;
+            const int* tab = S.d_table + (size_t)p0 * 16;
             if (ndot == 0)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<0, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.tiles.d_stWord, P.tiles.d_stKoff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
+                hipExtLaunchKernelGGL((k_spmv_pipe_st<0, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
             else if (ndot == 1)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<1, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.tiles.d_stWord, P.tiles.d_stKoff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
+                hipExtLaunchKernelGGL((k_spmv_pipe_st<1, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
             else if (ndot == 2)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<2, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.tiles.d_stWord, P.tiles.d_stKoff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
+                hipExtLaunchKernelGGL((k_spmv_pipe_st<2, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
             else
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<3, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.tiles.d_stWord, P.tiles.d_stKoff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, w1);
+                hipExtLaunchKernelGGL((k_spmv_pipe_st<3, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, w1);
             return ndot > 0 ? grid : 0;
         }
         if (ndot == 0)
@@ -2423,13 +2425,13 @@ void launch_ilu_factor(opmhip_ctx* c, bool fix_zero_diagonal, const FactorRider*
     const Pattern& P = c->pat;
     const int ps = prof_begin(c, PROF_ILU_FACTOR);
     if (P.fillLevel > 0) {   // ILU(n): no rider (a CPR context factors ILU0)
-        hipLaunchKernelGGL(k_ilun_scatter, dim3((P.Nb + 255) / 256), dim3(256), 0, c->stream, P.Nb, P.d_rowptr, P.d_col, c->d_A, P.d_fillDest,
-                           P.d_flrowptr, P.d_furowptr, c->d_fL, c->d_fU, c->d_invD, fix_zero_diagonal ? 1 : 0);
+        hipLaunchKernelGGL(k_ilun_scatter, dim3((P.Nb + 255) / 256), dim3(256), 0, c->stream, P.Nb, P.d_rowptr, P.d_col, c->d_A, P.d_fdest,
+                           P.d_lrowptr, P.d_urowptr, c->d_L, c->d_U, c->d_invD, fix_zero_diagonal ? 1 : 0);
         for (int col = 0; col < P.numColors; ++col) {
             const int r0 = P.colorPrefix[col], n = P.colorPrefix[col + 1] - r0;
             if (n > 0)
-                hipLaunchKernelGGL(k_ilun_factor, dim3((n + 63) / 64), dim3(64), 0, c->stream, r0, r0 + n, P.d_flrowptr, P.d_flcol, P.d_furowptr,
-                                   P.d_fucol, c->d_fL, c->d_fU, c->d_invD);
+                hipLaunchKernelGGL(k_ilun_factor, dim3((n + 63) / 64), dim3(64), 0, c->stream, r0, r0 + n, P.d_lrowptr, P.d_lcol, P.d_urowptr,
+                                   P.d_ucol, c->d_L, c->d_U, c->d_invD);
         }
         prof_end(c, ps);
         return;
@@ -2473,7 +2475,7 @@ void launch_ilu_apply(opmhip_ctx* c, const double* d, double* v, double w_overri
         auto npos = [&](int col) { return P.tiles.ctSchedOff[col + 1] - P.tiles.ctSchedOff[col]; };
         static const bool explicitIdx = [] { const char* e = tuning_env("OPMHIP_SWEEP_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch
         const bool st = P.sweepStencil && !explicitIdx;   // column indices and row bounds of the heavy sweeps from the stencil form
-        const SweepStencil SL{P.d_swWord[0], P.d_swKoff[0], P.d_swTable[0]}, SU{P.d_swWord[1], P.d_swKoff[1], P.d_swTable[1]};
+        const SweepStencil SL{P.sw[0].d_word, P.sw[0].d_koff, P.sw[0].d_table}, SU{P.sw[1].d_word, P.sw[1].d_koff, P.sw[1].d_table};
         for (int col = 0; col < C - 1; ++col) {
             const int nct = npos(col);
             if (nct <= 0) continue;
@@ -2529,31 +2531,26 @@ void launch_ilu_apply(opmhip_ctx* c, const double* d, double* v, double w_overri
         prof_end(c, ps);
         return;
     }
-    // ILU(n), n >= 1: the same sweeps over the filled factors, by the levels of the filled pattern (its colours), on tiles cut for its rows.
-    // The tile kernels hold a row in LDS only where the tile fits (TileCtx::staged) and read it from memory otherwise, so rows of any
-    // length are safe.
-    const bool fill = P.fillLevel > 0;
-    const std::vector<int>& ctile = fill ? P.ftiles.colorTile : P.tiles.colorTile;
-    const int* row0 = fill ? P.d_frow0 : P.tiles.d_row0;
-    const int *lrp = fill ? P.d_flrowptr : P.d_lrowptr, *lcl = fill ? P.d_flcol : P.d_lcol;
-    const int *urp = fill ? P.d_furowptr : P.d_urowptr, *ucl = fill ? P.d_fucol : P.d_ucol;
-    const double *Lv = fill ? c->d_fL : c->d_L, *Uv = fill ? c->d_fU : c->d_U;
+    // ILU(n), n >= 1: the same sweeps over the filled factors, by the levels of the filled pattern (its colours), on the tiles cut for its
+    // rows (Pattern::ftiles).  The tile kernels hold a row in LDS only where the tile fits (TileCtx::staged) and read it from memory
+    // otherwise, so rows of any length are safe.
+    const TileSet& T = P.fillLevel > 0 ? P.ftiles : P.tiles;
     for (int col = 1; col < C; ++col) {
-        const int tb = ctile[col], nt = ctile[col + 1] - tb;
+        const int tb = T.colorTile[col], nt = T.colorTile[col + 1] - tb;
         if (nt <= 0) continue;
         if (col < C - 1)
-            hipLaunchKernelGGL(k_ilu_sweep<SW_L>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, row0, lrp, lcl, Lv,
+            hipLaunchKernelGGL(k_ilu_sweep<SW_L>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, T.d_row0, P.d_lrowptr, P.d_lcol, c->d_L,
                                c->d_invD, d, vu, v, addp, mode, w, c->d_done);
         else
-            hipLaunchKernelGGL(k_ilu_sweep<SW_LF>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, row0, lrp, lcl, Lv,
+            hipLaunchKernelGGL(k_ilu_sweep<SW_LF>, grid(nt), dim3(64), 0, c->stream, tb, nt, n0, 0, T.d_row0, P.d_lrowptr, P.d_lcol, c->d_L,
                                c->d_invD, d, vu, v, addp, mode, w, c->d_done);
     }
     for (int col = (C > 1 ? C - 2 : 0); col >= 0; --col) {
-        const int tb = ctile[col], nt = ctile[col + 1] - tb;
+        const int tb = T.colorTile[col], nt = T.colorTile[col + 1] - tb;
         if (nt <= 0) continue;
         // gathers only reach later colours (>= n0 rows in), so the d/vu split of the gather is inert here (n0 = 0)
-        hipLaunchKernelGGL(k_ilu_sweep<SW_UF>, grid(nt), dim3(64), 0, c->stream, tb, nt, 0, col == 0 ? 1 : 0, row0, urp, ucl,
-                           Uv, c->d_invD, d, vu, v, addp, mode, w, c->d_done);
+        hipLaunchKernelGGL(k_ilu_sweep<SW_UF>, grid(nt), dim3(64), 0, c->stream, tb, nt, 0, col == 0 ? 1 : 0, T.d_row0, P.d_urowptr, P.d_ucol,
+                           c->d_U, c->d_invD, d, vu, v, addp, mode, w, c->d_done);
     }
     prof_end(c, ps);
 }

@@ -6,7 +6,7 @@
 // permutations are inverse to each other, the reordered pattern is the natural one renamed, rows of one colour do not meet unless they
 // belong to one chain (the property tests/test_graphcoloring.cpp:44-110 checks of the reference's colouring), the tiles cut [0, Nb) into
 // pieces no longer than a wavefront can take, every launch schedule visits every tile once, every entry of the matrix has one place in
-// L, U or on the diagonal.
+// L, U or on the diagonal, every stencil form in force (SpMV, rest product, both sweep parts) decodes back to the columns it stands for.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -132,6 +132,19 @@ static void release(opmhip_ctx& c) {
     c.allocs.clear();
 }
 
+// rows [r0, r1) of a block-CSR decoded back from their stencil form (table `slot`): each row's first entry, its columns in order, no more
+static bool decodes(const opmhip::StencilForm& S, int slot, const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1) {
+    for (int r = r0; r < r1; ++r) {
+        const int len = rowptr[r + 1] - rowptr[r];
+        if (len > 8 || (int)S.koff[r] != rowptr[r] - rowptr[r0]) return false;
+        for (int u = 0; u < 8; ++u) {
+            const unsigned idx = (S.word[r] >> (4 * u)) & 0xFu;
+            if (u >= len ? idx != 15u : (idx >= 15u || r + S.table[(size_t)16 * slot + idx] != col[rowptr[r] + u])) return false;
+        }
+    }
+    return true;
+}
+
 static void check_pattern(const char* name, const Graph& g, int kind, int chain) {
     using namespace opmhip;
     opmhip_ctx c;
@@ -221,6 +234,22 @@ static void check_pattern(const char* name, const Graph& g, int kind, int chain)
         }
     }
     CHECK(std::count(rowSeen.begin(), rowSeen.end(), 0) == 0, "%s: rows without a launch position", name);
+    // its stencil form, in every part of the schedule that has it
+    CHECK(T.stencil == (T.stencilPart[0] || T.stencilPart[1]), "%s: stencil flags", name);
+    if (T.stencil) {
+        CHECK((int)T.st.word.size() == Nb && (int)T.st.koff.size() == Nb && (int)T.st.table.size() == 16 * T.nsched, "%s: SpMV stencil sizes", name);
+        for (int p = 0; p < T.nsched; ++p)
+            if (T.stencilPart[p < T.nschedInt ? 0 : 1])
+                CHECK(decodes(T.st, p, P.rowptr, P.col, T.spmvSched[4 * p], T.spmvSched[4 * p + 1]), "%s: SpMV stencil of position %d", name, p);
+    }
+    // the sweeps' stencil form of both factor parts, one table per tile
+    CHECK(!P.sweepStencil || P.chained, "%s: sweep stencil without chains", name);
+    for (int part = 0; part < 2 && P.sweepStencil; ++part) {
+        const StencilForm& S = P.sw[part];
+        CHECK((int)S.word.size() == Nb && (int)S.koff.size() == Nb && (int)S.table.size() == 16 * T.ntiles(), "%s: sweep stencil %d sizes", name, part);
+        for (int t = 0; t < T.ntiles(); ++t)
+            CHECK(decodes(S, t, part == 0 ? P.lrowptr : P.urowptr, part == 0 ? P.lcol : P.ucol, T.row0[t], T.row0[t + 1]), "%s: sweep stencil %d of tile %d", name, part, t);
+    }
     // the chain kernels' schedule: every chain-tile once per colour
     if (!T.ctSchedOff.empty()) {
         CHECK((int)T.ctSchedOff.size() == ncol + 1 && T.ctSchedOff[ncol] == (int)T.ctSched.size(), "%s: chain-tile schedule offsets", name);
@@ -272,16 +301,10 @@ static void check_pattern(const char* name, const Graph& g, int kind, int chain)
             if (r1 <= r0) continue;
             CHECK(r0 >= 0 && r1 <= Nb && r1 - r0 <= 64 && R.sched[4 * p + 2] == P.rrowptr[r0] && R.sched[4 * p + 3] == P.rrowptr[r1] && P.rrowptr[r1] - P.rrowptr[r0] <= TILE_CAP_BLOCKS,
                   "%s: rest position %d", name, p);
+            CHECK(decodes(R, p, P.rrowptr, P.rcol, r0, r1), "%s: rest stencil of position %d", name, p);
             for (int r = r0; r < r1; ++r) {
                 CHECK(!seen[r], "%s: row %d in two rest positions", name, r);
                 seen[r] = 1;
-                const int len = P.rrowptr[r + 1] - P.rrowptr[r];
-                CHECK(len <= 8 && (int)R.koff[r] == P.rrowptr[r] - P.rrowptr[r0], "%s: rest row %d: %d entries, first at %d", name, r, len, (int)R.koff[r]);
-                for (int u = 0; u < 8; ++u) {
-                    const unsigned idx = (R.word[r] >> (4 * u)) & 0xFu;
-                    if (u >= len) { CHECK(idx == 15u, "%s: rest row %d slot %d not empty", name, r, u); continue; }
-                    CHECK(idx < 15u && r + R.table[(size_t)16 * p + idx] == P.rcol[P.rrowptr[r] + u], "%s: rest row %d slot %d column", name, r, u);
-                }
                 if (g.Nghost > 0)
                     for (int k = P.rowptr[r]; k < P.rowptr[r + 1]; ++k) CHECK(P.col[k] < Nb, "%s: rest position %d (interior) reads ghost column %d", name, p, P.col[k]);
             }

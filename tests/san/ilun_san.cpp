@@ -69,10 +69,7 @@ static void run_case(int no, int Nb, int kind, int n, const std::vector<int>& ro
     const Pattern& P = c.pat;
     const bool fill = n > 0;
     CHECK(P.fillLevel == n, "case %d: fill level %d", no, P.fillLevel);
-    const std::vector<int>& lrp = fill ? P.flrowptr : P.lrowptr;
-    const std::vector<int>& lcl = fill ? P.flcol : P.lcol;
-    const std::vector<int>& urp = fill ? P.furowptr : P.urowptr;
-    const std::vector<int>& ucl = fill ? P.fucol : P.ucol;
+    const std::vector<int> &lrp = P.lrowptr, &lcl = P.lcol, &urp = P.urowptr, &ucl = P.ucol;
     std::vector<int> levelOf(Nb);
     for (int l = 0; l < P.numColors; ++l)
         for (int p = P.colorPrefix[l]; p < P.colorPrefix[l + 1]; ++p) levelOf[p] = l;
@@ -90,15 +87,14 @@ static void run_case(int no, int Nb, int kind, int n, const std::vector<int>& ro
         // every matrix entry has its place: the diagonal, or the L / U entry of its column
         for (int k = P.rowptr[p]; k < P.rowptr[p + 1]; ++k) {
             const int j = P.col[k];
-            if (!fill) continue;
-            const int d = P.fillDest[k];
+            const int d = P.fdest[k];
             if (j == p) CHECK(d == -1, "case %d: diagonal has a place %d", no, d);
             else if (j < p) CHECK(d >= lrp[p] && d < lrp[p + 1] && lcl[d] == j, "case %d: entry (%d, %d) -> %d", no, p, j, d);
             else CHECK(d <= -2 && -2 - d >= urp[p] && -2 - d < urp[p + 1] && ucl[-2 - d] == j, "case %d: entry (%d, %d) -> %d", no, p, j, d);
         }
     }
     if (fill) {
-        CHECK((long long)P.fnl + P.fnu + Nb <= (long long)ILUN_BUDGET_FACTOR * (long long)col.size(), "case %d: over the budget", no);
+        CHECK((long long)P.nl + P.nu + Nb <= (long long)ILUN_BUDGET_FACTOR * (long long)col.size(), "case %d: over the budget", no);
         const TileSet& T = P.ftiles;
         CHECK(T.row0.front() == 0 && T.row0.back() == Nb && (int)T.colorTile.size() == P.numColors + 1, "case %d: tiles", no);
         for (int l = 0; l < P.numColors; ++l) CHECK(T.row0[T.colorTile[l]] == P.colorPrefix[l], "case %d: level %d's tiles", no, l);
