@@ -8,7 +8,7 @@
 // 92-160), the fine smoother (ILU0, relaxation 1), one V-cycle as coarse solve, prolongation damping 1.6.
 // NOT the reference's: the AMG itself.  Dune::Amg (not in the reference tree) aggregates with a sequential front algorithm
 // and smooths with ILU0, both level-scheduled sequential sweeps; here the hierarchy is one that needs no schedule per level:
-// aggregates from two passes of pairwise matching per level (host, once per pattern, from the first pressure matrix; the
+// aggregates from two passes of pairwise matching per level (host, cpr_setup.cpp, once per pattern, from the first pressure matrix; the
 // Galerkin VALUES are recomputed on the device for every solve), damped-Jacobi smoothing, dense LU on the coarsest level.
 // The CPU restatement of exactly this algorithm is oracle/cpr.hpp; the device reproduces its preconditioner application bit
 // for bit in the same ordering (same summation orders, -ffp-contract=off).
@@ -31,114 +31,9 @@
 namespace opmhip {
 
 constexpr int CPR_P = 1;             // pressure index inside a block (BlackOilIndices::pressureSwitchIdx)
-constexpr int CPR_COARSE_DIRECT = 128;
-constexpr int CPR_MAX_LEVELS = 15;
-
-// ---------------------------------------------------------------- host: hierarchy (mirrors oracle/cpr.hpp) -------------
-namespace {
-struct HCsr {
-    int n = 0;
-    std::vector<int> rowptr, col;
-    std::vector<double> val;
-};
-// natOf / atNat (level 0 only, else NULL): natural id of every internal index and its inverse - the cells are visited in
-// NATURAL order, ties to the lowest natural id: the aggregates of the natural-order matrix whatever the ILU ordering is
-// (matching colour by colour pairs cells across the grid and stalls after five levels; oracle/cpr.hpp: same statements)
-void pairwise(const HCsr& A, double beta, bool anySign, std::vector<int>& agg, int& na, const int* natOf = nullptr, const int* atNat = nullptr) {
-    const int n = A.n;
-    agg.assign(n, -1);
-    na = 0;
-    for (int v = 0; v < n; ++v) {
-        const int i = atNat ? atNat[v] : v;
-        if (agg[i] >= 0) continue;
-        double mx = 0.0;
-        for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
-            if (A.col[k] != i) mx = std::max(mx, anySign ? std::fabs(A.val[k]) : -A.val[k]);
-        int best = -1;
-        double bv = 0.0;
-        for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) {
-            const int j = A.col[k];
-            if (j == i || agg[j] >= 0) continue;
-            const double s = anySign ? std::fabs(A.val[k]) : -A.val[k];
-            if (s >= beta * mx && (s > bv || (natOf && best >= 0 && s == bv && natOf[j] < natOf[best]))) { best = j; bv = s; }
-        }
-        agg[i] = na;
-        if (best >= 0) agg[best] = na;
-        ++na;
-    }
-}
-// Galerkin product for piecewise-constant prolongation: coarse pattern (columns ascending), gather lists (fine entries of a
-// coarse entry in ascending order), values.  Row by row over the members of each aggregate: the few (coarse column, fine
-// entry) pairs of a coarse row are sorted on the spot - O(nnz log(row)) instead of a stable sort of all nnz keys (round 2: 1.5 s
-// of host time for the hierarchy of a 10^6-cell grid, most of it here); same lists, same sums, same order.
-void galerkin(const HCsr& A, const std::vector<int>& agg, int nc, HCsr& C, std::vector<int>& gptr, std::vector<int>& gidx) {
-    const int nnz = (int)A.col.size();
-    std::vector<int> mp(nc + 1, 0), mi(A.n);
-    for (int i = 0; i < A.n; ++i) mp[agg[i] + 1]++;
-    for (int I = 0; I < nc; ++I) mp[I + 1] += mp[I];
-    {
-        std::vector<int> w(mp.begin(), mp.end() - 1);
-        for (int i = 0; i < A.n; ++i) mi[w[agg[i]]++] = i;   // members ascending
-    }
-    // the coarse rows are independent: slices of them are built by a few host threads, each into vectors of its own, and
-    // joined in order - the same lists and sums whatever the number of threads
-    const int T = std::max(1, std::min({(int)std::thread::hardware_concurrency(), 8, nc / 4096 + 1}));
-    struct Part { std::vector<int> rowlen, col, glen, gidx; std::vector<double> val; };
-    std::vector<Part> parts(T);
-    auto work = [&](int t) {
-        Part& Q = parts[t];
-        const int I0 = (int)((long long)nc * t / T), I1 = (int)((long long)nc * (t + 1) / T);
-        std::vector<std::pair<int, int>> pairs;   // (coarse column, fine entry) of the coarse row in hand
-        Q.rowlen.reserve(I1 - I0);
-        for (int I = I0; I < I1; ++I) {
-            pairs.clear();
-            for (int q = mp[I]; q < mp[I + 1]; ++q) {
-                const int i = mi[q];
-                for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) pairs.emplace_back(agg[A.col[k]], k);
-            }
-            std::sort(pairs.begin(), pairs.end());
-            int len = 0;
-            for (size_t q = 0; q < pairs.size();) {
-                const int cc = pairs[q].first;
-                double sum = 0.0;
-                size_t e = q;
-                while (e < pairs.size() && pairs[e].first == cc) { sum += A.val[pairs[e].second]; Q.gidx.push_back(pairs[e].second); ++e; }
-                Q.col.push_back(cc);
-                Q.val.push_back(sum);
-                Q.glen.push_back((int)(e - q));
-                ++len;
-                q = e;
-            }
-            Q.rowlen.push_back(len);
-        }
-    };
-    if (T == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; ++t) th.emplace_back(work, t);
-        for (auto& x : th) x.join();
-    }
-    C.n = nc;
-    C.rowptr.assign(nc + 1, 0);
-    C.col.clear();
-    C.val.clear();
-    gptr.assign(1, 0);
-    gidx.clear();
-    gidx.reserve(nnz);
-    int I = 0;
-    for (const Part& Q : parts) {
-        for (int len : Q.rowlen) { C.rowptr[I + 1] = C.rowptr[I] + len; ++I; }
-        C.col.insert(C.col.end(), Q.col.begin(), Q.col.end());
-        C.val.insert(C.val.end(), Q.val.begin(), Q.val.end());
-        for (int gl : Q.glen) gptr.push_back(gptr.back() + gl);
-        gidx.insert(gidx.end(), Q.gidx.begin(), Q.gidx.end());
-    }
-}
-}  // namespace
 
 // ---------------------------------------------------------------- kernels -----------------------------------------------
 #define CPR_DONE_CHECK if (*done != 0.0) return;
-constexpr int CPR_MAX_W = 96;   // longest row an ELL level may have
 // closed-form 3x3 inverse, expression tree of Opm::Detail::Inverter<3> (linalg/MatrixBlock.hpp:722-747); same as solver.hip
 __device__ __forceinline__ void inv3(const double* m, double* inv) {
     const double t4 = m[0] * m[4], t6 = m[0] * m[5], t8 = m[1] * m[3];
@@ -472,7 +367,7 @@ __global__ __launch_bounds__(256) void k_cpr_resid(int n, int W, const int* __re
 // (column -> vector entry) round trips - 12 us for 14 000 rows.  Here CPR_LPR lanes share a row (row-major storage): every
 // lane fetches its entries and forms its products at once, then the group subtracts the products one after the other in
 // the row's order - the same roundings as the one-thread loop (padding entries are 0 * x there too).
-constexpr int CPR_LPR = 16, CPR_LPR_SLOTS = CPR_MAX_W / CPR_LPR, CPR_LPR_ROWS = 32768;
+constexpr int CPR_LPR = 16, CPR_LPR_SLOTS = CPR_MAX_W / CPR_LPR;
 static_assert(CPR_COARSE_DIRECT <= 128, "k_cpr_dense_solve: two rows per lane of one wavefront, 128 columns per staging pass");
 static_assert(CPR_MAX_W % CPR_LPR == 0 && 256 % CPR_LPR == 0, "lane groups tile a row and a workgroup");
 __device__ __forceinline__ double cpr_group_subtract(double s, const double (&p)[CPR_LPR_SLOTS], int W) {
@@ -940,199 +835,15 @@ __global__ __launch_bounds__(256) void k_cpr_unpad(int NG, const int* __restrict
 static inline dim3 g256(int n) { return dim3((n + 255) / 256); }
 
 // ---------------------------------------------------------------- setup --------------------------------------------------
-// Host-side description of the hierarchy (cpr_build_coarse_host): everything the device arrays of a level are uploaded from.
-// The set-up is split in two so that its expensive half - matching, Galerkin lists, level images: pure host work on copies -
-// can run on a thread of its own beside the solves (--cpr-reuse-setup=2 with opmhip_config.cpr_async_setup), and only the uploads
-// touch the context.
-// ILU0 smoothing schedule of one level, from its image: which slots of a row are lower / upper entries in the elimination order
-// `pos`, the lower slots in ascending position, and per colour the sequences of rows a thread walks.  colour[i] ascending = the
-// order of the launches; rows of one colour may depend on each other only along a sequence (a chain of level 0's line colouring).
-struct CprIluHost {
-    int ncol = 0, MW = 0, WL = 0, WU = 0;
-    std::vector<int> nseq, nsteps, off, rowAt, wl, wu;   // wl / wu: lower / upper entries per row of a colour at most
-    std::vector<char> fast;
-    std::vector<unsigned> mask;
-    std::vector<unsigned char> lorder;
-    // simple: a level whose elimination steps touch nothing but the diagonal (no triangles in its graph: step (i, j) finds of row j's
-    // upper entries only (j, i) in row i - a seven-point grid in any of the orderings here), whose couplings inside a colour join
-    // neighbours of a sequence and whose rows hold their lower entries in elimination order: U keeps the matrix's own values,
-    // l_ij = a_ij / u_jj, u_ii = a_ii - sum_j l_ij a_ji - a recurrence along the sequences with loads that depend on nothing it computes
-    // (k_cpr_ilu_factor_simple).  tpos: per lower entry (slot order) the place of the transposed entry (j, i) in the level's image
-    bool simple = false;
-    std::vector<int> tpos;
-    std::string error;
-};
-struct CprHostLevel {
-    int n = 0, nnz = 0, nc = 0, W = 0;
-    bool rm = false;
-    std::vector<int> ecol, rlen, diag;                           // ELL image of the level's pattern
-    std::vector<int> agg, mptr, midx, mem4, gptr, gidx, cpos;    // transfer to the next level (empty on the coarsest)
-    CprIluHost ilu;                                              // ncol > 0: the level's ILU0 smoothing schedule
-};
-struct CprHostCoarse {
-    CprHostLevel l0;                 // of level 0 only the transfer part (its image belongs to the pattern: cpr_setup_level0)
-    std::vector<CprHostLevel> lv;    // levels 1 ..
-    double tAgg = 0.0, tGal = 0.0, tImg = 0.0;
-    std::string error;               // non-empty: the build failed
-    HCsr lastA;                      // the last level's matrix and the place of its entries in that level's image
-    std::vector<int> lastPos;
-};
+// The host half of the set-up - matching, Galerkin lists, level images, ILU0 schedules - is cpr_setup.cpp: pure host work on copies,
+// no HIP call.  What follows uploads it.  A structure being built on a host thread beside the solves (--cpr-reuse-setup=2 with
+// opmhip_config.cpr_async_setup):
 struct CprAsyncJob {
     std::thread th;
     std::atomic<int> ready{0};
     CprHostCoarse result;
     ~CprAsyncJob() { if (th.joinable()) th.join(); }
 };
-// ELL image of a level's pattern: columns (padding: the row itself), row lengths, position of the diagonal, position of every
-// CSR entry
-static bool ell_image(const HCsr& A, CprHostLevel& L, std::vector<int>& pos, bool rowMajor, int ncols = INT_MAX) {
-    const int n = A.n;
-    int W = 1;
-    for (int i = 0; i < n; ++i) W = std::max(W, A.rowptr[i + 1] - A.rowptr[i]);
-    L.n = n; L.nnz = (int)A.col.size(); L.W = W; L.rm = rowMajor;
-    if (W > CPR_MAX_W) return false;
-    // entry j of row i: [j * n + i] (one thread per row reads coalesced) or, row-major, [i * W + j] (a group of lanes per row does)
-    auto at = [&](int j, int i) { return rowMajor ? (size_t)i * W + j : (size_t)j * n + i; };
-    L.ecol.assign((size_t)W * n, 0); L.rlen.assign(n, 0); L.diag.assign(n, 0);
-    pos.resize(A.col.size());
-    for (int i = 0; i < n; ++i) {
-        const int kb = A.rowptr[i], len = A.rowptr[i + 1] - kb;
-        L.rlen[i] = len;
-        for (int j = 0; j < W; ++j) L.ecol[at(j, i)] = (j < len && A.col[kb + j] < ncols) ? A.col[kb + j] : i;   // padding and ghost columns (value 0 for good): the row itself
-        for (int j = 0; j < len; ++j) {
-            pos[kb + j] = (int)at(j, i);
-            if (A.col[kb + j] == i) L.diag[i] = (int)at(j, i);
-        }
-    }
-    return true;
-}
-
-static void cpr_ilu_schedule(const CprHostLevel& L, const std::vector<int>& pos, const std::vector<int>& colour, int ncol, CprIluHost& S) {
-    const int n = L.n, W = L.W;
-    auto at = [&](int j, int i) { return L.rm ? (size_t)i * W + j : (size_t)j * n + i; };
-    S.ncol = ncol;
-    S.MW = (W + 31) / 32;
-    S.mask.assign((size_t)2 * S.MW * n, 0u);
-    std::vector<std::vector<std::pair<int, int>>> low(n);   // (position, slot) of every lower entry
-    int WL = 0;
-    for (int i = 0; i < n; ++i) {
-        for (int j = 0; j < L.rlen[i]; ++j) {
-            const int c = L.ecol[at(j, i)];
-            if (c == i) continue;   // the diagonal, or a ghost column's slot (value 0 for good)
-            if (pos[c] < pos[i]) { S.mask[(size_t)(j >> 5) * n + i] |= 1u << (j & 31); low[i].emplace_back(pos[c], j); }
-            else S.mask[(size_t)(S.MW + (j >> 5)) * n + i] |= 1u << (j & 31);
-        }
-        std::sort(low[i].begin(), low[i].end());
-        WL = std::max(WL, (int)low[i].size());
-    }
-    S.WL = std::max(WL, 1);
-    if (W > 254) { S.error = "cpr: ILU0 smoothing of a level with rows of more than 254 entries"; return; }
-    S.lorder.assign((size_t)S.WL * n, 255);
-    for (int i = 0; i < n; ++i)
-        for (size_t q = 0; q < low[i].size(); ++q) S.lorder[q * n + i] = (unsigned char)low[i][q].second;
-    // sequences: rows of a colour in ascending position; a row with a lower entry of its own colour continues that row's sequence
-    std::vector<int> byPos(n);
-    for (int i = 0; i < n; ++i) byPos[pos[i]] = i;
-    std::vector<int> seqOf(n, -1), idxIn(n, 0);
-    std::vector<std::vector<std::vector<int>>> seqs(ncol);
-    for (int p = 0; p < n; ++p) {
-        const int i = byPos[p], cc = colour[i];
-        int sq = -1;
-        for (auto& e : low[i]) {
-            const int j = L.ecol[at(e.second, i)];
-            if (colour[j] != cc) {
-                if (colour[j] > cc) { S.error = "cpr: ILU0 smoothing: the colours are not an elimination order"; return; }
-                continue;
-            }
-            if (sq >= 0 && seqOf[j] != sq) { S.error = "cpr: ILU0 smoothing: a row depends on two sequences of its own colour"; return; }
-            sq = seqOf[j];
-        }
-        if (sq < 0) { sq = (int)seqs[cc].size(); seqs[cc].emplace_back(); }
-        seqOf[i] = sq;
-        idxIn[i] = (int)seqs[cc][sq].size();
-        seqs[cc][sq].push_back(i);
-    }
-    S.wl.assign(ncol, 0); S.wu.assign(ncol, 0);
-    for (int i = 0; i < n; ++i) {
-        int nu = 0;
-        for (int w = 0; w < S.MW; ++w) nu += __builtin_popcount(S.mask[(size_t)(S.MW + w) * n + i]);
-        S.wl[colour[i]] = std::max(S.wl[colour[i]], (int)low[i].size());
-        S.wu[colour[i]] = std::max(S.wu[colour[i]], nu);
-        S.WU = std::max(S.WU, nu);
-    }
-    S.WU = std::max(S.WU, 1);
-    S.nseq.assign(ncol, 0); S.nsteps.assign(ncol, 0); S.off.assign(ncol + 1, 0); S.fast.assign(ncol, 1);
-    for (int cc = 0; cc < ncol; ++cc) {
-        int steps = 0;
-        for (auto& q : seqs[cc]) steps = std::max(steps, (int)q.size());
-        S.nseq[cc] = (int)seqs[cc].size();
-        S.nsteps[cc] = steps;
-        S.off[cc + 1] = S.off[cc] + steps * S.nseq[cc];
-    }
-    S.rowAt.assign(S.off[ncol], -1);
-    for (int cc = 0; cc < ncol; ++cc)
-        for (int t = 0; t < S.nseq[cc]; ++t)
-            for (size_t st = 0; st < seqs[cc][t].size(); ++st) S.rowAt[S.off[cc] + st * S.nseq[cc] + t] = seqs[cc][t][st];
-    // fast: every coupling inside the colour joins neighbours of a sequence (the sweeps may then hand the value on in a register)
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < L.rlen[i]; ++j) {
-            const int c = L.ecol[at(j, i)];
-            if (c == i || colour[c] != colour[i]) continue;
-            if (seqOf[c] != seqOf[i] || std::abs(idxIn[c] - idxIn[i]) != 1) S.fast[colour[i]] = 0;
-        }
-    // simple?
-    bool simple = !L.rm;
-    for (int cc = 0; cc < ncol && simple; ++cc) simple = S.fast[cc] != 0;
-    std::vector<int> tpos(simple ? (size_t)S.WL * n : 0, -1);
-    for (int i = 0; i < n && simple; ++i) {
-        int q = 0, lastPos = -1;
-        for (int j = 0; j < L.rlen[i] && simple; ++j) {
-            if (!((S.mask[(size_t)(j >> 5) * n + i] >> (j & 31)) & 1u)) continue;
-            const int cj = L.ecol[at(j, i)];
-            if (pos[cj] < lastPos) simple = false;   // the row's order is not the elimination order
-            lastPos = pos[cj];
-            // row cj's upper entries that row i holds too: must be (cj, i) alone
-            int found = -1;
-            for (int t = 0; t < L.rlen[cj] && simple; ++t) {
-                if (!((S.mask[(size_t)(S.MW + (t >> 5)) * n + cj] >> (t & 31)) & 1u)) continue;
-                const int ct = L.ecol[at(t, cj)];
-                if (ct == i) { found = (int)at(t, cj); continue; }
-                for (int u = 0; u < L.rlen[i]; ++u)
-                    if (L.ecol[at(u, i)] == ct && (int)at(u, i) != L.diag[i] && ct != i) { simple = false; break; }
-            }
-            if (found < 0) simple = false;   // (an unsymmetric pattern)
-            if (simple) tpos[(size_t)q * n + i] = found;
-            ++q;
-        }
-    }
-    S.simple = simple;
-    if (simple) S.tpos = std::move(tpos);
-}
-// greedy multi-colouring of a level's graph in index order, colour-major elimination positions (oracle/cpr.hpp: ilu_factor, colour = true)
-static int cpr_greedy_colours(const CprHostLevel& L, std::vector<int>& colour, std::vector<int>& pos) {
-    const int n = L.n, W = L.W;
-    auto at = [&](int j, int i) { return L.rm ? (size_t)i * W + j : (size_t)j * n + i; };
-    colour.assign(n, -1);
-    int nc = 0;
-    std::vector<char> used;
-    for (int i = 0; i < n; ++i) {
-        used.assign(nc + 1, 0);
-        for (int j = 0; j < L.rlen[i]; ++j) {
-            const int c = L.ecol[at(j, i)];
-            if (colour[c] >= 0) used[colour[c]] = 1;
-        }
-        int k = 0;
-        while (used[k]) ++k;
-        colour[i] = k;
-        nc = std::max(nc, k + 1);
-    }
-    pos.assign(n, 0);
-    int p = 0;
-    for (int k = 0; k < nc; ++k)
-        for (int i = 0; i < n; ++i)
-            if (colour[i] == k) pos[i] = p++;
-    return nc;
-}
 static int cpr_upload_ilu(opmhip_ctx* c, const CprIluHost& S, CprLevelDev& L) {
     if (!S.error.empty()) return fail(c, OPMHIP_ANALYSIS_FAILED, "%s", S.error.c_str());
     int rc;
@@ -1348,31 +1059,16 @@ static int cpr_setup_level0_body(opmhip_ctx* c) {
     if ((rc = upload_ell(c, H0, R.lv[0], spans ? P.Nloc : P.Nb))) return rc;
     {   // level 0's ELL columns in stencil form (EllStencil), where the pattern has it: single domain, rows of <= 8 entries, <= 15 offsets per group of 32 rows
         static const bool off = [] { const char* e = tuning_env("OPMHIP_CPR_ELL_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch
+        // the shared encoder (reorder.cpp), tile = aligned group of 32 rows: with rows of <= 8 entries a group's first entry lies at most
+        // 31 x 8 = 248 blocks in, so only the offset count refuses one; the first-entry bytes are not uploaded (ELL values go by slot)
         bool ok = !off && P.Nghost == 0 && R.lv[0].W <= 8;
         const int ng = (P.Nb + 31) / 32;
-        std::vector<unsigned> word(ok ? P.Nb : 0, 0xFFFFFFFFu);
-        std::vector<int> table(ok ? (size_t)16 * ng : 0, 0);
-        for (int g = 0; g < ng && ok; ++g) {
-            const int r0 = 32 * g, r1 = std::min(P.Nb, r0 + 32);
-            std::vector<int> offs;
-            for (int r = r0; r < r1; ++r)
-                for (int k = P.rowptr[r]; k < P.rowptr[r + 1]; ++k) offs.push_back(P.col[k] - r);
-            std::sort(offs.begin(), offs.end());
-            offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-            if (offs.size() > 15) { ok = false; break; }
-            for (size_t q = 0; q < offs.size(); ++q) table[(size_t)16 * g + q] = offs[q];
-            for (int r = r0; r < r1; ++r) {
-                unsigned w = 0xFFFFFFFFu;
-                for (int u = 0; u < P.rowptr[r + 1] - P.rowptr[r]; ++u) {
-                    const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), P.col[P.rowptr[r] + u] - r) - offs.begin());
-                    w = (w & ~(0xFu << (4 * u))) | ((unsigned)idx << (4 * u));
-                }
-                word[r] = w;
-            }
-        }
+        StencilForm S;
+        if (ok) reset_stencil(S, P.Nb, ng);
+        for (int g = 0; g < ng && ok; ++g) ok = encode_stencil(P.rowptr, P.col, 32 * g, std::min(P.Nb, 32 * g + 32), g, S);
         if (ok) {
-            if ((rc = dev_upload(c, &R.lv[0].d_sword, word))) return rc;
-            if ((rc = dev_upload(c, &R.lv[0].d_stable, table))) return rc;
+            if ((rc = dev_upload(c, &R.lv[0].d_sword, S.word))) return rc;
+            if ((rc = dev_upload(c, &R.lv[0].d_stable, S.table))) return rc;
         }
     }
     if (cpr_ilu_levels(c) > 0 && !spans) {   // ILU0 smoothing of level 0: in the stored order, the block ILU0's colours are this one's
@@ -1388,112 +1084,6 @@ static int cpr_setup_level0_body(opmhip_ctx* c) {
     OPMHIP_HIP(c, hipMemsetAsync(R.d_pcol, 0, (size_t)3 * R.lv[0].W * P.Nb * sizeof(double), c->stream));   // the padding stays 0
     R.level0 = true;
     return OPMHIP_SUCCESS;
-}
-// The coarsening itself: A = the finest level of the hierarchy being built (CSR with values), pos = the place of every entry of A in
-// that level's image on the device; natOf / atNat: see pairwise (level 0 of a reordered system, else NULL).  stopRows: a level of at
-// most this many rows is the last one (CPR_COARSE_DIRECT: it is solved directly; a rank whose hierarchy is continued across the ranks
-// stops at opmhip_config.cpr_gather_rows).  The last level's matrix stays in out.lastA / lastPos.
-static void cpr_coarsen_host(HCsr A, std::vector<int> pos, const int* natOf, const int* atNat, double beta, int lprRows, int iluLevels, int stopRows, CprHostCoarse& out) {
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-#define CPR_T(acc, stmt) do { const double t_ = now(); stmt; acc += now() - t_; } while (0)
-    out.lv.clear();
-    CprHostLevel* cur = &out.l0;   // the level being coarsened (its transfer part is filled here)
-    cur->n = A.n;
-    int nlev = 1;
-    while (true) {
-        const bool last = A.n <= stopRows || nlev >= CPR_MAX_LEVELS;
-        if (last) break;
-        std::vector<int> a1, a2, g1p, g1i;
-        int n1 = 0, n2 = 0;
-        HCsr A1;
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            const double b = attempt == 0 ? beta : 0.0;
-            const bool lvl0 = nlev == 1;   // the finest level is stored in the ILU ordering: visit it in natural order
-            CPR_T(out.tAgg, pairwise(A, b, attempt == 2, a1, n1, lvl0 ? natOf : nullptr, lvl0 ? atNat : nullptr));
-            CPR_T(out.tGal, galerkin(A, a1, n1, A1, g1p, g1i));
-            CPR_T(out.tAgg, pairwise(A1, b, attempt == 2, a2, n2));
-            if (n2 <= (int)(0.5 * A.n)) break;
-        }
-        if (n2 >= (int)(0.8 * A.n)) break;   // coarsening stalls: this level is the coarsest
-        std::vector<int> agg(A.n);
-        for (int i = 0; i < A.n; ++i) agg[i] = a2[a1[i]];
-        HCsr Ac;
-        std::vector<int> gptr, gidx;
-        CPR_T(out.tGal, galerkin(A, agg, n2, Ac, gptr, gidx));
-        {   // a coarse level whose rows outgrow the ELL image (fault- and NNC-heavy patterns): stop here, this level is the coarsest
-            int Wc = 1;
-            for (int I = 0; I < Ac.n; ++I) Wc = std::max(Wc, Ac.rowptr[I + 1] - Ac.rowptr[I]);
-            if (Wc > CPR_MAX_W) break;
-        }
-        for (int& g : gidx) g = pos[g];                       // gather lists address the fine level's ELL array
-        std::vector<int> mptr(n2 + 1, 0), midx(A.n);
-        for (int i = 0; i < A.n; ++i) mptr[agg[i] + 1]++;
-        for (int I = 0; I < n2; ++I) mptr[I + 1] += mptr[I];
-        {
-            std::vector<int> wpos(mptr.begin(), mptr.end() - 1);
-            for (int i = 0; i < A.n; ++i) midx[wpos[agg[i]]++] = i;
-        }
-        cur->nc = n2;
-        {   // four-int member records (two pairwise passes: never more than four members) for cpr_restricted
-            std::vector<int> mem4((size_t)4 * n2, -1);
-            bool fits = true;
-            for (int I = 0; I < n2 && fits; ++I) {
-                fits = mptr[I + 1] - mptr[I] <= 4 && mptr[I + 1] > mptr[I];
-                for (int q = mptr[I]; fits && q < mptr[I + 1]; ++q) mem4[(size_t)4 * I + (q - mptr[I])] = midx[q];
-            }
-            if (fits) cur->mem4 = std::move(mem4); else cur->mem4.clear();
-        }
-        cur->agg = std::move(agg); cur->mptr = std::move(mptr); cur->midx = std::move(midx);
-        cur->gptr = std::move(gptr); cur->gidx = std::move(gidx);
-        out.lv.emplace_back();
-        std::vector<int> cposv;
-        bool fitsW = true;
-        const bool iluLevel = nlev < iluLevels;   // (level index nlev: the one being added)
-        CPR_T(out.tImg, fitsW = ell_image(Ac, out.lv.back(), cposv, Ac.n <= lprRows && !iluLevel));
-        if (!fitsW) { out.error = "cpr: a row of a pressure-AMG level outgrew the level image"; return; }
-        if (iluLevel) {   // ILU0 smoothing: greedy multi-colouring of the level's graph, colour by colour
-            std::vector<int> colour, posv;
-            const int ncolours = cpr_greedy_colours(out.lv.back(), colour, posv);
-            CPR_T(out.tImg, cpr_ilu_schedule(out.lv.back(), posv, colour, ncolours, out.lv.back().ilu));
-            if (!out.lv.back().ilu.error.empty()) { out.error = out.lv.back().ilu.error; return; }
-        }
-        // (out.lv may have reallocated: cur is looked up again)
-        CprHostLevel* fine = out.lv.size() == 1 ? &out.l0 : &out.lv[out.lv.size() - 2];
-        fine->cpos = cposv;                                   // where the coarse entries go
-        cur = &out.lv.back();
-        pos = std::move(cposv);
-        A = std::move(Ac);
-        ++nlev;
-    }
-    out.lastA = std::move(A);
-    out.lastPos = std::move(pos);
-#undef CPR_T
-}
-// ---- everything below level 0's image, on the host: two passes of pairwise matching per level, Galerkin lists, level images.
-//      Pure host work on its arguments (no context, no HIP call): may run on a thread of its own.  ell0: level 0's value image
-//      (W0 x Nb, as on the device) of the pressure matrix the structure is built from.
-static void cpr_build_coarse_host(const Pattern& P, const std::vector<double>& ell0, double beta, int lprRows, int iluLevels, int stopRows, CprHostCoarse& out) {
-    HCsr A;
-    A.n = P.Nb; A.rowptr = P.rowptr; A.col = P.col;
-    CprHostLevel img0;
-    std::vector<int> pos;   // ELL position of every CSR entry of the level being coarsened
-    (void)ell_image(A, img0, pos, false, P.Nb);
-    if (P.Nghost > 0) {   // the host copy the hierarchy is built from: owned columns only (pos follows the entries that stay)
-        HCsr F;
-        std::vector<int> fpos;
-        F.n = P.Nb; F.rowptr.assign(P.Nb + 1, 0);
-        for (int i = 0; i < P.Nb; ++i) {
-            for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
-                if (A.col[k] < P.Nb) { F.col.push_back(A.col[k]); fpos.push_back(pos[k]); }
-            F.rowptr[i + 1] = (int)F.col.size();
-        }
-        A = std::move(F);
-        pos = std::move(fpos);
-    }
-    const int nnz0 = (int)A.col.size();
-    A.val.resize(nnz0);
-    for (int k = 0; k < nnz0; ++k) A.val[k] = ell0[pos[k]];
-    cpr_coarsen_host(std::move(A), std::move(pos), P.fromOrder.data(), P.toOrder.data(), beta, lprRows, iluLevels, stopRows, out);
 }
 // ---- the device side of it: transfer arrays of every level, images of the levels below level 0 --------------------------------
 // gathered: R's last level is continued across the ranks (cpr_gather_setup), not solved by R

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/opmhip.h"
+#include "cpr_setup.hpp"
 
 namespace opmhip {
 
@@ -46,6 +47,11 @@ struct StencilForm {
     unsigned char* d_koff = nullptr;
     int* d_table = nullptr;
 };
+// the form of one tile (reorder.cpp): reset_stencil sizes it for Nb rows and `tables` tables (every word 15s, every table 0s); encode_stencil
+// writes rows [r0, r1) of a block-CSR with their offsets in table `slot`.  False where the tile has more than 15 offsets (nothing written) or a
+// row more than 8 entries or a first entry more than 255 blocks in (the table and the rows before that one are written): the form does not fit.
+void reset_stencil(StencilForm& S, int Nb, size_t tables);
+bool encode_stencil(const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1, int slot, StencilForm& S);
 
 struct TileSet {            // tiles over one block-CSR row-pointer array, never crossing a colour boundary
     std::vector<int> row0;  // [ntiles+1]
@@ -265,7 +271,7 @@ struct CprLevelDev {
     // into the table of <= 15 column offsets its aligned group of 32 rows shares; NULL: the explicit column image d_ecol is read
     unsigned* d_sword = nullptr;
     int* d_stable = nullptr;
-    // ILU0 smoothing (opmhip_config.cpr_amg_ilu_levels; cpr.hip: CprIluHost): scalar factors in the level's own image (strict lower = L,
+    // ILU0 smoothing (opmhip_config.cpr_amg_ilu_levels; cpr_setup.hpp: CprIluHost): scalar factors in the level's own image (strict lower = L,
     // diagonal = 1 / U_ii, strict upper = U), per row the words that say which slots are lower / upper entries in the level's elimination
     // order, the lower slots in the order the factorisation visits them, and a launch schedule: colour by colour, one thread per SEQUENCE
     // of rows that depend on each other inside the colour (level 0 of a line-coloured pattern: the chains; otherwise single rows)

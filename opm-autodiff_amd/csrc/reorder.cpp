@@ -290,14 +290,13 @@ void tile_offsets(const std::vector<int>& rowptr, const std::vector<int>& col, i
     std::sort(offs.begin(), offs.end());
     offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
 }
+}  // namespace
+
 void reset_stencil(StencilForm& S, int Nb, size_t tables) {
     S.word.assign(Nb, 0xFFFFFFFFu);
     S.koff.assign(Nb, 0);
     S.table.assign(16 * tables, 0);
 }
-// Rows [r0, r1) of a block-CSR in stencil form (internal.hpp: StencilForm), their offsets in table `slot`.  False where the tile has more
-// than 15 offsets (nothing written) or a row more than 8 entries or a first entry more than 255 blocks in (the table and the rows before
-// that one are written): the form does not fit.
 bool encode_stencil(const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1, int slot, StencilForm& S) {
     std::vector<int> offs;
     tile_offsets(rowptr, col, r0, r1, offs);
@@ -316,6 +315,8 @@ bool encode_stencil(const std::vector<int>& rowptr, const std::vector<int>& col,
     }
     return true;
 }
+
+namespace {
 int upload_stencil(opmhip_ctx* c, StencilForm& S) {
     int rc;
     if ((rc = dev_upload(c, &S.d_word, S.word))) return rc;

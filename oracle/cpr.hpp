@@ -1,6 +1,6 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see linalg.hpp).
 // CPU restatement of the CPR (constrained pressure residual) preconditioner of the hot path, the checker of
-// opm-autodiff_amd/csrc/cpr.hip.
+// opm-autodiff_amd/csrc/cpr.hip and cpr_setup.cpp.
 //
 // What follows the reference line by line (in tree):
 //   two-level structure        opm/simulators/linalg/twolevelmethodcpr.hh:476-498  (pre-smoothing 0 steps, coarse correction,

@@ -3,7 +3,8 @@ table blobs) built with g++ under AddressSanitizer + UBSan + libstdc++'s contain
 decomposed subdomains with ghost columns, irregular patterns with rows of up to 20 blocks, every ordering and chain lengths from 1 to 64
 (tests/san/host_logic_san.cpp, which also checks the invariants every ordering must keep).  No GPU: the harness serves the three HIP
 runtime calls of reorder.cpp from the host heap.  The GPU sanitizers are not available on the pool; this is the CPU build the brief asks
-to run them on."""
+to run them on.  The CPR pressure-AMG set-up (csrc/cpr_setup.cpp) is built the same way, linked alone (tests/san/cpr_setup_san.cpp: level
+invariants on every hierarchy, the oracle's hierarchy alongside)."""
 import os
 import shutil
 import subprocess
@@ -30,3 +31,24 @@ def test_reorder_and_fluid_tables_under_asan_ubsan(tmp_path):
     assert "all checks passed" in out and "FAILED" not in out
     assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-4000:]
     assert out.count("\nok  ") > 150   # every case of the list ran
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_cpr_setup_under_asan_ubsan(tmp_path):
+    # cpr_setup.cpp alone, no HIP stand-ins: the link fails if the set-up half of the CPR calls the HIP runtime
+    exe = str(tmp_path / "cpr_setup_san")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           "-D_GLIBCXX_ASSERTIONS", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           os.path.join(ROOT, "tests", "san", "cpr_setup_san.cpp"), os.path.join(CSRC, "cpr_setup.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("OPMHIP_TUNING", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "all checks passed" in out and "FAILED" not in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-4000:]
+    assert out.count("; oracle agrees: levels, n, nc, agg, coarsest matrix\n") == 104   # every set-up of the list, each against the oracle
+    for stop in ("rows", "stall", "width"):   # every rule that ends a hierarchy was met
+        assert "(last: %s)" % stop in out

@@ -3,7 +3,8 @@
 #   1. the oracle (oracle/*.hpp, oracle_capi.cpp) with AddressSanitizer + UBSan + libstdc++'s container assertions, then every CPU test
 #      that uses it against that build (tests/conftest.py: ORACLE_LIB); libasan is preloaded into python, leak checking off (the
 #      interpreter's own allocations would drown the report);
-#   2. the library's host-side logic - what tests/test_host_logic_sanitized.py builds and runs in the CPU suite.
+#   2. the library's host-side logic (csrc/reorder.cpp, fluid_tables.cpp and the CPR hierarchy set-up cpr_setup.cpp) - what
+#      tests/test_host_logic_sanitized.py builds and runs in the CPU suite.
 # Takes about four minutes.  The GPU tests can use an assertions-only build of the oracle (no sanitizer runtime in the process):
 #   ORACLE_LIB=$OUT/liboracle_assert.so python -m pytest tests -m gpu
 set -e
