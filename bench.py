@@ -19,9 +19,17 @@ a GPU and fails loudly when fewer than N devices are visible).  Restricted-addit
 (px 100) x (py 100) x (pz 100) grid (opm-autodiff_amd/ras.py), 10^6 cells per GPU, halo exchange and scalar all-reduces
 over RCCL inside libopmhip (weak scaling; 8 GPUs = BASELINE configs[3], 200^3).  Prints ONE JSON line on rank 0.
 
-After the K timed steps the run goes on (untimed) to Newton iteration `--steady-after` and times `--steady-steps` more:
-the steady-state phase of the simulation (10-day steps, ~30 linear iterations per Newton iteration) beside the easy
-start-up phase the K steps measure.  `value` is the K-step figure the contract asks for; `steady_state` is an extra key.
+A plain run does what `value` needs and nothing else: it sets the case up, runs the W warm-up steps, times the K steps,
+writes `--dump-outputs` if asked and prints the line (kernel scopes and the roofline's `achieved` come from the K steps'
+own profile).  `--full` adds, after the K timed steps and outside them, what the benchmark measures beside `value`:
+- the steady-state window: the run goes on (untimed) to Newton iteration `--steady-after` and times `--steady-steps`
+  more, the steady-state phase of the simulation (10-day steps, ~30 linear iterations per Newton iteration) beside the
+  easy start-up phase the K steps measure (`steady_state`);
+- the same case with the CPR preconditioners, each in a context of its own (`cpr`, `cpr_quasiimpes`, ...), and the
+  drop-in solver with host pointers (`plugin`), on one GPU with ILU0 (`--no-cpr-side-run` leaves them out);
+- the kernel probes behind `stream_ceiling` and `roofline.full_spmv`;
+- the CPU port's baseline (`cpu_baseline`, `gpu_over_cpu`; `--no-cpu-baseline` leaves it out);
+- N > 1: the one-domain iteration count of the same case beside the decomposed one (`comm`).
 """
 import argparse
 import hashlib
@@ -255,10 +263,10 @@ COMM_SCOPES = ("halo", "allreduce", "cpr_gather")
 
 
 def single_domain_comparator(detail_path, n, steps, warmup, preconditioner, flags_default):
-    """Linear iterations per Newton iteration of the ONE-domain run of this bench that a decomposed run's count is put beside - read from the
-    detail file an N = 1 run left on this box (the driver runs N = 1 first), and only if that run was the same case: same cells per GPU, same
-    window, same preconditioner, default ordering / smoother flags on both sides.  None otherwise: no typed-in figure stands in for a
-    measurement nobody made on this box."""
+    """Linear iterations per Newton iteration of the ONE-domain run of this bench that a decomposed --full run's count is put beside - read from
+    the detail file an N = 1 run left beside this run's own (the default detail files of both share one folder; the driver runs N = 1 first),
+    and only if that run was the same case: same cells per GPU, same window, same preconditioner, default ordering / smoother flags on both
+    sides.  None otherwise: no typed-in figure stands in for a measurement nobody made on this box."""
     try:
         with open(detail_path) as f:
             d = json.load(f)
@@ -302,6 +310,7 @@ def compact_line(out, detail_path):
     else (kernel scopes per window, reports, time steps, thread sweep, device) is in the file `detail` names."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     line = {k: _r(out[k]) for k in keep}
+    line["full"] = bool(out.get("full"))   # false: a plain run, none of the --full extras was measured
     line["config"] = out["config"]
     line["newton_iterations_per_s_global"] = _r(out["newton_iterations_per_s_global"])
     line["linear_iterations_per_newton"] = _r(out["linear_iterations_per_newton"], 2)
@@ -341,7 +350,7 @@ def compact_line(out, detail_path):
         if out.get(k) is not None:
             line[k] = one(out[k])
     line["cpr_amg_ilu_levels"] = out.get("cpr_amg_ilu_levels")
-    line["stream_read_GBps"] = out["stream_ceiling"]["read_GBps"]
+    line["stream_read_GBps"] = (out.get("stream_ceiling") or {}).get("read_GBps")
     if out.get("rccl"):
         line["rccl"] = {"nranks": out["rccl"]["nranks"], "kind": out["rccl"]["kind"]}
     if out.get("comm"):
@@ -457,9 +466,11 @@ def main():
     ap.add_argument("--chain-length", type=int, default=0, help="rows per chain of the line-coloured ILU0 ordering; 0: the library's choice (10 at 10^6 cells)")
     ap.add_argument("--full-line", action="store_true", help="tools/ only: print the full record as the one line (tens of KB: the driver could not parse that from its tail of stdout)")
     ap.add_argument("--detail", default=None, help="file for the full record (per-window kernel scopes, reports, time steps); default gpurun_out/bench_detail.json (N > 1: bench_detail_nN.json)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--steady-after", type=int, default=200, help="second timed window starts at this Newton iteration (0: none)")
-    ap.add_argument("--steady-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the line carries beside `value`: the steady-state window, "
+                                                        "the CPR side runs, the kernel probes, the CPU baseline (module docstring); a plain run does none of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--steady-after", type=int, default=200, help="--full: second timed window starts at this Newton iteration (0: none)")
+    ap.add_argument("--steady-steps", type=int, default=100, help="--full: Newton iterations of the second timed window")
     ap.add_argument("--preconditioner", default="ilu0", choices=["ilu0", "cpr", "cpr_trueimpes", "cpr_quasiimpes"], help="--linear-solver-configuration of the run behind `value`")
     ap.add_argument("--cpr-reuse-setup", type=int, default=3, choices=[0, 1, 2, 3], help="Flow's --cpr-reuse-setup for the CPR runs: when the hierarchy's structure is built anew (3 = never, the default of Flow)")
     ap.add_argument("--cpr-amg-ilu-levels", type=int, default=None, help="CPR runs: this many of the pressure AMG's finest levels smooth with ILU0 (the reference's AMG smoother) instead of damped Jacobi; default: the library's choice (opmhip_default_config: -1 = level 0 where the block ordering has at most three colours), reported in cpr_amg_ilu_levels")
@@ -467,7 +478,7 @@ def main():
                     help="BiCGStab with one reduction per half iteration (opmhip_config.fused_reductions). Default: off on one GPU (there it is even, profiles/r06_fused_ab.txt), "
                          "on for --gpus N > 1 with ILU0, where every reduction is an all-reduce over xGMI (two per iteration instead of four); --no-fused-reductions: off")
     ap.add_argument("--no-fused-reductions", dest="fused_reductions", action="store_false")
-    ap.add_argument("--no-cpr-side-run", action="store_true", help="skip the side runs with the CPR preconditioners (extra keys `cpr`, `cpr_quasiimpes`)")
+    ap.add_argument("--no-cpr-side-run", action="store_true", help="--full without the side runs with the CPR preconditioners (extra keys `cpr`, `cpr_quasiimpes`) and the plug-in window")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (state, Newton update, CNV norms, time-stepping position) as DIR/<name>.npy, "
                          "at most 64 MB in all (a fixed, seeded sample of cells beyond that; N > 1: one set per rank, <name>_rank<r>.npy)")
@@ -657,7 +668,7 @@ def main():
                   "timesteps_chopped": S["timesteps_chopped"], "linear_solve_GBps": S["linear_solve_GBps"], "report": S["report"],
                   "kernels": S["kernels"], "profiled": S["profiled"]}
 
-    if a.steady_after > 0 and a.steady_steps > 0:
+    if a.full and a.steady_after > 0 and a.steady_steps > 0:
         steady = guarded("steady-state window", steady_window)
     # the same workload with the CPR preconditioners, side by side, each in its own context with its own warm-up and timed
     # windows: "cpr" = cpr_trueimpes (what the name means in Flow, setupPropertyTree.cpp:62-76) and "cpr_quasiimpes"
@@ -696,7 +707,7 @@ def main():
                 del model2
         return run
 
-    if a.preconditioner == "ilu0" and world == 1 and not a.no_cpr_side_run:
+    if a.full and a.preconditioner == "ilu0" and world == 1 and not a.no_cpr_side_run:
         for prec in ("cpr", "cpr_quasiimpes"):
             cpr_sides[prec] = guarded("CPR side run (%s)" % prec, cpr_window(prec))
         if a.cpr_amg_ilu_levels != 0:   # the same with damped Jacobi on every level of the pressure AMG
@@ -707,10 +718,10 @@ def main():
             cpr_sides["cpr_reuse_setup_2"] = guarded("CPR side run (cpr, --cpr-reuse-setup=2, rebuild beside the solves)", cpr_window("cpr", cpr_reuse_setup=2, cpr_async_setup=1))
             cpr_sides["cpr_reuse_setup_2_sync"] = guarded("CPR side run (cpr, --cpr-reuse-setup=2)", cpr_window("cpr", cpr_reuse_setup=2))
     # what a kernel that only streams reaches on THIS card (reads the Jacobian's values once per launch)
-    stream = guarded("stream_read probe", lambda: {"ms": model.time_kernel("stream_read", reps=20)})
+    stream = guarded("stream_read probe", lambda: {"ms": model.time_kernel("stream_read", reps=20)}) if a.full else {}
     # the whole block-CSR product (SURVEY 8d's 579.44 MB at 100^3) back to back, 20 launches: with the half-product form in force no kernel
     # of a solve computes it any more, so it is timed here, outside the solve, for the record north_star asks for
-    full_spmv = guarded("full SpMV probe", lambda: {"ms": model.time_kernel("spmv", reps=20)}) if a.preconditioner == "ilu0" else {}
+    full_spmv = guarded("full SpMV probe", lambda: {"ms": model.time_kernel("spmv", reps=20)}) if (a.full and a.preconditioner == "ilu0") else {}
     stream_ms = stream.get("ms")
     stream_GBps = 72.0 * nnzb / stream_ms / 1e6 if stream_ms else None
 
@@ -742,7 +753,7 @@ def main():
             del sv
         o["bytes_h2d"] = 72 * nnzb + 24 * Nb
         return o
-    plugin = guarded("plug-in window", plugin_window) if (world == 1 and a.preconditioner == "ilu0" and not a.no_cpr_side_run) else None
+    plugin = guarded("plug-in window", plugin_window) if (a.full and world == 1 and a.preconditioner == "ilu0" and not a.no_cpr_side_run) else None
 
     dots_separate = os.environ.get("OPMHIP_TUNING", "") == "1" and os.environ.get("OPMHIP_DOTS_SEPARATE", "0") not in ("", "0")
     sp = kernels.get("spmv", {"avg_ms": float("nan"), "algorithmic_GBps": float("nan")})
@@ -792,21 +803,19 @@ def main():
         "cpr_reuse_setup_2": cpr_sides.get("cpr_reuse_setup_2"),
         "cpr_reuse_setup_2_sync": cpr_sides.get("cpr_reuse_setup_2_sync"),
         "preconditioner": a.preconditioner,
+        "full": a.full,
         # opmhip_solve_system with host pointers on this case's Jacobian (second context): milliseconds per linear solve by phase
         "plugin": plugin,
         "rccl": rccl,
         # decomposed runs: the communication spans of the profiled solves of the window behind `value` (halo: pack -> exchange -> ghosts in, on
         # the halo stream beside the interior tiles; allreduce: local sums -> all-reduce; cpr_gather: the joined level's all-gather + cycle),
-        # max / mean over the ranks, and the iteration count next to the one-domain figure of the same case (N = 1 run of this bench)
+        # max / mean over the ranks, and the iteration count (--full: beside the one-domain figure of the same case, added below)
         "comm": None if W["comm"] is None else dict(W["comm"], profiled_solves=W["profiled"]["solves"], profiled_every=PROFILE_EVERY,
-                                                    linear_iterations_per_newton=round(W["linear_iterations_per_newton"], 2),
-                                                    single_domain_linear_iterations_per_newton=single_domain_comparator(
-                                                        os.path.join(ROOT, "gpurun_out", "bench_detail.json"), n, a.steps, a.warmup, a.preconditioner,
-                                                        a.reorder is None and a.chain_length == 0 and a.cpr_amg_ilu_levels is None and a.cpr_reuse_setup == 3)),
+                                                    linear_iterations_per_newton=round(W["linear_iterations_per_newton"], 2)),
         "device": device_info(torch, local_rank),
-        "stream_ceiling": {"read_GBps": round(stream_GBps, 1) if stream_GBps else None, "bytes_per_launch": 72 * nnzb,
-                           "avg_launch_ms": round(stream_ms, 5) if stream_ms else None, "error": stream.get("error"),
-                           "kernel": "k_stream_read: the Jacobian's value array read once, 16-B loads, nothing else (back to back, 20 launches)"},
+        "stream_ceiling": None if not a.full else {"read_GBps": round(stream_GBps, 1) if stream_GBps else None, "bytes_per_launch": 72 * nnzb,
+                                                   "avg_launch_ms": round(stream_ms, 5) if stream_ms else None, "error": stream.get("error"),
+                                                   "kernel": "k_stream_read: the Jacobian's value array read once, 16-B loads, nothing else (back to back, 20 launches)"},
         "product_form": product_form,
         "dumped_outputs": None if dumped is None else {"dir": a.dump_outputs, "arrays": dumped},
         "roofline": {"bound": "hbm", "kernel": ("k_spmv_pipe_st<UADD>: the block-CSR product in its half-product form - the matrix without its U part "
@@ -828,13 +837,17 @@ def main():
                      "operand_bytes_per_launch": B["spmv"] if dots_separate else B["spmv_operands"],
                      "scalar_products": "k_dots behind every product (OPMHIP_DOTS_SEPARATE)" if dots_separate else "folded into the kernel (one partial sum per workgroup)"},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pkg, case, src, nnzb)
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     if rank == 0:
         # the full record goes to a file; the line on stdout is what the driver parses and stays under 4 KB
         # (N > 1 runs write a file of their own: the N = 1 record stays where the later runs of a scaling series look for their comparators)
         detail = a.detail or os.path.join(ROOT, "gpurun_out", "bench_detail.json" if world == 1 else "bench_detail_n%d.json" % world)
+        if a.full and out["comm"] is not None:   # read before this run's own record is written
+            out["comm"]["single_domain_linear_iterations_per_newton"] = single_domain_comparator(
+                os.path.join(os.path.dirname(os.path.abspath(detail)), "bench_detail.json"), n, a.steps, a.warmup, a.preconditioner,
+                a.reorder is None and a.chain_length == 0 and a.cpr_amg_ilu_levels is None and a.cpr_reuse_setup == 3)
         try:
             os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
             with open(detail, "w") as f:

@@ -182,7 +182,7 @@ def test_bench_two_ranks_control_plane_over_gloo(tmp_path):
     detail = str(tmp_path / "detail.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "tests", "bench_fake_rank.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--cells-per-edge", "10", "--steady-after", "12", "--steady-steps", "4",
+           os.path.join(ROOT, "tests", "bench_fake_rank.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--cells-per-edge", "10", "--steady-after", "12", "--steady-steps", "4",
            "--detail", detail]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -201,6 +201,16 @@ def test_bench_two_ranks_control_plane_over_gloo(tmp_path):
     full = json.load(open(detail))
     assert full["rccl"]["rank_devices"] == [0, 1] and full["rccl"]["selftest_sum"] == full["rccl"]["selftest_expected"] == [3.0, 4.0]
     assert full["steady_state"]["steps"] == 4 and full["spmv_boundary_share_of_time"] == 0.2
+    # without --full: the same control plane and timed window, and nothing after it - no steady-state window, no one-domain comparator
+    plain = subprocess.run(cmd[:8] + [str(free_port()), cmd[9]] + ["--gpus", "2", "--steps", "6", "--warmup", "2", "--cells-per-edge", "10", "--detail", str(tmp_path / "plain.json")],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert plain.returncode == 0, (plain.stdout[-1500:], plain.stderr[-3000:])
+    lines = [ln for ln in plain.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    p = json.loads(lines[0])
+    assert p["full"] is False and p["n_gpus"] == 2 and p["steps"] == 6 and p["rccl"] == {"nranks": 2, "kind": "rccl"} and p["steady_state"] is None
+    assert p["comm"]["halo"]["launches_per_rank"] > 0 and "single_domain_linear_iterations_per_newton" not in p["comm"]
+    assert json.load(open(tmp_path / "plain.json"))["steady_state"] is None
     # a communicator that does not span the ranks that were asked for: every rank exits non-zero, no line
     bad = subprocess.run(cmd[:8] + [str(free_port()), cmd[9]] + ["--gpus", "2", "--steps", "2", "--warmup", "1", "--cells-per-edge", "10", "--steady-after", "0"], capture_output=True, text=True, timeout=600,
                          env=dict(env, OPMHIP_FAKE_NRANKS="1"), cwd=ROOT)

@@ -1,4 +1,4 @@
-"""bench.py's one JSON line on a small grid: the keys the driver's contract names are there, with the roofline and the CPU
+"""bench.py's one JSON line on a small grid: the keys the driver's contract names are there, with the roofline and (--full) the CPU
 baseline objects, the numbers hang together, and the line stays short enough for the driver to parse from the tail of stdout (round 4's
 22 KB line was cut in half); the full record is in the file the line names."""
 import json
@@ -16,7 +16,7 @@ def test_bench_line_contract(tmp_path):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "24", "--steps", "4", "--warmup", "2", "--steady-after", "8",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "24", "--steps", "4", "--warmup", "2", "--steady-after", "8",
                         "--steady-steps", "3", "--detail", detail], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = r.stdout.strip().splitlines()
@@ -39,7 +39,7 @@ def test_bench_line_contract(tmp_path):
     fcb = full["cpu_baseline"]
     assert fcb["host"]["physical_cores_in_mask"] >= 1 and abs(fcb["value"] - cb["value"]) < 1e-3
     assert cb["cores"] == 1 or str(cb["cores"]) in fcb["host"]["thread_sweep_newton_its_per_s"]
-    assert d["steady_state"]["value"] > 0 and full["steady_state"]["steps"] == 3 and d["stream_read_GBps"] > 0
+    assert d["full"] is True and d["steady_state"]["value"] > 0 and full["steady_state"]["steps"] == 3 and d["stream_read_GBps"] > 0
     # no ordering / smoother flag was passed: the line reports what the library chose (a 24^3 grid: the greedy colouring, red-black)
     assert d["config"]["ilu_ordering"] == "graph_coloring_greedy" and d["config"]["ilu_colors"] == 2 and d["config"]["ilu_chain_length"] == 0
     assert d["config"]["ilu_ordering_chosen_by"].startswith("library default") and d["cpr_amg_ilu_levels"] == 1
@@ -89,3 +89,32 @@ def test_dump_outputs_are_the_last_timed_newton_iteration(tmp_path, pkg):
     assert np.array_equal(d["newton_update.npy"], model.get_result().reshape(-1, 3))
     assert np.array_equal(d["cnv_residual_norms.npy"], np.array(sim.model.residual_norms_history[-1]))
     assert np.array_equal(d["time_stepping.npy"], np.array([sim.time, sim.dt, sim.iteration, sim.model.last_linear_iterations], np.float64))
+
+
+def test_plain_run_times_the_steps_of_a_full_run_and_nothing_else(tmp_path):
+    """without --full the run sets up, warms up, times the steps, dumps and prints: the line carries the contract's keys and what the timed
+    steps' own profile gives (kernel scopes, the roofline's achieved bandwidth), none of the extras; and its timed steps are those of a --full
+    run of the same arguments - the same linear iterations and time steps, the same arrays after the last of them, bit for bit"""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    n, steps, warmup = 16, 3, 2
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--steady-after", "8", "--steady-steps", "2", "--no-cpr-side-run", "--no-cpu-baseline"])):
+        detail, dump = tmp_path / (mode + ".json"), tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", str(steps), "--warmup", str(warmup),
+                            "--detail", str(detail), "--dump-outputs", str(dump)] + extra, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs[mode] = (json.loads(r.stdout.strip().splitlines()[-1]), json.load(open(detail)), {f: np.load(dump / f) for f in sorted(os.listdir(dump))})
+    d, rec, arrays = runs["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline", "kernel_GBps"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    assert d["roofline"]["achieved"] > 0 and d["kernel_GBps"]["spmv"] > 0 and "full_spmv" not in d["roofline"] and d["roofline"]["frac_of_stream_ceiling"] is None
+    assert "cpu_baseline" not in d and d["steady_state"] is None and d["stream_read_GBps"] is None and "plugin" not in d and "cpr" not in d
+    assert "cpu_baseline" not in rec and rec["stream_ceiling"] is None and rec["plugin"] is None
+    assert all(rec[k] is None for k in ("steady_state", "cpr", "cpr_quasiimpes", "cpr_amg_jacobi_smoother", "cpr_reuse_setup_2", "cpr_reuse_setup_2_sync"))
+    fd, frec, farrays = runs["full"]
+    assert fd["full"] is True and fd["steady_state"]["value"] > 0 and fd["stream_read_GBps"] > 0
+    assert rec["linear_iterations_per_newton"] == frec["linear_iterations_per_newton"] and rec["time_steps_days"] == frec["time_steps_days"]
+    assert sorted(arrays) == sorted(farrays) and all(np.array_equal(arrays[f], farrays[f]) for f in arrays)

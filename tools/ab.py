@@ -36,8 +36,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = "bench.py"   # relative to ROOT, where every step runs
-BASE_ARGS = ["--steps", "20", "--warmup", "5", "--steady-after", "0", "--no-cpu-baseline", "--no-cpr-side-run"]
-PMC_SCRIPT = "bench.py --steps 6 --warmup 1 --no-cpu-baseline --steady-after 0 --no-cpr-side-run"
+BASE_ARGS = ["--full", "--steps", "20", "--warmup", "5", "--steady-after", "0", "--no-cpu-baseline", "--no-cpr-side-run"]   # --full: the kernel probes run (column `stream`), --steady-after N opens the steady window
+PMC_SCRIPT = "bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --steady-after 0 --no-cpr-side-run"
 SNAPSHOT_GROUPS = ["FETCH_SIZE", "WRITE_SIZE", "TCC_HIT_sum TCC_MISS_sum"]
 DEFAULT_COLS = ["value", "its", "kernels.spmv.avg_ms", "kernels.ilu_apply.avg_ms", "kernels.ilu_factor.avg_ms", "kernels.vector.avg_ms"]
 ALIASES = {"value": "value", "steady": "steady_state.value", "its": "linear_iterations_per_newton", "stream": "stream_ceiling.read_GBps"}
@@ -129,7 +129,7 @@ def plan_run(a, out):
 def plan_snapshot(a, out):
     n = a.name
     f = lambda suffix: os.path.join(out, n + suffix)   # noqa: E731
-    full = [sys.executable, BENCH, "--steps", "20", "--warmup", "5"]
+    full = [sys.executable, BENCH, "--full", "--steps", "20", "--warmup", "5"]
     raw = os.path.join(out, "rocprof")
     return [step("bench", full + ["--detail", f("_bench_detail.json")], f("_bench.json"), os.path.join(out, "bench.err"), limit=a.bench_limit),
             step("bench under rocprofv3 --stats",
