@@ -1011,11 +1011,6 @@ constexpr int ASM_PRE = 10;  // what a diagonal lane fetches ahead for its cell:
 //      drift (into the same registers, parked in LDS before the arithmetic starts)
 // The arithmetic then runs out of LDS / registers.  LDS: the own records are dead once every face is evaluated; the face
 // fluxes and the tile's blocks take their place (11 KiB per workgroup instead of 18).
-#ifdef OPMHIP_ASM_SOFT_SYNC
-__device__ __forceinline__ void asm_wave_sync() { asm volatile("" ::: "memory"); }  // one wavefront per workgroup: its LDS accesses execute in program order
-#else
-__device__ __forceinline__ void asm_wave_sync() { __syncthreads(); }
-#endif
 template <bool EXT>
 __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, const int4* __restrict__ sched, const int2* __restrict__ desc, int wet,
                                                           EntryStatic ES, CellStatic C, const double* __restrict__ iq,
@@ -1087,7 +1082,7 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
         }
         qJ.r[4 * 9] = drift ? C.poro[I] : 1.0;   // referencePorosity
     }
-    asm_wave_sync();
+    __syncthreads();
     const double zI = sgeo[lrow], VI = sgeo[ASM_MAX_ROWS + lrow];
     Ad f[3];         // off-diagonal lane: face flux seen from cell I; diagonal lane: storage term
     double blk[BB];  // off-diagonal lane: block (I,J)
@@ -1115,7 +1110,7 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
             if (EXT && ph == GAS && wet) f[EQ_OIL] = f[EQ_OIL] + qI.ad(Lay<EXT>::F_RV) * surfaceVolume;   // vaporised oil
         }
     }
-    asm_wave_sync();   // every read of the own records is done: their LDS becomes sflux / sblk
+    __syncthreads();   // every read of the own records is done: their LDS becomes sflux / sblk
     if (isOff) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) store_ad(&sflux[tid * 12 + e * 4], f[e]);
@@ -1123,7 +1118,7 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
 #pragma unroll
         for (int q = 0; q < BB; ++q) b[q] = blk[q];
     }
-    asm_wave_sync();
+    __syncthreads();
     if (isDiag) {
         Ad R[3] = {ad_const(0.0), ad_const(0.0), ad_const(0.0)};
         // flux terms first (FvBaseLocalResidual::eval), faces in ascending NATURAL neighbour order whatever the
@@ -1180,7 +1175,7 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
             b[e * 3 + 0] = R[e].d0; b[e * 3 + 1] = R[e].d1; b[e * 3 + 2] = R[e].d2;
         }
     }
-    asm_wave_sync();
+    __syncthreads();
     // stream the tile's blocks out: contiguous range [k0, k1) x 72 B
     {
         const int head = (k0 - k0e) * BB;      // doubles to skip at the front (0 or 9)
@@ -1196,16 +1191,12 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
         double2* d2 = reinterpret_cast<double2*>(dst);
         // nontemporal: the Jacobian leaves for good (500 MB), the intensive-quantity records the neighbouring tiles gather stay in L2
         // (0.607 -> 0.601 ms in alternation, profiles/r06_nt_operands_ab.txt)
-#ifndef OPMHIP_ASM_PLAIN_STORES
         typedef double v2d_a __attribute__((ext_vector_type(2)));
         for (int i = (b >> 1) + tid; i < (e >> 1); i += ASM_THREADS) {
             const double2 t = s2[i];
             v2d_a v; v.x = t.x; v.y = t.y;
             __builtin_nontemporal_store(v, reinterpret_cast<v2d_a*>(&d2[i]));
         }
-#else
-        for (int i = (b >> 1) + tid; i < (e >> 1); i += ASM_THREADS) d2[i] = s2[i];
-#endif
     }
 }
 

@@ -410,15 +410,13 @@ int opmhip_solve_system(opmhip_ctx* c, int N, int nnz, int dim, double* vals, co
         if (!vals && !c->system_loaded) return fail(c, OPMHIP_NOT_READY, "solve_system: vals == NULL but no matrix is resident on the device");
         int rc;
         if ((rc = upload_system(c, vals, b))) return rc;
-        static const bool zfixSeparate = [] { const char* e = tuning_env("OPMHIP_ZFIX_SEPARATE"); return e && e[0] == '1'; }();   // A/B switch
         const bool zfix = !vals && c->cfg.zero_diag_fix;   // device-assembled Jacobian: the same fix-up as the uploaded one gets
-        if (zfix && zfixSeparate) launch_zero_diag_fix(c);
         if ((rc = upload_wells(c, wells))) return rc;
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         const double t1 = now();
         FactorRider rider;   // CPR: weights and level 0's values of the pressure hierarchy are formed while the rows are in LDS
         if ((rc = cpr_factor_rider(c, &rider))) return rc;
-        launch_ilu_factor(c, zfix && !zfixSeparate, &rider);  // ... applied as the rows are staged
+        launch_ilu_factor(c, zfix, &rider);  // ... applied as the rows are staged
         OPMHIP_HIP(c, hipGetLastError());
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         c->factored = true;

@@ -493,12 +493,10 @@ __global__ __launch_bounds__(256) void k_cpr_prolong(int n, double damp, const i
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) xp[i] = x[i] + damp * xc[agg[i]];
 }
-// vfine != NULL (level 0): the result goes straight into the block vector v = (0, x_p, 0) (moveToFineLevel: the pressure
-// component only) - k_cpr_prolong_fine's statement, one launch and one pass over x_p less
 template <bool ST>
 __global__ __launch_bounds__(256) void k_cpr_post(int n, int W, double omega, const int* __restrict__ ecol, const double* __restrict__ val,
                                                   const double* __restrict__ dinv, const double* __restrict__ b, const double* __restrict__ xp,
-                                                  double* __restrict__ xout, double* __restrict__ vfine, const double* __restrict__ done, const EllStencil S) {
+                                                  double* __restrict__ xout, const double* __restrict__ done, const EllStencil S) {
     CPR_DONE_CHECK
     const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
     if (!ST && i0 >= n) return;
@@ -514,31 +512,13 @@ __global__ __launch_bounds__(256) void k_cpr_post(int n, int W, double omega, co
 #pragma unroll 4
         for (int j = 0; j < W; ++j) s -= val[(size_t)j * n + i] * xp[ecol[(size_t)j * n + i]];
     }
-    const double xo = xp[i] + omega * dinv[i] * s;
-    xout[i] = xo;
-    if (vfine) {
-        double* v = &vfine[(size_t)i * BS];
-#pragma unroll
-        for (int k = 0; k < BS; ++k) v[k] = (k == CPR_P) ? xo : 0.0;
-    }
-}
-// v = (0, x_p, 0)  (moveToFineLevel: the pressure component only)
-__global__ __launch_bounds__(256) void k_cpr_prolong_fine(int Nb, const double* __restrict__ xc, double* __restrict__ v, const double* __restrict__ done) {
-    CPR_DONE_CHECK
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= Nb * BS) return;
-    v[e] = (e % BS == CPR_P) ? xc[e / BS] : 0.0;
+    xout[i] = xp[i] + omega * dinv[i] * s;
 }
 __global__ __launch_bounds__(256) void k_cpr_sub(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ r,
                                                  const double* __restrict__ done) {
     CPR_DONE_CHECK
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n) r[e] = a[e] - b[e];
-}
-__global__ __launch_bounds__(256) void k_cpr_add(int n, double* __restrict__ v, const double* __restrict__ z, const double* __restrict__ done) {
-    CPR_DONE_CHECK
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) v[e] += z[e];
 }
 
 
@@ -662,7 +642,7 @@ __global__ __launch_bounds__(64) void k_cpr_ilu_factor_simple(int nseq, int nste
 }
 // One colour of a sweep; a thread walks its sequence of rows.  BWD = false: v_i = d_i - sum over the lower entries, in the row's
 // order; BWD = true: v_i = (v_i - sum over the upper entries) / U_ii, steps in reverse; out != NULL (the backward sweeps of a
-// post-smoothing): out_i = add_i + v_i, the statement "x += t" of the cycle (vfine: and the block vector (0, out_i, 0)).
+// post-smoothing): out_i = add_i + v_i, the statement "x += t" of the cycle.
 // FAST (cpr_ilu_schedule: every coupling inside the colour joins neighbours of a sequence): the value of the row before is handed
 // on in a register, every value read from memory was written by an earlier launch - gathers (vg) and stores (v) touch different
 // entries, so the loads of later steps need not wait for the stores of earlier ones.  Otherwise values of the thread's own earlier
@@ -670,7 +650,7 @@ __global__ __launch_bounds__(64) void k_cpr_ilu_factor_simple(int nseq, int nste
 template <bool BWD, bool FAST, int WQ>
 __device__ __forceinline__ void cpr_ilu_sweep_body(int t, int nseq, int nsteps, const int* __restrict__ rowAt, int n, int wq, const double* __restrict__ fv,
                                                    const int* __restrict__ fc, const double* __restrict__ ud, const double* __restrict__ d, const double* vg,
-                                                   double* v, const double* __restrict__ add, double* __restrict__ out, double* __restrict__ vfine) {
+                                                   double* v, const double* __restrict__ add, double* __restrict__ out) {
     int iprev = -1;
     double vprev = 0.0;
 #pragma unroll 2
@@ -702,15 +682,7 @@ __device__ __forceinline__ void cpr_ilu_sweep_body(int t, int nseq, int nsteps, 
         if (BWD) s = s * ud[i];
         v[i] = s;
         if (FAST) { iprev = i; vprev = s; }
-        if (BWD && out) {
-            const double xo = add[i] + s;
-            out[i] = xo;
-            if (vfine) {
-                double* vf = &vfine[(size_t)i * BS];
-#pragma unroll
-                for (int k = 0; k < BS; ++k) vf[k] = (k == CPR_P) ? xo : 0.0;
-            }
-        }
+        if (BWD && out) out[i] = add[i] + s;
     }
 }
 // FAST colours, written for the shape the launch has: a colour of a line-coloured level 0 offers one thread per chain - 50 000 threads for
@@ -722,7 +694,7 @@ template <bool BWD, int WQ, int G>
 __global__ __launch_bounds__(64) void k_cpr_ilu_sweep_fast(int nseq, int nsteps, const int* __restrict__ rowAt, int n, int wq, const double* __restrict__ fv,
                                                            const int* __restrict__ fc, const double* __restrict__ ud, const double* __restrict__ d,
                                                            const double* __restrict__ vg, double* __restrict__ v, const double* __restrict__ add,
-                                                           double* __restrict__ out, double* __restrict__ vfine, const double* __restrict__ done) {
+                                                           double* __restrict__ out, const double* __restrict__ done) {
     CPR_DONE_CHECK
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nseq) return;
@@ -767,26 +739,17 @@ __global__ __launch_bounds__(64) void k_cpr_ilu_sweep_fast(int nseq, int nsteps,
             v[ri[u]] = s;
             iprev = ri[u];
             vprev = s;
-            if (BWD && out) {
-                const double xo = da[u] + s;
-                out[ri[u]] = xo;
-                if (vfine) {
-                    double* vf = &vfine[(size_t)ri[u] * BS];
-#pragma unroll
-                    for (int k = 0; k < BS; ++k) vf[k] = (k == CPR_P) ? xo : 0.0;
-                }
-            }
+            if (BWD && out) out[ri[u]] = da[u] + s;
         }
     }
 }
 template <bool BWD, int WQ>
 __global__ __launch_bounds__(256) void k_cpr_ilu_sweep(int nseq, int nsteps, const int* __restrict__ rowAt, int n, int wq, const double* __restrict__ fv,
                                                        const int* __restrict__ fc, const double* __restrict__ ud, const double* __restrict__ d,
-                                                       double* v, const double* __restrict__ add, double* __restrict__ out, double* __restrict__ vfine,
-                                                       const double* __restrict__ done) {
+                                                       double* v, const double* __restrict__ add, double* __restrict__ out, const double* __restrict__ done) {
     CPR_DONE_CHECK
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nseq) cpr_ilu_sweep_body<BWD, false, WQ>(t, nseq, nsteps, rowAt, n, wq, fv, fc, ud, d, v, v, add, out, vfine);
+    if (t < nseq) cpr_ilu_sweep_body<BWD, false, WQ>(t, nseq, nsteps, rowAt, n, wq, fv, fc, ud, d, v, v, add, out);
 }
 
 
@@ -1004,11 +967,6 @@ int cpr_factor_rider(opmhip_ctx* c, FactorRider* r) {
     //  leaves before that must not make the next cpr_update skip its own pass over the matrix)
     return OPMHIP_SUCCESS;
 }
-// levels of up to this many rows are kept row-major and run the lane-group kernels (OPMHIP_CPR_LPR_ROWS: measurement switch)
-static int cpr_lpr_rows() {
-    static const int v = [] { const char* e = tuning_env("OPMHIP_CPR_LPR_ROWS"); return e ? std::atoi(e) : CPR_LPR_ROWS; }();
-    return v;
-}
 static bool cpr_gathering(const opmhip_ctx* c);
 // opmhip_config.cpr_amg_ilu_levels as it is in force: < 0 = the library's choice - level 0 where the block ILU0's ordering has few colours
 // (a sweep of level 0 is one launch per colour: four launches per application with two colours, +5 ... +8 % Newton iterations/s on the
@@ -1058,10 +1016,9 @@ static int cpr_setup_level0_body(opmhip_ctx* c) {
     (void)ell_image(A, H0, pos, false, spans ? P.Nloc : P.Nb);
     if ((rc = upload_ell(c, H0, R.lv[0], spans ? P.Nloc : P.Nb))) return rc;
     {   // level 0's ELL columns in stencil form (EllStencil), where the pattern has it: single domain, rows of <= 8 entries, <= 15 offsets per group of 32 rows
-        static const bool off = [] { const char* e = tuning_env("OPMHIP_CPR_ELL_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch
         // the shared encoder (reorder.cpp), tile = aligned group of 32 rows: with rows of <= 8 entries a group's first entry lies at most
         // 31 x 8 = 248 blocks in, so only the offset count refuses one; the first-entry bytes are not uploaded (ELL values go by slot)
-        bool ok = !off && P.Nghost == 0 && R.lv[0].W <= 8;
+        bool ok = P.Nghost == 0 && R.lv[0].W <= 8;
         const int ng = (P.Nb + 31) / 32;
         StencilForm S;
         if (ok) reset_stencil(S, P.Nb, ng);
@@ -1351,12 +1308,12 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
     JD.omega = R.omega; JD.damp = R.damp; JD.beta = R.beta;
     CprHostLevel img0;
     std::vector<int> posg;
-    if (!ell_image(J, img0, posg, NG <= cpr_lpr_rows())) return fail(c, OPMHIP_ANALYSIS_FAILED, "cpr: a row of the joined level has %d entries (limit %d): lower opmhip_config.cpr_gather_rows' level count or raise the limit", img0.W, CPR_MAX_W);
+    if (!ell_image(J, img0, posg, NG <= CPR_LPR_ROWS)) return fail(c, OPMHIP_ANALYSIS_FAILED, "cpr: a row of the joined level has %d entries (limit %d): lower opmhip_config.cpr_gather_rows' level count or raise the limit", img0.W, CPR_MAX_W);
     JD.lv.emplace_back();
     // (from here on only device memory can fail, and on one rank alone: noted, agreed on at the end)
     note(upload_ell(c, img0, JD.lv[0]));
     CprHostCoarse HJ;
-    cpr_coarsen_host(J, posg, nullptr, nullptr, R.beta, cpr_lpr_rows(), 0, CPR_COARSE_DIRECT, HJ);
+    cpr_coarsen_host(J, posg, nullptr, nullptr, R.beta, CPR_LPR_ROWS, 0, CPR_COARSE_DIRECT, HJ);
     if (!lerr) note(cpr_upload_coarse(c, JD, HJ, false));
     // 7. what the solves need on the device
     G.nloc = nloc; G.off = offs[me]; G.NG = NG; G.maxn = maxn; G.maxnnz = maxnnz; G.nnzG = (int)J.col.size();
@@ -1400,7 +1357,7 @@ static int cpr_setup_coarse_now(opmhip_ctx* c) {
     int rc;
     if ((rc = cpr_download_level0(c, ell))) return rc;
     CprHostCoarse H;
-    cpr_build_coarse_host(c->pat, ell, R.beta, cpr_lpr_rows(), cpr_gathering(c) ? 0 : cpr_ilu_levels(c), cpr_stop_rows(c), H);
+    cpr_build_coarse_host(c->pat, ell, R.beta, CPR_LPR_ROWS, cpr_gathering(c) ? 0 : cpr_ilu_levels(c), cpr_stop_rows(c), H);
     const double t1 = now();
     const size_t mark = c->allocs.size();
     const bool gathered = cpr_gathering(c);
@@ -1524,10 +1481,10 @@ int cpr_update(opmhip_ctx* c, bool solveBoundary) {
         if ((rc = cpr_download_level0(c, *ell))) { R.job.reset(); prof_end(c, ps); return rc; }
         const Pattern* pat = &c->pat;   // outlives the job: cpr_release_structure / cpr_shutdown join it before the pattern goes
         const double beta = R.beta;
-        const int lpr = cpr_lpr_rows(), iluLevels = cpr_ilu_levels(c);
+        const int iluLevels = cpr_ilu_levels(c);
         CprAsyncJob* raw = job.get();
-        job->th = std::thread([raw, ell, pat, beta, lpr, iluLevels]() {
-            cpr_build_coarse_host(*pat, *ell, beta, lpr, iluLevels, CPR_COARSE_DIRECT, raw->result);
+        job->th = std::thread([raw, ell, pat, beta, iluLevels]() {
+            cpr_build_coarse_host(*pat, *ell, beta, CPR_LPR_ROWS, iluLevels, CPR_COARSE_DIRECT, raw->result);
             raw->ready.store(1, std::memory_order_release);
         });
     }
@@ -1541,39 +1498,38 @@ int cpr_update(opmhip_ctx* c, bool solveBoundary) {
 // is level l smoothed with its ILU0 (a level that has the schedule and is not the coarsest)?
 static bool cpr_ilu_active(const CprDev& R, size_t l) { return l + 1 < R.lv.size() && R.lv[l].ilu; }
 // v = (U^-1 L^-1) d with the level's ILU0: forward colour by colour, backward in reverse; out != NULL: out = add + v as the
-// backward sweeps store (and, vfine, the block vector (0, out, 0))
+// backward sweeps store
 template <bool BWD, int WQ>
-static void cpr_ilu_launch(opmhip_ctx* c, const CprLevelDev& L, int cc, const double* d, double* v, const double* add, double* out, double* vfine) {
+static void cpr_ilu_launch(opmhip_ctx* c, const CprLevelDev& L, int cc, const double* d, double* v, const double* add, double* out) {
     const int nseq = L.iluNseq[cc], nsteps = L.iluNsteps[cc], wq = BWD ? L.iluWu[cc] : L.iluWl[cc];
     const int* rowAt = L.d_rowAt + L.iluOff[cc];
     const double* fv = BWD ? L.d_iuv : L.d_ilv;
     const int* fc = BWD ? L.d_iuc : L.d_ilc;
     if (L.iluFast[cc] && WQ > 0 && nsteps > 1) {
         constexpr int G = WQ <= 4 ? 12 : WQ <= 6 ? 10 : 6;   // (WQ = 6, G = 10: about 440 registers, no spills - and one wavefront per SIMD is all a colour offers)
-        hipLaunchKernelGGL((k_cpr_ilu_sweep_fast<BWD, (WQ > 0 ? WQ : 1), G>), dim3((nseq + 63) / 64), dim3(64), 0, c->stream, nseq, nsteps, rowAt, L.n, wq, fv, fc, L.d_iud, d, (const double*)v, v, add, out, vfine, c->d_done);
-    } else hipLaunchKernelGGL((k_cpr_ilu_sweep<BWD, WQ>), g256(nseq), dim3(256), 0, c->stream, nseq, nsteps, rowAt, L.n, wq, fv, fc, L.d_iud, d, v, add, out, vfine, c->d_done);
+        hipLaunchKernelGGL((k_cpr_ilu_sweep_fast<BWD, (WQ > 0 ? WQ : 1), G>), dim3((nseq + 63) / 64), dim3(64), 0, c->stream, nseq, nsteps, rowAt, L.n, wq, fv, fc, L.d_iud, d, (const double*)v, v, add, out, c->d_done);
+    } else hipLaunchKernelGGL((k_cpr_ilu_sweep<BWD, WQ>), g256(nseq), dim3(256), 0, c->stream, nseq, nsteps, rowAt, L.n, wq, fv, fc, L.d_iud, d, v, add, out, c->d_done);
 }
 template <bool BWD>
-static void cpr_ilu_colour(opmhip_ctx* c, const CprLevelDev& L, int cc, const double* d, double* v, const double* add, double* out, double* vfine) {
+static void cpr_ilu_colour(opmhip_ctx* c, const CprLevelDev& L, int cc, const double* d, double* v, const double* add, double* out) {
     if (L.iluNseq[cc] == 0) return;
     const int wq = BWD ? L.iluWu[cc] : L.iluWl[cc];
-    if (wq <= 1) cpr_ilu_launch<BWD, 1>(c, L, cc, d, v, add, out, vfine);
-    else if (wq <= 2) cpr_ilu_launch<BWD, 2>(c, L, cc, d, v, add, out, vfine);
-    else if (wq <= 4) cpr_ilu_launch<BWD, 4>(c, L, cc, d, v, add, out, vfine);
-    else if (wq <= 6) cpr_ilu_launch<BWD, 6>(c, L, cc, d, v, add, out, vfine);
-    else if (wq <= 8) cpr_ilu_launch<BWD, 8>(c, L, cc, d, v, add, out, vfine);
-    else cpr_ilu_launch<BWD, 0>(c, L, cc, d, v, add, out, vfine);
+    if (wq <= 1) cpr_ilu_launch<BWD, 1>(c, L, cc, d, v, add, out);
+    else if (wq <= 2) cpr_ilu_launch<BWD, 2>(c, L, cc, d, v, add, out);
+    else if (wq <= 4) cpr_ilu_launch<BWD, 4>(c, L, cc, d, v, add, out);
+    else if (wq <= 6) cpr_ilu_launch<BWD, 6>(c, L, cc, d, v, add, out);
+    else if (wq <= 8) cpr_ilu_launch<BWD, 8>(c, L, cc, d, v, add, out);
+    else cpr_ilu_launch<BWD, 0>(c, L, cc, d, v, add, out);
 }
-static void cpr_ilu_smooth(opmhip_ctx* c, const CprLevelDev& L, const double* d, double* v, const double* add, double* out, double* vfine) {
+static void cpr_ilu_smooth(opmhip_ctx* c, const CprLevelDev& L, const double* d, double* v, const double* add, double* out) {
     const int nc = (int)L.iluNseq.size();
-    for (int cc = 0; cc < nc; ++cc) cpr_ilu_colour<false>(c, L, cc, d, v, nullptr, nullptr, nullptr);
-    for (int cc = nc - 1; cc >= 0; --cc) cpr_ilu_colour<true>(c, L, cc, d, v, add, out, vfine);
+    for (int cc = 0; cc < nc; ++cc) cpr_ilu_colour<false>(c, L, cc, d, v, nullptr, nullptr);
+    for (int cc = nc - 1; cc >= 0; --cc) cpr_ilu_colour<true>(c, L, cc, d, v, add, out);
 }
 // does level l (> 0) form its right-hand side itself, from the finer level's residual (cpr_restricted)?  Then no restriction
 // kernel runs between the two levels.  Lane-group levels do, and the dense solve of the coarsest level.
 static bool cpr_forms_rhs(const CprDev& R, size_t l) {
-    static const bool off = tuning_env("OPMHIP_CPR_UNFUSED") != nullptr;   // A/B switch: the restriction as a launch of its own
-    if (off || l == 0 || l >= R.lv.size() || !R.lv[l - 1].d_mem4) return false;
+    if (l == 0 || l >= R.lv.size() || !R.lv[l - 1].d_mem4) return false;
     if (R.gather.on && l + 1 == R.lv.size()) return false;   // the level that is gathered: its right-hand side is what travels
     return R.lv[l].rm || (l + 1 == R.lv.size() && R.coarse_direct);
 }
@@ -1585,9 +1541,8 @@ static bool cpr_presmooth_rides(const CprDev& R, size_t l) {
     if (l + 1 == R.lv.size()) return !R.coarse_direct;   // Jacobi coarse "solve": starts with the same statement
     return !L.rm;                                         // lane-group levels form it on the fly inside k_cpr_down_lpr
 }
-// one V(1,1) cycle on level l from x = 0; returns the buffer that holds the level's result (fineOut != NULL on level 0: the
-// result is written there as the block vector (0, x_p, 0) instead, and NULL comes back)
-static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l, double* fineOut = nullptr) {
+// one V(1,1) cycle on level l from x = 0; returns the buffer that holds the level's result
+static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l) {
     CprLevelDev& L = R.lv[l];
     const double* done = c->d_done;
     const bool fused = cpr_forms_rhs(R, l);           // b = restriction of the finer level's residual, formed by this level's first kernel
@@ -1615,7 +1570,7 @@ static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l, double* fine
     const bool ilu = cpr_ilu_active(R, l);
     const EllStencil S0{L.d_sword, L.d_stable};
     if (ilu) {   // pre-smoothing from x = 0 with the level's ILU0, then the residual
-        cpr_ilu_smooth(c, L, L.d_b, L.d_x, nullptr, nullptr, nullptr);
+        cpr_ilu_smooth(c, L, L.d_b, L.d_x, nullptr, nullptr);
         if (S0.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S0);
         else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S0);
     } else
@@ -1639,18 +1594,17 @@ static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l, double* fine
         hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, R.damp, L.d_agg, xc, L.d_x, L.d_r, done);
         if (S0.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_r, L.d_x, done, S0);
         else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_r, L.d_x, done, S0);
-        cpr_ilu_smooth(c, L, L.d_x, L.d_t, L.d_r, L.d_x2, fineOut);
-        return fineOut ? nullptr : L.d_x2;
+        cpr_ilu_smooth(c, L, L.d_x, L.d_t, L.d_r, L.d_x2);
+        return L.d_x2;
     }
     if (L.rm) hipLaunchKernelGGL(k_cpr_up_lpr, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, R.damp, L.d_ecol, L.d_val, L.d_dinv, L.d_agg, xc, L.d_b, L.d_x, L.d_x2, done);
     else {   // large levels: the prolonged iterate first (into the residual buffer, free by now), then one gathered value per entry
         hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, R.damp, L.d_agg, xc, L.d_x, L.d_r, done);
         {
             const EllStencil S{L.d_sword, L.d_stable};
-            if (S.word) hipLaunchKernelGGL(k_cpr_post<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, fineOut, done, S);
-            else hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, fineOut, done, S);
+            if (S.word) hipLaunchKernelGGL(k_cpr_post<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
+            else hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
         }
-        if (fineOut) return nullptr;
     }
     return L.d_x2;
 }
@@ -1692,7 +1646,7 @@ static const double* cpr_gathered_cycle(opmhip_ctx* c, const double* d) {
     prof_span_end(c, span);
     hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, 1.0, G.d_cagg, xG + G.off, L.d_x, L.d_r, done);   // x' = x + (the joined level's result, per aggregate)
     keep(comm_halo_f64(c, L.d_r, 1));
-    hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, (double*)nullptr, done, S);
+    hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
     keep(comm_halo_f64(c, L.d_x2, 1));
     return L.d_x2;
 }
@@ -1701,7 +1655,6 @@ static const double* cpr_gathered_cycle(opmhip_ctx* c, const double* d) {
 void launch_cpr_apply(opmhip_ctx* c, const double* d, double* v) {
     const Pattern& P = c->pat;
     CprDev& R = c->cpr;
-    const int n = P.Nb * BS;
     const double* done = c->d_done;
     int ps = prof_begin(c, PROF_CPR_AMG);
     if (R.gather.on) {
@@ -1722,26 +1675,6 @@ void launch_cpr_apply(opmhip_ctx* c, const double* d, double* v) {
     // v = (0, x_p, 0) + ILU0(d - A (0, x_p, 0)): the block vector (0, x_p, 0) itself is never formed - the residual kernel reads
     // x_p, and the backward sweeps of the smoother add their result to it as they store (second_result, solver.hip): the
     // expansion pass, the addition kernel and a 24-byte-per-row store of the post-smoothing are gone
-    static const bool separate = tuning_env("OPMHIP_CPR_SEPARATE_ADD") != nullptr;   // A/B switch: the three steps as kernels of their own
-    if (separate) {
-        const bool direct = R.lv.size() > 1 && !R.lv[0].rm;   // level 0's post-smoother writes v = (0, x_p, 0) itself
-        const double* xp = cpr_vcycle(c, R, 0, direct ? v : nullptr);
-        if (xp) hipLaunchKernelGGL(k_cpr_prolong_fine, g256(n), dim3(256), 0, c->stream, P.Nb, xp, v, done);
-        else xp = R.lv[0].d_x2;   // k_cpr_post left the pressure solution there as well
-        prof_end(c, ps);
-        ps = prof_begin(c, PROF_VECTOR);
-        {
-        const EllStencil S{R.lv[0].d_sword, R.lv[0].d_stable};
-        if (S.word) hipLaunchKernelGGL(k_cpr_presid<true>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, done, S);
-        else hipLaunchKernelGGL(k_cpr_presid<false>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, done, S);
-    }
-        prof_end(c, ps);
-        launch_ilu_apply(c, R.d_r, R.d_z, 1.0);                           // fine smoother: ILU0, relaxation 1
-        ps = prof_begin(c, PROF_VECTOR);
-        hipLaunchKernelGGL(k_cpr_add, g256(n), dim3(256), 0, c->stream, n, v, R.d_z, done);
-        prof_end(c, ps);
-        return;
-    }
     const double* xp = cpr_vcycle(c, R, 0);
     prof_end(c, ps);
     // post-smoothing on the updated residual r = d - A (0, x_p, 0)

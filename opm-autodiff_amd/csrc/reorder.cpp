@@ -352,8 +352,6 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
     if (!P.ualias || !P.chained) return;
     struct Rt { int r0, r1; };
     std::vector<int> offs;
-    static const int maxRows = [] { const char* e = tuning_env("OPMHIP_REST_ROWS"); const int v = e ? std::atoi(e) : 64; return v < 1 ? 1 : (v > 64 ? 64 : v); }();   // measurement switch: rows per tile at most
-    static const int maxBlocks = [] { const char* e = tuning_env("OPMHIP_REST_BLOCKS"); const int v = e ? std::atoi(e) : TILE_CAP_BLOCKS; return v < 8 ? 8 : (v > TILE_CAP_BLOCKS ? TILE_CAP_BLOCKS : v); }();
     std::vector<Rt> out;   // launch positions of both parts, padding = {0, 0}
     int nInt = 0;
     // Decomposed runs (ghost columns): the INTERIOR tiles take this form; the boundary tiles - rows with ghost columns at arbitrary offsets,
@@ -368,7 +366,7 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
                 if (order[b] < 0) continue;
                 const int r0 = T.row0[order[b]], r1 = T.row0[order[b] + 1];
                 if (r1 <= r0) continue;
-                if (cur.r1 > cur.r0 && r0 == cur.r1 && r1 - cur.r0 <= maxRows && P.rrowptr[r1] - P.rrowptr[cur.r0] <= maxBlocks) {
+                if (cur.r1 > cur.r0 && r0 == cur.r1 && r1 - cur.r0 <= 64 && P.rrowptr[r1] - P.rrowptr[cur.r0] <= TILE_CAP_BLOCKS) {
                     tile_offsets(P.rrowptr, P.rcol, cur.r0, r1, offs);
                     if (offs.size() <= 15) { cur.r1 = r1; continue; }
                 }
@@ -530,8 +528,7 @@ void build_ilu0_split(Pattern& P) {
     // symbolic elimination: which entries of row p the step against row j updates (k_ilu_factor looks them up instead of merging two
     // column lists per L entry - three dependent rounds of loads became one)
     P.lmatch.assign(P.nnzb, -2);
-    static const bool general = [] { const char* e = tuning_env("OPMHIP_FACTOR_GENERAL"); return e && e[0] == '1'; }();   // A/B switch: every step by the general search
-    for (int p = 0; p < Nb && !general; ++p) {
+    for (int p = 0; p < Nb; ++p) {
         const int kb = P.rowptr[p], ke = P.rowptr[p + 1];
         for (int k = kb; k < ke; ++k) {
             const int j = P.col[k];
@@ -912,11 +909,7 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
                 return fail(c, OPMHIP_ANALYSIS_FAILED, "line colouring: a chain-tile has %d steps (limit 128); lower the chain length", T.ctFirst[q + 1] - T.ctFirst[q]);
     }
 
-    {
-        // OPMHIP_XCD_GROUP: chain-tiles per XCD group of the launch schedules (0 = identity map); tuning knob, see DESIGN.md
-        const char* e = tuning_env("OPMHIP_XCD_GROUP");
-        build_schedules(P, e ? std::atoi(e) : OPMHIP_XCD_GROUP_DEFAULT);
-    }
+    build_schedules(P, OPMHIP_XCD_GROUP_DEFAULT);   // chain-tiles per XCD group of the launch schedules (0 = identity map), see DESIGN.md
     int rc;
     if ((rc = dev_upload(c, &P.tiles.d_spmvSched, P.tiles.spmvSched))) return rc;
     for (int part = 0; part < 2 && P.sweepStencil; ++part)

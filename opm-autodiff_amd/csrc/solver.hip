@@ -35,12 +35,8 @@ namespace opmhip {
 // in 16-KiB tiles reaches 6.2 TB/s with plain loads and 6.9 TB/s with nontemporal ones.
 typedef double v2d_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 ld_stream(const double2* p) {
-#if defined(OPMHIP_NO_NT_LOADS)
-    return *p;
-#else
     const v2d_t t = __builtin_nontemporal_load(reinterpret_cast<const v2d_t*>(p));
     return make_double2(t.x, t.y);
-#endif
 }
 // (round 6, measured and not kept: the sweeps' own once-read items - D^-1, the light sweeps' blocks, the right-hand side - as nontemporal
 // loads: one M^-1 0.143 -> 0.153 / 0.152 / 0.142 ms, all three 0.171; profiles/r06_nt_operands_ab.txt)
@@ -81,21 +77,9 @@ __device__ __forceinline__ void stage_ints(const int* __restrict__ src, int* __r
 #pragma unroll 4
     for (int i = lane; i < n; i += 64) dst[i] = src[i];
 }
-// Workgroup -> tile map.  Default: identity - measured on MI355X the round-robin dealing of consecutive workgroups
-// over the 8 XCDs streams the matrix through all 8 L2s at once and was faster (SpMV 0.112 vs 0.125 ms at 100^3) than
-// the XCD-contiguous map below, which keeps each XCD on one contiguous eighth of the tile range (b and b+8 share an
-// XCD) so that gathered vector entries stay in one 4 MB L2; build with -DOPMHIP_XCD_MAP to get it.  Speed only; any
-// placement gives the same result.
-__device__ __forceinline__ int xcd_tile(int b, int nt) {
-#if defined(OPMHIP_XCD_MAP)
-    const int chunk = (nt + 7) >> 3;
-    const int t = (b & 7) * chunk + (b >> 3);
-    return t;  // may be >= nt for the padded tail: callers check
-#else
-    (void)nt;
-    return b;
-#endif
-}
+// Workgroup b runs tile b: measured on MI355X, the round-robin dealing of consecutive workgroups over the 8 XCDs streams the
+// matrix through all 8 L2s at once and was faster (SpMV 0.112 vs 0.125 ms at 100^3) than an XCD-contiguous map that keeps
+// each XCD on one contiguous eighth of the tile range so that gathered vector entries stay in one 4 MB L2.
 
 // y -= A x, y += A x, y = A x in dune-common DenseMatrix order (row outer, column inner)
 __device__ __forceinline__ void blk_mmv(const double* A, const double x0, const double x1, const double x2, double* y) {
@@ -681,24 +665,18 @@ __global__ __launch_bounds__(64) void k_spmv_pipe_st(int npos, const int4* __res
         // the operands every row reads once per launch (the scalar products' second vectors, the backward sweep's row sums): nontemporal, so
         // that they do not push the gathered vector out of L2 - the rest product 0.0792 -> 0.0758 ms, +1.9 % Newton its/s in alternation
         // (profiles/r06_nt_operands_ab.txt); the result's stores stay plain (the vector kernel behind the product reads them at once)
-#ifdef OPMHIP_PLAIN_OPERANDS
-#define OPMHIP_LD1(p) (*(p))
-#else
-#define OPMHIP_LD1(p) __builtin_nontemporal_load(p)
-#endif
         if constexpr (NDOT >= 1) {
             const double* wr = &w0[(size_t)rr * BS];
-            b.ww[0] = OPMHIP_LD1(wr); b.ww[1] = OPMHIP_LD1(wr + 1); b.ww[2] = OPMHIP_LD1(wr + 2);
+            b.ww[0] = __builtin_nontemporal_load(wr); b.ww[1] = __builtin_nontemporal_load(wr + 1); b.ww[2] = __builtin_nontemporal_load(wr + 2);
         }
         if constexpr (NDOT == 3) {
             const double* wr = &w1[(size_t)rr * BS];
-            b.w2[0] = OPMHIP_LD1(wr); b.w2[1] = OPMHIP_LD1(wr + 1); b.w2[2] = OPMHIP_LD1(wr + 2);
+            b.w2[0] = __builtin_nontemporal_load(wr); b.w2[1] = __builtin_nontemporal_load(wr + 1); b.w2[2] = __builtin_nontemporal_load(wr + 2);
         }
         if constexpr (UADD) {
             const double* ur = &uadd[(size_t)rr * BS];
-            b.uu[0] = OPMHIP_LD1(ur); b.uu[1] = OPMHIP_LD1(ur + 1); b.uu[2] = OPMHIP_LD1(ur + 2);
+            b.uu[0] = __builtin_nontemporal_load(ur); b.uu[1] = __builtin_nontemporal_load(ur + 1); b.uu[2] = __builtin_nontemporal_load(ur + 2);
         }
-#undef OPMHIP_LD1
     };
     StW wq;
     StS sb;
@@ -783,7 +761,7 @@ __global__ __launch_bounds__(64) void k_ilu_sweep(int tile_begin, int ntc, int n
                                                   const double* __restrict__ d, double* __restrict__ vu, double* __restrict__ v,
                                                   const double* __restrict__ addp, int relax_mode, double w, const double* __restrict__ done) {
     TILE_LDS
-    const int lane = threadIdx.x, tl = xcd_tile(blockIdx.x, ntc);
+    const int lane = threadIdx.x, tl = blockIdx.x;
     if (tl >= ntc || *done != 0.0) return;
     const int t = tile_begin + tl;
     const int r0 = tile_row0[t], r1 = tile_row0[t + 1];
@@ -1789,13 +1767,6 @@ __device__ __forceinline__ void block_partials(double a, double b, double* part,
 // k_bicg_upd2) are read - and x written - nontemporally: they then do not take the place of the vectors the next kernels come back for
 // (p, r, s: the sweeps' right-hand sides) in L2 and the Infinity Cache.  One M^-1 0.145 -> 0.135 ms, +3 % Newton its/s in alternation
 // (profiles/r06_nt_operands_ab.txt).
-#ifdef OPMHIP_PLAIN_VEC
-#define OPMHIP_VLD(p) (*(p))
-#define OPMHIP_VST(v, p) (*(p) = (v))
-#else
-#define OPMHIP_VLD(p) __builtin_nontemporal_load(p)
-#define OPMHIP_VST(v, p) __builtin_nontemporal_store(v, p)
-#endif
 // (measured and not kept: r in the p-update likewise, the factorisation's L stores likewise - nothing either way)
 // r = rw = p = b, x = 0, partial b.b
 __global__ __launch_bounds__(VB) void k_bicg_init(int n, const double* __restrict__ b, double* __restrict__ r,
@@ -1823,7 +1794,7 @@ __global__ __launch_bounds__(VB) void k_bicg_pupdate(int n, const double* __rest
 #pragma unroll
     for (int u = 0; u < VPT; ++u) {
         const int e = base + u * VB;
-        if (e < n) p[e] = (p[e] - omega * OPMHIP_VLD(&v[e])) * beta + r[e];
+        if (e < n) p[e] = (p[e] - omega * __builtin_nontemporal_load(&v[e])) * beta + r[e];
     }
 }
 // r -= alpha v ; partial r.r.  The first half's "x += alpha pw" (bda/cusparseSolverBackend.cu:110) waits for the second
@@ -1843,7 +1814,7 @@ __global__ __launch_bounds__(VB) void k_bicg_upd1(int n, const double* __restric
     for (int u = 0; u < VPT; ++u) {
         const int e = base + u * VB;
         if (e < n) {
-            const double re = r[e] - alpha * OPMHIP_VLD(&v[e]);
+            const double re = r[e] - alpha * __builtin_nontemporal_load(&v[e]);
             r[e] = re;
             s += re * re;
         }
@@ -1875,9 +1846,9 @@ __global__ __launch_bounds__(VB) void k_bicg_upd2(int n, const double* __restric
     for (int u = 0; u < VPT; ++u) {
         const int e = base + u * VB;
         if (e < n) {
-            const double xh = OPMHIP_VLD(&x[e]) + alpha * (ws * OPMHIP_VLD(&pw[e]));   // the first half's update
-            OPMHIP_VST(xh + omega * (ws * OPMHIP_VLD(&sv[e])), &x[e]);
-            const double re = r[e] - omega * OPMHIP_VLD(&tv[e]);
+            const double xh = __builtin_nontemporal_load(&x[e]) + alpha * (ws * __builtin_nontemporal_load(&pw[e]));   // the first half's update
+            __builtin_nontemporal_store(xh + omega * (ws * __builtin_nontemporal_load(&sv[e])), &x[e]);
+            const double re = r[e] - omega * __builtin_nontemporal_load(&tv[e]);
             r[e] = re;
             s += re * re;
             q += rw[e] * re;
@@ -2243,17 +2214,13 @@ int launch_wells_recover(opmhip_ctx* c, const double* d_resWell, const double* x
 #define OPMHIP_SPMV_PIPE_WGS 2048
 #endif
 constexpr int SPMV_PIPE_WGS = OPMHIP_SPMV_PIPE_WGS;  // resident single-wave workgroups the pipelined SpMV is sized for (256 CUs x 8)
-static int spmv_pipe_env() {   // OPMHIP_SPMV_PIPE (tuning): 0 = off, n > 1 = workgroups the pipelined kernel is sized for
-    static const int v = [] { const char* e = tuning_env("OPMHIP_SPMV_PIPE"); return e ? std::atoi(e) : -1; }();
-    return v;
-}
 // cfg.spmv_pipe_wgs: resident workgroups the pipelined kernel is sized for (0 = default, < 0 = never use it)
 static int spmv_pipe_wgs(const opmhip_ctx* c) {
-    return c->cfg.spmv_pipe_wgs != 0 ? c->cfg.spmv_pipe_wgs : (spmv_pipe_env() > 1 ? spmv_pipe_env() : SPMV_PIPE_WGS);
+    return c->cfg.spmv_pipe_wgs != 0 ? c->cfg.spmv_pipe_wgs : SPMV_PIPE_WGS;
 }
 static bool spmv_pipelined(const opmhip_ctx* c) {
     const int w = spmv_pipe_wgs(c);
-    return c->pat.maxRowBlocks <= PGCH && w > 0 && c->pat.tiles.nsched > w && spmv_pipe_env() != 0;
+    return c->pat.maxRowBlocks <= PGCH && w > 0 && c->pat.tiles.nsched > w;
 }
 // opmhip_config.half_product resolved: > 0 wherever the pattern allows it (Pattern::ualias, a line-coloured ordering, the rest's stencil
 // form - RestSched::on); 0, the library's choice: there, where the system is large enough for the pipelined kernels (the size the form
@@ -2263,8 +2230,7 @@ bool half_product_wanted(const opmhip_ctx* c) {
     const Pattern& P = c->pat;
     if (!P.rest.on || c->cfg.half_product < 0 || use_cpr(c)) return false;   // (CPR: the product follows the two-level application, not a sweep)
     if (c->cfg.half_product > 0) return true;
-    static const bool off = [] { const char* e = tuning_env("OPMHIP_HALF_PRODUCT"); return e && e[0] == '0'; }();   // A/B switch
-    return !off && spmv_pipelined(c);
+    return spmv_pipelined(c);
 }
 // the scalar products ride in the product's kernel unless wells modify y after it (then k_dots forms them afterwards)
 static bool spmv_dots_env() {   // OPMHIP_DOTS_SEPARATE=1 (tuning / A-B measurements): k_dots behind every product, as with wells
@@ -2289,8 +2255,7 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
         // resident, all ending together; small systems: one tile per workgroup.
         const RestSched& R = P.rest;
         const int4* rsched = reinterpret_cast<const int4*>(R.d_sched) + p0;
-        static const int restWgs = [] { const char* e = tuning_env("OPMHIP_REST_WGS"); return e ? std::atoi(e) : 0; }();   // measurement switch
-        const int pipeWgs = restWgs > 0 ? restWgs : std::max(8, spmv_pipe_wgs(c));
+        const int pipeWgs = std::max(8, spmv_pipe_wgs(c));
         const int steps = std::min((np + pipeWgs - 1) / pipeWgs, PIPE_MAX_STEPS);
         const int grid = 8 * (((np + steps - 1) / steps + 7) / 8);
         const int* tab = R.d_table + (size_t)p0 * 16;
@@ -2311,9 +2276,8 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
         const int pipeWgs = spmv_pipe_wgs(c);
         const int steps = std::min((np + pipeWgs - 1) / pipeWgs, PIPE_MAX_STEPS);   // beyond that: more workgroups than are resident
         const int grid = 8 * (((np + steps - 1) / steps + 7) / 8);
-        static const bool explicitIdx = [] { const char* e = tuning_env("OPMHIP_SPMV_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch: the explicit index streams
         const bool inInt = p0 < P.tiles.nschedInt, inBnd = p0 + np > P.tiles.nschedInt;   // which parts of the schedule this launch covers
-        if ((!inInt || P.tiles.stencilPart[0]) && (!inBnd || P.tiles.stencilPart[1]) && !explicitIdx) {
+        if ((!inInt || P.tiles.stencilPart[0]) && (!inBnd || P.tiles.stencilPart[1])) {
             const StencilForm& S = P.tiles.st;
             const int* tab = S.d_table + (size_t)p0 * 16;
             if (ndot == 0)
@@ -2374,9 +2338,8 @@ static int ms_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) 
 int launch_spmv(opmhip_ctx* c, double* x, double* y, int ndot, const double* w0, double xs, bool exchange, const double* uadd, const double* w1) {
     const Pattern& P = c->pat;
     const bool wells = c->wells.num_wells > 0;
-    static const bool explicitIdx3 = [] { const char* e = tuning_env("OPMHIP_SPMV_EXPLICIT"); return e && e[0] == '1'; }();
     const bool bndPlain = uadd && P.Nghost > 0 && P.tiles.nsched > P.tiles.nschedInt;   // half-product form in a subdomain: its boundary tiles run the whole product
-    const bool plain3 = spmv_pipelined(c) && !explicitIdx3;                              // the plain pipelined stencil kernel can carry three sums
+    const bool plain3 = spmv_pipelined(c);                                               // the plain pipelined stencil kernel can carry three sums
     const bool rides3 = uadd ? (!bndPlain || (plain3 && P.tiles.stencilPart[1]))
                              : (plain3 && P.tiles.stencilPart[0] && (P.tiles.nsched == P.tiles.nschedInt || P.tiles.stencilPart[1]));
     const int fused = (spmv_dots_separate(c) || (ndot == 3 && !rides3)) ? 0 : ndot;
@@ -2473,8 +2436,7 @@ void launch_ilu_apply(opmhip_ctx* c, const double* d, double* v, double w_overri
         const int ds = P.tiles.descStride, S1 = P.tiles.descS1;
         auto desc = [&](int col) { return P.tiles.d_ctDesc + (size_t)P.tiles.ctSchedOff[col] * ds; };
         auto npos = [&](int col) { return P.tiles.ctSchedOff[col + 1] - P.tiles.ctSchedOff[col]; };
-        static const bool explicitIdx = [] { const char* e = tuning_env("OPMHIP_SWEEP_EXPLICIT"); return e && e[0] == '1'; }();   // A/B switch
-        const bool st = P.sweepStencil && !explicitIdx;   // column indices and row bounds of the heavy sweeps from the stencil form
+        const bool st = P.sweepStencil;   // column indices and row bounds of the heavy sweeps from the stencil form
         const SweepStencil SL{P.sw[0].d_word, P.sw[0].d_koff, P.sw[0].d_table}, SU{P.sw[1].d_word, P.sw[1].d_koff, P.sw[1].d_table};
         for (int col = 0; col < C - 1; ++col) {
             const int nct = npos(col);
