@@ -20,10 +20,11 @@ pytestmark = pytest.mark.gpu
 def zero_diag_fixed(Nb, rp, ci, v):
     """the matrix with the zero-diagonal fix both sides apply (bda/BdaBridge.cpp:125-161), so the oracle's factorisation sees it too"""
     v = np.array(v, np.float64).reshape(-1, 3, 3)
-    for i in range(Nb):
-        k = rp[i] + int(np.nonzero(ci[rp[i]:rp[i + 1]] == i)[0][0])
-        d = v[k][np.arange(3), np.arange(3)]
-        v[k][np.arange(3), np.arange(3)] = np.where(d == 0.0, 1e-15, d)
+    rp, ci = np.asarray(rp), np.asarray(ci)
+    dk = np.flatnonzero(ci == np.repeat(np.arange(Nb), np.diff(rp)))
+    assert len(dk) == Nb
+    d = v[dk][:, np.arange(3), np.arange(3)]
+    v[dk[:, None], np.arange(3), np.arange(3)] = np.where(d == 0.0, 1e-15, d)
     return np.ascontiguousarray(v.reshape(-1))
 
 
@@ -34,53 +35,143 @@ def padded(orc, Nb, rp, ci, v, f):
     fr = np.empty_like(to)
     fr[to] = np.arange(Nb, dtype=to.dtype)
     rr, rc, rv = orc.reorder_matrix(Nb, rp, ci, v, to, fr)
-    prp = np.zeros(Nb + 1, np.int32)
-    cols, lpos, dpos, upos = [], [], [], []
-    for p in range(Nb):
-        lc = f["lcol"][f["lrowptr"][p]:f["lrowptr"][p + 1]]
-        uc = f["ucol"][f["urowptr"][p]:f["urowptr"][p + 1]]
-        o = len(cols)
-        lpos.extend(range(o, o + len(lc)))
-        dpos.append(o + len(lc))
-        upos.extend(range(o + len(lc) + 1, o + len(lc) + 1 + len(uc)))
-        cols.extend(lc.tolist() + [p] + uc.tolist())
-        prp[p + 1] = len(cols)
-    pcl = np.array(cols, np.int32)
-    pv = np.zeros((len(cols), 3, 3))
-    rv3 = rv.reshape(-1, 3, 3)
-    for p in range(Nb):
-        row = pcl[prp[p]:prp[p + 1]]
-        for k in range(rr[p], rr[p + 1]):
-            pv[prp[p] + int(np.searchsorted(row, rc[k]))] = rv3[k]
-    return prp, pcl, np.ascontiguousarray(pv.reshape(-1)), (np.array(lpos), np.array(dpos), np.array(upos)), fr
+    lrp, urp = f["lrowptr"].astype(np.int64), f["urowptr"].astype(np.int64)
+    nl, nu = np.diff(lrp), np.diff(urp)
+    prp = np.zeros(Nb + 1, np.int64)
+    prp[1:] = np.cumsum(nl + 1 + nu)
+    lrow, urow = np.repeat(np.arange(Nb), nl), np.repeat(np.arange(Nb), nu)
+    lpos = prp[lrow] + np.arange(len(lrow)) - lrp[lrow]
+    dpos = prp[:-1] + nl
+    upos = prp[urow] + nl[urow] + 1 + np.arange(len(urow)) - urp[urow]
+    pcl = np.empty(int(prp[-1]), np.int32)
+    pcl[lpos], pcl[dpos], pcl[upos] = f["lcol"], np.arange(Nb), f["ucol"]
+    key = np.repeat(np.arange(Nb, dtype=np.int64), np.diff(prp)) * Nb + pcl          # ascending: rows, then L < diagonal < U
+    akey = np.repeat(np.arange(Nb, dtype=np.int64), np.diff(rr)) * Nb + rc
+    at = np.minimum(np.searchsorted(key, akey), len(key) - 1)
+    assert np.array_equal(key[at], akey)                        # every entry of A has its place in the filled pattern
+    pv = np.zeros((len(pcl), 3, 3))
+    pv[at] = rv.reshape(-1, 3, 3)
+    return prp.astype(np.int32), pcl, np.ascontiguousarray(pv.reshape(-1)), (lpos, dpos, upos), fr
 
 
-def check_against_oracle(pkg, orc, Nb, rp, ci, v, reorder, n=1, modes=(("post_scale", 0.9), ("in_sweep", 0.9))):
-    v = zero_diag_fixed(Nb, rp, ci, v)
+def _inv3(m):
+    """inverses of a stack of 3x3 blocks in the dtype given (np.linalg.inv has no extended precision)"""
+    a, b, c, d, e, g, h, i, k = (m[:, r, s] for r in range(3) for s in range(3))
+    co = np.stack([e * k - g * i, -(b * k - c * i), b * g - c * e,
+                   -(d * k - g * h), a * k - c * h, -(a * g - c * d),
+                   d * i - e * h, -(a * i - b * h), a * e - b * d], axis=1).reshape(-1, 3, 3)
+    det = a * co[:, 0, 0] + b * co[:, 1, 0] + c * co[:, 2, 0]
+    return co / det[:, None, None]
+
+
+def ilu_identity_error(prp, pcl, pv, lpos, dpos, upos, f, rows=None):
+    """the defining identity of ILU on its pattern, ((I + L)(D + U))_ij = A_ij for every (i, j) of the filled pattern, D = inv(invD),
+    all products formed in extended precision: -> max over the pattern of |A - (I + L)(D + U)| / (eps * bound), bound = the magnitudes
+    the rounding of the elimination can reach (|L||U| summed over k, the entry's own term, A) times the terms in the entry.  rows: a
+    boolean mask of the rows to check (every row by default; a row's identity needs only its own L and the U rows it meets)"""
+    ld = np.longdouble
+    Nb = len(prp) - 1
+    sel = np.ones(Nb, bool) if rows is None else np.asarray(rows, bool)
+    L, U, iD = f["L"].astype(ld), f["U"].astype(ld), f["invD"].astype(ld)
+    aL, aU, aiD = np.abs(f["L"]), np.abs(f["U"]), np.abs(f["invD"])
+    D = _inv3(iD)
+    aD = np.abs(D).astype(np.float64)
+    A = pv.reshape(-1, 3, 3).astype(ld)
+    aA = np.abs(pv.reshape(-1, 3, 3))
+    nnz = len(pcl)
+    key = np.repeat(np.arange(Nb, dtype=np.int64), np.diff(prp)) * Nb + pcl
+    lrow = np.repeat(np.arange(Nb, dtype=np.int64), np.diff(f["lrowptr"]))
+    lk = f["lcol"].astype(np.int64)
+    urp = f["urowptr"].astype(np.int64)
+    cnt = np.where(sel[lrow], urp[lk + 1] - urp[lk], 0)            # every L_ik meets row k of U
+    a = np.repeat(np.arange(len(lk)), cnt)
+    b = np.arange(len(a)) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(urp[lk], cnt)
+    tk = lrow[a] * Nb + f["ucol"][b]
+    at = np.minimum(np.searchsorted(key, tk), nnz - 1)
+    hit = key[at] == tk                                             # products that fall outside the pattern are dropped by ILU
+    a, b, at = a[hit], b[hit], at[hit]
+    S = np.zeros((nnz, 3, 3), ld)
+    M = np.zeros((nnz, 3, 3))
+    terms = np.zeros(nnz)
+    order = np.argsort(at, kind="stable")
+    a, b, at = a[order], b[order], at[order]
+    if len(at):
+        starts = np.flatnonzero(np.r_[True, at[1:] != at[:-1]])
+        S[at[starts]] = np.add.reduceat(np.matmul(L[a], U[b]), starts, axis=0)
+        M[at[starts]] = np.add.reduceat(np.matmul(aL[a], aU[b]), starts, axis=0)
+        terms[at[starts]] = np.diff(np.r_[starts, len(at)])
+    own = np.zeros((nnz, 3, 3), ld)
+    aown = np.zeros((nnz, 3, 3))
+    ls, us = sel[lrow], sel[np.repeat(np.arange(Nb), np.diff(f["urowptr"]))]
+    lp, lc, dp, up = lpos[ls], f["lcol"][ls], dpos[sel], upos[us]
+    own[lp] = np.matmul(L[ls], D[lc])
+    aown[lp] = np.matmul(np.matmul(aA[lp] + M[lp], aiD[lc]), aD[lc])
+    own[dp] = D[sel]
+    aown[dp] = np.matmul(np.matmul(aD[sel], aiD[sel]), aD[sel])
+    own[up] = U[us]
+    aown[up] = aU[us]
+    chk = np.repeat(sel, np.diff(prp))
+    R = np.abs(A[chk] - S[chk] - own[chk]).astype(np.float64)
+    bound = (3.0 * terms[chk] + 8.0)[:, None, None] * (M[chk] + aown[chk] + aA[chk]) * np.finfo(np.float64).eps
+    return float(np.max(R / np.maximum(bound, np.finfo(np.float64).tiny)))
+
+
+IDENTITY_ULPS = 4.0   # ilu_identity_error's bound is already a first-order rounding bound; a few of it
+
+
+def compare_factors(orc, s, Nb, rp, ci, v, mode, w, fill=True, identity=True, cache=None, identity_rows=None):
+    """the factors and one M^-1 application of context s (v, the matrix it factored - the zero-diagonal fix applied - uploaded or
+    assembled, factored) against the oracle's ILU0 of the permuted matrix padded to the filled pattern: bit for bit.  fill: True - the
+    pattern has fill, False - none, None - either.  identity: the ILU identity in extended precision as well.  cache: a dict that keeps
+    the padded matrix and the oracle's factors for the next call with the same filled pattern (another relaxation mode).  identity_rows:
+    check the identity on that many rows drawn at random (large systems: the products in extended precision are slow)"""
+    info = s.ilu_info()
+    assert not s.product_form()["half_product"] and not s.product_form()["u_is_upper_a"]
+    f = s.ilu_factors()
+    assert len(f["lcol"]) == info["nl"] and len(f["ucol"]) == info["nu"]
+    assert s.ordering_info()["colors"] == info["levels"]
+    same = cache is not None and "f" in cache and all(np.array_equal(cache["f"][k], f[k]) for k in ("to", "lrowptr", "lcol", "urowptr", "ucol"))
+    if same:
+        prp, pcl, pv, (lpos, dpos, upos), fr, lu_o = cache["padded"]
+    else:
+        prp, pcl, pv, (lpos, dpos, upos), fr = padded(orc, Nb, rp, ci, v, f)
+        lu_o = orc.ilu0_factor(Nb, prp, pcl, pv).reshape(-1, 3, 3)
+        if cache is not None:
+            cache.update(f=f, padded=(prp, pcl, pv, (lpos, dpos, upos), fr, lu_o))
+    if fill is not None:
+        assert (len(pcl) > len(ci)) == fill                     # there is fill / there is none
+    for dev, ora in ((f["L"], lu_o[lpos]), (f["U"], lu_o[upos]), (f["invD"], lu_o[dpos])):
+        np.testing.assert_allclose(dev, ora, rtol=1e-12, atol=1e-12 * max(np.abs(ora).max(initial=0.0), 1e-300))
+        assert np.array_equal(dev, ora)                         # same elimination order, same block products
+    if identity and not same:
+        rows = None
+        if identity_rows is not None and identity_rows < Nb:
+            rows = np.zeros(Nb, bool)
+            rows[np.random.default_rng(6).choice(Nb, identity_rows, replace=False)] = True
+        err = ilu_identity_error(prp, pcl, pv, lpos, dpos, upos, f, rows)
+        assert err <= IDENTITY_ULPS, err
+    to = f["to"]
+    d = np.random.default_rng(5).standard_normal(3 * Nb)
+    z = s.ilu0_apply(d)
+    zo = orc.ilu0_apply(Nb, prp, pcl, lu_o.reshape(-1), np.ascontiguousarray(d.reshape(Nb, 3)[fr].reshape(-1)), w=w, mode=mode)
+    assert np.array_equal(z, zo.reshape(Nb, 3)[to].reshape(-1))
+    return prp, pcl, pv, fr, to, f
+
+
+def check_against_oracle(pkg, orc, Nb, rp, ci, v, reorder, n=1, modes=(("post_scale", 0.9), ("in_sweep", 0.9)), fill=True, identity=False,
+                         device_fix=False):
+    """device_fix: the matrix goes up as it is and the library's zero-diagonal fix must make it the oracle's"""
+    vf = zero_diag_fixed(Nb, rp, ci, v)
+    cache = {}
     for mode, w in modes:
         s = pkg.capi.HipSolver(reorder=reorder, ilu_fillin_level=n, relax_mode=mode, ilu_relaxation=w)
         s.set_pattern(Nb, rp, ci)
-        info = s.ilu_info()
-        assert info["fill_level"] == n
-        assert not s.product_form()["half_product"] and not s.product_form()["u_is_upper_a"]
-        s.upload_system(v)
+        assert s.ilu_info()["fill_level"] == n
+        s.upload_system(np.array(v, np.float64) if device_fix else vf)
         s.ilu0_factor(want_factors=False)
-        f = s.ilu_factors()
-        assert len(f["lcol"]) == info["nl"] and len(f["ucol"]) == info["nu"]
-        assert s.ordering_info()["colors"] == info["levels"]
-        prp, pcl, pv, (lpos, dpos, upos), fr = padded(orc, Nb, rp, ci, v, f)
-        assert len(pcl) > len(ci)                                   # there is fill
-        lu_o = orc.ilu0_factor(Nb, prp, pcl, pv).reshape(-1, 3, 3)
-        for dev, ora in ((f["L"], lu_o[lpos]), (f["U"], lu_o[upos]), (f["invD"], lu_o[dpos])):
-            np.testing.assert_allclose(dev, ora, rtol=1e-12, atol=1e-12 * np.abs(ora).max())
-            assert np.array_equal(dev, ora)                         # same elimination order, same block products
-        to = f["to"]
-        d = np.random.default_rng(5).standard_normal(3 * Nb)
-        z = s.ilu0_apply(d)
-        zo = orc.ilu0_apply(Nb, prp, pcl, lu_o.reshape(-1), np.ascontiguousarray(d.reshape(Nb, 3)[fr].reshape(-1)), w=w, mode=mode)
-        assert np.array_equal(z, zo.reshape(Nb, 3)[to].reshape(-1))
+        prp, pcl, pv, fr, to, _ = compare_factors(orc, s, Nb, rp, ci, vf, mode, w, fill=fill, identity=identity, cache=cache)
         s.close()
-    return prp, pcl, pv, fr, to, v
+    return prp, pcl, pv, fr, to, vf
 
 
 def spe1_jacobian(pkg, orc):

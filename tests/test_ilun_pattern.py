@@ -70,9 +70,11 @@ def to_csr(rows):
 
 
 # ---- the rule, restated ---------------------------------------------------------------------------------------------------------------
-def fill_pattern(rows, n):
-    """rows: list of sets (ascending elimination order) -> list of dicts col -> generation"""
+def fill_pattern(rows, n, limit=None):
+    """rows: list of sets (ascending elimination order) -> list of dicts col -> generation; None as soon as the rows hold more than
+    `limit` entries (the memory guard's question, answered without filling the rest)"""
     F = []
+    total = 0
     for i, r in enumerate(rows):
         pat = {j: 0 for j in r}
         k = -1
@@ -86,6 +88,9 @@ def fill_pattern(rows, n):
                     if j >= k and g < n and j not in pat:
                         pat[j] = g + 1
         F.append(pat)
+        total += len(pat)
+        if limit is not None and total > limit:
+            return None
     return F
 
 
@@ -178,13 +183,15 @@ def natural_fill_of(res):
     return s
 
 
-def restated_fill(rows, base, n):
-    """the fill rule in the elimination order `base` (natural row -> position), back in natural numbering"""
+def restated_fill(rows, base, n, limit=None):
+    """the fill rule in the elimination order `base` (natural row -> position), back in natural numbering; None: more than `limit` entries"""
     N = len(rows)
     ib = np.empty(N, np.int64)
     ib[base] = np.arange(N)
     prow = [{int(base[j]) for j in rows[int(ib[b])]} for b in range(N)]
-    F = fill_pattern(prow, n)
+    F = fill_pattern(prow, n, limit)
+    if F is None:
+        return None
     return {(int(ib[b]), int(ib[j])) for b in range(N) for j in F[b]}
 
 
@@ -240,3 +247,50 @@ def test_memory_guard_refuses_ilu2_on_a_20_cube(harness, tmp_path):
     res = run(harness, tmp_path, [(grid(20, 20, 20), LEVEL, 2), (grid(20, 20, 20), LEVEL, 1)])
     assert res[0]["rc"] == -4            # OPMHIP_INVALID_ARGUMENT: refused, nothing allocated
     assert res[1]["rc"] == 0 and res[1]["levels"] > 20
+
+
+# ---- the exact-LU limit ---------------------------------------------------------------------------------------------------------------
+EXACT_GRIDS = [(6, 5, 1), (4, 3, 2), (5, 4, 3), (8, 6, 1), (1, 1, 30)]   # natural order: the complete fill fits 8 x nnzb
+
+
+def complete_fill(rows, base):
+    """the filled pattern of the complete LU by a plain dense boolean elimination of the pattern taken in the elimination order `base`
+    (natural row -> position), back in natural numbering"""
+    N = len(rows)
+    B = np.zeros((N, N), bool)
+    for i, r in enumerate(rows):
+        B[base[i], [base[j] for j in r]] = True
+    for k in range(N):
+        below = k + 1 + np.flatnonzero(B[k + 1:, k])
+        B[np.ix_(below, np.arange(k + 1, N))] |= B[k, k + 1:]
+    ib = np.empty(N, np.int64)
+    ib[base] = np.arange(N)
+    return {(int(ib[a]), int(ib[b])) for a, b in zip(*np.nonzero(B))}
+
+
+def test_fill_level_of_the_size_is_the_complete_lu(harness, tmp_path):
+    """n >= Nb: no generation reaches n, so the symbolic pass is the complete symbolic LU - in every ordering whose complete fill fits the
+    budget; where it does not, the guard refuses.  The elimination order comes from the same ordering at n = 1 (it does not depend on n)."""
+    kinds = (LEVEL, JP, GREEDY, LINE, AUTO, D2)
+    cases, shapes = [], []
+    for g in EXACT_GRIDS + [(6, 5, 4)]:   # (6, 5, 4): 5818 blocks of complete fill against a budget of 5536 in natural order
+        N = g[0] * g[1] * g[2]
+        for kind in kinds:
+            cases += [(grid(*g), kind, 1), (grid(*g), kind, N), (grid(*g), kind, N + 7)]
+            shapes.append(g)
+    results = run(harness, tmp_path, cases)
+    for q in range(0, len(cases), 3):
+        rows, kind, _ = cases[q]
+        r1, rN, rM = results[q:q + 3]
+        assert r1["rc"] == 0
+        full = complete_fill(rows, r1["base"])
+        assert full == restated_fill(rows, r1["base"], len(rows))       # the rule restated reaches the same limit
+        nnzb = sum(len(r) for r in rows)
+        for res in (rN, rM):
+            if len(full) > BUDGET * nnzb:
+                assert res["rc"] == -4, (kind, len(rows))
+                continue
+            assert res["rc"] == 0 and np.array_equal(res["base"], r1["base"])
+            assert natural_fill_of(res) == full, (kind, len(rows))
+        if kind == LEVEL:
+            assert (rN["rc"] == 0) == (shapes[q // 3] in EXACT_GRIDS)     # natural order: the complete LU fits the budget, but for (6, 5, 4)
