@@ -203,6 +203,9 @@ typedef struct opmhip_result {
  * setReordering to do) to pinned host memory after every product, calls ms_apply(ms_user, h_x, h_y) - which performs
  * y -= C^T (D^-1 (B x)) for every multisegment well, e.g. by looping MultisegmentWellContribution::apply(h_x, h_y) - and takes
  * h_y back.  num_wells counts the STANDARD wells only.  The callback runs on the calling thread, inside opmhip_solve_system.
+ * That round trip is the reference's shape and the default here; it drains the stream twice per product.  The alternative is the
+ * device-resident form of the same operator, opmhip_set_ms_wells below: the wells' arrays are handed over once, D is inverted on the
+ * device and every product applies the wells in one kernel, with no host in the loop.  A solve takes one form or the other, never both.
  *
  * Decomposed runs (ABI 9).  Cell indices are the rank's local ones and must be OWNED cells (< Nb).  By default Flow's partitioner keeps
  * every well inside one subdomain (--allow-distributed-wells=false, ebos/eclbasevanguard.hh:148-151): distributed = 0, each rank hands
@@ -233,6 +236,59 @@ typedef struct opmhip_wells {
     int distributed;         /* decomposed runs only (ignored on one rank); see above.  0: every well of the list lies inside this rank's
                               * subdomain; 1: the same list of wells on every rank, each rank with the perforations in ITS cells */
 } opmhip_wells;
+
+/* Multisegment wells, device-resident form (additive to ABI 11).  The constructor arguments of Opm::MultisegmentWellContribution
+ * (bda/MultisegmentWellContribution.hpp:95-117), concatenated over the wells; dim = 3, dim_wells = 4.  Well w has Mb = Mb_pointers[w + 1] -
+ * Mb_pointers[w] segments, M = 4 Mb scalar well equations and the blocks block_pointers[w] .. block_pointers[w + 1] - 1.
+ *   B and C share one blocked-CSR pattern (one 4 x 3 block per perforation): Brows holds, well after well, Mb + 1 block-row pointers RELATIVE
+ *   to the well's first block (so each well's part starts with 0; well w's part starts at Brows[Mb_pointers[w] + w]); Bcols the cell of
+ *   each block (natural order); the values are indexed as the reference's apply indexes them: Bvals[blk * 12 + j * 3 + k],
+ *   Cvals[blk * 12 + j + k * 3] (j the well equation in B, the cell equation in C).
+ *   D (M x M) in scalar CSC as UMFPack takes it: Dcol_pointers holds, well after well, M + 1 column pointers relative to the well's first
+ *   entry (well w's part starts at Dcol_pointers[4 * Mb_pointers[w] + w]); Drows / Dvals the entries, well w's from Dnnz_pointers[w] on.
+ *   Entries that name the same place are added up.
+ * opmhip_set_ms_wells takes the list over for EVERY operator application that follows - opmhip_solve_system with ILU0 / ILU(n) / CPR,
+ * opmhip_spmv, opmhip_preconditioned_product - until it is replaced or cleared (ms == NULL or num_ms_wells == 0).  It is independent of
+ * the per-solve opmhip_wells list (standard wells), which every call that takes one sets anew; the multisegment wells are applied in front
+ * of the standard wells, as in the CUDA back-end.  Flow rebuilds its wells for every solve over a fixed pattern: an array that arrives
+ * unchanged is not copied again, and D is inverted again only when Dvals (or the structure) changed.
+ * What the device does: per change of values one workgroup per well scatters D into a dense M x M array, eliminates it with PARTIAL
+ * PIVOTING (row exchanges over the whole column - D mixes flow and pressure rows of very different scale) and leaves the explicit D^-1
+ * (Gauss-Jordan), so that a product costs one dense matrix-vector product instead of M dependent substitution steps.  Per product one
+ * workgroup per well forms z1 = B (xs x) in the statement order of MultisegmentWellContribution.cpp:78-90, z2 = D^-1 z1, and
+ * y[cell] -= C^T z2 in the order of :97-108.  Where no cell is shared between two blocks of the list the updates of y are plain stores;
+ * otherwise they are atomic adds and the result is then defined up to the order of two additions (as for standard wells).
+ * Accuracy: that of an explicit inverse - a forward error of the order M eps cond(D) |z2|, NOT the componentwise bound of a pivoted solve;
+ * for a badly row-scaled D the two differ (numpy's inv(D) @ z shows the same).
+ * Size caps: a well may have at most OPMHIP_MS_WELLS_MAX_M scalar equations (its z1, z2 live in LDS, its dense D^-1 takes 8 M^2 bytes and
+ * the elimination is M^3 work for one workgroup) and the list's dense arrays at most OPMHIP_MS_WELLS_MAX_KIB KiB in all.  A list above
+ * either cap is refused (INVALID_ARGUMENT) and leaves no list set, so that the caller can fall back to the callback form.
+ * Refused with a text that names the reason: before the pattern is set (NOT_READY); INVALID_ARGUMENT for dim / dim_wells other than 3 / 4,
+ * a null array, inconsistent pointers, a cell outside [0, Nb), a well above the caps, a decomposed context (nranks > 1), and a SINGULAR D:
+ * a zero pivot is flagged on the device and reported by the next call that synchronises anyway - opmhip_solve_system, opmhip_spmv,
+ * opmhip_preconditioned_product, opmhip_get_ms_wells_info - which returns INVALID_ARGUMENT and clears the list; never a silent NaN.
+ * A solve that is handed opmhip_wells.num_ms_wells > 0 with a callback WHILE a device list is set is refused (INVALID_ARGUMENT): the
+ * operator would be applied twice. */
+#define OPMHIP_MS_WELLS_MAX_M 256      /* 64 segments */
+#define OPMHIP_MS_WELLS_MAX_KIB 32768  /* 32 MiB of dense D^-1 over the list: 64 wells of the largest size */
+typedef struct opmhip_ms_wells {
+    int num_ms_wells;
+    int dim, dim_wells;          /* 3, 4 */
+    const int* Mb_pointers;      /* [num_ms_wells+1] segment ranges */
+    const int* Brows;            /* [Mb_pointers[n] + n] per well Mb+1 block-row pointers, relative to the well's first block */
+    const int* block_pointers;   /* [num_ms_wells+1] block ranges */
+    const int* Bcols;            /* [nblocks] cell of each block */
+    const double* Bvals;         /* [nblocks*12] */
+    const double* Cvals;         /* [nblocks*12] */
+    const int* Dcol_pointers;    /* [4*Mb_pointers[n] + n] per well 4 Mb + 1 column pointers, relative to the well's first entry */
+    const int* Drows;            /* [Dnnz] scalar row inside the well */
+    const double* Dvals;         /* [Dnnz] */
+    const int* Dnnz_pointers;    /* [num_ms_wells+1] entry ranges */
+} opmhip_ms_wells;
+int opmhip_set_ms_wells(opmhip_ctx* ctx, const opmhip_ms_wells* ms);
+/* info[0] wells held on the device, info[1] the largest M = 4 Mb among them, info[2] device memory held for them in KiB (rounded up),
+ * info[3] inversions of the list done so far on this context (unchanged values are not factored again).  Reports a pending singular D. */
+int opmhip_get_ms_wells_info(opmhip_ctx* ctx, int info[4]);
 
 /* ---- lifetime ------------------------------------------------------------------------------------------ */
 void opmhip_default_config(opmhip_config* cfg);

@@ -73,6 +73,54 @@ class Wells(C.Structure):
                 ("num_ms_wells", C.c_int), ("ms_apply", MS_APPLY_FN), ("ms_user", C.c_void_p), ("distributed", C.c_int)]
 
 
+class MsWells(C.Structure):
+    """opmhip_ms_wells: multisegment wells for the device-resident form (opmhip_set_ms_wells)"""
+    _fields_ = [("num_ms_wells", C.c_int), ("dim", C.c_int), ("dim_wells", C.c_int), ("Mb_pointers", C.c_void_p), ("Brows", C.c_void_p),
+                ("block_pointers", C.c_void_p), ("Bcols", C.c_void_p), ("Bvals", C.c_void_p), ("Cvals", C.c_void_p),
+                ("Dcol_pointers", C.c_void_p), ("Drows", C.c_void_p), ("Dvals", C.c_void_p), ("Dnnz_pointers", C.c_void_p)]
+
+
+def _header_define(name):
+    with open(HEADER_PATH) as f:
+        return int(re.search(r"#define\s+%s\s+(\d+)" % name, f.read()).group(1))
+
+
+def ms_wells_caps():
+    """(largest M = 4 Mb of one well, KiB of dense D^-1 over the list) the device form takes: OPMHIP_MS_WELLS_MAX_M / _MAX_KIB of the header"""
+    return _header_define("OPMHIP_MS_WELLS_MAX_M"), _header_define("OPMHIP_MS_WELLS_MAX_KIB")
+
+
+def make_ms_wells(wells):
+    """list of per-well dicts(Brows [Mb+1], Bcols [nblk], Bvals [nblk*12], Cvals [nblk*12], Dcolptr [4 Mb+1], Drows [nnz], Dvals [nnz]) - the
+    constructor arguments of Opm::MultisegmentWellContribution, cells in natural order - -> (MsWells struct, keep-alive list).
+    Ragged input (lengths that do not fit each other) raises ValueError."""
+    if not wells:
+        return None, []
+    Mbp, blkp, nzp = [0], [0], [0]
+    cat = {k: [] for k in ("Brows", "Bcols", "Bvals", "Cvals", "Dcolptr", "Drows", "Dvals")}
+    for n, w in enumerate(wells):
+        a = {k: np.asarray(w[k]).reshape(-1) for k in cat}
+        Mb, nblk, nnz = len(a["Brows"]) - 1, len(a["Bcols"]), len(a["Dvals"])
+        if Mb < 1:
+            raise ValueError("multisegment well %d: Brows needs Mb + 1 >= 2 entries" % n)
+        if a["Brows"][0] != 0 or a["Brows"][-1] != nblk or np.any(np.diff(a["Brows"]) < 0):
+            raise ValueError("multisegment well %d: Brows must rise from 0 to the number of blocks (%d)" % (n, nblk))
+        if len(a["Bvals"]) != 12 * nblk or len(a["Cvals"]) != 12 * nblk:
+            raise ValueError("multisegment well %d: Bvals / Cvals need 12 values per block (%d blocks)" % (n, nblk))
+        if len(a["Dcolptr"]) != 4 * Mb + 1:
+            raise ValueError("multisegment well %d: Dcolptr needs 4 Mb + 1 = %d entries, has %d" % (n, 4 * Mb + 1, len(a["Dcolptr"])))
+        if len(a["Drows"]) != nnz or a["Dcolptr"][0] != 0 or a["Dcolptr"][-1] != nnz or np.any(np.diff(a["Dcolptr"]) < 0):
+            raise ValueError("multisegment well %d: Dcolptr must rise from 0 to len(Dvals) = len(Drows)" % n)
+        for k in cat:
+            cat[k].append(a[k])
+        Mbp.append(Mbp[-1] + Mb)
+        blkp.append(blkp[-1] + nblk)
+        nzp.append(nzp[-1] + nnz)
+    keep = [_i32(Mbp), _i32(np.concatenate(cat["Brows"])), _i32(blkp), _i32(np.concatenate(cat["Bcols"])), _f64(np.concatenate(cat["Bvals"])),
+            _f64(np.concatenate(cat["Cvals"])), _i32(np.concatenate(cat["Dcolptr"])), _i32(np.concatenate(cat["Drows"])), _f64(np.concatenate(cat["Dvals"])), _i32(nzp)]
+    return MsWells(len(wells), 3, 4, *[_ptr(k) for k in keep]), keep
+
+
 def declared_symbols():
     """Every function name include/opmhip.h declares."""
     with open(HEADER_PATH) as f:
@@ -121,6 +169,8 @@ def lib():
         L.opmhip_get_product_form.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_set_ilu_fillin_level.argtypes = [vp, C.c_int]
         L.opmhip_get_ilu_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.opmhip_set_ms_wells.argtypes = [vp, C.POINTER(MsWells)]
+        L.opmhip_get_ms_wells_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_get_ilu_factors.argtypes = [vp, ip, ip, ip, ip, ip, dp, dp, dp]
         L.opmhip_time_kernel.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.opmhip_cpr_levels.argtypes = [vp, ip, ip, C.c_int]
@@ -344,6 +394,18 @@ class HipSolver:
 
     def set_ilu_fillin_level(self, n):
         self._check(lib().opmhip_set_ilu_fillin_level(self._h, int(n)))
+
+    def set_ms_wells(self, wells):
+        """opmhip_set_ms_wells: the multisegment wells (list of dicts, see make_ms_wells) on the device for every operator application that
+        follows; None or an empty list clears them"""
+        ms, keep = make_ms_wells(wells)
+        self._check(lib().opmhip_set_ms_wells(self._h, C.byref(ms) if ms else None))
+
+    def ms_wells_info(self):
+        """opmhip_get_ms_wells_info: wells on the device, largest M = 4 Mb, device KiB held for them, inversions done so far"""
+        info = (C.c_int * 4)()
+        self._check(lib().opmhip_get_ms_wells_info(self._h, C.byref(info)))
+        return {"wells": int(info[0]), "max_m": int(info[1]), "kib": int(info[2]), "factorisations": int(info[3])}
 
     def ilu_info(self):
         """opmhip_get_ilu_info: fill level in force, blocks of L and U, levels (colours) per sweep"""

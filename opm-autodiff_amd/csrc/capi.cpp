@@ -88,6 +88,9 @@ static int upload_wells_local(opmhip_ctx* c, const opmhip_wells* w) {
         // what the library needs is the callback and two pinned vectors for the round trip (bda/WellContributions.cu:160-187)
         if (!w->ms_apply) return fail(c, OPMHIP_INVALID_ARGUMENT, "wells: num_ms_wells = %d but ms_apply == NULL", w->num_ms_wells);
         if (c->comm.nranks > 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "wells: multisegment wells through the host callback are not supported in decomposed runs");
+        if (W.ms.num > 0)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "wells: num_ms_wells = %d with a callback while a device-resident list of %d multisegment wells is set "
+                        "(opmhip_set_ms_wells): the operator would be applied twice", w->num_ms_wells, W.ms.num);
         const size_t bytes = (size_t)c->pat.Nb * BS * sizeof(double);
         if (!W.h_x) OPMHIP_HIP(c, hipHostMalloc((void**)&W.h_x, bytes));
         if (!W.h_y) OPMHIP_HIP(c, hipHostMalloc((void**)&W.h_y, bytes));
@@ -167,6 +170,38 @@ static int upload_wells_local(opmhip_ctx* c, const opmhip_wells* w) {
     if (!same_d(W.h_C, w->Cnnzs, (size_t)np * 12) && (rc = put_d(W.d_C, W.h_C, w->Cnnzs, (size_t)np * 12))) return rc;
     if (!same_d(W.h_B, w->Bnnzs, (size_t)np * 12) && (rc = put_d(W.d_B, W.h_B, w->Bnnzs, (size_t)np * 12))) return rc;
     W.nperf = np;
+    return OPMHIP_SUCCESS;
+}
+
+// ---- multisegment wells on the device (opmhip_set_ms_wells) ----
+static void ms_wells_clear(opmhip_ctx* c) {
+    MsWellsDev& S = c->wells.ms;
+    S.num = S.maxM = 0;
+    S.flag_pending = false;
+}
+static void ms_wells_release(opmhip_ctx* c) {
+    MsWellsDev& S = c->wells.ms;
+    ms_wells_clear(c);
+    S.atomic = false;
+    dev_free(c, &S.d_desc); dev_free(c, &S.d_Brows); dev_free(c, &S.d_cell); dev_free(c, &S.d_blkrow); dev_free(c, &S.d_Dcolp); dev_free(c, &S.d_Drows);
+    dev_free(c, &S.d_flag); dev_free(c, &S.d_B); dev_free(c, &S.d_C); dev_free(c, &S.d_Dvals); dev_free(c, &S.d_inv);
+    S.bytes = 0;
+    S.h_Mbp.clear(); S.h_Brows.clear(); S.h_blkp.clear(); S.h_Bcols.clear(); S.h_Dcolp.clear(); S.h_Drows.clear(); S.h_Dnzp.clear();
+    S.h_Bvals.clear(); S.h_Cvals.clear(); S.h_Dvals.clear();
+}
+// The pivot flags of the last inversion, looked at where the host waits for the stream anyway (the caller has just synchronised, or this
+// does): a singular D clears the list and is INVALID_ARGUMENT - the operator is never applied with a broken inverse.
+static int ms_wells_check(opmhip_ctx* c) {
+    MsWellsDev& S = c->wells.ms;
+    if (!S.flag_pending) return OPMHIP_SUCCESS;
+    OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+    S.flag_pending = false;
+    for (int w = 0; w < S.num; ++w)
+        if (S.h_flag[w] != 0) {
+            const int col = S.h_flag[w] - 1;
+            ms_wells_release(c);
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: D of multisegment well %d is singular (no non-zero pivot in column %d of its elimination); the list is cleared", w, col);
+        }
     return OPMHIP_SUCCESS;
 }
 
@@ -341,6 +376,7 @@ void opmhip_destroy(opmhip_ctx* c) {
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->wells.h_x) (void)hipHostFree(c->wells.h_x);
     if (c->wells.h_y) (void)hipHostFree(c->wells.h_y);
+    if (c->wells.ms.h_flag) (void)hipHostFree(c->wells.ms.h_flag);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -413,6 +449,7 @@ int opmhip_solve_system(opmhip_ctx* c, int N, int nnz, int dim, double* vals, co
         const bool zfix = !vals && c->cfg.zero_diag_fix;   // device-assembled Jacobian: the same fix-up as the uploaded one gets
         if ((rc = upload_wells(c, wells))) return rc;
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if ((rc = ms_wells_check(c))) return rc;   // a device-resident multisegment list whose D turned out singular
         const double t1 = now();
         FactorRider rider;   // CPR: weights and level 0's values of the pressure hierarchy are formed while the rows are in LDS
         if ((rc = cpr_factor_rider(c, &rider))) return rc;
@@ -588,6 +625,7 @@ int opmhip_spmv(opmhip_ctx* c, const double* x, double* y) {
         if (!c->system_loaded) return fail(c, OPMHIP_NOT_READY, "spmv before a matrix was uploaded");
         OPMHIP_HIP(c, hipSetDevice(c->device));
         int rc;
+        if ((rc = ms_wells_check(c))) return rc;
         if ((rc = vec_in(c, x, c->d_pw))) return rc;
         if ((rc = launch_spmv(c, c->d_pw, c->d_v, 0, nullptr, 1.0, true))) return rc;
         OPMHIP_HIP(c, hipGetLastError());
@@ -635,6 +673,7 @@ int opmhip_preconditioned_product(opmhip_ctx* c, const double* d, double* t, dou
         if (!c->factored) return fail(c, OPMHIP_NOT_READY, "preconditioned_product before ilu0_factor");
         OPMHIP_HIP(c, hipSetDevice(c->device));
         int rc;
+        if ((rc = ms_wells_check(c))) return rc;
         if ((rc = vec_in(c, d, c->d_p))) return rc;
         // BiCGStab's statements for one half iteration (solver.hip: enqueue_half): the sweeps leave the vector without the relaxation factor,
         // the product applies it; with the half-product form the backward sweeps' row sums go along
@@ -719,6 +758,153 @@ int opmhip_get_ordering_info(opmhip_ctx* c, int info[4]) {
     info[2] = P.numColors;
     info[3] = cpr_ilu_levels_in_force(c);
     return OPMHIP_SUCCESS;
+}
+
+int opmhip_set_ms_wells(opmhip_ctx* c, const opmhip_ms_wells* ms) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        MsWellsDev& S = c->wells.ms;
+        if (!ms || ms->num_ms_wells == 0) {   // cleared: the arrays stay for the next list
+            OPMHIP_HIP(c, hipSetDevice(c->device));
+            if (S.flag_pending) OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+            ms_wells_clear(c);
+            S.h_Dvals.clear();   // (a list that comes back is inverted again)
+            return OPMHIP_SUCCESS;
+        }
+        if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "set_ms_wells before the pattern is set (the cells are translated to the ILU ordering)");
+        if (c->comm.nranks > 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: multisegment wells on the device are not supported in decomposed runs");
+        const int nw = ms->num_ms_wells;
+        if (nw < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: negative well count");
+        if (ms->dim != 3 || ms->dim_wells != 4) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: dim = %d, dim_wells = %d; only 3 and 4 are supported", ms->dim, ms->dim_wells);
+        if (!ms->Mb_pointers || !ms->Brows || !ms->block_pointers || !ms->Bcols || !ms->Bvals || !ms->Cvals || !ms->Dcol_pointers || !ms->Drows || !ms->Dvals || !ms->Dnnz_pointers)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: null array");
+        // a refused list leaves none in force: the caller falls back to the callback form
+        auto refuse = [&](int rc) { ms_wells_clear(c); S.h_Dvals.clear(); return rc; };
+        if (ms->Mb_pointers[0] != 0 || ms->block_pointers[0] != 0 || ms->Dnnz_pointers[0] != 0)
+            return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (Mb_pointers, block_pointers and Dnnz_pointers start at 0)"));
+        std::vector<MsWellDesc> desc(nw);
+        size_t invDoubles = 0;
+        int maxM = 0;
+        for (int w = 0; w < nw; ++w) {
+            const int Mb = ms->Mb_pointers[w + 1] - ms->Mb_pointers[w], nblk = ms->block_pointers[w + 1] - ms->block_pointers[w];
+            const int nnz = ms->Dnnz_pointers[w + 1] - ms->Dnnz_pointers[w];
+            if (Mb < 1 || nblk < 0 || nnz < 0) return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (well %d: %d segments, %d blocks, %d entries of D)", w, Mb, nblk, nnz));
+            if (4 * (long long)Mb > OPMHIP_MS_WELLS_MAX_M)
+                return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d has %d segments, M = %lld > OPMHIP_MS_WELLS_MAX_M = %d: above the size cap of the device form (use the callback form)",
+                                   w, Mb, 4 * (long long)Mb, OPMHIP_MS_WELLS_MAX_M));
+            MsWellDesc& d = desc[w];
+            d.Mb = Mb; d.nblk = nblk;
+            d.seg0 = ms->Mb_pointers[w] + w; d.blk0 = ms->block_pointers[w];
+            d.dcol0 = 4 * ms->Mb_pointers[w] + w; d.dnz0 = ms->Dnnz_pointers[w];
+            d.inv0 = (int)invDoubles;
+            invDoubles += (size_t)16 * Mb * Mb;
+            if (invDoubles * sizeof(double) > (size_t)OPMHIP_MS_WELLS_MAX_KIB * 1024)
+                return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: the dense D^-1 of the list exceed OPMHIP_MS_WELLS_MAX_KIB = %d KiB at well %d: above the size cap of the device form (use the callback form)",
+                                   OPMHIP_MS_WELLS_MAX_KIB, w));
+            maxM = std::max(maxM, 4 * Mb);
+            const int* br = ms->Brows + d.seg0;
+            bool ok = br[0] == 0 && br[Mb] == nblk;
+            for (int r = 0; r < Mb && ok; ++r) ok = br[r] <= br[r + 1];
+            const int* cp = ms->Dcol_pointers + d.dcol0;
+            ok = ok && cp[0] == 0 && cp[4 * Mb] == nnz;
+            for (int q = 0; q < 4 * Mb && ok; ++q) ok = cp[q] <= cp[q + 1];
+            if (!ok) return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (Brows or Dcol_pointers of well %d)", w));
+            for (int k = 0; k < nnz; ++k) {
+                if (ms->Drows[d.dnz0 + k] < 0 || ms->Drows[d.dnz0 + k] >= 4 * Mb)
+                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d, entry %d of D: row %d outside [0, %d)", w, k, ms->Drows[d.dnz0 + k], 4 * Mb));
+                if (!std::isfinite(ms->Dvals[d.dnz0 + k]))
+                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d, entry %d of D is not finite", w, k));
+            }
+        }
+        const size_t nseg = (size_t)ms->Mb_pointers[nw], nblk = (size_t)ms->block_pointers[nw], nnz = (size_t)ms->Dnnz_pointers[nw];
+        for (size_t k = 0; k < nblk; ++k)
+            if (ms->Bcols[k] < 0 || ms->Bcols[k] >= c->pat.Nb)
+                return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: block %zu: cell %d out of range [0, %d)", k, ms->Bcols[k], c->pat.Nb));
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        auto same_i = [](const std::vector<int>& h, const int* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(int)) == 0); };
+        auto same_d = [](const std::vector<double>& h, const double* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(double)) == 0); };
+        const bool structure = S.d_desc && same_i(S.h_Mbp, ms->Mb_pointers, (size_t)nw + 1) && same_i(S.h_Brows, ms->Brows, nseg + nw) && same_i(S.h_blkp, ms->block_pointers, (size_t)nw + 1) &&
+                               same_i(S.h_Bcols, ms->Bcols, nblk) && same_i(S.h_Dcolp, ms->Dcol_pointers, 4 * nseg + nw) && same_i(S.h_Drows, ms->Drows, nnz) &&
+                               same_i(S.h_Dnzp, ms->Dnnz_pointers, (size_t)nw + 1);
+        const bool sB = structure && same_d(S.h_Bvals, ms->Bvals, nblk * 12), sC = structure && same_d(S.h_Cvals, ms->Cvals, nblk * 12);
+        const bool sD = structure && same_d(S.h_Dvals, ms->Dvals, nnz);
+        int rc;
+        if (!(structure && sB && sC && sD)) OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels on the stream may still read what the copies below replace
+        if (!structure) {
+            // a new list: the index arrays anew, cells in the internal order, per block its segment row, and whether two blocks meet in a cell
+            ms_wells_release(c);
+            std::vector<int> cell(nblk), blkrow(nblk);
+            std::vector<char> seen((size_t)c->pat.Nb, 0);
+            bool shared = false;
+            for (int w = 0; w < nw; ++w) {
+                const int* br = ms->Brows + desc[w].seg0;
+                for (int r = 0; r < desc[w].Mb; ++r)
+                    for (int k = br[r]; k < br[r + 1]; ++k) blkrow[(size_t)desc[w].blk0 + k] = r;
+            }
+            for (size_t k = 0; k < nblk; ++k) {
+                cell[k] = c->pat.toOrder[ms->Bcols[k]];
+                if (seen[(size_t)ms->Bcols[k]]) shared = true;
+                seen[(size_t)ms->Bcols[k]] = 1;
+            }
+            if (!S.h_flag || S.cap_flag < (size_t)nw) {
+                if (S.h_flag) (void)hipHostFree(S.h_flag);
+                S.h_flag = nullptr;
+                OPMHIP_HIP(c, hipHostMalloc((void**)&S.h_flag, (size_t)nw * sizeof(int)));
+                S.cap_flag = (size_t)nw;
+            }
+            auto up_i = [&](int** d, const int* p, size_t n) -> int {
+                int r = dev_alloc(c, d, n);
+                if (r) return r;
+                if (n > 0) OPMHIP_HIP(c, hipMemcpy(*d, p, n * sizeof(int), hipMemcpyHostToDevice));
+                return OPMHIP_SUCCESS;
+            };
+            if ((rc = dev_alloc(c, &S.d_desc, (size_t)nw))) return refuse(rc);
+            OPMHIP_HIP(c, hipMemcpy(S.d_desc, desc.data(), (size_t)nw * sizeof(MsWellDesc), hipMemcpyHostToDevice));
+            if ((rc = up_i(&S.d_Brows, ms->Brows, nseg + nw)) || (rc = up_i(&S.d_cell, cell.data(), nblk)) || (rc = up_i(&S.d_blkrow, blkrow.data(), nblk)) ||
+                (rc = up_i(&S.d_Dcolp, ms->Dcol_pointers, 4 * nseg + nw)) || (rc = up_i(&S.d_Drows, ms->Drows, nnz)) || (rc = dev_alloc(c, &S.d_flag, (size_t)nw)) ||
+                (rc = dev_alloc(c, &S.d_B, nblk * 12)) || (rc = dev_alloc(c, &S.d_C, nblk * 12)) || (rc = dev_alloc(c, &S.d_Dvals, nnz)) || (rc = dev_alloc(c, &S.d_inv, invDoubles))) {
+                ms_wells_release(c);
+                return rc;
+            }
+            S.bytes = (size_t)nw * sizeof(MsWellDesc) + sizeof(int) * (nseg + nw + 2 * nblk + 4 * nseg + nw + nnz + nw) + sizeof(double) * (nblk * 24 + nnz + invDoubles);
+            S.atomic = shared;
+            S.h_Mbp.assign(ms->Mb_pointers, ms->Mb_pointers + nw + 1); S.h_Brows.assign(ms->Brows, ms->Brows + nseg + nw);
+            S.h_blkp.assign(ms->block_pointers, ms->block_pointers + nw + 1); S.h_Bcols.assign(ms->Bcols, ms->Bcols + nblk);
+            S.h_Dcolp.assign(ms->Dcol_pointers, ms->Dcol_pointers + 4 * nseg + nw); S.h_Drows.assign(ms->Drows, ms->Drows + nnz);
+            S.h_Dnzp.assign(ms->Dnnz_pointers, ms->Dnnz_pointers + nw + 1);
+        }
+        // a failed copy leaves the record of that array empty: the next call copies it again
+        auto put_d = [&](double* d, std::vector<double>& h, const double* p, size_t n) -> int {
+            h.clear();
+            if (n > 0) OPMHIP_HIP(c, hipMemcpy(d, p, n * sizeof(double), hipMemcpyHostToDevice));
+            h.assign(p, p + n);
+            return OPMHIP_SUCCESS;
+        };
+        if (!sB && (rc = put_d(S.d_B, S.h_Bvals, ms->Bvals, nblk * 12))) return refuse(rc);
+        if (!sC && (rc = put_d(S.d_C, S.h_Cvals, ms->Cvals, nblk * 12))) return refuse(rc);
+        if (!sD && (rc = put_d(S.d_Dvals, S.h_Dvals, ms->Dvals, nnz))) return refuse(rc);
+        S.num = nw;
+        S.maxM = maxM;
+        if (!sD) {
+            launch_ms_wells_factor(c);
+            OPMHIP_HIP(c, hipGetLastError());
+        }
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_ms_wells_info(opmhip_ctx* c, int info[4]) {
+    if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        int rc;
+        if ((rc = ms_wells_check(c))) return rc;
+        const MsWellsDev& S = c->wells.ms;
+        info[0] = S.num;
+        info[1] = S.maxM;
+        info[2] = S.num > 0 ? (int)((S.bytes + 1023) / 1024) : 0;
+        info[3] = S.factorisations;
+        return OPMHIP_SUCCESS;
+    });
 }
 
 int opmhip_set_ilu_fillin_level(opmhip_ctx* c, int n) {

@@ -149,6 +149,32 @@ struct Pattern {
 // ILU(n) memory guard: the filled factors (L, U and the diagonal, in blocks) may hold at most this many times the blocks of the matrix
 constexpr int ILUN_BUDGET_FACTOR = 8;
 
+// Multisegment wells in their device-resident form (opmhip_set_ms_wells): a list that stays until it is replaced or cleared, beside the
+// per-solve WellsDev.  Per well one descriptor; D^-1 dense and COLUMN-major (element (i, j) of well w at inv[inv0 + j * M + i]) - the
+// elimination's lanes and the product's threads both run down a column.
+struct MsWellDesc {
+    int Mb, nblk;      // segments, blocks
+    int seg0;          // well's part of Brows (Mb + 1 entries)
+    int blk0;          // first block
+    int dcol0, dnz0;   // well's part of Dcol_pointers (4 Mb + 1 entries), first entry of D
+    int inv0;          // first double of the dense D^-1
+};
+struct MsWellsDev {
+    int num = 0, maxM = 0;
+    bool atomic = false;         // some cell is shared between two blocks of the list: y is updated by atomic adds
+    bool flag_pending = false;   // an inversion was enqueued whose pivot flags have not been looked at yet
+    int factorisations = 0;
+    size_t bytes = 0;            // device memory held
+    MsWellDesc* d_desc = nullptr;
+    int *d_Brows = nullptr, *d_cell = nullptr, *d_blkrow = nullptr, *d_Dcolp = nullptr, *d_Drows = nullptr, *d_flag = nullptr;
+    double *d_B = nullptr, *d_C = nullptr, *d_Dvals = nullptr, *d_inv = nullptr;
+    int* h_flag = nullptr;       // pinned, one int per well: 0, or 1 + the column whose pivot was zero
+    size_t cap_flag = 0;
+    // the list as handed over last time (natural cell numbers): what arrives unchanged is not copied again
+    std::vector<int> h_Mbp, h_Brows, h_blkp, h_Bcols, h_Dcolp, h_Drows, h_Dnzp;
+    std::vector<double> h_Bvals, h_Cvals, h_Dvals;
+};
+
 struct WellsDev {
     int num_wells = 0, nperf = 0;
     int *d_val_pointers = nullptr, *d_Ccols = nullptr, *d_Bcols = nullptr;
@@ -168,7 +194,8 @@ struct WellsDev {
     opmhip_ms_apply_fn ms_apply = nullptr;
     void* ms_user = nullptr;
     double *h_x = nullptr, *h_y = nullptr;   // pinned, Nb * 3 doubles each, natural order
-    bool any() const { return num_wells > 0 || num_ms > 0; }
+    MsWellsDev ms;   // ... or on the device, in the same place (opmhip_set_ms_wells)
+    bool any() const { return num_wells > 0 || num_ms > 0 || ms.num > 0; }
 };
 
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
@@ -610,6 +637,7 @@ void cpr_shutdown(opmhip_ctx* c);   // joins a structure build in flight (before
 bool cpr_coarse_pivot_failed(opmhip_ctx* c);
 int cpr_ilu_levels_in_force(const opmhip_ctx* c);   // opmhip_config.cpr_amg_ilu_levels with "< 0: the library's choice" resolved (0 without CPR)
 inline bool use_cpr(const opmhip_ctx* c) { return c->cfg.preconditioner == OPMHIP_PRECOND_CPR_QUASIIMPES || c->cfg.preconditioner == OPMHIP_PRECOND_CPR_TRUEIMPES; }
+void launch_ms_wells_factor(opmhip_ctx* c);   // D -> D^-1 of every well of the device-resident multisegment list; pivot flags to MsWellsDev::d_flag
 int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs = 1.0);   // distributed wells: one all-reduce inside
 void launch_lu_to_natural(opmhip_ctx* c, double* d_out_internal_layout);
 int bicgstab(opmhip_ctx* c, opmhip_result* res);

@@ -1707,6 +1707,141 @@ __global__ __launch_bounds__(64) void k_wells_recover(const int* __restrict__ vp
     }
 }
 
+// ---- multisegment wells on the device (opmhip_set_ms_wells) ----
+// D -> D^-1, one workgroup per well: D is scattered from its CSC form into the well's dense M x M array (column-major, M = 4 Mb <= MSW_MAX_M),
+// eliminated in place by Gauss-Jordan steps with partial pivoting - the pivot of step k is the largest entry of column k in rows k .. M - 1,
+// the smaller row number where two are equal - and the columns are put back in the reverse order of the row exchanges, which leaves the
+// explicit inverse.  Per step: column k to LDS (the multipliers), the pivot search by the first wavefront, the pivot row scaled to LDS while
+// the old row k moves to its place, then every entry's update - wavefronts over the columns, lanes down a column.  A zero (or non-finite)
+// pivot ends the well's elimination: flag[w] = 1 + k, read by the host where it synchronises next; 0 otherwise.
+constexpr int MSW_MAX_M = OPMHIP_MS_WELLS_MAX_M;
+constexpr int MSW_FACTOR_THREADS = 512, MSW_APPLY_THREADS = 1024;
+static_assert(MSW_MAX_M % 64 == 0 && MSW_MAX_M <= MSW_APPLY_THREADS, "k_ms_wells_apply: one thread per well equation and part of the columns");
+__global__ __launch_bounds__(MSW_FACTOR_THREADS) void k_ms_wells_factor(const MsWellDesc* __restrict__ desc, const int* __restrict__ Dcolp,
+                                                                        const int* __restrict__ Drows, const double* __restrict__ Dvals,
+                                                                        double* __restrict__ inv, int* __restrict__ flag) {
+    __shared__ double col[MSW_MAX_M], rs[MSW_MAX_M];
+    __shared__ int piv[MSW_MAX_M];
+    __shared__ int s_p;
+    const MsWellDesc d = desc[blockIdx.x];
+    const int M = 4 * d.Mb, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    constexpr int T = MSW_FACTOR_THREADS, WAVES = MSW_FACTOR_THREADS / 64;
+    double* W = inv + d.inv0;
+    for (int e = t; e < M * M; e += T) W[e] = 0.0;
+    __syncthreads();
+    for (int c = t; c < M; c += T) {   // one thread per column: entries that name the same place are added in their order
+        const int* cp = Dcolp + d.dcol0;
+        for (int k = cp[c]; k < cp[c + 1]; ++k) W[c * M + Drows[d.dnz0 + k]] += Dvals[d.dnz0 + k];
+    }
+    __syncthreads();
+    for (int k = 0; k < M; ++k) {
+        for (int i = t; i < M; i += T) col[i] = W[k * M + i];
+        __syncthreads();
+        if (wave == 0) {
+            double best = -1.0;
+            int bi = M;
+            for (int i = k + lane; i < M; i += 64) {
+                const double a = fabs(col[i]);
+                if (a > best) { best = a; bi = i; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off);
+                const int oi = __shfl_xor(bi, off);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            }
+            if (lane == 0) s_p = (best > 0.0 && best <= 1.7976931348623157e308) ? bi : -1;
+        }
+        __syncthreads();
+        const int p = s_p;
+        if (p < 0) {   // (the same for every thread)
+            if (t == 0) flag[blockIdx.x] = k + 1;
+            return;
+        }
+        const double pv = col[p];
+        for (int j = t; j < M; j += T) {
+            const double a = W[j * M + p];
+            rs[j] = (j == k) ? 1.0 / pv : a / pv;
+            if (p != k) W[j * M + p] = W[j * M + k];
+        }
+        if (t == 0) piv[k] = p;
+        __syncthreads();
+        const double rk = rs[k];
+        for (int j = wave; j < M; j += WAVES) {
+            const double rj = rs[j];
+            for (int i = lane; i < M; i += 64) {
+                double* w = W + j * M + i;
+                if (i == k) { *w = rj; continue; }
+                const double f = (i == p) ? col[k] : col[i];   // (the row that stands at p now is the old row k)
+                *w = (j == k) ? -(f * rk) : *w - f * rj;
+            }
+        }
+        __syncthreads();
+    }
+    for (int k = M - 1; k >= 0; --k) {   // thread i touches row i alone: no barrier between the exchanges
+        const int p = piv[k];
+        if (p == k) continue;
+        for (int i = t; i < M; i += T) {
+            const double a = W[k * M + i];
+            W[k * M + i] = W[p * M + i];
+            W[p * M + i] = a;
+        }
+    }
+    if (t == 0) flag[blockIdx.x] = 0;
+}
+// y -= C^T (D^-1 (B (xs x))) for the wells of the list, one workgroup per well, z1 and z2 in LDS:
+// z1 = B (xs x): per segment row its blocks in ascending order, each block's sum over k formed first (MultisegmentWellContribution.cpp:78-90);
+// z2 = D^-1 z1: thread i forms row i's sum over one part of the columns (the parts: MSW_APPLY_THREADS / (M rounded up to 64) equal ranges,
+//      so that a well of any size keeps every wavefront loading), the parts are added in their order;
+// y[cell] -= C^T z2 per block (:97-108).  ATOMIC: a cell is shared between two blocks of the list - their updates meet: atomic adds.
+template <bool ATOMIC>
+__global__ __launch_bounds__(MSW_APPLY_THREADS) void k_ms_wells_apply(const MsWellDesc* __restrict__ desc, const int* __restrict__ Brows,
+                                                                      const int* __restrict__ cell, const int* __restrict__ blkrow,
+                                                                      const double* __restrict__ B, const double* __restrict__ C,
+                                                                      const double* __restrict__ inv, const double* __restrict__ x,
+                                                                      double* __restrict__ y, double xs) {
+    __shared__ double z1[MSW_MAX_M], z2[MSW_MAX_M], part[MSW_APPLY_THREADS];
+    const MsWellDesc d = desc[blockIdx.x];
+    const int M = 4 * d.Mb, t = threadIdx.x;
+    if (t < M) {
+        const int row = t >> 2, j = t & 3;
+        const int* br = Brows + d.seg0;
+        double z = 0.0;
+        for (int blk = d.blk0 + br[row]; blk < d.blk0 + br[row + 1]; ++blk) {
+            const double* xb = x + (size_t)cell[blk] * 3;
+            double temp = 0.0;
+            for (int k = 0; k < 3; ++k) temp += B[(size_t)blk * 12 + j * 3 + k] * (xs * xb[k]);
+            z += temp;
+        }
+        z1[t] = z;
+    }
+    __syncthreads();
+    const int M64 = (M + 63) & ~63, nsplit = MSW_APPLY_THREADS / M64, chunk = (M + nsplit - 1) / nsplit;
+    const int sp = t / M64, i = t - sp * M64;
+    if (sp < nsplit && i < M) {
+        const double* W = inv + d.inv0 + i;
+        const int j0 = sp * chunk, j1 = min(M, j0 + chunk);
+        double s = 0.0;
+        for (int j = j0; j < j1; ++j) s += W[j * M] * z1[j];
+        part[sp * M64 + i] = s;
+    }
+    __syncthreads();
+    if (t < M) {
+        double s = part[t];
+        for (int q = 1; q < nsplit; ++q) s += part[q * M64 + t];
+        z2[t] = s;
+    }
+    __syncthreads();
+    for (int e = t; e < d.nblk * 3; e += MSW_APPLY_THREADS) {
+        const int blk = d.blk0 + e / 3, j = e % 3;
+        const double* zz = z2 + blkrow[blk] * 4;
+        double temp = 0.0;
+        for (int k = 0; k < 4; ++k) temp += C[(size_t)blk * 12 + j + k * 3] * zz[k];
+        double* yp = y + (size_t)cell[blk] * 3 + j;
+        if (ATOMIC) atomicAdd(yp, -temp);
+        else *yp -= temp;
+    }
+}
+
 // A(Ccols[c], Bcols[b]) += -C_c^T (D^-1 B_b) for every perforation pair (c, b) of well w0 + blockIdx.x
 // (StandardWell::addWellContributions, wells/StandardWell_impl.hpp:1688-1712; sums in the order of Detail::multMatrix
 // and Detail::negativeMultMatrixTransposed, linalg/MatrixBlock.hpp:496-570).  entry[] holds, per pair, the position of
@@ -2172,6 +2307,21 @@ void launch_lu_to_natural(opmhip_ctx* c, double* d_out) {
     hipLaunchKernelGGL(k_lu_to_bcrs, dim3(cdiv((size_t)P.Nb, 256)), dim3(256), 0, c->stream, P.Nb, P.d_rowptr, P.d_col, P.d_lrowptr,
                        P.d_urowptr, c->d_L, c->d_U, c->d_invD, d_out);
 }
+void launch_ms_wells_factor(opmhip_ctx* c) {
+    MsWellsDev& S = c->wells.ms;
+    hipLaunchKernelGGL(k_ms_wells_factor, dim3(S.num), dim3(MSW_FACTOR_THREADS), 0, c->stream, S.d_desc, S.d_Dcolp, S.d_Drows, S.d_Dvals, S.d_inv, S.d_flag);
+    (void)hipMemcpyAsync(S.h_flag, S.d_flag, (size_t)S.num * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    S.flag_pending = true;
+    S.factorisations++;
+}
+// the device-resident multisegment wells, in the place of the host round trip: no copy, no synchronisation
+static void launch_ms_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
+    const MsWellsDev& S = c->wells.ms;
+    if (S.atomic)
+        hipLaunchKernelGGL(k_ms_wells_apply<true>, dim3(S.num), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
+    else
+        hipLaunchKernelGGL(k_ms_wells_apply<false>, dim3(S.num), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
+}
 int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
     const WellsDev& W = c->wells;
     if (W.num_wells <= 0) return OPMHIP_SUCCESS;
@@ -2309,7 +2459,8 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
 // Multisegment wells: y -= C^T (D^-1 (B (xs x))) on the HOST, by the caller's objects (opmhip_wells.ms_apply) - x and y to pinned memory in
 // the natural order, the callback, y back: the round trip the reference's back-ends make after every product
 // (bda/WellContributions.cu:160-187; MultisegmentWellContribution::apply, bda/MultisegmentWellContribution.cpp:70-110).  The stream is
-// drained twice per product; a deck with multisegment wells pays what it pays in the reference.
+// drained twice per product: a deck whose multisegment wells come this way pays what it pays in the reference.  The alternative is the
+// device-resident list of opmhip_set_ms_wells (k_ms_wells_factor / k_ms_wells_apply): the same operator with no host in the loop.
 static int ms_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
     WellsDev& W = c->wells;
     const size_t n = (size_t)c->pat.Nb * BS;
@@ -2365,6 +2516,7 @@ int launch_spmv(opmhip_ctx* c, double* x, double* y, int ndot, const double* w0,
         if (nBnd > 0) cnt += launch_spmv_part(c, bnd0, nBnd, x, y, fused, w0, xs, cnt, bndPlain ? PROF_SPMV_BOUNDARY : PROF_SPMV, uBnd, w1);
     }
     if (c->wells.num_ms > 0 && (rc = ms_wells_apply(c, x, y, xs))) return rc;   // in front of the standard wells, bda/WellContributions.cu:160-187
+    if (c->wells.ms.num > 0) launch_ms_wells_apply(c, x, y, xs);               // ... or the list on the device, in the same place
     if (wells && (rc = launch_wells_apply(c, x, y, xs))) return rc;
     if (fused == 0 && ndot > 0) {
         const int n = P.Nb * BS;

@@ -39,7 +39,8 @@ public:
                                  std::vector<unsigned>& BrowPointers, unsigned DnumBlocks, double* Dvalues, UMFPackIndex* DcolPointers,
                                  UMFPackIndex* DrowIndices, std::vector<double>& Cvalues)
         : dim(dim_), dim_wells(dim_wells_), M(Mb_ * dim_wells_), Mb(Mb_), Cvals(std::move(Cvalues)), Bvals(std::move(Bvalues)),
-          Bcols(std::move(BcolIndices)), Brows(std::move(BrowPointers)), z1(M), z2(M), lu((size_t)M * M, 0.0), piv(M) {
+          Bcols(std::move(BcolIndices)), Brows(std::move(BrowPointers)), z1(M), z2(M), lu((size_t)M * M, 0.0), piv(M),
+          Dcols(DcolPointers, DcolPointers + M + 1), Drows(DrowIndices, DrowIndices + DcolPointers[M]), Dvals(Dvalues, Dvalues + DcolPointers[M]) {
         (void)DnumBlocks;
         for (unsigned c = 0; c < M; ++c)
             for (int k = DcolPointers[c]; k < DcolPointers[c + 1]; ++k) lu[(size_t)DrowIndices[k] * M + c] += Dvalues[k];
@@ -89,6 +90,13 @@ public:
             }
     }
     void setReordering(int* toOrder_, bool reorder_) { toOrder = toOrder_; reorder = reorder_; }
+    // the read-only accessor INTEGRATION.md's patch adds to the reference class: the constructor's arguments as the object keeps them
+    // (D's CSC arrays included), for a back-end that applies the well on the device (opmhip_set_ms_wells)
+    void getHostArrays(unsigned* Mb_, const unsigned** Brows_, const unsigned** Bcols_, const double** Bvals_, const double** Cvals_,
+                       const UMFPackIndex** DcolPointers_, const UMFPackIndex** DrowIndices_, const double** Dvals_) const {
+        *Mb_ = Mb; *Brows_ = Brows.data(); *Bcols_ = Bcols.data(); *Bvals_ = Bvals.data(); *Cvals_ = Cvals.data();
+        *DcolPointers_ = Dcols.data(); *DrowIndices_ = Drows.data(); *Dvals_ = Dvals.data();
+    }
 private:
     unsigned getColIdx(unsigned idx) const { return reorder ? (unsigned)toOrder[idx] : idx; }
     unsigned dim, dim_wells, M, Mb;
@@ -96,6 +104,8 @@ private:
     std::vector<unsigned> Bcols, Brows;
     std::vector<double> z1, z2, lu;
     std::vector<unsigned> piv;
+    std::vector<UMFPackIndex> Dcols, Drows;   // D as it arrived (CSC)
+    std::vector<double> Dvals;
     int* toOrder = nullptr;
     bool reorder = false;
 };
@@ -119,6 +129,7 @@ public:
     // the accessors INTEGRATION.md's patch adds to the reference class (num_std_wells and the list are private there)
     unsigned getNumStdWells() const { return numWells; }
     unsigned getNumMSWells() const { return (unsigned)multisegments.size(); }
+    const MultisegmentWellContribution& getMSWell(unsigned i) const { return *multisegments[i]; }
     void applyMSWellsHost(double* h_x, double* h_y) {   // the loop of WellContributions.cu:175-178 / WellContributions.cpp:128-132, natural order
         for (auto& well : multisegments) {
             well->setReordering(nullptr, false);

@@ -17,8 +17,10 @@
 #else
 #include "BdaCompat.hpp"
 #endif
+#include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/opmhip.h"
 
@@ -34,6 +36,48 @@ class hipSolverBackend : public BdaSolver<block_size> {
     opmhip_ctx* ctx = nullptr;
     opmhip_wells wells{};
     bool haveWells = false;
+    // --- multisegment wells on the device (ms_wells_on_device): the objects' arrays concatenated in the form opmhip_ms_wells takes
+    bool msOnDevice = false, msDeviceSet = false, msFallbackSaid = false;
+    std::vector<int> msMbp, msBrows, msBlkp, msBcols, msDcolp, msDrows, msDnzp;
+    std::vector<double> msBvals, msCvals, msDvals;
+    // true: the list is on the device; false: the library refused it (size cap) and the callback form is to be used
+    bool setMsWellsOnDevice(WellContributions& wellContribs) {
+        const unsigned n = wellContribs.getNumMSWells();
+        msMbp.assign(1, 0); msBlkp.assign(1, 0); msDnzp.assign(1, 0);
+        msBrows.clear(); msBcols.clear(); msDcolp.clear(); msDrows.clear(); msBvals.clear(); msCvals.clear(); msDvals.clear();
+        for (unsigned w = 0; w < n; ++w) {
+            unsigned Mb = 0;
+            const unsigned *Brows = nullptr, *Bcols = nullptr;
+            const double *Bv = nullptr, *Cv = nullptr, *Dv = nullptr;
+            const Opm::MultisegmentWellContribution::UMFPackIndex *Dcp = nullptr, *Dri = nullptr;
+            wellContribs.getMSWell(w).getHostArrays(&Mb, &Brows, &Bcols, &Bv, &Cv, &Dcp, &Dri, &Dv);
+            const size_t nblk = Brows[Mb], nnz = (size_t)Dcp[4 * Mb];
+            msBrows.insert(msBrows.end(), Brows, Brows + Mb + 1);
+            msBcols.insert(msBcols.end(), Bcols, Bcols + nblk);
+            msBvals.insert(msBvals.end(), Bv, Bv + nblk * 12);
+            msCvals.insert(msCvals.end(), Cv, Cv + nblk * 12);
+            msDcolp.insert(msDcolp.end(), Dcp, Dcp + 4 * Mb + 1);
+            msDrows.insert(msDrows.end(), Dri, Dri + nnz);
+            msDvals.insert(msDvals.end(), Dv, Dv + nnz);
+            msMbp.push_back(msMbp.back() + (int)Mb);
+            msBlkp.push_back(msBlkp.back() + (int)nblk);
+            msDnzp.push_back(msDnzp.back() + (int)nnz);
+        }
+        opmhip_ms_wells ms{};
+        ms.num_ms_wells = (int)n;
+        ms.dim = 3; ms.dim_wells = 4;
+        ms.Mb_pointers = msMbp.data(); ms.Brows = msBrows.data(); ms.block_pointers = msBlkp.data(); ms.Bcols = msBcols.data();
+        ms.Bvals = msBvals.data(); ms.Cvals = msCvals.data(); ms.Dcol_pointers = msDcolp.data(); ms.Drows = msDrows.data();
+        ms.Dvals = msDvals.data(); ms.Dnnz_pointers = msDnzp.data();
+        const int rc = opmhip_set_ms_wells(ctx, &ms);
+        if (rc == OPMHIP_SUCCESS) return true;
+        if (rc != OPMHIP_INVALID_ARGUMENT) throw std::logic_error(std::string("hipSolverBackend: ") + opmhip_last_error(ctx));
+        if (verbosity >= 1 && !msFallbackSaid) {
+            std::fprintf(stderr, "hipSolverBackend: multisegment wells stay on the host callback: %s\n", opmhip_last_error(ctx));
+            msFallbackSaid = true;
+        }
+        return false;
+    }
 
 public:
     /// ilu_reorder as --opencl-ilu-reorder: "auto" (default: the library's measured choice - line colouring on large structured grids,
@@ -43,11 +87,13 @@ public:
     /// linsolver as --linear-solver-configuration: "ilu0" | "cpr_quasiimpes" | "cpr" = "cpr_trueimpes" (setupPropertyTree.cpp:46-138).
     /// The true-IMPES variant needs the model's storage term: the caller hands the result of
     /// ISTLSolverEbos::getTrueImpesWeights (ISTLSolverEbos.hpp:466-475) to setCprWeights() before each solve.
+    /// ms_wells_on_device: multisegment wells are handed to the library once per solve and applied on the device (opmhip_set_ms_wells) instead
+    /// of through the host round trip after every product; a list the library refuses (its size cap) falls back to the callback.
     hipSolverBackend(int linear_solver_verbosity, int maxit_, double tolerance_, unsigned int deviceID_,
                      const std::string& ilu_reorder = "auto", double ilu_relaxation = 0.9,
                      const std::string& linsolver = "ilu0", int cpr_reuse_setup = 3, int cpr_amg_ilu_levels = -1, int cpr_gather_rows = 0,
-                     int ilu_fillin_level = 0)
-        : Base(linear_solver_verbosity, maxit_, tolerance_, deviceID_) {
+                     int ilu_fillin_level = 0, bool ms_wells_on_device = false)
+        : Base(linear_solver_verbosity, maxit_, tolerance_, deviceID_), msOnDevice(ms_wells_on_device) {
         static_assert(block_size == 3, "libopmhip handles 3x3 blocks (three-phase black-oil)");
         opmhip_config cfg;
         opmhip_default_config(&cfg);
@@ -104,6 +150,18 @@ public:
         // belong to the standard ones only.  Multisegment wells stay what they are in the reference - host objects with a sparse LU of D -
         // and are applied through the host round trip of its back-ends (bda/WellContributions.cu:160-187): the library calls back.
         opmhip_wells* wp = nullptr;
+        if (msOnDevice) {
+            if (wellContribs.getNumMSWells() > 0 && !this->initialized) {
+                // the device list names cells, which the library translates to its ordering: the pattern first (solve_system's own first-call branch)
+                const int rcp = opmhip_set_pattern(ctx, N_ / 3, nnz_ / 9, rows, cols);
+                if (rcp != OPMHIP_SUCCESS) return rcp == OPMHIP_INVALID_ARGUMENT ? SolverStatus::BDA_SOLVER_UNKNOWN_ERROR : SolverStatus::BDA_SOLVER_ANALYSIS_FAILED;
+                this->initialized = true;
+            }
+            if (wellContribs.getNumMSWells() == 0 && msDeviceSet) {   // the wells of an earlier solve are gone
+                opmhip_set_ms_wells(ctx, nullptr);
+                msDeviceSet = false;
+            }
+        }
         if (wellContribs.getNumWells() > 0) {
             wells = opmhip_wells{};
             wells.num_wells = (int)wellContribs.getNumStdWells();
@@ -122,6 +180,11 @@ public:
 #endif
             }
             wells.num_ms_wells = (int)wellContribs.getNumMSWells();
+            // on the device: the list goes over before the solve (unchanged arrays are not copied again) and the solve's own list names none
+            if (wells.num_ms_wells > 0 && msOnDevice) {
+                msDeviceSet = setMsWellsOnDevice(wellContribs);
+                if (msDeviceSet) wells.num_ms_wells = 0;
+            }
             if (wells.num_ms_wells > 0) {
                 wells.ms_user = &wellContribs;
                 wells.ms_apply = [](void* user, const double* h_x, double* h_y) {

@@ -2,10 +2,12 @@
 // (MatrixMarket, ISTL_STRUCT blocked 3 3), run bda::hipSolverBackend<3>::solve_system + get_result with tol / maxit
 // from the command line, print the solution.  The expected vector is checked by the calling pytest
 // (tests/test_gpu_host_cpp.py) against the fixture in tests/golden/linalg/expected.json.
-//   usage: test_hipSolver matr33.txt rhs3.txt tol maxit reorder [wells|mswells|msonly|-] [linsolver]     (linsolver: ilu0 | cpr | cpr_trueimpes | cpr_quasiimpes;
+//   usage: test_hipSolver matr33.txt rhs3.txt tol maxit reorder [wells|mswells|msonly|mswells_dev|msonly_dev|-] [linsolver]     (linsolver: ilu0 | cpr | cpr_trueimpes | cpr_quasiimpes;
 //   a CPR run solves twice, the second time behind recreateCprHierarchy(): the --cpr-reuse-setup=1 path of the plug-in)
 //   wells: one standard well; mswells: that standard well and one multisegment well (two segments, three perforations); msonly: the
 //   multisegment well alone - WellContributions::getNumWells() then counts wells the C arrays do not hold (bda/WellContributions.hpp:164-166)
+//   mswells_dev / msonly_dev: the same wells with the plug-in's ms_wells_on_device switch - the multisegment well is applied on the device
+//   (opmhip_set_ms_wells), no callback
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -63,15 +65,17 @@ int main(int argc, char** argv) {
     const double tolerance = std::atof(argv[3]);
     const int maxit = std::atoi(argv[4]);
     std::unique_ptr<bda::hipSolverBackend<3>> backend;
+    std::string wellMode = argc > 6 ? argv[6] : "-";
+    const bool msOnDevice = wellMode == "mswells_dev" || wellMode == "msonly_dev";
+    if (msOnDevice) wellMode.resize(wellMode.size() - 4);
     try {
         backend.reset(new bda::hipSolverBackend<3>(/*verbosity=*/0, maxit, tolerance, /*deviceID=*/0, argv[5], /*w=*/1.0, argc > 7 ? argv[7] : "ilu0",
-                                                   /*cpr_reuse_setup=*/argc > 7 ? 1 : 3));
+                                                   /*cpr_reuse_setup=*/argc > 7 ? 1 : 3, /*cpr_amg_ilu_levels=*/-1, /*cpr_gather_rows=*/0, /*ilu_fillin_level=*/0, msOnDevice));
     } catch (const std::logic_error& error) {
         std::fprintf(stderr, "Problem with initializing a device: %s\n", error.what());  // the reference skips here
         return 77;
     }
     Opm::WellContributions wellContribs;
-    const std::string wellMode = argc > 6 ? argv[6] : "-";
     if (wellMode == "wells" || wellMode == "mswells") {
         // one standard well with two perforations (cells 1 and Nb - 2), filled the way StandardWellEval does
         // (wells/StandardWellEval.cpp:1206-1250: C, D, B); the shim reads the arrays back - directly from the stand-in
