@@ -676,6 +676,77 @@ int opmhip_set_source(opmhip_ctx* ctx, const double* source, const double* dsour
  * n == 0: no sources at all.  ABI 11 */
 int opmhip_set_source_cells(opmhip_ctx* ctx, int n, const int* cells, const double* source, const double* dsource);
 
+/* ---- analytic aquifers (Carter-Tracy, Fetkovich), resident on the device.  Additive to ABI 11 ----------------------------
+ * replaces: aquiferModel_.addToSource in EclProblem::source (ebos/eclproblem.hh:1843) and the classes behind it,
+ * opm/simulators/aquifers/AquiferInterface.hpp, AquiferCarterTracy.hpp, AquiferFetkovich.hpp, BlackoilAquiferModel_impl.hpp.
+ * An aquifer's influx depends on the connected cell's present water pressure and carries a derivative, so it is formed anew in
+ * front of every linearisation - on the device, from the cached intensive quantities, without a host round trip.  The aquifers'
+ * state (pressure_previous_, W_flux_, fluxValue_, aquifer_pressure_) lives on the device from time step to time step.
+ * The list: the aquifers concatenated, Carter-Tracy first, then Fetkovich - the order of BlackoilAquiferModel::addToSource
+ * (BlackoilAquiferModel_impl.hpp:112-127); only what the in-tree code reads from AQUCT_data / AQUFETP_data.  Every per-aquifer
+ * array has num_aquifers entries; an entry that belongs to the other type is ignored.
+ * NOT covered: decomposed contexts (alphai_, the equilibrium pressure and W_flux_ are sums over the ranks: refused); numerical
+ * aquifers (they are grid cells and need nothing from this library); the AQUTAB default influence table and the deck-level
+ * formulas for the time constant and the influx constant (opm-common's, not in the reference tree: the caller hands in Tc, beta
+ * and the table). */
+typedef struct opmhip_aquifers {
+    int num_aquifers;
+    const int* type;               /* 0 Carter-Tracy, 1 Fetkovich; no Carter-Tracy aquifer behind a Fetkovich one */
+    const int* id;                 /* aquiferID, reported back only */
+    const int* conn_pointers;      /* [num_aquifers + 1] connection ranges */
+    const int* cell;               /* per connection: natural id of an owned cell; within one aquifer a cell at most once
+                                    * (cellToConnectionIdx_ keeps one connection per cell, AquiferInterface.hpp:248); a cell may be in several aquifers */
+    const double* alpha;           /* per connection: alphai_, the normalised area fraction (initializeConnections, :224-317, is grid work: the caller's) */
+    const double* time_constant;   /* Tc_ [s], > 0 */
+    const double* water_density;   /* rhow_ */
+    const double* datum_depth;     /* aquiferDepth() */
+    const double* initial_pressure;     /* pa0_ where has_initial_pressure is set */
+    const int* has_initial_pressure;    /* 0: equilibrate with the reservoir at opmhip_set_aquifers (calculateReservoirEquilibrium, :330-373); NULL = all given */
+    const double* influx_constant; /* Carter-Tracy: beta_ */
+    const int* table_pointers;     /* [num_aquifers + 1] node ranges of the influence tables (Carter-Tracy: >= 2 nodes, td ascending; Fetkovich: empty) */
+    const double* td;              /* dimensionless_time nodes */
+    const double* pd;              /* dimensionless_pressure nodes */
+    const double* prod_index;      /* Fetkovich */
+    const double* total_compr;     /* Fetkovich; total_compr * initial_watvolume > 0 */
+    const double* initial_watvolume;    /* Fetkovich */
+    const int* has_restart;        /* restart values (initFromRestart, :91-102); NULL = none.  Refused for a Carter-Tracy aquifer as the
+                                    * reference refuses them (AquiferCarterTracy.hpp:107-111) */
+    const double* restart_W_flux;  /* W_flux_ */
+    const double* restart_pressure;     /* Fetkovich: aquifer_pressure_ */
+} opmhip_aquifers;
+/* replaces: initialSolutionApplied -> initQuantities (AquiferInterface.hpp:104-107, 167-183): call it after opmhip_set_static and
+ * opmhip_set_state.  NULL or num_aquifers == 0 clears the list.  Where the initial pressure is absent it is computed once, here:
+ * p_w and rho_w of the connected cells are gathered from the intensive-quantity cache and summed on the host in ascending cell
+ * order (the reference's element loop) with the gravity constant the assembly uses.  W_flux_ = 0 unless restart data was given.
+ * OPMHIP_NOT_READY before static / state; OPMHIP_INVALID_ARGUMENT (the text names the reason) for a null array or inconsistent
+ * pointers, a cell outside [0, Nb) or repeated within an aquifer, Tc <= 0, a table that is not ascending or has fewer than two nodes,
+ * total_compr * initial_watvolume <= 0, restart data for a Carter-Tracy aquifer, a decomposed context.  A refused call leaves no list set. */
+int opmhip_set_aquifers(opmhip_ctx* ctx, const opmhip_aquifers* aquifers);
+/* replaces: AquiferInterface::beginTimeStep (:109-128) - pressure_previous_ = p_w of the state now present, on the device - and the
+ * per-step scalars of calculateEqnConstants / getInfluenceTableValues (AquiferCarterTracy.hpp:113-160: td = time / Tc, PI(td + dt)
+ * and its derivative by linear interpolation with linear extrapolation - opm-common's linearInterpolation is not in the reference
+ * tree: restated, UNVERIFIED) and of AquiferFetkovich::calculateInflowRate (:143-144: (1 - exp(-dt / Tc)) / (dt / Tc)); computed on
+ * the host, sent up asynchronously.  time = simulator.time(), the start of the step.  Call it beside opmhip_begin_time_step, and again
+ * before every retry of a chopped step.  A no-op without aquifers. */
+int opmhip_aquifers_begin_time_step(opmhip_ctx* ctx, double time, double dt);
+/* what aquiferData() reports, per aquifer (any pointer may be NULL): W_flux_ (volume), pressure (Fetkovich: aquifer_pressure_,
+ * Carter-Tracy: pa0_), the sum of the last assemble's Qai_ in connection order (fluxRate), pa0_ (initPressure) */
+int opmhip_get_aquifers(opmhip_ctx* ctx, double* W_flux, double* pressure, double* flux_rate, double* init_pressure);
+/* for tests: Qai_ of the last assemble per connection, q4[4 i + 0..3] = value, d/dSw, d/dp, d/dX */
+int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
+/* With aquifers set:
+ * opmhip_assemble returns OPMHIP_NOT_READY before the first opmhip_aquifers_begin_time_step and OPMHIP_INVALID_ARGUMENT when its dt
+ * is not that call's.  Every assemble forms Qai_ from the state now present (calculateInflowRate in the statement order of
+ * AquiferCarterTracy.hpp:135-169 / AquiferFetkovich.hpp:112-148) and adds it, with its three derivatives (p_w depends on Sw and p),
+ * to the water equation's source of the connected cells, Carter-Tracy before Fetkovich.  The caller's source arrays hold exactly
+ * what the caller put there afterwards: the connected cells' water rows are saved, raised and restored around the assembly
+ * kernel, traffic proportional to the connections.  Per cell the assembly forms ((w + Q_1 + ...) / V - drift) * V where the
+ * reference forms w / V + Q_1 / V + ... (ebos/eclproblem.hh:1838-1843): at most one rounding apart, and only in a cell that has both
+ * a well rate and an aquifer connection.
+ * opmhip_end_time_step also does endTimeStep of both classes (AquiferCarterTracy.hpp:62-70, AquiferFetkovich.hpp:64-70): W_flux_ += Q_i * dt
+ * over the aquifer's connections in connection order; fluxValue_ = W_flux_; aquifer_pressure_ = pa0_ - W_flux_ / (total_compr *
+ * initial_watvolume).  opmhip_update_failed leaves the aquifers alone: a rolled-back step never reaches endTimeStep. */
+
 /* replaces: model().linearizer().linearizeDomain() (flow/BlackoilModelEbos.hpp:424), then .jacobian() /
  * .residual() (:339-340, :526-527).  iteration == 0 also (re)fills the cached old-time-level storage term
  * (recycleFirstIterationStorage, ebos/eclproblem.hh:1758-1765).  Jacobian and residual stay on the device for

@@ -80,6 +80,66 @@ class MsWells(C.Structure):
                 ("Dcol_pointers", C.c_void_p), ("Drows", C.c_void_p), ("Dvals", C.c_void_p), ("Dnnz_pointers", C.c_void_p)]
 
 
+class Aquifers(C.Structure):
+    """opmhip_aquifers: analytic aquifers for the device-resident form (opmhip_set_aquifers)"""
+    _fields_ = [("num_aquifers", C.c_int), ("type", C.c_void_p), ("id", C.c_void_p), ("conn_pointers", C.c_void_p), ("cell", C.c_void_p),
+                ("alpha", C.c_void_p), ("time_constant", C.c_void_p), ("water_density", C.c_void_p), ("datum_depth", C.c_void_p),
+                ("initial_pressure", C.c_void_p), ("has_initial_pressure", C.c_void_p), ("influx_constant", C.c_void_p),
+                ("table_pointers", C.c_void_p), ("td", C.c_void_p), ("pd", C.c_void_p), ("prod_index", C.c_void_p), ("total_compr", C.c_void_p),
+                ("initial_watvolume", C.c_void_p), ("has_restart", C.c_void_p), ("restart_W_flux", C.c_void_p), ("restart_pressure", C.c_void_p)]
+
+
+AQUIFER_TYPES = {"carter_tracy": 0, "fetkovich": 1}
+
+
+def make_aquifers(aquifers):
+    """list of per-aquifer dicts (aquifers.carter_tracy / aquifers.fetkovich: type, id, cells, alpha, time_constant, water_density,
+    datum_depth, initial_pressure | None = equilibrate, and influx_constant, td, pd or prod_index, total_compr, initial_watvolume,
+    restart | None), Carter-Tracy first, cells in natural order -> (Aquifers struct, keep-alive list).
+    Ragged input (lengths that do not fit each other, an unknown type, a missing entry) raises ValueError."""
+    if not aquifers:
+        return None, []
+    cp, tp = [0], [0]
+    col = {k: [] for k in ("type", "id", "time_constant", "water_density", "datum_depth", "initial_pressure", "has_initial_pressure", "influx_constant",
+                           "prod_index", "total_compr", "initial_watvolume", "has_restart", "restart_W_flux", "restart_pressure")}
+    cells, alpha, td, pd = [], [], [], []
+    for n, a in enumerate(aquifers):
+        try:
+            kind = AQUIFER_TYPES[a["type"]]
+            cl, al = np.asarray(a["cells"]).reshape(-1), np.asarray(a["alpha"], float).reshape(-1)
+            if len(cl) != len(al):
+                raise ValueError("aquifer %d: %d cells, %d alphas" % (n, len(cl), len(al)))
+            for k in ("id", "time_constant", "water_density", "datum_depth"):
+                col[k].append(a[k])
+            ip = a.get("initial_pressure")
+            col["initial_pressure"].append(0.0 if ip is None else float(ip))
+            col["has_initial_pressure"].append(int(ip is not None))
+            t, p = (np.asarray(a[k], float).reshape(-1) for k in ("td", "pd")) if kind == 0 else (np.zeros(0), np.zeros(0))
+            if len(t) != len(p):
+                raise ValueError("aquifer %d: influence table with %d times, %d pressures" % (n, len(t), len(p)))
+            col["influx_constant"].append(float(a["influx_constant"]) if kind == 0 else 0.0)
+            for k in ("prod_index", "total_compr", "initial_watvolume"):
+                col[k].append(float(a[k]) if kind == 1 else 0.0)
+            rs = a.get("restart")
+            col["has_restart"].append(int(rs is not None))
+            col["restart_W_flux"].append(float(rs["W_flux"]) if rs is not None else 0.0)
+            col["restart_pressure"].append(float(rs.get("pressure", 0.0)) if rs is not None else 0.0)
+        except KeyError as e:
+            raise ValueError("aquifer %d: missing entry %s" % (n, e))
+        col["type"].append(kind)
+        cells.append(cl); alpha.append(al); td.append(t); pd.append(p)
+        cp.append(cp[-1] + len(cl))
+        tp.append(tp[-1] + len(t))
+    i32 = ("type", "id", "has_initial_pressure", "has_restart")
+    arr = {k: (_i32(v) if k in i32 else _f64(v)) for k, v in col.items()}
+    arr.update(conn_pointers=_i32(cp), cell=_i32(np.concatenate(cells)), alpha=_f64(np.concatenate(alpha)), table_pointers=_i32(tp),
+               td=_f64(np.concatenate(td)), pd=_f64(np.concatenate(pd)))
+    s = Aquifers(len(aquifers))
+    for name, _ in Aquifers._fields_[1:]:
+        setattr(s, name, arr[name].ctypes.data)
+    return s, arr
+
+
 def _header_define(name):
     with open(HEADER_PATH) as f:
         return int(re.search(r"#define\s+%s\s+(\d+)" % name, f.read()).group(1))
@@ -533,6 +593,10 @@ def _bind_assembly(L):
     L.opmhip_set_hysteresis.argtypes = [vp, C.c_int, vp, vp]
     L.opmhip_get_hysteresis.argtypes = [vp, vp, vp, vp, vp]
     L.opmhip_set_hysteresis_params.argtypes = [vp, vp, vp]
+    L.opmhip_set_aquifers.argtypes = [vp, C.POINTER(Aquifers)]
+    L.opmhip_aquifers_begin_time_step.argtypes = [vp, C.c_double, C.c_double]
+    L.opmhip_get_aquifers.argtypes = [vp, vp, vp, vp, vp]
+    L.opmhip_get_aquifer_rates.argtypes = [vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -780,6 +844,32 @@ class HipModel(HipSolver):
 
     def set_drift_compensation(self, enable=True, max_compensation=0.1):
         self._check(lib().opmhip_set_drift_compensation(self._h, int(enable), max_compensation))
+
+    def set_aquifers(self, aquifers):
+        """opmhip_set_aquifers: the analytic aquifers (list of dicts, see make_aquifers) on the device, initialised from the state now
+        present; None or an empty list clears them"""
+        aq, keep = make_aquifers(aquifers)
+        self._naq = self._naqconn = 0      # a refused call leaves no list set
+        self._check(lib().opmhip_set_aquifers(self._h, C.byref(aq) if aq else None))
+        if aq:
+            self._naq, self._naqconn = aq.num_aquifers, len(keep["cell"])
+
+    def aquifers_begin_time_step(self, time, dt):
+        """opmhip_aquifers_begin_time_step: pressure_previous_ and the step's scalars; beside begin_time_step, before every retry too"""
+        self._check(lib().opmhip_aquifers_begin_time_step(self._h, float(time), float(dt)))
+
+    def get_aquifers(self):
+        """aquiferData() per aquifer: dict(W_flux, pressure, flux_rate, init_pressure) of arrays"""
+        n = getattr(self, "_naq", 0)
+        out = {k: np.zeros(n) for k in ("W_flux", "pressure", "flux_rate", "init_pressure")}
+        self._check(lib().opmhip_get_aquifers(self._h, *[_ptr(out[k]) for k in ("W_flux", "pressure", "flux_rate", "init_pressure")]))
+        return out
+
+    def aquifer_rates(self):
+        """Qai_ of the last assemble per connection: (connections, 4) = value, d/dSw, d/dp, d/dX"""
+        q = np.zeros((getattr(self, "_naqconn", 0), 4))
+        self._check(lib().opmhip_get_aquifer_rates(self._h, _ptr(q)))
+        return q
 
     def set_source(self, source, dsource=None):
         s, d = _f64(source), _f64(dsource)

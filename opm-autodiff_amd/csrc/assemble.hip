@@ -1425,6 +1425,98 @@ void launch_drift_update(opmhip_ctx* c, double dt) {
     hipLaunchKernelGGL(k_drift_update, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->d_b, dt, c->asmb.d_drift);
 }
 
+// ============================== analytic aquifers (opmhip_set_aquifers) =======================================
+// AquiferInterface::addToSource (opm/simulators/aquifers/AquiferInterface.hpp:130-153) with calculateInflowRate of
+// AquiferCarterTracy.hpp:135-169 and AquiferFetkovich.hpp:112-148, statement by statement (the library is built with
+// -ffp-contract=off: the expression trees below are the ones a NumPy restatement has to copy to get the same bits).
+// Plain wave64 kernels, one lane per connected cell / connection / aquifer; no atomics.
+struct AqArrays {
+    const int *of, *pos;                        // per connection: aquifer, cell (internal position)
+    const double *alpha, *pprev;                // per connection: alphai_, pressure_previous_
+    const double *par, *step, *state;           // per aquifer: AQ_PAR constants, AQ_STEP scalars of the time step, AQ_STATE state
+};
+__device__ __forceinline__ Ad aquifer_rate(const double* __restrict__ par, const double* __restrict__ step, const double* __restrict__ state,
+                                           double alpha, double cellDepth, double pprev, const Ad& pcur) {
+    const double gdz = GRAVITY * (cellDepth - par[AQ_DATUM]);
+    if (par[AQ_TYPE] == 0.0) {   // Carter-Tracy: dpai, calculateEqnConstants, Eq 5.7
+        const double dpai = par[AQ_PA0] + par[AQ_RHOW] * gdz - pprev;
+        const double denom = par[AQ_TC] * (step[AQ_PITD] - step[AQ_TD] * step[AQ_PITDPRIME]);
+        const double a = (par[AQ_BETA] * dpai - state[AQ_AUX] * step[AQ_PITDPRIME]) / denom;
+        const double b = par[AQ_BETA] / denom;
+        return alpha * (a - b * (pcur - pprev));
+    }
+    // Fetkovich: dpai carries the derivative, Eq 5.14
+    const Ad dpai = (state[AQ_AUX] + par[AQ_RHOW] * gdz) - pcur;
+    return (step[AQ_COEF] * alpha * par[AQ_PI]) * dpai;
+}
+// AquiferInterface::beginTimeStep: pressure_previous_ of every connection
+__global__ __launch_bounds__(64) void k_aquifer_begin(int nc, int ncell, const int* __restrict__ pos, const double* __restrict__ iq, double* __restrict__ pprev) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < nc) pprev[i] = iq_at(iq, ncell, F_P + WATER, pos[i])[0];
+}
+// In front of k_assemble, one lane per DISTINCT connected cell: Qai_ of the cell's connections (stored for opmhip_end_time_step and the
+// tests) added, in aquifer order, to the water row of the cell's source and its derivative; what the caller had there is kept in `save`
+__global__ __launch_bounds__(64) void k_aquifer_apply(int nd, int ncell, AqArrays Q, const int* __restrict__ cpos, const int* __restrict__ cptr,
+                                                      const int* __restrict__ cconn, const double* __restrict__ iq, const double* __restrict__ depth,
+                                                      double* __restrict__ source, double* __restrict__ dsource, double* __restrict__ save, double* __restrict__ q4) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= nd) return;
+    const int c = cpos[t];
+    const Ad pw = load_ad(iq_at(iq, ncell, F_P + WATER, c));
+    const double z = depth[c];
+    double* s = source + (size_t)c * 3 + EQ_WATER;
+    double* ds = dsource + (size_t)c * 9 + EQ_WATER * 3;
+    Ad w{*s, ds[0], ds[1], ds[2]};
+    store_ad(save + (size_t)4 * t, w);
+    for (int k = cptr[t]; k < cptr[t + 1]; ++k) {
+        const int i = cconn[k], a = Q.of[i];
+        const Ad q = aquifer_rate(Q.par + (size_t)a * AQ_PAR, Q.step + (size_t)a * AQ_STEP, Q.state + (size_t)a * AQ_STATE, Q.alpha[i], z, Q.pprev[i], pw);
+        store_ad(q4 + (size_t)4 * i, q);
+        w = w + q;
+    }
+    *s = w.v; ds[0] = w.d0; ds[1] = w.d1; ds[2] = w.d2;
+}
+// behind k_assemble: the caller's rows back
+__global__ __launch_bounds__(64) void k_aquifer_restore(int nd, const int* __restrict__ cpos, const double* __restrict__ save, double* __restrict__ source,
+                                                        double* __restrict__ dsource) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= nd) return;
+    const int c = cpos[t];
+    const Ad w = load_ad(save + (size_t)4 * t);
+    double* ds = dsource + (size_t)c * 9 + EQ_WATER * 3;
+    source[(size_t)c * 3 + EQ_WATER] = w.v; ds[0] = w.d0; ds[1] = w.d1; ds[2] = w.d2;
+}
+// endTimeStep of both classes (AquiferCarterTracy.hpp:62-70, AquiferFetkovich.hpp:64-70, 122-133), one lane per aquifer: the reference's
+// loop over Qai_ in connection order, left to right - once per time step, a serial sum is the sum to the bit
+__global__ __launch_bounds__(64) void k_aquifer_end(int na, double dt, const int* __restrict__ ptr, const double* __restrict__ par, const double* __restrict__ q4,
+                                                    double* __restrict__ state) {
+    const int a = blockIdx.x * 64 + threadIdx.x;
+    if (a >= na) return;
+    double W = state[(size_t)a * AQ_STATE + AQ_WFLUX];
+    for (int i = ptr[a]; i < ptr[a + 1]; ++i) W += q4[(size_t)4 * i] * dt;
+    state[(size_t)a * AQ_STATE + AQ_WFLUX] = W;
+    const double* p = par + (size_t)a * AQ_PAR;
+    state[(size_t)a * AQ_STATE + AQ_AUX] = p[AQ_TYPE] == 0.0 ? W : p[AQ_PA0] - (W / p[AQ_CV]);
+}
+static AqArrays aquifer_arrays(const AquifersDev& Q) { return AqArrays{Q.d_of, Q.d_pos, Q.d_alpha, Q.d_pprev, Q.d_par, Q.d_step, Q.d_state}; }
+void launch_aquifer_begin(opmhip_ctx* c) {
+    const AquifersDev& Q = c->asmb.aq;
+    hipLaunchKernelGGL(k_aquifer_begin, dim3((Q.nc + 63) / 64), dim3(64), 0, c->stream, Q.nc, c->pat.Nloc, Q.d_pos, c->asmb.d_iq, Q.d_pprev);
+}
+void launch_aquifer_apply(opmhip_ctx* c) {
+    const AquifersDev& Q = c->asmb.aq;
+    hipLaunchKernelGGL(k_aquifer_apply, dim3((Q.nd + 63) / 64), dim3(64), 0, c->stream, Q.nd, c->pat.Nloc, aquifer_arrays(Q), Q.d_cpos, Q.d_cptr, Q.d_cconn,
+                       c->asmb.d_iq, c->asmb.d_depth, c->asmb.d_source, c->asmb.d_dsource, Q.d_save, Q.d_q);
+}
+void launch_aquifer_restore(opmhip_ctx* c) {
+    const AquifersDev& Q = c->asmb.aq;
+    hipLaunchKernelGGL(k_aquifer_restore, dim3((Q.nd + 63) / 64), dim3(64), 0, c->stream, Q.nd, Q.d_cpos, Q.d_save, c->asmb.d_source, c->asmb.d_dsource);
+}
+void launch_aquifer_end(opmhip_ctx* c, double dt) {
+    const AquifersDev& Q = c->asmb.aq;
+    hipLaunchKernelGGL(k_aquifer_end, dim3((Q.num + 63) / 64), dim3(64), 0, c->stream, Q.num, dt, Q.d_ptr, Q.d_par, Q.d_q, Q.d_state);
+}
+
 // ============================== small permutation helpers =====================================================
 __global__ void k_cellvec_to_internal_u8(int Nb, const int* __restrict__ fromOrder, const unsigned char* __restrict__ nat, unsigned char* __restrict__ internal) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;

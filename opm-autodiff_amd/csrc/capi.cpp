@@ -378,6 +378,8 @@ void opmhip_destroy(opmhip_ctx* c) {
     if (c->wells.h_y) (void)hipHostFree(c->wells.h_y);
     if (c->wells.ms.h_flag) (void)hipHostFree(c->wells.ms.h_flag);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
+    if (c->asmb.aq.h_step) (void)hipHostFree(c->asmb.aq.h_step);
+    if (c->asmb.aq.ev_step) (void)hipEventDestroy(c->asmb.aq.ev_step);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->prof.ev) (void)hipEventDestroy(e);

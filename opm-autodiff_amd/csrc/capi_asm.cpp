@@ -849,6 +849,10 @@ int opmhip_end_time_step(opmhip_ctx* c, double dt) {
         OPMHIP_HIP(c, hipSetDevice(c->device));
         if (A.drsdt_on || A.drvdt_on) launch_last_rs_rv(c);   // updateCompositionChangeLimits_ (eclproblem.hh:1125)
         A.storage_frozen = false;
+        if (A.aq.num > 0) {   // aquiferModel_.endTimeStep (eclproblem.hh:1101-1135 -> BlackoilAquiferModel_impl.hpp)
+            launch_aquifer_end(c, dt);
+            OPMHIP_HIP(c, hipGetLastError());
+        }
         if (!A.drift_enabled) return OPMHIP_SUCCESS;
         launch_drift_update(c, dt);
         OPMHIP_HIP(c, hipGetLastError());
@@ -974,15 +978,264 @@ int opmhip_set_source_cells(opmhip_ctx* c, int n, const int* cells, const double
     });
 }
 
+// ---- analytic aquifers ---------------------------------------------------------------------------------------------------------------
+namespace {
+void aquifers_release(opmhip_ctx* c) {   // the stream is idle
+    AquifersDev& Q = c->asmb.aq;
+    dev_free(c, &Q.d_ptr); dev_free(c, &Q.d_of); dev_free(c, &Q.d_pos);
+    dev_free(c, &Q.d_alpha); dev_free(c, &Q.d_pprev); dev_free(c, &Q.d_q);
+    dev_free(c, &Q.d_par); dev_free(c, &Q.d_step); dev_free(c, &Q.d_state);
+    dev_free(c, &Q.d_cpos); dev_free(c, &Q.d_cptr); dev_free(c, &Q.d_cconn); dev_free(c, &Q.d_save);
+    if (Q.h_step) { (void)hipHostFree(Q.h_step); Q.h_step = nullptr; }
+    Q.num = Q.nc = Q.nd = 0;
+    Q.stepped = false;
+    Q.h_ptr.clear(); Q.h_id.clear(); Q.h_tabptr.clear(); Q.h_par.clear(); Q.h_td.clear(); Q.h_pd.clear();
+}
+// opm-common's linearInterpolation / linearInterpolationDerivative (not in the reference tree: restated, UNVERIFIED): the interval
+// j with x[j] <= xv, the first / last interval outside the table (linear extrapolation); value = slope * (xv - x[j]) + y[j]
+int table_interval(const double* x, int n, double xv) {
+    const int j = (int)(std::upper_bound(x, x + n, xv) - x) - 1;
+    return std::min(std::max(j, 0), n - 2);
+}
+double table_slope(const double* x, const double* y, int n, double xv) {
+    const int j = table_interval(x, n, xv);
+    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]);
+}
+double table_value(const double* x, const double* y, int n, double xv) {
+    const int j = table_interval(x, n, xv);
+    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]) * (xv - x[j]) + y[j];
+}
+}  // namespace
+
+int opmhip_set_aquifers(opmhip_ctx* c, const opmhip_aquifers* aq) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AsmDev& A = c->asmb;
+        AquifersDev& Q = A.aq;
+        const Pattern& P = c->pat;
+        if (!A.static_set) return fail(c, OPMHIP_NOT_READY, "set_aquifers before set_static");
+        if (!A.state_set) return fail(c, OPMHIP_NOT_READY, "set_aquifers before set_state: the aquifers are initialised from the initial solution");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        aquifers_release(c);   // whatever happens below, the old list is gone: a refused call leaves no list set
+        if (!aq || aq->num_aquifers == 0) return OPMHIP_SUCCESS;
+        if (c->comm.nranks > 1)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: decomposed context (%d ranks) - alphai_, the equilibrium pressure and W_flux_ are sums over the ranks, which is not built", c->comm.nranks);
+        const int na = aq->num_aquifers;
+        if (na < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: num_aquifers = %d", na);
+        if (!aq->type || !aq->id || !aq->conn_pointers || !aq->time_constant || !aq->water_density || !aq->datum_depth)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (type, id, conn_pointers, time_constant, water_density, datum_depth are mandatory)");
+        if (aq->conn_pointers[0] != 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: conn_pointers[0] = %d, not 0", aq->conn_pointers[0]);
+        bool anyCT = false, anyFet = false;
+        for (int a = 0; a < na; ++a) {
+            if (aq->conn_pointers[a + 1] < aq->conn_pointers[a]) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: conn_pointers descend at aquifer %d", a);
+            if (aq->type[a] != 0 && aq->type[a] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: type[%d] = %d (0 Carter-Tracy, 1 Fetkovich)", a, aq->type[a]);
+            if (aq->type[a] == 0 && anyFet) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: Carter-Tracy aquifer %d behind a Fetkovich one (Carter-Tracy first: the order of addToSource)", a);
+            (aq->type[a] == 0 ? anyCT : anyFet) = true;
+        }
+        const int nc = aq->conn_pointers[na];
+        if (nc > 0 && (!aq->cell || !aq->alpha)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (cell / alpha)");
+        if (anyCT && (!aq->influx_constant || !aq->table_pointers || !aq->td || !aq->pd))
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (a Carter-Tracy aquifer needs influx_constant, table_pointers, td, pd)");
+        if (anyFet && (!aq->prod_index || !aq->total_compr || !aq->initial_watvolume))
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (a Fetkovich aquifer needs prod_index, total_compr, initial_watvolume)");
+        if (aq->has_restart && (!aq->restart_W_flux || (anyFet && !aq->restart_pressure)))
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (has_restart without restart_W_flux / restart_pressure)");
+        std::vector<double> par((size_t)na * AQ_PAR, 0.0), td, pd;
+        std::vector<int> tabptr(na + 1, 0), need_eq;
+        for (int a = 0; a < na; ++a) {
+            double* p = &par[(size_t)a * AQ_PAR];
+            if (!(aq->time_constant[a] > 0.0)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: aquifer %d has time constant Tc = %g, must be positive", a, aq->time_constant[a]);
+            const bool has_p = !aq->has_initial_pressure || aq->has_initial_pressure[a];
+            if (has_p && !aq->initial_pressure) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (initial_pressure)");
+            const bool restart = aq->has_restart && aq->has_restart[a];
+            p[AQ_TYPE] = aq->type[a]; p[AQ_TC] = aq->time_constant[a]; p[AQ_RHOW] = aq->water_density[a]; p[AQ_DATUM] = aq->datum_depth[a];
+            p[AQ_PA0] = has_p ? aq->initial_pressure[a] : 0.0;
+            if (!has_p) need_eq.push_back(a);
+            tabptr[a + 1] = tabptr[a];
+            if (aq->type[a] == 0) {
+                if (restart) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: restart data for Carter-Tracy aquifer %d - restart-based initialisation is not supported for Carter-Tracy aquifers (as in the reference)", a);
+                p[AQ_BETA] = aq->influx_constant[a];
+                const int t0 = aq->table_pointers[a], t1 = aq->table_pointers[a + 1];
+                if (t0 < 0 || t1 - t0 < 2) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: the influence table of aquifer %d has fewer than two nodes", a);
+                for (int i = t0 + 1; i < t1; ++i)
+                    if (!(aq->td[i] > aq->td[i - 1])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: the influence table of aquifer %d is not ascending at node %d", a, i - t0);
+                td.insert(td.end(), aq->td + t0, aq->td + t1);
+                pd.insert(pd.end(), aq->pd + t0, aq->pd + t1);
+                tabptr[a + 1] = (int)td.size();
+            } else {
+                p[AQ_PI] = aq->prod_index[a];
+                p[AQ_CV] = aq->total_compr[a] * aq->initial_watvolume[a];
+                if (!(p[AQ_CV] > 0.0)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: Fetkovich aquifer %d has total_compr * initial_watvolume = %g, must be positive", a, p[AQ_CV]);
+            }
+        }
+        // connections; the distinct connected cells, each with its connections in aquifer order (= ascending connection number)
+        std::vector<int> of(nc), pos(nc), cpos, cptr, cconn(nc);
+        {
+            std::vector<int> seen(P.Nb, -1), slot(P.Nb, -1), count;
+            for (int a = 0; a < na; ++a)
+                for (int i = aq->conn_pointers[a]; i < aq->conn_pointers[a + 1]; ++i) {
+                    const int cell = aq->cell[i];
+                    if (cell < 0 || cell >= P.Nb) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: connection %d of aquifer %d names cell %d, outside [0, %d)", i - aq->conn_pointers[a], a, cell, P.Nb);
+                    if (seen[cell] == a) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: cell %d is repeated within aquifer %d (one connection per cell)", cell, a);
+                    seen[cell] = a;
+                    of[i] = a;
+                    pos[i] = P.toOrder[cell];
+                    if (slot[cell] < 0) { slot[cell] = (int)cpos.size(); cpos.push_back(pos[i]); count.push_back(0); }
+                    count[slot[cell]]++;
+                }
+            cptr.assign(cpos.size() + 1, 0);
+            for (size_t t = 0; t < cpos.size(); ++t) cptr[t + 1] = cptr[t] + count[t];
+            std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+            for (int i = 0; i < nc; ++i) cconn[fill[slot[aq->cell[i]]]++] = i;
+        }
+        // calculateReservoirEquilibrium (AquiferInterface.hpp:330-373) for the aquifers without an initial pressure
+        if (!need_eq.empty()) {
+            const int IQS = iq_doubles_per_cell(c);
+            std::vector<double> depth(P.Nloc), rec;
+            OPMHIP_HIP(c, hipMemcpy(depth.data(), A.d_depth, depth.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int a : need_eq) {
+                const int i0 = aq->conn_pointers[a], n = aq->conn_pointers[a + 1] - i0;
+                std::vector<int> order(n), p(n);
+                for (int i = 0; i < n; ++i) order[i] = i0 + i;
+                std::sort(order.begin(), order.end(), [&](int x, int y) { return aq->cell[x] < aq->cell[y]; });   // the element loop
+                for (int i = 0; i < n; ++i) p[i] = pos[order[i]];
+                rec.resize((size_t)n * IQS);
+                if (n > 0) {
+                    int rc = stage_cell_positions(c, p);
+                    if (rc) return rc;
+                    launch_iq_gather(c, n, A.d_cell_pos, A.d_stage_cell);
+                    OPMHIP_HIP(c, hipGetLastError());
+                    OPMHIP_HIP(c, hipMemcpyAsync(rec.data(), A.d_stage_cell, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                    OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+                }
+                const double datum = aq->datum_depth[a];
+                double sumAlpha = 0.0, sumPw = 0.0;
+                for (int i = i0; i < i0 + n; ++i) sumAlpha += aq->alpha[i];
+                for (int i = 0; i < n; ++i) {
+                    const double pw = rec[(size_t)i * IQS + 4 * 3], rho = rec[(size_t)i * IQS + 4 * 12];   // fields p_w, rho_w of the record
+                    const double gdz = 9.80665 * (depth[p[i]] - datum);   // the assembly's gravity constant (assemble.hip GRAVITY)
+                    sumPw += aq->alpha[order[i]] * (pw - rho * gdz);
+                }
+                par[(size_t)a * AQ_PAR + AQ_PA0] = sumPw / sumAlpha;
+            }
+        }
+        std::vector<double> state((size_t)na * AQ_STATE, 0.0);
+        for (int a = 0; a < na; ++a) {
+            const bool restart = aq->has_restart && aq->has_restart[a];
+            state[(size_t)a * AQ_STATE + AQ_WFLUX] = restart ? aq->restart_W_flux[a] : 0.0;
+            state[(size_t)a * AQ_STATE + AQ_AUX] = aq->type[a] == 0 ? 0.0 : (restart ? aq->restart_pressure[a] : par[(size_t)a * AQ_PAR + AQ_PA0]);
+        }
+        const int rc = [&]() -> int {
+            int r;
+            const std::vector<int> ptr(aq->conn_pointers, aq->conn_pointers + na + 1);
+            const std::vector<double> alpha(aq->alpha, aq->alpha + nc), zc((size_t)4 * std::max(nc, 1), 0.0);
+            if ((r = dev_upload(c, &Q.d_ptr, ptr)) || (r = dev_upload(c, &Q.d_of, of)) || (r = dev_upload(c, &Q.d_pos, pos)) || (r = dev_upload(c, &Q.d_alpha, alpha)) ||
+                (r = dev_upload(c, &Q.d_par, par)) || (r = dev_upload(c, &Q.d_state, state)) || (r = dev_upload(c, &Q.d_q, zc)) ||
+                (r = dev_upload(c, &Q.d_cpos, cpos)) || (r = dev_upload(c, &Q.d_cptr, cptr)) || (r = dev_upload(c, &Q.d_cconn, cconn)))
+                return r;
+            if ((r = dev_alloc(c, &Q.d_pprev, (size_t)nc)) || (r = dev_alloc(c, &Q.d_step, (size_t)na * AQ_STEP)) || (r = dev_alloc(c, &Q.d_save, cpos.size() * 4))) return r;
+            OPMHIP_HIP(c, hipMemset(Q.d_pprev, 0, (size_t)std::max(nc, 1) * sizeof(double)));
+            OPMHIP_HIP(c, hipMemset(Q.d_step, 0, (size_t)na * AQ_STEP * sizeof(double)));
+            OPMHIP_HIP(c, hipHostMalloc((void**)&Q.h_step, (size_t)na * AQ_STEP * sizeof(double), hipHostMallocDefault));
+            if (!Q.ev_step) OPMHIP_HIP(c, hipEventCreateWithFlags(&Q.ev_step, hipEventDisableTiming));
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+            return OPMHIP_SUCCESS;
+        }();
+        if (rc) { aquifers_release(c); return rc; }
+        Q.num = na; Q.nc = nc; Q.nd = (int)cpos.size();
+        Q.h_ptr.assign(aq->conn_pointers, aq->conn_pointers + na + 1);
+        Q.h_id.assign(aq->id, aq->id + na);
+        Q.h_par = par; Q.h_tabptr = tabptr; Q.h_td = td; Q.h_pd = pd;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_aquifers_begin_time_step(opmhip_ctx* c, double time, double dt) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AquifersDev& Q = c->asmb.aq;
+        if (Q.num == 0) return OPMHIP_SUCCESS;
+        if (!(dt > 0.0) || !std::isfinite(time)) return fail(c, OPMHIP_INVALID_ARGUMENT, "aquifers_begin_time_step: dt must be positive, time finite");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        if (Q.stepped) OPMHIP_HIP(c, hipEventSynchronize(Q.ev_step));   // the last call's copy has read the staging area
+        for (int a = 0; a < Q.num; ++a) {
+            const double* p = &Q.h_par[(size_t)a * AQ_PAR];
+            double* s = Q.h_step + (size_t)a * AQ_STEP;
+            s[AQ_TD] = s[AQ_PITD] = s[AQ_PITDPRIME] = s[AQ_COEF] = 0.0;
+            if (p[AQ_TYPE] == 0.0) {   // calculateEqnConstants (AquiferCarterTracy.hpp:150-153)
+                const double td_plus_dt = (dt + time) / p[AQ_TC];
+                const int t0 = Q.h_tabptr[a], n = Q.h_tabptr[a + 1] - t0;
+                s[AQ_TD] = time / p[AQ_TC];
+                s[AQ_PITD] = table_value(&Q.h_td[t0], &Q.h_pd[t0], n, td_plus_dt);
+                s[AQ_PITDPRIME] = table_slope(&Q.h_td[t0], &Q.h_pd[t0], n, td_plus_dt);
+            } else {                   // AquiferFetkovich.hpp:143-144
+                const double td_Tc = dt / p[AQ_TC];
+                s[AQ_COEF] = (1 - std::exp(-td_Tc)) / td_Tc;
+            }
+        }
+        OPMHIP_HIP(c, hipMemcpyAsync(Q.d_step, Q.h_step, (size_t)Q.num * AQ_STEP * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        OPMHIP_HIP(c, hipEventRecord(Q.ev_step, c->stream));
+        if (Q.nc > 0) launch_aquifer_begin(c);
+        OPMHIP_HIP(c, hipGetLastError());
+        Q.stepped = true;
+        Q.step_dt = dt;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_aquifers(opmhip_ctx* c, double* W_flux, double* pressure, double* flux_rate, double* init_pressure) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AquifersDev& Q = c->asmb.aq;
+        if (Q.num == 0) return OPMHIP_SUCCESS;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        std::vector<double> state((size_t)Q.num * AQ_STATE), q((size_t)4 * std::max(Q.nc, 1));
+        OPMHIP_HIP(c, hipMemcpy(state.data(), Q.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (flux_rate) OPMHIP_HIP(c, hipMemcpy(q.data(), Q.d_q, q.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int a = 0; a < Q.num; ++a) {
+            const double* p = &Q.h_par[(size_t)a * AQ_PAR];
+            if (W_flux) W_flux[a] = state[(size_t)a * AQ_STATE + AQ_WFLUX];
+            if (pressure) pressure[a] = p[AQ_TYPE] == 0.0 ? p[AQ_PA0] : state[(size_t)a * AQ_STATE + AQ_AUX];
+            if (init_pressure) init_pressure[a] = p[AQ_PA0];
+            if (flux_rate) {
+                double f = 0.0;
+                for (int i = Q.h_ptr[a]; i < Q.h_ptr[a + 1]; ++i) f += q[(size_t)4 * i];
+                flux_rate[a] = f;
+            }
+        }
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_aquifer_rates(opmhip_ctx* c, double* q4) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AquifersDev& Q = c->asmb.aq;
+        if (Q.nc == 0) return OPMHIP_SUCCESS;
+        if (!q4) return fail(c, OPMHIP_INVALID_ARGUMENT, "get_aquifer_rates: q4 == NULL");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        OPMHIP_HIP(c, hipMemcpy(q4, Q.d_q, (size_t)4 * Q.nc * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
 int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double* residual) {
     if (!c) return OPMHIP_INVALID_ARGUMENT;
     return guarded(c, [&]() -> int {
         if (!c->asmb.state_set) return fail(c, OPMHIP_NOT_READY, "assemble before set_state");
         if (!(dt > 0.0) || iteration < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: dt must be positive, iteration >= 0");
+        const AquifersDev& Q = c->asmb.aq;
+        if (Q.num > 0 && !Q.stepped) return fail(c, OPMHIP_NOT_READY, "assemble: aquifers are set but opmhip_aquifers_begin_time_step was not called");
+        if (Q.num > 0 && dt != Q.step_dt) return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: dt = %.17g, the aquifers' time step was begun with dt = %.17g", dt, Q.step_dt);
         OPMHIP_HIP(c, hipSetDevice(c->device));
         c->asmb.last_dt = dt;
         c->asmb.last_iteration = iteration;
+        if (Q.nd > 0) launch_aquifer_apply(c);     // aquiferModel_.addToSource (ebos/eclproblem.hh:1843)
         launch_assemble(c, dt, iteration);
+        if (Q.nd > 0) launch_aquifer_restore(c);   // the caller's source arrays as the caller left them
         OPMHIP_HIP(c, hipGetLastError());
         c->system_loaded = true;
         c->factored = false;

@@ -198,8 +198,30 @@ struct WellsDev {
     bool any() const { return num_wells > 0 || num_ms > 0 || ms.num > 0; }
 };
 
+// Analytic aquifers on the device (opmhip_set_aquifers).  nc connections (aquifers concatenated, Carter-Tracy first), nd distinct connected
+// cells.  Per aquifer: AQ_PAR constants, AQ_STEP scalars of the time step under way (host-computed, opmhip_aquifers_begin_time_step), AQ_STATE
+// state doubles that live from time step to time step.
+enum { AQ_TYPE = 0, AQ_TC, AQ_RHOW, AQ_DATUM, AQ_PA0, AQ_BETA, AQ_PI, AQ_CV, AQ_PAR };   // AQ_CV = total_compr * initial_watvolume
+enum { AQ_TD = 0, AQ_PITD, AQ_PITDPRIME, AQ_COEF, AQ_STEP };                            // Carter-Tracy: td, PI(td + dt), PI'(td + dt); Fetkovich: coef
+enum { AQ_WFLUX = 0, AQ_AUX, AQ_STATE };                                                // AQ_AUX: fluxValue_ (Carter-Tracy) / aquifer_pressure_ (Fetkovich)
+struct AquifersDev {
+    int num = 0, nc = 0, nd = 0;
+    bool stepped = false;       // an opmhip_aquifers_begin_time_step has been seen
+    double step_dt = 0.0;
+    std::vector<int> h_ptr, h_id, h_tabptr;
+    std::vector<double> h_par, h_td, h_pd;
+    int *d_ptr = nullptr, *d_of = nullptr, *d_pos = nullptr;          // [num + 1]; per connection: its aquifer, its cell (internal position)
+    double *d_alpha = nullptr, *d_pprev = nullptr, *d_q = nullptr;    // per connection: alphai_, pressure_previous_, Qai_ (value + 3 derivatives)
+    double *d_par = nullptr, *d_step = nullptr, *d_state = nullptr;
+    int *d_cpos = nullptr, *d_cptr = nullptr, *d_cconn = nullptr;     // distinct cells: position, range into d_cconn, their connections in aquifer order
+    double* d_save = nullptr;                                         // per distinct cell: the caller's source water row and its three derivatives
+    double* h_step = nullptr;                                         // pinned staging of d_step
+    hipEvent_t ev_step = nullptr;                                     // "h_step has been read"
+};
+
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
 struct AsmDev {
+    AquifersDev aq;
     bool fluid_set = false, static_set = false, state_set = false, assembled = false;
     double *d_tab_dbl = nullptr;
     int* d_tab_idx = nullptr;
@@ -656,6 +678,10 @@ int launch_ghost_refresh(opmhip_ctx* c);
 void launch_newton_update(opmhip_ctx* c, const double* d_dx_internal, double relax);
 void launch_assemble(opmhip_ctx* c, double dt, int iteration);
 void launch_drift_update(opmhip_ctx* c, double dt);
+void launch_aquifer_begin(opmhip_ctx* c);    // pressure_previous_ = p_w of the connected cells
+void launch_aquifer_apply(opmhip_ctx* c);    // Qai_ of every connection; saved and raised source rows of the connected cells (in front of k_assemble)
+void launch_aquifer_restore(opmhip_ctx* c);  // the caller's source rows back (behind k_assemble)
+void launch_aquifer_end(opmhip_ctx* c, double dt);
 void launch_last_rs_rv(opmhip_ctx* c);
 void launch_set_limits(opmhip_ctx* c, double dt);
 void launch_min_pressure(opmhip_ctx* c, bool init);

@@ -220,6 +220,27 @@ def five_spot_source(case, rate_sm3_per_day=50.0):
     return np.ascontiguousarray(src.reshape(-1))
 
 
+def two_aquifers(case, grid, dims):
+    """A Carter-Tracy aquifer on the I- side and a Fetkovich aquifer under the grid (records for capi.HipModel.set_aquifers /
+    aquifers.HostAquifers), sized for a measurement rather than for a field: both equilibrate with the reservoir.  grid, dims: what
+    transmissibility.cornerpoint_faces / cartesian_faces gave for `case` (the Norne-shaped case of the tests), or None, None for a
+    cartesian_case.  The influence table has the shape of a radial infinite-acting aquifer's (AQUTAB's default lives in opm-common)."""
+    from . import aquifers as _aq
+    g = case if grid is None else (grid, dims)
+    nx, ny, nz = (case["nx"], case["ny"], case["nz"]) if grid is None else dims
+    depth = np.asarray(case["depth"])
+    side = _aq.connections(g, (0, nx - 1, 0, ny - 1, 0, nz - 1), "I-")
+    under = _aq.connections(g, (0, nx - 1, 0, ny - 1, 0, nz - 1), "K+")
+    keep = lambda c: dict(cells=c["cells"][c["alpha"] > 0.0], alpha=c["alpha"][c["alpha"] > 0.0])   # a cell without the face carries no influx
+    side, under = keep(side), keep(under)
+    td = [0.01, 0.05, 0.1, 0.5, 1.0, 5.0, 10.0, 50.0, 100.0]
+    pd = [0.112, 0.229, 0.315, 0.616, 0.802, 1.362, 1.651, 2.388, 2.723]   # concave and ascending, as such a table is; the values UNVERIFIED
+    datum = float(depth.max())
+    return [_aq.carter_tracy(1, side, time_constant=200.0 * 86400.0, influx_constant=2.0e-4, water_density=1000.0, datum_depth=datum, td=td, pd=pd),
+            _aq.fetkovich(2, under, time_constant=_aq.fetkovich_time_constant(1.0e-9, 2.0e10, 5.0e-8), prod_index=5.0e-8, total_compr=1.0e-9, initial_watvolume=2.0e10,
+                          water_density=1000.0, datum_depth=datum)]
+
+
 def write_case_binary(case, path, source=None):
     """Case file for the C++ host driver (opm-autodiff_amd/host/test_BlackoilModelHip.cpp): named raw arrays."""
     import struct

@@ -64,8 +64,10 @@ class ModelParameters:
 class BlackoilModelHip:
     """model = capi.HipModel (device context) ; one instance drives one grid on one GPU."""
 
-    def __init__(self, model, param=None, well_model=None):
-        """well_model (wells.StandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
+    def __init__(self, model, param=None, well_model=None, aquifer_model=None):
+        """aquifer_model (aquifers.DeviceAquifers, aquifers.HostAquifers or None): the analytic aquifers - aquiferModel_ of EclProblem
+        (initialSolutionApplied here, beginTimeStep / addToSource / endTimeStep below); the model's state must be set.
+        well_model (wells.StandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
         reservoir's linearisation (BlackoilModelEbos::assembleReservoir -> wellModel().assemble, flow/BlackoilModelEbos.hpp:418-428),
         eliminated from the linear system by the device (wells/StandardWell_impl.hpp:1254-1311) and updated with the reservoir"""
         self.m = model
@@ -75,6 +77,9 @@ class BlackoilModelHip:
         self.current_relaxation = 1.0
         self.last_linear_iterations = 0
         self._well_saved = None
+        self.aquifers = aquifer_model
+        if aquifer_model is not None:
+            aquifer_model.initial_solution_applied(model)
 
     # -- BlackoilModelEbos::getReservoirConvergence ------------------------------------------------------------
     def get_convergence(self, dt, iteration):
@@ -127,12 +132,23 @@ class BlackoilModelHip:
                 self.wells.calculate_explicit_quantities(iq)  # the completions' pressure differences, constant through the time step (:824-827)
                 self.wells.solve_well_equations(iq)          # prepareTimeStep: the wells alone against the frozen reservoir
             self.wells.update_well_controls()
+            host_aq = self.aquifers is not None and not self.aquifers.on_device    # then the influx joins the wells' rates below
             if hasattr(self.m, "set_source_cells"):
                 wa = self.wells.assemble(iq)
-                self.m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
+                if not host_aq:
+                    self.m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
             else:
                 wa = self.wells.assemble(iq, iq.shape[0])
                 self.m.set_source(wa["source"], wa["dsource"])
+                if host_aq:
+                    raise NotImplementedError("HostAquifers beside a well model needs a model object with set_source_cells")
+        if self.aquifers is not None and not self.aquifers.on_device:
+            # aquiferModel_.addToSource (ebos/eclproblem.hh:1843) on the host: the connected cells' records come down, their rates go up.
+            # The device form (opmhip_set_aquifers) needs nothing here: opmhip_assemble forms the influx itself
+            if wa is not None:
+                self.aquifers.add_to_source(self.m, wa["cells"], wa["source_cells"], wa["dsource_cells"])
+            else:
+                self.aquifers.add_to_source(self.m)
         self.m.assemble(dt, iteration, fetch=False)          # assembleReservoir -> linearizeDomain (asynchronous)
         conv, norms = self.get_convergence(dt, iteration)    # synchronises: reads the reduced scalars back
         if wa is not None:
@@ -202,13 +218,18 @@ class BlackoilModelHip:
         return self.m.relative_change() if hasattr(self.m, "relative_change") else None
 
     # -- EclProblem::beginTimeStep (ebos/eclproblem.hh:1042-1075): DRSDT / DRVDT caps of a step of size dt, minimum pressure --
-    def begin_time_step(self, dt):
+    def begin_time_step(self, dt, time=0.0):
+        """time: simulator.time(), the start of the step - the Carter-Tracy aquifers' dimensionless time"""
         if hasattr(self.m, "begin_time_step"):
             self.m.begin_time_step(dt)
+        if self.aquifers is not None:
+            self.aquifers.begin_time_step(self.m, time, dt)   # aquiferModel_.beginTimeStep (ebos/eclproblem.hh:1042-1075)
 
     # -- EclProblem::endTimeStep (ebos/eclproblem.hh:1101-1135): the drift of the accepted step ------------------
     def end_time_step(self, dt):
-        self.m.end_time_step(dt)
+        self.m.end_time_step(dt)      # with aquifers on the device: their endTimeStep too
+        if self.aquifers is not None and not self.aquifers.on_device:
+            self.aquifers.end_time_step(dt)
 
 
 @dataclass
@@ -307,7 +328,10 @@ class AdaptiveTimeStepping:
             if self.iteration == 0 and self.restarts == 0:
                 self.model.advance_time_level()
             if self.iteration == 0 and hasattr(self.model, "begin_time_step"):
-                self.model.begin_time_step(self.dt)      # also in front of every retry of a chopped step
+                if getattr(self.model, "aquifers", None) is not None:
+                    self.model.begin_time_step(self.dt, time=self.time)
+                else:
+                    self.model.begin_time_step(self.dt)      # also in front of every retry of a chopped step
             failed = False
             try:
                 rep = self.model.nonlinear_iteration(self.iteration, self.dt)
