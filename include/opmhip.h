@@ -747,6 +747,80 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * over the aquifer's connections in connection order; fluxValue_ = W_flux_; aquifer_pressure_ = pa0_ - W_flux_ / (total_compr *
  * initial_watvolume).  opmhip_update_failed leaves the aquifers alone: a rolled-back step never reaches endTimeStep. */
 
+/* ---- standard wells, resident on the device.  Additive to ABI 11 -----------------------------------------------------------
+ * The well model the Python package states on the host (wells.py StandardWells: vertical standard wells, 4 unknowns per well - the
+ * surface rates of oil, water and gas INTO the reservoir and the bottom-hole pressure -, rate or BHP control with one BHP limit, no
+ * crossflow, no storage term, an explicit head per completion from the perforated cell's oil density), formed on the device from
+ * the cached intensive quantities: nothing of a Newton iteration crosses to the host but one read-back of 10 doubles per well.
+ * The arithmetic is wells.py's arithmetic="stated", operation by operation (the library is built without floating-point
+ * contraction): the per-well sums run over the perforations in perforation order, D^-1 is Gauss-Jordan on [D | I] with partial
+ * pivoting (largest |entry| of the column, lowest row on ties), D^-1 r a row-times-vector product in ascending column order.
+ * NOT covered: the reference's well-bore density (StandardWellGeneric::computeConnectionPressureDelta), groups, THP, VFP, crossflow,
+ * decomposed contexts (refused), the matrix-add form (opmhip_add_well_contributions stays with host lists).
+ * Phases: 0 water, 1 oil, 2 gas (the intensive-quantity record's order); components: 0 oil, 1 water, 2 gas (the equations' order). */
+typedef struct opmhip_std_wells {
+    int num_wells;
+    const int* perf_pointers;      /* [num_wells + 1] perforation ranges, every well at least one perforation */
+    const int* cell;               /* per perforation: natural id of the perforated cell; a cell may be named by several wells */
+    const double* tw;              /* per perforation: connection transmissibility factor */
+    const double* dz;              /* per perforation: cell depth - the well's reference depth; head = (rho_o * g) * dz */
+    const int* producer;           /* per well: 1 producer, 0 injector */
+    const int* inj_phase;          /* per well: the injected phase (ignored for a producer) */
+    const int* rate_component;     /* per well: the component the rate target is about */
+    const double* rate_target;     /* per well: surface volume rate, positive */
+    const double* bhp_limit;       /* per well: lower (producer) / upper (injector) limit, the target under BHP control */
+    const int* control;            /* per well: 0 rate, 1 bhp */
+    const double* x;               /* optional [num_wells * 4]: q_o, q_w, q_g, bhp to start from; NULL = zeros.  (The first
+                                    * opmhip_std_wells_begin_iteration(0) sets the bottom-hole pressures anew, as the host form does.) */
+} opmhip_std_wells;
+/* Call it once, after opmhip_set_static and opmhip_set_state; NULL or num_wells == 0 clears the list.  The list is validated, the
+ * cells are permuted to the internal order, and every distinct perforated cell gets the list of its perforations in perforation
+ * order.  OPMHIP_NOT_READY before static / state; OPMHIP_INVALID_ARGUMENT (the text names the reason) for a null array, inconsistent
+ * pointers, a cell outside [0, Nb), an unknown phase or component, a control other than 0 / 1, a decomposed context.  A refused call
+ * leaves no list set. */
+int opmhip_set_std_wells(opmhip_ctx* ctx, const opmhip_std_wells* wells);
+/* replaces: wellModel().beginIteration (wells/BlackoilWellModel_impl.hpp:148-171).  iteration == 0: the completions' pressure
+ * differences (calculateExplicitQuantities, :824-827), then the wells alone against the frozen reservoir (prepareTimeStep /
+ * solveWellEqUntilConverged: at most 20 Newton iterations of StandardWell_impl.hpp:195-420, 516-640 per well, each well stopping
+ * on its own); on the first call ever the bottom-hole pressures start 1 bar below (producer) / above (injector) the first
+ * perforated cell's oil pressure.  Every iteration: updateWellControls - a rate target whose BHP leaves its limit goes under BHP
+ * control, under BHP control the well returns to its target once the rate exceeds it.  Asynchronous: no read-back.  A no-op without
+ * a list. */
+int opmhip_std_wells_begin_iteration(opmhip_ctx* ctx, int iteration);
+/* replaces: StandardWell::apply(r) (wells/StandardWell_impl.hpp:1283-1296): r -= C^T D^-1 r_w with the resident r_w, B, C, D^-1 of
+ * the last opmhip_assemble.  Asynchronous.  OPMHIP_NOT_READY without a list or before an assembly. */
+int opmhip_std_wells_apply_residual(opmhip_ctx* ctx);
+/* replaces: recoverWellSolutionAndUpdateWellState (wells/StandardWell_impl.hpp:1298-1311, BlackoilWellModel_impl.hpp:1033-1042):
+ * x_w = D^-1 (r_w - B x) from the resident solution of the last solve, then the well unknowns -= relax * x_w.  Asynchronous. */
+int opmhip_std_wells_update(opmhip_ctx* ctx, double relax);
+/* the one read-back of a Newton iteration (any pointer may be NULL): x [num_wells * 4], control [num_wells], res_well
+ * [num_wells * 4] (r_w of the last assemble: what getWellConvergence looks at).  Waits for the stream; a D that met a zero pivot
+ * since the last look is reported here (see below). */
+int opmhip_get_std_wells(opmhip_ctx* ctx, double* x, int* control, double* res_well);
+/* WCONPROD / WCONINJE events, restart, tests (any pointer may be NULL: that part stays): the well unknowns, the controls in force,
+ * the rate targets.  What the last assemble formed is stale afterwards: opmhip_solve_system wants a new assemble first. */
+int opmhip_set_std_wells_state(opmhip_ctx* ctx, const double* x, const int* control, const double* rate_target);
+/* for tests (any pointer may be NULL), what the last begin_iteration / assemble / update left: head [nperf], D and D^-1
+ * [num_wells * 16], B and C [nperf * 12] in opmhip_wells' layout, rates [nperf * 15] (3 components x value, d/dSw, d/dp, d/dX,
+ * d/dbhp), x_w [num_wells * 4] */
+int opmhip_get_std_wells_blocks(opmhip_ctx* ctx, double* head, double* D, double* Dinv, double* B, double* C, double* rates, double* xw);
+/* With a list set:
+ * opmhip_assemble forms, in front of the assembly kernel and of the aquifers' influx (the host order: wells' rates first), the
+ * perforation rates with their five derivatives, r_w, D, D^-1, B and C (computePerfRate, assembleWellEqWithoutIteration:
+ * StandardWell_impl.hpp:195-420, 516-640) and adds the rates of every distinct perforated cell, in perforation order, to its rows of
+ * the source arrays (computeTotalRatesForDof, BlackoilWellModel_impl.hpp:496-512); behind the assembly kernel the caller's rows are
+ * put back.  It stays a pure function of the device state: the controls change in opmhip_std_wells_begin_iteration only.  A well
+ * none of whose completions flows keeps its bottom-hole pressure (its control row becomes bhp-update = 0).  A D that meets a zero
+ * pivot sets a flag on the device; the next opmhip_get_std_wells or opmhip_solve_system reports OPMHIP_INVALID_ARGUMENT (well and
+ * column are named) and the list is cleared - its D^-1 is stored as zeros, never as NaNs.
+ * opmhip_solve_system(wells = NULL) takes the resident B / C / D^-1 as its operator form; a host list with num_wells > 0 is
+ * refused by every call that takes one (the operator would be applied twice); OPMHIP_NOT_READY before the first assemble.
+ * opmhip_advance_time_level / opmhip_update_failed also save / restore the well unknowns and the controls.
+ * Two wells in one cell: the new kernels add in perforation order, but the existing operator kernels (y -= C^T D^-1 B x, r -= C^T D^-1
+ * r_w) add two wells' contributions to a shared cell atomically, in either order - with a host list as with the resident one.  A run
+ * with such a cell is therefore not reproducible to the bit from run to run, nor against the host path; every other run is.
+ * With no list set, no existing call launches, copies or decides anything else than before. */
+
 /* replaces: model().linearizer().linearizeDomain() (flow/BlackoilModelEbos.hpp:424), then .jacobian() /
  * .residual() (:339-340, :526-527).  iteration == 0 also (re)fills the cached old-time-level storage term
  * (recycleFirstIterationStorage, ebos/eclproblem.hh:1758-1765).  Jacobian and residual stay on the device for

@@ -89,6 +89,34 @@ class Aquifers(C.Structure):
                 ("initial_watvolume", C.c_void_p), ("has_restart", C.c_void_p), ("restart_W_flux", C.c_void_p), ("restart_pressure", C.c_void_p)]
 
 
+class StdWells(C.Structure):
+    """opmhip_std_wells: standard wells for the device-resident form (opmhip_set_std_wells)"""
+    _fields_ = [("num_wells", C.c_int), ("perf_pointers", C.c_void_p), ("cell", C.c_void_p), ("tw", C.c_void_p), ("dz", C.c_void_p),
+                ("producer", C.c_void_p), ("inj_phase", C.c_void_p), ("rate_component", C.c_void_p), ("rate_target", C.c_void_p),
+                ("bhp_limit", C.c_void_p), ("control", C.c_void_p), ("x", C.c_void_p)]
+
+
+def make_std_wells(w):
+    """dict(perf_pointers, cell, tw, dz per perforation; producer, inj_phase, rate_component, rate_target, bhp_limit, control per well;
+    x (num_wells x 4) or None) - wells.DeviceStandardWells builds it - -> (StdWells struct, keep-alive dict)"""
+    if not w:
+        return None, {}
+    i32 = ("perf_pointers", "cell", "producer", "inj_phase", "rate_component", "control")
+    arr = {k: (_i32(w[k]) if k in i32 else _f64(w[k])) for k in ("perf_pointers", "cell", "tw", "dz", "producer", "inj_phase", "rate_component",
+                                                                  "rate_target", "bhp_limit", "control")}
+    arr["x"] = _f64(np.asarray(w["x"], float).reshape(-1)) if w.get("x") is not None else None
+    nw = len(arr["perf_pointers"]) - 1
+    nperf = int(arr["perf_pointers"][-1]) if nw >= 0 else -1
+    if nw < 0 or any(len(arr[k]) != nperf for k in ("cell", "tw", "dz")) or any(len(arr[k]) != nw for k in ("producer", "inj_phase", "rate_component",
+                                                                                                          "rate_target", "bhp_limit", "control")) \
+            or (arr["x"] is not None and len(arr["x"]) != 4 * nw):
+        raise ValueError("make_std_wells: array lengths do not fit perf_pointers")
+    s = StdWells(nw)
+    for name, _ in StdWells._fields_[1:]:
+        setattr(s, name, None if arr[name] is None else arr[name].ctypes.data)
+    return s, arr
+
+
 AQUIFER_TYPES = {"carter_tracy": 0, "fetkovich": 1}
 
 
@@ -597,6 +625,13 @@ def _bind_assembly(L):
     L.opmhip_aquifers_begin_time_step.argtypes = [vp, C.c_double, C.c_double]
     L.opmhip_get_aquifers.argtypes = [vp, vp, vp, vp, vp]
     L.opmhip_get_aquifer_rates.argtypes = [vp, vp]
+    L.opmhip_set_std_wells.argtypes = [vp, C.POINTER(StdWells)]
+    L.opmhip_std_wells_begin_iteration.argtypes = [vp, C.c_int]
+    L.opmhip_std_wells_apply_residual.argtypes = [vp]
+    L.opmhip_std_wells_update.argtypes = [vp, C.c_double]
+    L.opmhip_get_std_wells.argtypes = [vp, vp, vp, vp]
+    L.opmhip_set_std_wells_state.argtypes = [vp, vp, vp, vp]
+    L.opmhip_get_std_wells_blocks.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -870,6 +905,59 @@ class HipModel(HipSolver):
         q = np.zeros((getattr(self, "_naqconn", 0), 4))
         self._check(lib().opmhip_get_aquifer_rates(self._h, _ptr(q)))
         return q
+
+    def _check(self, rc):
+        """(a singular D reported by opmhip_get_std_wells / opmhip_solve_system clears the resident list: the sizes kept here follow.
+        The words looked for are those of std_wells_check's message in csrc/capi_asm.cpp: change both together)"""
+        try:
+            return HipSolver._check(self, rc)
+        except OpmHipError as e:
+            if "std_wells" in str(e) and "the list is cleared" in str(e):
+                self._nsw = self._nswperf = 0
+            raise
+
+    def set_std_wells(self, wells):
+        """opmhip_set_std_wells: the standard wells (dict, see make_std_wells) on the device; None clears them"""
+        sw, keep = make_std_wells(wells)
+        self._nsw = self._nswperf = 0      # a refused call leaves no list set
+        self._check(lib().opmhip_set_std_wells(self._h, C.byref(sw) if sw else None))
+        if sw:
+            self._nsw, self._nswperf = sw.num_wells, len(keep["cell"])
+
+    def std_wells_begin_iteration(self, iteration):
+        """opmhip_std_wells_begin_iteration: wellModel().beginIteration - at iteration 0 the heads and the wells alone, always the controls"""
+        self._check(lib().opmhip_std_wells_begin_iteration(self._h, int(iteration)))
+
+    def std_wells_apply_residual(self):
+        """opmhip_std_wells_apply_residual: r -= C^T D^-1 r_w with the resident blocks of the last assemble"""
+        self._check(lib().opmhip_std_wells_apply_residual(self._h))
+
+    def std_wells_update(self, relax=1.0):
+        """opmhip_std_wells_update: x_w = D^-1 (r_w - B x), well unknowns -= relax x_w, on the device"""
+        self._check(lib().opmhip_std_wells_update(self._h, float(relax)))
+
+    def get_std_wells(self):
+        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp, r_w (wells, 4))"""
+        n = getattr(self, "_nsw", 0)
+        x, ctl, rw = np.zeros((n, 4)), np.zeros(n, np.int32), np.zeros((n, 4))
+        self._check(lib().opmhip_get_std_wells(self._h, _ptr(x), _ptr(ctl), _ptr(rw)))
+        return x, ctl, rw
+
+    def set_std_wells_state(self, x=None, control=None, rate_target=None):
+        """opmhip_set_std_wells_state: well unknowns, controls in force, rate targets; None = that part stays"""
+        x, control, rate_target = _f64(x), _i32(control), _f64(rate_target)
+        n = getattr(self, "_nsw", 0)
+        if (x is not None and x.size != 4 * n) or (control is not None and control.size != n) or (rate_target is not None and rate_target.size != n):
+            raise ValueError("set_std_wells_state: array lengths do not fit the %d wells set" % n)
+        self._check(lib().opmhip_set_std_wells_state(self._h, _ptr(x), _ptr(control), _ptr(rate_target)))
+
+    def std_wells_blocks(self):
+        """for tests: dict(head, D, Dinv, B, C, rates, xw) as the last begin_iteration / assemble / update left them"""
+        n, p = getattr(self, "_nsw", 0), getattr(self, "_nswperf", 0)
+        out = dict(head=np.zeros(p), D=np.zeros((n, 4, 4)), Dinv=np.zeros((n, 4, 4)), B=np.zeros((p, 4, 3)), C=np.zeros((p, 4, 3)), rates=np.zeros((p, 3, 5)),
+                   xw=np.zeros((n, 4)))
+        self._check(lib().opmhip_get_std_wells_blocks(self._h, *[_ptr(out[k]) for k in ("head", "D", "Dinv", "B", "C", "rates", "xw")]))
+        return out
 
     def set_source(self, source, dsource=None):
         s, d = _f64(source), _f64(dsource)

@@ -1517,6 +1517,260 @@ void launch_aquifer_end(opmhip_ctx* c, double dt) {
     hipLaunchKernelGGL(k_aquifer_end, dim3((Q.num + 63) / 64), dim3(64), 0, c->stream, Q.num, dt, Q.d_ptr, Q.d_par, Q.d_q, Q.d_state);
 }
 
+// ============================== standard wells on the device (opmhip_set_std_wells) ===========================
+// computePerfRate and assembleWellEqWithoutIteration (wells/StandardWell_impl.hpp:195-420, 516-640) in the minimal form and in the
+// operation order of wells.py StandardWells(arithmetic="stated") - the library is built with -ffp-contract=off, so that every
+// expression below rounds where its NumPy counterpart rounds.  A5: value, d/dSw, d/dp, d/dX of the perforated cell, d/dbhp.
+// Plain wave64 kernels; no atomics; every sum over perforations is added by one lane in perforation order.
+struct A5 { double v[5]; };
+__device__ __forceinline__ A5 sw_load(const double* __restrict__ p) { return A5{{p[0], p[1], p[2], p[3], 0.0}}; }
+__device__ __forceinline__ A5 sw_mul(const A5& a, const A5& b) {   // the product rule of wells.py's `mul`
+    A5 o;
+    o.v[0] = a.v[0] * b.v[0];
+#pragma unroll
+    for (int i = 1; i < 5; ++i) o.v[i] = a.v[0] * b.v[i] + b.v[0] * a.v[i];
+    return o;
+}
+__device__ __forceinline__ A5 sw_scale(double s, const A5& a) { return A5{{s * a.v[0], s * a.v[1], s * a.v[2], s * a.v[3], s * a.v[4]}}; }
+__device__ __forceinline__ A5 sw_add(const A5& a, const A5& b) { return A5{{a.v[0] + b.v[0], a.v[1] + b.v[1], a.v[2] + b.v[2], a.v[3] + b.v[3], a.v[4] + b.v[4]}}; }
+__device__ __forceinline__ void sw_store(double* o, const A5& a) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = a.v[i];
+}
+// the connection rates of one perforation into the reservoir, out[component * 5 + (value, d/dSw, d/dp, d/dX, d/dbhp)]
+__device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head, bool producer, int injPhase,
+                                              double* out) {
+#pragma unroll
+    for (int i = 0; i < 15; ++i) out[i] = 0.0;
+    A5 dd = sw_load(iq_at(iq, ncell, F_P + OIL, c));
+    dd.v[0] = dd.v[0] - (bhp + head);   // the head between the reference depth and the completion is explicit
+    dd.v[4] = -1.0;
+    const double ntw = -tw;
+    if (producer) {   // phase rate = -Tw mob drawdown, surface volumes through 1/B, dissolved gas with the oil
+        if (!(dd.v[0] > 0.0)) return;   // no crossflow
+        A5 surf[3];
+#pragma unroll
+        for (int ph = 0; ph < 3; ++ph)
+            surf[ph] = sw_mul(sw_load(iq_at(iq, ncell, F_B + ph, c)), sw_scale(ntw, sw_mul(sw_load(iq_at(iq, ncell, F_MOB + ph, c)), dd)));
+        sw_store(out + EQ_OIL * 5, surf[OIL]);
+        sw_store(out + EQ_WATER * 5, surf[WATER]);
+        sw_store(out + EQ_GAS * 5, sw_add(surf[GAS], sw_mul(sw_load(iq_at(iq, ncell, F_RS, c)), surf[OIL])));
+    } else {          // total mobility, the injected phase's 1/B
+        if (!(dd.v[0] < 0.0)) return;
+        const A5 tot = sw_add(sw_add(sw_load(iq_at(iq, ncell, F_MOB + 0, c)), sw_load(iq_at(iq, ncell, F_MOB + 1, c))), sw_load(iq_at(iq, ncell, F_MOB + 2, c)));
+        const A5 vol = sw_scale(ntw, sw_mul(tot, dd));
+        const int comp = injPhase == GAS ? EQ_GAS : (injPhase == WATER ? EQ_WATER : EQ_OIL);
+        sw_store(out + comp * 5, sw_mul(sw_load(iq_at(iq, ncell, F_B + injPhase, c)), vol));
+    }
+}
+// wells.py invert4_stated: Gauss-Jordan on [D | I], partial pivoting (largest |entry| of the column, lowest row on ties), the pivot row
+// divided by the pivot, every other row updated as a - f * b.  -> 0, or 1 + the column without a pivot (inv is then left alone)
+__device__ int sw_invert4(const double* D, double* inv) {
+    double a[4][8];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) { a[i][j] = D[i * 4 + j]; a[i][4 + j] = i == j ? 1.0 : 0.0; }
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r)
+            if (fabs(a[r][col]) > fabs(a[piv][col])) piv = r;
+        if (!(fabs(a[piv][col]) > 0.0)) return 1 + col;
+        if (piv != col)
+            for (int j = 0; j < 8; ++j) { const double t = a[col][j]; a[col][j] = a[piv][j]; a[piv][j] = t; }
+        const double p = a[col][col];
+        for (int j = 0; j < 8; ++j) a[col][j] = a[col][j] / p;
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = a[r][col];
+            for (int j = 0; j < 8; ++j) a[r][j] = a[r][j] - f * a[col][j];
+        }
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) inv[i * 4 + j] = a[i][4 + j];
+    return 0;
+}
+struct SwArrays {
+    int num;
+    const int *vp, *cell, *wi;                  // perforation ranges, perforated cells (internal positions), per well: producer, injected phase, rate component
+    const double *wd, *tw, *dz;                 // per well: rate target, bhp limit; per perforation
+    double *head, *pr, *pack, *Dmat, *B, *C, *Dinv;
+};
+// One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
+// global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
+// without a flowing completion, and D^-1.  SOLVE: the well alone against the frozen reservoir (StandardWells.solve_well_equations) - the
+// heads first, then that body in a loop of at most 20 with the well's own stopping test, x -= D^-1 r_w in between; nothing but x, the
+// heads and the flag is written.
+template <bool SOLVE>
+__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, const double* __restrict__ iq, int first) {
+    __shared__ double sums[64 * 6];
+    __shared__ double xs[4];
+    __shared__ int s_active;
+    const int w = blockIdx.x, lane = threadIdx.x;
+    const int pb = W.vp[w], pe = W.vp[w + 1];
+    const bool producer = W.wi[3 * w] != 0;
+    const int injPhase = W.wi[3 * w + 1], comp = W.wi[3 * w + 2];
+    double* x = W.pack + (size_t)4 * w;
+    double* flag = W.pack + (size_t)9 * W.num + w;
+    if (SOLVE)   // calculate_explicit_quantities: (rho_o g) dz, constant through the time step; lane l owns perforations pb + l + 64 k here and below
+        for (int p = pb + lane; p < pe; p += 64) W.head[p] = (iq_at(iq, ncell, F_RHO + OIL, W.cell[p])[0] * GRAVITY) * W.dz[p];
+    if (lane == 0) {
+        for (int i = 0; i < 4; ++i) xs[i] = x[i];
+        if (SOLVE && first) xs[3] = iq_at(iq, ncell, F_P + OIL, W.cell[pb])[0] + (producer ? -1e5 : 1e5);
+        s_active = 1;
+    }
+    __syncthreads();
+    for (int it = 0; it < (SOLVE ? 20 : 1); ++it) {
+        const double bhp = xs[3];
+        double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // lane 0: sums of the rates and of d/dbhp
+        for (int p0 = pb; p0 < pe; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < pe) {
+                double q[15];
+                sw_perf_rates(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, q);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { sums[lane * 6 + c] = q[c * 5]; sums[lane * 6 + 3 + c] = q[c * 5 + 4]; }
+                if (!SOLVE) {
+                    double* pr = W.pr + (size_t)15 * p;
+                    double* B = W.B + (size_t)12 * p;
+                    double* C = W.C + (size_t)12 * p;
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) pr[i] = q[i];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        for (int v = 0; v < 3; ++v) { B[c * 3 + v] = -q[c * 5 + 1 + v]; C[c * 3 + v] = 0.0; }
+                        B[9 + c] = 0.0;
+                        C[9 + c] = -q[c * 5 + 4];
+                    }
+                }
+            }
+            __syncthreads();
+            if (lane == 0) {
+                const int m = pe - p0 < 64 ? pe - p0 : 64;
+                for (int j = 0; j < m; ++j)
+                    for (int k = 0; k < 6; ++k) S[k] = (p0 == pb && j == 0) ? sums[k] : S[k] + sums[j * 6 + k];
+            }
+            __syncthreads();
+        }
+        if (lane == 0) {
+            double r[4], D[16], inv[16];
+            for (int i = 0; i < 16; ++i) { D[i] = 0.0; inv[i] = 0.0; }
+            for (int c = 0; c < 3; ++c) { r[c] = xs[c] - S[c]; D[c * 4 + c] = 1.0; D[c * 4 + 3] = -S[3 + c]; }
+            if (W.pack[(size_t)4 * W.num + w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
+            else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
+            // a well none of whose completions flows has no rate that answers to its bottom-hole pressure: it keeps the pressure
+            if (D[3] == 0.0 && D[7] == 0.0 && D[11] == 0.0 && D[15] == 0.0) { r[3] = 0.0; D[12] = D[13] = D[14] = 0.0; D[15] = 1.0; }
+            const int sing = sw_invert4(D, inv);
+            if (sing) *flag = (double)sing;   // sticky: cleared by the host once it has looked
+            if (SOLVE) {
+                s_active = 0;
+                if (!sing) {
+                    double dx[4];
+                    for (int i = 0; i < 4; ++i) {
+                        double s = inv[i * 4] * r[0];
+                        for (int j = 1; j < 4; ++j) s += inv[i * 4 + j] * r[j];
+                        dx[i] = s;
+                        xs[i] = xs[i] - s;
+                    }
+                    const double mdx = fmax(fmax(fabs(dx[0]), fabs(dx[1])), fabs(dx[2])), mx = fmax(fmax(fabs(xs[0]), fabs(xs[1])), fabs(xs[2]));
+                    const bool small = mdx <= 1e-12 * fmax(1e-6, mx) && fabs(dx[3]) <= 1e-3;
+                    s_active = small ? 0 : 1;
+                }
+            } else {
+                for (int i = 0; i < 4; ++i) W.pack[(size_t)5 * W.num + 4 * w + i] = r[i];
+                for (int i = 0; i < 16; ++i) { W.Dmat[(size_t)16 * w + i] = D[i]; W.Dinv[(size_t)16 * w + i] = inv[i]; }   // a singular D: zeros, never NaNs
+            }
+        }
+        __syncthreads();
+        if (!SOLVE || !s_active) break;   // uniform: s_active is the workgroup's
+    }
+    if (SOLVE && lane == 0)
+        for (int i = 0; i < 4; ++i) x[i] = xs[i];
+}
+// update_well_controls, one lane per well
+__global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ pack) {
+    const int w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= num) return;
+    const bool producer = wi[3 * w] != 0;
+    const int comp = wi[3 * w + 2];
+    const double target = wd[2 * w], limit = wd[2 * w + 1];
+    double* x = pack + (size_t)4 * w;
+    double* control = pack + (size_t)4 * num + w;
+    if (*control == 0.0) {
+        if ((producer && x[3] < limit) || (!producer && x[3] > limit)) { *control = 1.0; x[3] = limit; }
+    } else if ((producer ? -1.0 : 1.0) * x[comp] > target) *control = 0.0;
+}
+// In front of k_assemble (and of k_aquifer_apply), one lane per DISTINCT perforated cell: the caller's source and dsource rows are kept in
+// `save`, the rates of the cell's perforations are added in perforation order (computeTotalRatesForDof)
+__global__ __launch_bounds__(64) void k_std_wells_source(int nd, const int* __restrict__ cpos, const int* __restrict__ cptr, const int* __restrict__ cperf,
+                                                         const double* __restrict__ pr, double* __restrict__ source, double* __restrict__ dsource, double* __restrict__ save) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= nd) return;
+    const int c = cpos[t];
+    double* s = source + (size_t)c * 3;
+    double* ds = dsource + (size_t)c * 9;
+    double v[12];
+    for (int i = 0; i < 3; ++i) v[i] = s[i];
+    for (int i = 0; i < 9; ++i) v[3 + i] = ds[i];
+    for (int i = 0; i < 12; ++i) save[(size_t)12 * t + i] = v[i];
+    for (int k = cptr[t]; k < cptr[t + 1]; ++k) {
+        const double* q = pr + (size_t)15 * cperf[k];
+        for (int e = 0; e < 3; ++e) {
+            v[e] += q[e * 5];
+            for (int d = 0; d < 3; ++d) v[3 + e * 3 + d] += q[e * 5 + 1 + d];
+        }
+    }
+    for (int i = 0; i < 3; ++i) s[i] = v[i];
+    for (int i = 0; i < 9; ++i) ds[i] = v[3 + i];
+}
+__global__ __launch_bounds__(64) void k_std_wells_restore(int nd, const int* __restrict__ cpos, const double* __restrict__ save, double* __restrict__ source,
+                                                          double* __restrict__ dsource) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= nd) return;
+    const int c = cpos[t];
+    for (int i = 0; i < 3; ++i) source[(size_t)c * 3 + i] = save[(size_t)12 * t + i];
+    for (int i = 0; i < 9; ++i) dsource[(size_t)c * 9 + i] = save[(size_t)12 * t + 3 + i];
+}
+// updateWellState: x -= relax * x_w
+__global__ __launch_bounds__(64) void k_std_wells_axpy(int n, double relax, const double* __restrict__ xw, double* __restrict__ x) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) x[i] = x[i] - relax * xw[i];
+}
+static SwArrays std_wells_arrays(const WellsDev& W) {
+    const StdWellsDev& S = W.sw;
+    return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.d_pack, S.d_Dmat, W.d_B, W.d_C, W.d_D};
+}
+// (booked under the profile's assembly class, one scope per function: a context with a list shows them in opmhip_profile_get)
+void launch_std_wells_solve(opmhip_ctx* c, bool first) {
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_eq<true>, dim3(c->wells.sw.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
+    prof_end(c, ps);
+}
+void launch_std_wells_controls(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_controls, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.d_pack);
+    prof_end(c, ps);
+}
+void launch_std_wells_assemble(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_eq<false>, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, 0);
+    hipLaunchKernelGGL(k_std_wells_source, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_cptr, S.d_cperf, S.d_pr, c->asmb.d_source,
+                       c->asmb.d_dsource, S.d_save);
+    prof_end(c, ps);
+}
+void launch_std_wells_restore(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_restore, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_save, c->asmb.d_source, c->asmb.d_dsource);
+    prof_end(c, ps);
+}
+void launch_std_wells_axpy(opmhip_ctx* c, double relax) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_axpy, dim3((4 * S.num + 63) / 64), dim3(64), 0, c->stream, 4 * S.num, relax, c->wells.d_xw, S.d_pack);
+    prof_end(c, ps);
+}
+
 // ============================== small permutation helpers =====================================================
 __global__ void k_cellvec_to_internal_u8(int Nb, const int* __restrict__ fromOrder, const unsigned char* __restrict__ nat, unsigned char* __restrict__ internal) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;

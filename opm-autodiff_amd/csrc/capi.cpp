@@ -83,6 +83,9 @@ static bool no_standard_wells(const opmhip_ctx* c, const opmhip_wells* w) {
 // the rank-local part of upload_wells: everything that can fail on this rank alone (validation, allocation, copies)
 static int upload_wells_local(opmhip_ctx* c, const opmhip_wells* w) {
     WellsDev& W = c->wells;
+    if (W.sw.num > 0 && w->num_wells > 0)
+        return fail(c, OPMHIP_INVALID_ARGUMENT, "wells: a host list of %d standard wells while a device-resident list of %d is set (opmhip_set_std_wells): the operator would be "
+                    "applied twice", w->num_wells, W.sw.num);
     if (w->num_ms_wells > 0) {
         // multisegment wells stay with the caller (their D^-1 is a sparse LU on the host, bda/MultisegmentWellContribution.cpp:35-62):
         // what the library needs is the callback and two pinned vectors for the round trip (bda/WellContributions.cu:160-187)
@@ -446,12 +449,22 @@ int opmhip_solve_system(opmhip_ctx* c, int N, int nnz, int dim, double* vals, co
         const Pattern& P = c->pat;
         if (N != P.Nb * 3 || nnz != P.nnzb * 9) return fail(c, OPMHIP_INVALID_ARGUMENT, "solve_system: size differs from the pattern set earlier");
         if (!vals && !c->system_loaded) return fail(c, OPMHIP_NOT_READY, "solve_system: vals == NULL but no matrix is resident on the device");
+        if (c->wells.sw.num > 0 && !c->wells.sw.assembled)
+            return fail(c, OPMHIP_NOT_READY, "solve_system: a device-resident list of standard wells is set (opmhip_set_std_wells) but not assembled: opmhip_assemble forms its B, C and D^-1");
         int rc;
         if ((rc = upload_system(c, vals, b))) return rc;
         const bool zfix = !vals && c->cfg.zero_diag_fix;   // device-assembled Jacobian: the same fix-up as the uploaded one gets
         if ((rc = upload_wells(c, wells))) return rc;
+        if (c->wells.sw.num > 0) {   // the zero-pivot flags of the resident standard wells ride on the synchronisation below
+            c->wells.sw.h_flag.resize(c->wells.sw.num);
+            OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.h_flag.data(), c->wells.sw.flag(), (size_t)c->wells.sw.num * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         if ((rc = ms_wells_check(c))) return rc;   // a device-resident multisegment list whose D turned out singular
+        if (c->wells.sw.num > 0) {                 // the resident standard wells: B, C, D^-1 as the last assemble formed them, in operator form
+            if ((rc = std_wells_check(c, c->wells.sw.h_flag.data()))) return rc;
+            c->wells.num_wells = c->wells.sw.num; c->wells.nperf = c->wells.sw.nperf; c->wells.distributed = false;
+        }
         const double t1 = now();
         FactorRider rider;   // CPR: weights and level 0's values of the pressure hierarchy are formed while the rows are in LDS
         if ((rc = cpr_factor_rider(c, &rider))) return rc;

@@ -499,6 +499,8 @@ int opmhip_advance_time_level(opmhip_ctx* c) {
         // ghost cells included: a later update_failed needs no communication
         OPMHIP_HIP(c, hipMemcpyAsync(A.d_pv_prev, A.d_pv, (size_t)c->pat.Nloc * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         OPMHIP_HIP(c, hipMemcpyAsync(A.d_meaning_prev, A.d_meaning, (size_t)c->pat.Nloc, hipMemcpyDeviceToDevice, c->stream));
+        if (c->wells.sw.num > 0)   // resident standard wells: the well state of the last accepted step (x | control)
+            OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_saved, c->wells.sw.d_pack, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         A.prev_set = true;
         return OPMHIP_SUCCESS;
     });
@@ -532,6 +534,10 @@ int opmhip_update_failed(opmhip_ctx* c) {
         OPMHIP_HIP(c, hipMemsetAsync(A.d_wasSwitched, 0, c->pat.Nloc, c->stream));
         launch_iq_update(c);
         OPMHIP_HIP(c, hipGetLastError());
+        if (c->wells.sw.num > 0) {
+            OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_pack, c->wells.sw.d_saved, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            c->wells.sw.assembled = false;
+        }
         A.assembled = false;
         return OPMHIP_SUCCESS;
     });
@@ -1222,20 +1228,281 @@ int opmhip_get_aquifer_rates(opmhip_ctx* c, double* q4) {
     });
 }
 
+// ---- standard wells on the device --------------------------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+void std_wells_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
+    dev_free(c, &S.d_pack); dev_free(c, &S.d_saved); dev_free(c, &S.d_Dmat);
+    dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
+    S.num = S.nperf = S.nd = 0;
+    S.initialised = S.assembled = false;
+    c->wells.num_wells = 0;   // no operator form of the list left behind for later products
+}
+}  // namespace
+
+// The zero-pivot flags as the caller has just read them back, where the host waits for the stream anyway.  A singular D clears the list and is
+// INVALID_ARGUMENT - the operator is never applied with a broken inverse.
+int opmhip::std_wells_check(opmhip_ctx* c, const double* h) {
+    StdWellsDev& S = c->wells.sw;
+    for (int w = 0; w < S.num; ++w)
+        if (h[w] != 0.0) {
+            const int col = (int)h[w] - 1;
+            std_wells_release(c);
+            // (capi.py's HipModel._check knows a cleared list by the words "std_wells" and "the list is cleared" of this text: change both together)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "std_wells: D of well %d is singular (no non-zero pivot in column %d of its elimination - a rate target on a component none of its "
+                        "completions can flow?); the list is cleared", w, col);
+        }
+    return OPMHIP_SUCCESS;
+}
+
+extern "C" {
+
+int opmhip_set_std_wells(opmhip_ctx* c, const opmhip_std_wells* sw) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AsmDev& A = c->asmb;
+        WellsDev& W = c->wells;
+        StdWellsDev& S = W.sw;
+        const Pattern& P = c->pat;
+        if (!A.static_set) return fail(c, OPMHIP_NOT_READY, "set_std_wells before set_static");
+        if (!A.state_set) return fail(c, OPMHIP_NOT_READY, "set_std_wells before set_state: the wells start from the reservoir state present");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        std_wells_release(c);   // whatever happens below, the old list is gone: a refused call leaves no list set
+        if (!sw || sw->num_wells == 0) return OPMHIP_SUCCESS;
+        if (c->comm.nranks > 1)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: decomposed context (%d ranks) - the per-well sums over the ranks are not built; hand the wells over as a host list (opmhip_wells.distributed)", c->comm.nranks);
+        const int nw = sw->num_wells;
+        if (nw < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: num_wells = %d", nw);
+        if (!sw->perf_pointers || !sw->cell || !sw->tw || !sw->dz || !sw->producer || !sw->inj_phase || !sw->rate_component || !sw->rate_target || !sw->bhp_limit || !sw->control)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: null array (only x is optional)");
+        if (sw->perf_pointers[0] != 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: inconsistent pointers (perf_pointers[0] = %d, not 0)", sw->perf_pointers[0]);
+        for (int w = 0; w < nw; ++w) {
+            if (sw->perf_pointers[w + 1] <= sw->perf_pointers[w]) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: inconsistent pointers (well %d has no perforation)", w);
+            if (sw->producer[w] != 0 && sw->producer[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: producer[%d] = %d (1 producer, 0 injector)", w, sw->producer[w]);
+            if (!sw->producer[w] && (sw->inj_phase[w] < 0 || sw->inj_phase[w] > 2))
+                return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: unknown phase: inj_phase[%d] = %d (0 water, 1 oil, 2 gas)", w, sw->inj_phase[w]);
+            if (sw->rate_component[w] < 0 || sw->rate_component[w] > 2)
+                return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: unknown component: rate_component[%d] = %d (0 oil, 1 water, 2 gas)", w, sw->rate_component[w]);
+            if (sw->control[w] != 0 && sw->control[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: control[%d] = %d (0 rate, 1 bhp)", w, sw->control[w]);
+            if (!std::isfinite(sw->rate_target[w]) || !std::isfinite(sw->bhp_limit[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: rate target / bhp limit of well %d is not finite", w);
+        }
+        const int np = sw->perf_pointers[nw];
+        // the perforated cells in the internal order; the distinct ones, each with its perforations in perforation order
+        std::vector<int> pos(np), cpos, cptr, cperf(np);
+        {
+            std::vector<int> slot(P.Nb, -1), count;
+            for (int p = 0; p < np; ++p) {
+                const int cell = sw->cell[p];
+                if (cell < 0 || cell >= P.Nb) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: perforation %d names cell %d, outside [0, %d)", p, cell, P.Nb);
+                if (!std::isfinite(sw->tw[p]) || !std::isfinite(sw->dz[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: tw / dz of perforation %d is not finite", p);
+                pos[p] = P.toOrder[cell];
+                if (slot[cell] < 0) { slot[cell] = (int)cpos.size(); cpos.push_back(pos[p]); count.push_back(0); }
+                count[slot[cell]]++;
+            }
+            cptr.assign(cpos.size() + 1, 0);
+            for (size_t t = 0; t < cpos.size(); ++t) cptr[t + 1] = cptr[t] + count[t];
+            std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+            for (int p = 0; p < np; ++p) cperf[fill[slot[sw->cell[p]]]++] = p;
+        }
+        std::vector<int> wi((size_t)3 * nw);
+        std::vector<double> wd((size_t)2 * nw), pack((size_t)10 * nw, 0.0);
+        for (int w = 0; w < nw; ++w) {
+            wi[3 * w] = sw->producer[w]; wi[3 * w + 1] = sw->producer[w] ? 0 : sw->inj_phase[w]; wi[3 * w + 2] = sw->rate_component[w];
+            wd[2 * w] = sw->rate_target[w]; wd[2 * w + 1] = sw->bhp_limit[w];
+            for (int i = 0; i < 4; ++i) pack[(size_t)4 * w + i] = sw->x ? sw->x[(size_t)4 * w + i] : 0.0;
+            pack[(size_t)4 * nw + w] = sw->control[w];
+        }
+        const int rc = [&]() -> int {
+            int r;
+            // WellsDev's arrays sized for the list: written by kernels from now on.  What they held of a host list is gone: the record of it
+            // is emptied, so that a later host list is copied again
+            if ((size_t)nw > W.cap_wells) {
+                dev_free(c, &W.d_val_pointers); dev_free(c, &W.d_D); dev_free(c, &W.d_res); dev_free(c, &W.d_xw); dev_free(c, &W.d_bx);
+                W.cap_wells = 0;
+                if ((r = dev_alloc(c, &W.d_val_pointers, (size_t)nw + 1)) || (r = dev_alloc(c, &W.d_D, (size_t)nw * 16)) || (r = dev_alloc(c, &W.d_res, (size_t)nw * 4)) ||
+                    (r = dev_alloc(c, &W.d_xw, (size_t)nw * 4)) || (r = dev_alloc(c, &W.d_bx, (size_t)nw * 4)))
+                    return r;
+                W.cap_wells = nw;
+            }
+            if ((size_t)np > W.cap_perf) {
+                dev_free(c, &W.d_Ccols); dev_free(c, &W.d_Bcols); dev_free(c, &W.d_C); dev_free(c, &W.d_B);
+                W.cap_perf = 0;
+                if ((r = dev_alloc(c, &W.d_Ccols, (size_t)np)) || (r = dev_alloc(c, &W.d_Bcols, (size_t)np)) || (r = dev_alloc(c, &W.d_C, (size_t)np * 12)) ||
+                    (r = dev_alloc(c, &W.d_B, (size_t)np * 12)))
+                    return r;
+                W.cap_perf = np;
+            }
+            W.h_vp.clear(); W.h_D.clear(); W.h_cc.clear(); W.h_bc.clear(); W.h_C.clear(); W.h_B.clear();
+            OPMHIP_HIP(c, hipMemcpy(W.d_val_pointers, sw->perf_pointers, ((size_t)nw + 1) * sizeof(int), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemcpy(W.d_Ccols, pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemcpy(W.d_Bcols, pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemset(W.d_D, 0, (size_t)nw * 16 * sizeof(double)));
+            OPMHIP_HIP(c, hipMemset(W.d_B, 0, (size_t)np * 12 * sizeof(double)));
+            OPMHIP_HIP(c, hipMemset(W.d_C, 0, (size_t)np * 12 * sizeof(double)));
+            OPMHIP_HIP(c, hipMemset(W.d_xw, 0, (size_t)nw * 4 * sizeof(double)));
+            const std::vector<double> tw(sw->tw, sw->tw + np), dz(sw->dz, sw->dz + np), zp((size_t)15 * np, 0.0), zw((size_t)16 * nw, 0.0);
+            if ((r = dev_upload(c, &S.d_wi, wi)) || (r = dev_upload(c, &S.d_wd, wd)) || (r = dev_upload(c, &S.d_tw, tw)) || (r = dev_upload(c, &S.d_dz, dz)) ||
+                (r = dev_upload(c, &S.d_head, std::vector<double>(np, 0.0))) || (r = dev_upload(c, &S.d_pr, zp)) || (r = dev_upload(c, &S.d_pack, pack)) ||
+                (r = dev_upload(c, &S.d_saved, std::vector<double>((size_t)5 * nw, 0.0))) || (r = dev_upload(c, &S.d_Dmat, zw)) || (r = dev_upload(c, &S.d_cpos, cpos)) ||
+                (r = dev_upload(c, &S.d_cptr, cptr)) || (r = dev_upload(c, &S.d_cperf, cperf)) || (r = dev_alloc(c, &S.d_save, cpos.size() * 12)))
+                return r;
+            OPMHIP_HIP(c, hipMemcpy(S.d_saved, pack.data(), (size_t)5 * nw * sizeof(double), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+            return OPMHIP_SUCCESS;
+        }();
+        if (rc) { std_wells_release(c); return rc; }
+        S.num = nw; S.nperf = np; S.nd = (int)cpos.size();
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_std_wells_begin_iteration(opmhip_ctx* c, int iteration) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        if (iteration < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "std_wells_begin_iteration: iteration = %d", iteration);
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        if (iteration == 0) {   // calculateExplicitQuantities, prepareTimeStep
+            launch_std_wells_solve(c, !S.initialised);
+            S.initialised = true;
+        }
+        launch_std_wells_controls(c);   // updateWellControls
+        OPMHIP_HIP(c, hipGetLastError());
+        S.assembled = false;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_std_wells_apply_residual(opmhip_ctx* c) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        WellsDev& W = c->wells;
+        if (W.sw.num == 0) return fail(c, OPMHIP_NOT_READY, "std_wells_apply_residual: no resident list (opmhip_set_std_wells)");
+        if (!W.sw.assembled || !c->asmb.assembled) return fail(c, OPMHIP_NOT_READY, "std_wells_apply_residual before opmhip_assemble: there is no r_w");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        W.num_wells = W.sw.num; W.nperf = W.sw.nperf; W.distributed = false;
+        launch_wells_residual(c, W.sw.rw(), c->d_b);   // wellModel().apply(r): r -= C^T D^-1 r_w
+        W.num_wells = 0;                               // the operator form is set per solve_system call
+        OPMHIP_HIP(c, hipGetLastError());
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_std_wells_update(opmhip_ctx* c, double relax) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        WellsDev& W = c->wells;
+        if (W.sw.num == 0) return fail(c, OPMHIP_NOT_READY, "std_wells_update: no resident list (opmhip_set_std_wells)");
+        if (!c->have_result) return fail(c, OPMHIP_NOT_READY, "std_wells_update before a solve");
+        if (!W.sw.assembled) return fail(c, OPMHIP_NOT_READY, "std_wells_update before opmhip_assemble: there is no r_w");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        W.num_wells = W.sw.num; W.nperf = W.sw.nperf; W.distributed = false;
+        const int rc = launch_wells_recover(c, W.sw.rw(), c->d_x, W.d_xw);   // x_w = D^-1 (r_w - B x)
+        W.num_wells = 0;
+        if (rc) return rc;
+        launch_std_wells_axpy(c, relax);
+        OPMHIP_HIP(c, hipGetLastError());
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells(opmhip_ctx* c, double* x, int* control, double* res_well) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        const size_t nw = S.num;
+        std::vector<double> h(10 * nw);
+        OPMHIP_HIP(c, hipMemcpyAsync(h.data(), S.d_pack, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        const int rc = std_wells_check(c, &h[9 * nw]);
+        if (rc) return rc;
+        if (x) std::memcpy(x, &h[0], 4 * nw * sizeof(double));
+        if (control)
+            for (size_t w = 0; w < nw; ++w) control[w] = h[4 * nw + w] != 0.0;
+        if (res_well) std::memcpy(res_well, &h[5 * nw], 4 * nw * sizeof(double));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* control, const double* rate_target) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_state: no resident list (opmhip_set_std_wells)");
+        const size_t nw = S.num;
+        if (control)
+            for (size_t w = 0; w < nw; ++w)
+                if (control[w] != 0 && control[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: control[%zu] = %d (0 rate, 1 bhp)", w, control[w]);
+        if (rate_target)
+            for (size_t w = 0; w < nw; ++w)
+                if (!std::isfinite(rate_target[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: rate_target[%zu] is not finite", w);
+        if (x)
+            for (size_t i = 0; i < 4 * nw; ++i)
+                if (!std::isfinite(x[i])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: x[%zu] is not finite", i);
+        S.assembled = false;   // from here on the device state changes: nothing a refusal above could have left half done
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // rare: events and restarts
+        if (x) OPMHIP_HIP(c, hipMemcpy(S.x(), x, 4 * nw * sizeof(double), hipMemcpyHostToDevice));
+        if (control) {
+            std::vector<double> h(nw);
+            for (size_t w = 0; w < nw; ++w) h[w] = control[w];
+            OPMHIP_HIP(c, hipMemcpy(S.control(), h.data(), nw * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (rate_target) {
+            std::vector<double> wd(2 * nw);
+            OPMHIP_HIP(c, hipMemcpy(wd.data(), S.d_wd, wd.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < nw; ++w) wd[2 * w] = rate_target[w];
+            OPMHIP_HIP(c, hipMemcpy(S.d_wd, wd.data(), wd.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        OPMHIP_HIP(c, hipDeviceSynchronize());
+        S.assembled = false;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_blocks(opmhip_ctx* c, double* head, double* D, double* Dinv, double* B, double* C, double* rates, double* xw) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const WellsDev& W = c->wells;
+        const StdWellsDev& S = W.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        const size_t nw = S.num, np = S.nperf;
+        if (head) OPMHIP_HIP(c, hipMemcpy(head, S.d_head, np * sizeof(double), hipMemcpyDeviceToHost));
+        if (D) OPMHIP_HIP(c, hipMemcpy(D, S.d_Dmat, nw * 16 * sizeof(double), hipMemcpyDeviceToHost));
+        if (Dinv) OPMHIP_HIP(c, hipMemcpy(Dinv, W.d_D, nw * 16 * sizeof(double), hipMemcpyDeviceToHost));
+        if (B) OPMHIP_HIP(c, hipMemcpy(B, W.d_B, np * 12 * sizeof(double), hipMemcpyDeviceToHost));
+        if (C) OPMHIP_HIP(c, hipMemcpy(C, W.d_C, np * 12 * sizeof(double), hipMemcpyDeviceToHost));
+        if (rates) OPMHIP_HIP(c, hipMemcpy(rates, S.d_pr, np * 15 * sizeof(double), hipMemcpyDeviceToHost));
+        if (xw) OPMHIP_HIP(c, hipMemcpy(xw, W.d_xw, nw * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
 int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double* residual) {
     if (!c) return OPMHIP_INVALID_ARGUMENT;
     return guarded(c, [&]() -> int {
         if (!c->asmb.state_set) return fail(c, OPMHIP_NOT_READY, "assemble before set_state");
         if (!(dt > 0.0) || iteration < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: dt must be positive, iteration >= 0");
         const AquifersDev& Q = c->asmb.aq;
+        StdWellsDev& SW = c->wells.sw;
         if (Q.num > 0 && !Q.stepped) return fail(c, OPMHIP_NOT_READY, "assemble: aquifers are set but opmhip_aquifers_begin_time_step was not called");
         if (Q.num > 0 && dt != Q.step_dt) return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: dt = %.17g, the aquifers' time step was begun with dt = %.17g", dt, Q.step_dt);
         OPMHIP_HIP(c, hipSetDevice(c->device));
         c->asmb.last_dt = dt;
         c->asmb.last_iteration = iteration;
+        if (SW.num > 0) { launch_std_wells_assemble(c); SW.assembled = true; }   // wellModel().assemble: rates first, then the aquifers (the host order)
         if (Q.nd > 0) launch_aquifer_apply(c);     // aquiferModel_.addToSource (ebos/eclproblem.hh:1843)
         launch_assemble(c, dt, iteration);
         if (Q.nd > 0) launch_aquifer_restore(c);   // the caller's source arrays as the caller left them
+        if (SW.num > 0) launch_std_wells_restore(c);
         OPMHIP_HIP(c, hipGetLastError());
         c->system_loaded = true;
         c->factored = false;

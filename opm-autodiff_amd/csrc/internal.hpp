@@ -175,7 +175,30 @@ struct MsWellsDev {
     std::vector<double> h_Bvals, h_Cvals, h_Dvals;
 };
 
+// Standard wells resident on the device (opmhip_set_std_wells): the well equations of wells.py's StandardWells, formed by kernels
+// into WellsDev's d_B / d_C / d_D (= D^-1) / d_val_pointers / d_Ccols / d_Bcols, which the existing operator kernels then read.
+// d_pack, one array so that a Newton iteration reads back once: x [4 num] | control [num] (0.0 rate, 1.0 bhp) | r_w [4 num] |
+// flag [num] (0.0, or 1 + the column whose pivot was zero; sticky until the host has looked).  d_saved: x | control of the last
+// opmhip_advance_time_level.
+struct StdWellsDev {
+    int num = 0, nperf = 0, nd = 0;
+    bool initialised = false;    // the first begin_iteration(0) has set the bottom-hole pressures
+    bool assembled = false;      // B, C, D^-1, r_w belong to the well unknowns now present
+    int* d_wi = nullptr;         // per well: producer, injected phase, rate component
+    double* d_wd = nullptr;      // per well: rate target, bhp limit
+    double *d_tw = nullptr, *d_dz = nullptr, *d_head = nullptr, *d_pr = nullptr;   // per perforation; d_pr: 15 doubles, [component][value, d/dSw, d/dp, d/dX, d/dbhp]
+    double *d_pack = nullptr, *d_saved = nullptr, *d_Dmat = nullptr;
+    int *d_cpos = nullptr, *d_cptr = nullptr, *d_cperf = nullptr;   // distinct perforated cells: position, range into d_cperf, their perforations in perforation order
+    double* d_save = nullptr;    // per distinct cell: the caller's 3 source and 9 dsource entries
+    std::vector<double> h_flag;  // opmhip_solve_system: the flags' copy, queued in front of the synchronisation it does anyway
+    double* x() const { return d_pack; }
+    double* control() const { return d_pack + (size_t)4 * num; }
+    double* rw() const { return d_pack + (size_t)5 * num; }
+    double* flag() const { return d_pack + (size_t)9 * num; }
+};
+
 struct WellsDev {
+    StdWellsDev sw;
     int num_wells = 0, nperf = 0;
     int *d_val_pointers = nullptr, *d_Ccols = nullptr, *d_Bcols = nullptr;
     double *d_C = nullptr, *d_D = nullptr, *d_B = nullptr;
@@ -682,6 +705,13 @@ void launch_aquifer_begin(opmhip_ctx* c);    // pressure_previous_ = p_w of the 
 void launch_aquifer_apply(opmhip_ctx* c);    // Qai_ of every connection; saved and raised source rows of the connected cells (in front of k_assemble)
 void launch_aquifer_restore(opmhip_ctx* c);  // the caller's source rows back (behind k_assemble)
 void launch_aquifer_end(opmhip_ctx* c, double dt);
+// standard wells on the device (opmhip_set_std_wells; assemble.hip)
+int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_asm.cpp: the zero-pivot flags as the caller has just read them back; a singular D clears the list
+void launch_std_wells_solve(opmhip_ctx* c, bool first);   // heads, then the wells alone against the frozen reservoir (iteration 0)
+void launch_std_wells_controls(opmhip_ctx* c);            // updateWellControls
+void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
+void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)
+void launch_std_wells_axpy(opmhip_ctx* c, double relax);  // x -= relax * x_w
 void launch_last_rs_rv(opmhip_ctx* c);
 void launch_set_limits(opmhip_ctx* c, double dt);
 void launch_min_pressure(opmhip_ctx* c, bool init);

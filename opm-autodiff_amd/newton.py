@@ -67,7 +67,7 @@ class BlackoilModelHip:
     def __init__(self, model, param=None, well_model=None, aquifer_model=None):
         """aquifer_model (aquifers.DeviceAquifers, aquifers.HostAquifers or None): the analytic aquifers - aquiferModel_ of EclProblem
         (initialSolutionApplied here, beginTimeStep / addToSource / endTimeStep below); the model's state must be set.
-        well_model (wells.StandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
+        well_model (wells.StandardWells, wells.DeviceStandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
         reservoir's linearisation (BlackoilModelEbos::assembleReservoir -> wellModel().assemble, flow/BlackoilModelEbos.hpp:418-428),
         eliminated from the linear system by the device (wells/StandardWell_impl.hpp:1254-1311) and updated with the reservoir"""
         self.m = model
@@ -122,7 +122,14 @@ class BlackoilModelHip:
         rep.total_linearizations = 1
         t0 = time.perf_counter()
         wa = None
-        if self.wells is not None:
+        dev_wells = self.wells is not None and getattr(self.wells, "on_device", False)
+        if dev_wells:
+            # the same on the device (opmhip_set_std_wells): nothing comes down and nothing goes up here - opmhip_assemble forms the well
+            # equations and the connection rates itself, in front of the reservoir's linearisation
+            if self.aquifers is not None and not self.aquifers.on_device:
+                raise NotImplementedError("HostAquifers beside DeviceStandardWells: the influx would replace the caller's source rows behind the wells' back")
+            self.wells.begin_iteration(iteration)
+        elif self.wells is not None:
             # wellModel().beginIteration / assemble (wells/BlackoilWellModel_impl.hpp:148-171, 1033-1101): controls, well equations at the
             # present reservoir state, their connection rates as the perforated cells' source terms (computeTotalRatesForDof :496-512)
             # (only the perforated cells' records come back from the device and only their rates go there: updatePerforationIntensiveQuantities
@@ -153,6 +160,9 @@ class BlackoilModelHip:
         conv, norms = self.get_convergence(dt, iteration)    # synchronises: reads the reduced scalars back
         if wa is not None:
             conv = conv and self.wells.converged(wa["res_well"])   # getWellConvergence (flow/BlackoilModelEbos.hpp:906-912)
+        if dev_wells:
+            self.wells.fetch()                                     # the one read-back: x, controls, r_w (the stream has just been drained)
+            conv = conv and self.wells.converged()
         t1 = time.perf_counter()
         # The reference books assembly under assemble_time and the convergence check under update_time
         # (BlackoilModelEbos.hpp:296-297, 311-323).  Both are enqueued back to back here and only the convergence
@@ -167,6 +177,9 @@ class BlackoilModelHip:
             if wa is not None:
                 self.m.wells_apply_residual(wa["wells"], wa["res_well"])        # wellModel().apply(r): r -= C^T D^-1 r_w (:523-527)
                 res = self.m.solve_jacobian_system(wells=wa["wells"])           # the operator A - C^T D^-1 B (WellModelMatrixAdapter)
+            elif dev_wells:
+                self.m.std_wells_apply_residual()
+                res = self.m.solve_jacobian_system()         # the resident B / C / D^-1 are its operator form
             else:
                 res = self.m.solve_jacobian_system()         # solveJacobianSystem: ILU0 setup + BiCGStab
             rep.linear_solve_setup_time += res.t_factor
@@ -181,6 +194,8 @@ class BlackoilModelHip:
                 self.current_relaxation = max(self.current_relaxation - self.param.relax_increment, self.param.relax_max)
             if wa is not None:   # recoverWellSolutionAndUpdateWellState (:1033-1042): x_w = D^-1 (r_w - B x), same relaxation
                 self.wells.update(self.m.wells_recover_solution(wa["wells"], wa["res_well"]), self.current_relaxation)
+            if dev_wells:
+                self.wells.update(self.current_relaxation)
             self.m.update(None, self.current_relaxation)      # stabilizeNonlinearUpdate (dampen) + updateSolution
             rep.update_time += time.perf_counter() - t2
         return rep
@@ -204,8 +219,8 @@ class BlackoilModelHip:
 
     # -- FvBaseDiscretization::advanceTimeLevel / updateFailed ---------------------------------------------------
     def advance_time_level(self):
-        self.m.advance_time_level()
-        if self.wells is not None:
+        self.m.advance_time_level()          # with wells on the device: their unknowns and controls too, here and in update_failed
+        if self.wells is not None and not getattr(self.wells, "on_device", False):
             self._well_saved = self.wells.state()      # the well state of the last accepted step (WellState copy of a failed step's restart)
 
     def update_failed(self):

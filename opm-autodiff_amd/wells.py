@@ -35,6 +35,62 @@ def peaceman_factor(perm, dx, dy, dz, diameter, skin=0.0):
     return 2.0 * np.pi * perm * dz / (np.log(r0 / (0.5 * diameter)) + skin)
 
 
+class SingularWellEquations(ValueError):
+    """invert4_stated met a column without a non-zero pivot; .column says which"""
+
+    def __init__(self, column):
+        ValueError.__init__(self, "D is singular: no non-zero pivot in column %d of its elimination" % column)
+        self.column = column
+
+
+def invert4_stated(D):
+    """D^-1 of one 4 x 4 matrix in an order a kernel can follow (csrc/assemble.hip sw_invert4 is this routine): Gauss-Jordan on [D | I],
+    column by column; the pivot is the largest |entry| of the column at or below the diagonal, the lowest row on ties; the pivot row is
+    divided by the pivot, every other row is updated as a - f * b - one rounding per operation.  A column without a non-zero pivot
+    raises SingularWellEquations instead of dividing by it."""
+    a = [[float(D[i][j]) for j in range(4)] + [1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+    for col in range(4):
+        piv = col
+        for r in range(col + 1, 4):
+            if abs(a[r][col]) > abs(a[piv][col]):
+                piv = r
+        if not abs(a[piv][col]) > 0.0:
+            raise SingularWellEquations(col)
+        a[col], a[piv] = a[piv], a[col]
+        p = a[col][col]
+        a[col] = [v / p for v in a[col]]
+        for r in range(4):
+            if r != col:
+                f = a[r][col]
+                a[r] = [a[r][j] - f * a[col][j] for j in range(8)]
+    return np.array([row[4:] for row in a])
+
+
+def sequential_sums(a, pointers):
+    """per range [pointers[k], pointers[k + 1]) of the rows of a (n x m): their sum, added row by row in ascending order starting from the
+    first row - the loop a single lane runs.  (np.add.reduceat reduces pairwise and gives other bits.)"""
+    a = np.asarray(a, float)
+    out = np.zeros((len(pointers) - 1,) + a.shape[1:])
+    for k in range(len(pointers) - 1):
+        if pointers[k + 1] > pointers[k]:
+            s = a[pointers[k]].copy()
+            for j in range(pointers[k] + 1, pointers[k + 1]):
+                s = s + a[j]
+            out[k] = s
+    return out
+
+
+def row_times_vector(M, r):
+    """M r for one 4 x 4 matrix, every row's products added in ascending column order starting from the first"""
+    out = []
+    for i in range(4):
+        s = float(M[i][0]) * float(r[0])
+        for j in range(1, 4):
+            s += float(M[i][j]) * float(r[j])
+        out.append(s)
+    return np.array(out)
+
+
 class Well:
     """name; cells: perforated cells (natural order); tw: connection transmissibility factors; ref_depth; producer or injector of `phase`;
     control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit"""
@@ -63,9 +119,18 @@ def _rows(iq, cells):
 
 class StandardWells:
     """All wells at once: every step below is one pass of array arithmetic over the perforations (nperf x 5: value, d/dSw, d/dp, d/dX of the
-    perforated cell, d/dbhp), per-well sums in the order of the perforations."""
+    perforated cell, d/dbhp), per-well sums in the order of the perforations.
 
-    def __init__(self, wells, cell_depth):
+    arithmetic="numpy" (the default): the sums by np.add.reduceat (which reduces pairwise), D^-1 by np.linalg.  arithmetic="stated": the
+    same equations in an order a kernel can follow, operation by operation - the sums by sequential_sums, D^-1 by invert4_stated, D^-1 r
+    by row_times_vector; everything else (the product rule, the drawdown, the branches, the guard, the control rows) is elementwise IEEE
+    arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
+    bit; a singular D raises SingularWellEquations there."""
+
+    def __init__(self, wells, cell_depth, arithmetic="numpy"):
+        if arithmetic not in ("numpy", "stated"):
+            raise ValueError("arithmetic: 'numpy' or 'stated'")
+        self.arithmetic = arithmetic
         self.wells = list(wells)
         self.nw = len(self.wells)
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
@@ -187,9 +252,13 @@ class StandardWells:
         r = np.zeros((self.nw, 4))
         D = np.zeros((self.nw, 4, 4))
         seg = self.vp[:-1]
-        r[:, :3] = self.x[:, :3] - np.add.reduceat(pr[:, :, 0], seg, axis=0)          # surface rate - sum of the connection rates
+        if self.arithmetic == "stated":
+            sums, dsums = sequential_sums(pr[:, :, 0], self.vp), sequential_sums(pr[:, :, 4], self.vp)
+        else:
+            sums, dsums = np.add.reduceat(pr[:, :, 0], seg, axis=0), np.add.reduceat(pr[:, :, 4], seg, axis=0)
+        r[:, :3] = self.x[:, :3] - sums          # surface rate - sum of the connection rates
         D[:, [0, 1, 2], [0, 1, 2]] = 1.0
-        D[:, :3, 3] = -np.add.reduceat(pr[:, :, 4], seg, axis=0)
+        D[:, :3, 3] = -dsums
         r[:, 3], D[:, 3, :] = self._control_rows()
         # a well none of whose completions flows (its bottom-hole pressure on the wrong side of every completion's pressure) has no rate that
         # answers to its bottom-hole pressure: under a rate target its equations would be singular.  It keeps its bottom-hole pressure for
@@ -211,7 +280,12 @@ class StandardWells:
         active = np.ones(self.nw, bool)
         for _ in range(iterations):
             r, D, *_ = self._assemble_wells(iq)
-            dx = np.linalg.solve(D, r[:, :, None])[:, :, 0]
+            if self.arithmetic == "stated":      # (a well that has stopped is not looked at again: its x and so its D no longer change)
+                dx = np.zeros((self.nw, 4))
+                for k in np.flatnonzero(active):
+                    dx[k] = row_times_vector(invert4_stated(D[k]), r[k])
+            else:
+                dx = np.linalg.solve(D, r[:, :, None])[:, :, 0]
             self.x[active] -= dx[active]
             small = (np.abs(dx[:, :3]).max(axis=1) <= 1e-12 * np.maximum(1e-6, np.abs(self.x[:, :3]).max(axis=1))) & (np.abs(dx[:, 3]) <= 1e-3)
             active &= ~small
@@ -224,7 +298,7 @@ class StandardWells:
         BlackoilWellModel::assemble at the present reservoir and well state.  ncells: also `source` / `dsource` as arrays over the whole grid
         (opmhip_set_source's form)."""
         rw, D, Bn, Cn, src, dsrc = self._assemble_wells(iq)
-        Dinv = np.linalg.inv(D)
+        Dinv = np.array([invert4_stated(d) for d in D]) if self.arithmetic == "stated" else np.linalg.inv(D)
         nu = len(self.ucells)
         source_cells, dsource_cells = np.zeros((nu, 3)), np.zeros((nu, 3, 3))
         np.add.at(source_cells, self.perf_row, src)
@@ -263,3 +337,66 @@ class StandardWells:
         self.x = st[0].copy()
         for w, c in zip(self.wells, st[1]):
             w.control = c
+
+
+class DeviceStandardWells:
+    """The same wells resident on the device (opmhip_set_std_wells): model is a capi.HipModel whose state is set.  The well unknowns, the
+    controls, the heads and the blocks B, C, D^-1 live there; what this object holds of them (x, controls, res_well) is the last read-back
+    (fetch).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
+    on_device = True
+
+    def __init__(self, wells, cell_depth, model):
+        self.wells = list(wells)
+        self.nw = len(self.wells)
+        self.m = model
+        phase = {"water": PH_W, "oil": PH_O, "gas": PH_G}
+        depth = np.asarray(cell_depth, float)
+        for w in self.wells:
+            if w.rate_control[0] != "rate" or (w.control[0] == "bhp" and w.control[1] != w.bhp_limit):
+                raise ValueError("DeviceStandardWells: well %s needs a rate target and, under BHP control, its limit as the target" % w.name)
+            if not w.producer and w.inj_phase not in phase:
+                raise ValueError("DeviceStandardWells: injector %s with unknown phase %r" % (w.name, w.inj_phase))
+        self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
+        self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
+        model.set_std_wells(dict(
+            perf_pointers=self.vp, cell=self.cells, tw=np.concatenate([w.tw for w in self.wells]),
+            dz=np.concatenate([depth[w.cells] - w.ref_depth for w in self.wells]),
+            producer=[int(w.producer) for w in self.wells], inj_phase=[0 if w.producer else phase[w.inj_phase] for w in self.wells],
+            rate_component=[w.rate_control[1] for w in self.wells], rate_target=[w.rate_control[2] for w in self.wells],
+            bhp_limit=[w.bhp_limit for w in self.wells], control=[int(w.control[0] == "bhp") for w in self.wells], x=None))
+        self.x = np.zeros((self.nw, 4))
+        self.res_well = np.zeros((self.nw, 4))
+
+    def begin_iteration(self, iteration):
+        self.m.std_wells_begin_iteration(iteration)
+
+    def fetch(self):
+        """opmhip_get_std_wells: x, the controls in force (onto the Well objects) and r_w of the last assemble"""
+        self.x, ctl, self.res_well = self.m.get_std_wells()
+        for w, k in zip(self.wells, ctl):
+            w.control = ("bhp", w.bhp_limit) if k else w.rate_control
+        return self.x
+
+    def update(self, relax=1.0):
+        self.m.std_wells_update(relax)
+
+    def converged(self, res_well=None, tol_rate=1e-7, tol_bhp=1.0):
+        """getWellConvergence on the last read-back"""
+        return StandardWells.converged(self, self.res_well if res_well is None else res_well, tol_rate, tol_bhp)
+
+    def set_rate_target(self, k, target):
+        """StandardWells.set_rate_target on the read-back state, sent up again (a report-step event: the read-back does not matter)"""
+        self.fetch()
+        StandardWells.set_rate_target(self, k, target)
+        self._send()
+
+    def _send(self):
+        self.m.set_std_wells_state(self.x, [int(w.control[0] == "bhp") for w in self.wells], [w.rate_control[2] for w in self.wells])
+
+    def state(self):
+        self.fetch()
+        return self.x.copy(), [w.control for w in self.wells]
+
+    def set_state(self, st):
+        StandardWells.set_state(self, st)
+        self._send()
