@@ -12,6 +12,7 @@ import uuid
 import numpy as np
 import pytest
 
+from cpr_dense import solve_dense
 from helpers import laplace_block_system
 
 pytestmark = pytest.mark.gpu
@@ -219,21 +220,6 @@ def test_no_host_in_the_loop(pkg):
     assert s.ms_wells_info()["wells"] == 0
 
 
-def _ld_solve(D, b):
-    """Gaussian elimination with partial pivoting in np.longdouble"""
-    A, x, n = D.astype(np.longdouble), b.astype(np.longdouble), len(b)
-    for k in range(n):
-        p = k + int(np.argmax(np.abs(A[k:, k])))
-        if p != k:
-            A[[k, p]], x[[k, p]] = A[[p, k]], x[[p, k]]
-        f = A[k + 1:, k] / A[k, k]
-        A[k + 1:, k:] -= np.outer(f, A[k, k:])
-        x[k + 1:] -= f * x[k]
-    for k in range(n - 1, -1, -1):
-        x[k] = (x[k] - A[k, k + 1:] @ x[k + 1:]) / A[k, k]
-    return x
-
-
 def test_pivoting_across_the_blocks(pkg):
     """a D whose leading 4 x 4 block is singular while D is not (two block rows exchanged): within the bound of the operator test - an
     elimination that exchanges rows only inside a block fails here"""
@@ -274,7 +260,7 @@ def test_badly_scaled_rows(pkg, Mb):
     x = rng.standard_normal(3 * Nb)
     B, C, D = pkg.mswells.dense_operators(w, Nb)
     z1 = B @ x
-    z_ld = _ld_solve(D, z1)
+    z_ld = solve_dense(D, z1, np.longdouble)   # Gaussian elimination with partial pivoting in np.longdouble
     e_ref = float(max(np.abs(np.linalg.solve(D, z1) - z_ld).max(), np.abs(np.linalg.inv(D) @ z1 - z_ld).max()))
     d, p, wv = _operator_difference(pkg, s, [w], x)
     z2 = np.asarray(z_ld, dtype=np.float64)

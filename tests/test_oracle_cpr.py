@@ -6,6 +6,10 @@ import os
 
 import numpy as np
 
+import pytest
+
+import cpr_dense
+import helpers
 import oracle_bind
 from test_oracle_linalg import _cmp, _load
 
@@ -160,3 +164,85 @@ def test_decomposed_cpr_with_a_joined_coarse_level(pkg, orc):
     assert alone.it >= 1.3 * one.it, (one.it, alone.it)
     for rows, it in its.items():
         assert it <= 1.3 * one.it + 1, (rows, it, one.it, alone.it)
+
+
+# ---- the oracle's CPR against the dense restatement of its definition (tests/cpr_dense.py) ---------------------------------------------
+# Every device test pins the kernels to oracle/cpr.hpp; these pin oracle/cpr.hpp to the algebra it claims to be: the hierarchy's
+# operators are Galerkin products, the smoothers sit where the cycle says, the dense substitutions solve the coarsest system.
+def _blackoil_system(pkg, orc, shape, dt_days):
+    case = pkg.decks.cartesian_case(*shape, state="mixed", heterogeneous=True)
+    o = oracle_bind.OracleModel(orc, case)
+    o.set_state(case["pv"], case["meaning"])
+    jac, _ = o.assemble(dt_days * 86400.0, 0)
+    return case["Nb"], case["rowptr"], case["col"], jac, (o, case)
+
+
+def _oracle_against_dense(orc, Nb, rp, ci, val, levels, what, weights=None, ilu=False, seed=0, red_black=False):
+    """oracle CPR and the dense form with the oracle's aggregates and weights on the probes of cpr_dense.probes, in the natural order or
+    - red_black - with the even cells before the odd ones (the aggregation still visits them in natural order, as on the device: the
+    hierarchy is the same, the block ILU0 is another); `levels`: the hierarchy the case was chosen for.  Returns the largest error ratio."""
+    fr = np.arange(Nb, dtype=np.int32)
+    if red_black:
+        fr = np.concatenate([fr[0::2], fr[1::2]])
+        to = np.empty(Nb, np.int32)
+        to[fr] = np.arange(Nb, dtype=np.int32)
+        rp, ci, val = orc.reorder_matrix(Nb, rp, ci, val, to, fr)
+    cpr = oracle_bind.OracleCpr(orc)
+    cpr.set_natural_ids(fr)
+    if ilu:
+        cpr.set_ilu_smoother(1, 1)
+    if weights is not None:
+        cpr.set_weights(weights[fr])
+    cpr.update(Nb, rp, ci, val)
+    n = [int(x) for x in cpr.levels()[0]]
+    assert n == levels, n
+    w = cpr.weights(Nb)
+    if weights is not None:
+        assert np.array_equal(w, weights[fr])
+    aggs = [cpr.aggregates(l, n[l]) for l in range(len(n) - 1)]
+    D = cpr_dense.probes(Nb, seed)
+    v = np.column_stack([cpr.apply(np.ascontiguousarray(D[:, k])) for k in range(D.shape[1])])
+    ref = [cpr_dense.DenseCpr(Nb, rp, ci, val, w, aggs, dtype=t, ilu0_level0=ilu).apply(D) for t in (np.longdouble, np.float64)]
+    return cpr_dense.assert_within(v, ref[0], ref[1], what)
+
+
+# black-oil Jacobians of the mixed heterogeneous case: shape, time step in days, red-black order, the level sizes the shape was chosen for.
+# The block ILU0 of a chain in its natural order is an exact LU: M^-1 d = A^-1 d there whatever the pressure stage did (as on matr33), so
+# the chains are also taken red-black, where it is not.
+DENSE_CASES = {
+    "one_level_120": ((6, 5, 4), 5.0, False, [120]),
+    "three_levels_504": ((9, 8, 7), 5.0, False, [504, 160, 57]),
+    "three_levels_504_red_black": ((9, 8, 7), 5.0, True, [504, 160, 57]),
+    "one_level_33": ((33, 1, 1), 5.0, False, [33]),
+    "one_level_33_red_black": ((33, 1, 1), 5.0, True, [33]),
+    "two_level_chain_129": ((129, 1, 1), 1.0, False, [129, 35]),
+    "two_level_chain_129_red_black": ((129, 1, 1), 1.0, True, [129, 35]),
+}
+TRUE_IMPES_LEVELS = [504, 152, 44]
+
+
+@pytest.mark.parametrize("name", list(DENSE_CASES))
+@pytest.mark.parametrize("ilu", [False, True], ids=["jacobi", "ilu0_level0"])
+def test_apply_is_the_dense_form_on_blackoil_jacobians(pkg, orc, name, ilu):
+    """quasi-IMPES weights; Jacobi everywhere, and level 0 smoothed by a scalar ILU0 (cpr_amg_ilu_levels = 1: what the benchmark's CPR
+    runs use; a one-level hierarchy is not factored).  Criterion: cpr_dense.assert_within, 16 times the dense form's own float64 error."""
+    shape, dt, red_black, levels = DENSE_CASES[name]
+    Nb, rp, ci, jac, _ = _blackoil_system(pkg, orc, shape, dt)
+    _oracle_against_dense(orc, Nb, rp, ci, jac, levels, "%s %s" % (name, "ilu0" if ilu else "jacobi"), ilu=ilu, red_black=red_black)
+
+
+@pytest.mark.parametrize("ilu", [False, True], ids=["jacobi", "ilu0_level0"])
+def test_apply_is_the_dense_form_without_blackoil_structure(orc, ilu):
+    """random dense 3 x 3 blocks on a 7-point pattern: nothing of the black-oil structure (small saturation columns, a dominant
+    pressure coupling) that could hide a component mixed up"""
+    Nb, rp, ci, v = helpers.laplace_block_system(8, 7, 6, seed=4)
+    _oracle_against_dense(orc, Nb, rp, ci, v, [336, 90], "laplace 8x7x6 %s" % ("ilu0" if ilu else "jacobi"), ilu=ilu, seed=1)
+
+
+@pytest.mark.parametrize("red_black", [False, True], ids=["natural", "red_black"])
+def test_apply_is_the_dense_form_with_true_impes_weights(pkg, orc, red_black):
+    """weights handed in (true-IMPES, from the storage term): another pressure system, hence other aggregates"""
+    dt = 5.0
+    Nb, rp, ci, jac, (o, case) = _blackoil_system(pkg, orc, (9, 8, 7), dt)
+    w = o.true_impes_weights(dt * 86400.0)
+    _oracle_against_dense(orc, Nb, rp, ci, jac, TRUE_IMPES_LEVELS, "true-IMPES 9x8x7", weights=w, seed=2, red_black=red_black)
