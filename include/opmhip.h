@@ -755,8 +755,10 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * The arithmetic is wells.py's arithmetic="stated", operation by operation (the library is built without floating-point
  * contraction): the per-well sums run over the perforations in perforation order, D^-1 is Gauss-Jordan on [D | I] with partial
  * pivoting (largest |entry| of the column, lowest row on ties), D^-1 r a row-times-vector product in ascending column order.
- * NOT covered: the reference's well-bore density (StandardWellGeneric::computeConnectionPressureDelta), groups, THP, VFP, crossflow,
- * decomposed contexts (refused), the matrix-add form (opmhip_add_well_contributions stays with host lists).
+ * The head is, on request, the reference's: from the density of the mixture in the well bore above every completion
+ * (opmhip_set_std_wells_head_model, below).
+ * NOT covered: groups, THP, VFP, crossflow, decomposed contexts (refused), the matrix-add form (opmhip_add_well_contributions stays
+ * with host lists).
  * Phases: 0 water, 1 oil, 2 gas (the intensive-quantity record's order); components: 0 oil, 1 water, 2 gas (the equations' order). */
 typedef struct opmhip_std_wells {
     int num_wells;
@@ -804,6 +806,58 @@ int opmhip_set_std_wells_state(opmhip_ctx* ctx, const double* x, const int* cont
  * [num_wells * 16], B and C [nperf * 12] in opmhip_wells' layout, rates [nperf * 15] (3 components x value, d/dSw, d/dp, d/dX,
  * d/dbhp), x_w [num_wells * 4] */
 int opmhip_get_std_wells_blocks(opmhip_ctx* ctx, double* head, double* D, double* Dinv, double* B, double* C, double* rates, double* xw);
+/* ---- the heads from the well-bore density.  Additive to ABI 11 -------------------------------------------------------------
+ * replaces: StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:1195-1210), that is
+ * computePropertiesForWellConnectionPressures (:899-1012), computeWellConnectionDensitesPressures (:1124-1189),
+ * StandardWellEval::computeConnectionDensities (wells/StandardWellEval.cpp:814-960) and
+ * StandardWellGeneric::computeConnectionPressureDelta (wells/StandardWellGeneric.cpp:158-193), in the statement order of
+ * wells.py StandardWells(head_model="wellbore", arithmetic="stated").  Per perforation the list then also keeps the pressure in the
+ * well bore there (it starts as the perforated cell's oil pressure, wells/WellState.cpp:298, and every opmhip_assemble sets it to
+ * bhp + head, StandardWell_impl.hpp:468) and the three component rates of the last opmhip_assemble (zero at the start).  At
+ * opmhip_std_wells_begin_iteration(0), in front of the wells alone, one wavefront per well forms
+ *   p_avg = (p_perf + p_above) / 2, p_above = bhp for the first perforation, else the pressure of the perforation above;
+ *   1/B_w(p_avg), RsSat(p_avg), RvSat(p_avg), 1/B_g at rv = min(|q_o| / |q_g|, RvSat) (the saturated curve where the well's oil
+ *     rate is zero, rv = 0 where its gas rate is not positive), 1/B_o at rs = min(|q_g| / |q_o|, RsSat) likewise - the well rates
+ *     are the well unknowns now present, the functions those of opmhip_fluid_probe / opmhip_gas_probe to the bit, the PVT region
+ *     and the surface densities the perforated cell's;
+ *   the flow past every perforation: the stored rates summed from the last perforation to the first; a producer all of whose
+ *     stored rates are exactly zero takes tw / sum(tw) * mobility_phase / sum_phases(1/B * mobility) of the perforated cell (every
+ *     phase in its own component's place.  KNOWN DIFFERENCE FROM FLOW: the reference writes the fractions in phase order - water,
+ *     oil, gas - into the component slots - oil, water, gas -, so that a producer at rest in oil-bearing cells starts with a column
+ *     of water; here oil mobility counts as oil.  The heads of a producer's first time step therefore differ from Flow's);
+ *   the mixture |q / ((q_o + q_w) + q_g)|; without flow an injector takes its injected phase, a producer's first perforation its
+ *     preferred phase and its later ones the corrected mixture x of the perforation above; the rs / rv correction with its 1e-12
+ *     guards and 1 - rs rv; density = (rho_o mix_o + rho_w mix_w + rho_g mix_g) / (x_o / b_o + x_w / b_w + x_g / b_g);
+ *   head = running sum of (dz * density) * g, dz = depth - depth of the perforation above (the reference depth for the first).
+ * Left out: solvent, salt, temperature, distributed wells' global perforation order, InjectorType::MULTI. */
+typedef struct opmhip_std_wells_wellbore {
+    const double* perf_depth;      /* per perforation: its depth */
+    const double* ref_depth;       /* per well: the depth the bottom-hole pressure refers to */
+    const int* preferred_phase;    /* per well: 0 water, 1 oil, 2 gas (read for producers) */
+} opmhip_std_wells_wellbore;
+/* Call it after opmhip_set_std_wells; NULL: back to the head from the perforated cell's oil density.  Replacing or clearing the
+ * list clears it.  OPMHIP_NOT_READY without a list; OPMHIP_INVALID_ARGUMENT (the text names the reason) for a null array, a depth
+ * that is not finite, an unknown phase.  A refused call leaves the model as it was.  The perforation pressures are taken from
+ * the perforated cells at the first opmhip_std_wells_begin_iteration(0) that follows, unless opmhip_set_std_wells_perf_state
+ * came first. */
+int opmhip_set_std_wells_head_model(opmhip_ctx* ctx, const opmhip_std_wells_wellbore* wellbore);
+/* for tests and restart files (any pointer may be NULL), per perforation, what the last begin_iteration(0) / assemble left: density,
+ * p_avg [nperf], mixture [nperf * 3] (components), perf_pressure [nperf], perf_rates [nperf * 3] (components); *perf_state_set: 1 once
+ * the perforation pressures exist (taken from the cells or handed in), 0 before and without the model.  Otherwise a no-op without
+ * the model. */
+int opmhip_get_std_wells_wellbore(opmhip_ctx* ctx, double* density, double* p_avg, double* mixture, double* perf_pressure, double* perf_rates,
+                                  int* perf_state_set);
+/* restart, tests (either pointer may be NULL: that part stays; both NULL: nothing happens): the perforation pressures [nperf] and
+ * the stored component rates [nperf * 3].  OPMHIP_NOT_READY without the model; OPMHIP_INVALID_ARGUMENT for rates alone while no
+ * pressures exist yet.  There is no call that takes the pressures away again: opmhip_set_std_wells_head_model anew starts over. */
+int opmhip_set_std_wells_perf_state(opmhip_ctx* ctx, const double* perf_pressure, const double* perf_rates);
+/* With the model in force opmhip_assemble also stores bhp + head and the rates' values per perforation (no launch is added to a
+ * Newton iteration), and opmhip_advance_time_level / opmhip_update_failed save / restore them with the well unknowns: the
+ * reference rolls back the whole well state.  Under this model the bottom-hole pressure is an input of the heads, so the roll-back
+ * also covers "the bottom-hole pressures have not been set yet": after a first time step that was given up, the next
+ * opmhip_std_wells_begin_iteration(0) takes them from the cells again and yields the heads of a context that never tried the step.
+ * Without it no call launches, copies or decides anything else than before. */
+
 /* With a list set:
  * opmhip_assemble forms, in front of the assembly kernel and of the aquifers' influx (the host order: wells' rates first), the
  * perforation rates with their five derivatives, r_w, D, D^-1, B and C (computePerfRate, assembleWellEqWithoutIteration:

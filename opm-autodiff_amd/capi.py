@@ -96,6 +96,26 @@ class StdWells(C.Structure):
                 ("bhp_limit", C.c_void_p), ("control", C.c_void_p), ("x", C.c_void_p)]
 
 
+class StdWellsWellbore(C.Structure):
+    """opmhip_std_wells_wellbore: what the heads from the well-bore density need beside the list (opmhip_set_std_wells_head_model)"""
+    _fields_ = [("perf_depth", C.c_void_p), ("ref_depth", C.c_void_p), ("preferred_phase", C.c_void_p)]
+
+
+def make_std_wells_wellbore(w, num_wells, nperf):
+    """dict(perf_depth per perforation; ref_depth, preferred_phase (0 water, 1 oil, 2 gas) per well) for a list of num_wells wells and nperf
+    perforations -> (StdWellsWellbore struct, keep-alive dict); None -> (None, {}).  Ragged input raises ValueError."""
+    if w is None:
+        return None, {}
+    arr = dict(perf_depth=_f64(np.asarray(w["perf_depth"], float).reshape(-1)), ref_depth=_f64(np.asarray(w["ref_depth"], float).reshape(-1)),
+               preferred_phase=_i32(np.asarray(w["preferred_phase"]).reshape(-1)))
+    if len(arr["perf_depth"]) != nperf or len(arr["ref_depth"]) != num_wells or len(arr["preferred_phase"]) != num_wells:
+        raise ValueError("make_std_wells_wellbore: array lengths do not fit the list (%d wells, %d perforations)" % (num_wells, nperf))
+    s = StdWellsWellbore()
+    for name, _ in StdWellsWellbore._fields_:
+        setattr(s, name, arr[name].ctypes.data)
+    return s, arr
+
+
 def make_std_wells(w):
     """dict(perf_pointers, cell, tw, dz per perforation; producer, inj_phase, rate_component, rate_target, bhp_limit, control per well;
     x (num_wells x 4) or None) - wells.DeviceStandardWells builds it - -> (StdWells struct, keep-alive dict)"""
@@ -632,6 +652,9 @@ def _bind_assembly(L):
     L.opmhip_get_std_wells.argtypes = [vp, vp, vp, vp]
     L.opmhip_set_std_wells_state.argtypes = [vp, vp, vp, vp]
     L.opmhip_get_std_wells_blocks.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.opmhip_set_std_wells_head_model.argtypes = [vp, C.POINTER(StdWellsWellbore)]
+    L.opmhip_get_std_wells_wellbore.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    L.opmhip_set_std_wells_perf_state.argtypes = [vp, vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -923,6 +946,33 @@ class HipModel(HipSolver):
         self._check(lib().opmhip_set_std_wells(self._h, C.byref(sw) if sw else None))
         if sw:
             self._nsw, self._nswperf = sw.num_wells, len(keep["cell"])
+
+    def set_std_wells_head_model(self, wellbore):
+        """opmhip_set_std_wells_head_model: the heads from the well-bore density (dict, see make_std_wells_wellbore); None: back to the
+        perforated cell's oil density.  A refused call leaves the model as it was."""
+        wb, keep = make_std_wells_wellbore(wellbore, getattr(self, "_nsw", 0), getattr(self, "_nswperf", 0))
+        self._check(lib().opmhip_set_std_wells_head_model(self._h, C.byref(wb) if wb else None))
+
+    def std_wells_wellbore(self):
+        """for tests and restart files: dict(density, p_avg, mixture (perforations, 3 components), perf_pressure, perf_rates (perforations, 3))
+        as the last begin_iteration(0) / assemble left them - zeros without the model - and perf_state_set: whether the perforation
+        pressures exist yet (the library's own flag: taken from the cells at the first begin_iteration(0) or handed in; update_failed goes
+        back to what advance_time_level saw)"""
+        p = getattr(self, "_nswperf", 0)
+        out = dict(density=np.zeros(p), p_avg=np.zeros(p), mixture=np.zeros((p, 3)), perf_pressure=np.zeros(p), perf_rates=np.zeros((p, 3)))
+        flag = C.c_int(0)
+        self._check(lib().opmhip_get_std_wells_wellbore(self._h, *[_ptr(out[k]) for k in ("density", "p_avg", "mixture", "perf_pressure", "perf_rates")],
+                                                        C.byref(flag)))
+        out["perf_state_set"] = bool(flag.value)
+        return out
+
+    def set_std_wells_perf_state(self, perf_pressure=None, perf_rates=None):
+        """opmhip_set_std_wells_perf_state: the perforation pressures and the stored component rates; None = that part stays"""
+        pp, pr = _f64(perf_pressure), _f64(perf_rates)
+        n = getattr(self, "_nswperf", 0)
+        if (pp is not None and pp.size != n) or (pr is not None and pr.size != 3 * n):
+            raise ValueError("set_std_wells_perf_state: array lengths do not fit the %d perforations set" % n)
+        self._check(lib().opmhip_set_std_wells_perf_state(self._h, _ptr(pp), _ptr(pr)))
 
     def std_wells_begin_iteration(self, iteration):
         """opmhip_std_wells_begin_iteration: wellModel().beginIteration - at iteration 0 the heads and the wells alone, always the controls"""

@@ -815,6 +815,26 @@ __global__ __launch_bounds__(256) IQ_OCC void k_newton_update<false>(int Nb, Tab
 }
 
 static Tables tables_of(const opmhip_ctx* c);
+// 1/B of the three phases at one point (plain doubles): the one body behind opmhip_fluid_probe / opmhip_gas_probe and the well-bore
+// density of the resident standard wells (k_std_wells_wellbore), which therefore carries the probes' bits
+__device__ __forceinline__ double pvt_invBw(const Tables& T, const PvtRegionDesc& D, double p) {
+    const GlobalTab W = T.dbl + D.water;   // p_ref, Bw_ref, c_w, mu_ref, c_v
+    const double X = W[2] * (p - W[0]);
+    return (1.0 + X * (1.0 + X / 2.0)) / W[1];
+}
+__device__ __forceinline__ double pvt_invBo(const Tables& T, int pr, const PvtRegionDesc& D, double p, double rs) {
+    const GlobalTab B = T.dbl;
+    if (rs >= rs_sat_value(T, pr, p)) return tab1<double, GlobalTab>(B + D.sat_p, B + D.sat_invB, D.sat_n, p);
+    return tab2<double, GlobalTab>(T, D, D.o_invB, rs, p);
+}
+__device__ __forceinline__ double pvt_invBg(const Tables& T, int pr, const PvtRegionDesc& D, double p, double rv) {
+    const GlobalTab B = T.dbl;
+    if (D.wg_n > 0) {
+        if (rv >= rv_sat_value(T, pr, p)) return tab1<double, GlobalTab>(B + D.wg_xs, B + D.wgs_invB, D.wg_n, p);
+        return tab2wg<double, GlobalTab>(T, D, D.wg_invB, p, rv);
+    }
+    return tab1<double, GlobalTab>(B + D.gas_p, B + D.gas_invB, D.gas_n, p);
+}
 // opmhip_fluid_probe: the property functions of update_iq at given points (plain doubles)
 __global__ __launch_bounds__(256) void k_fluid_probe(Tables T, int pr, int sr, int n, const double* __restrict__ p,
                                                      const double* __restrict__ rs, const double* __restrict__ sw,
@@ -826,22 +846,14 @@ __global__ __launch_bounds__(256) void k_fluid_probe(Tables T, int pr, int sr, i
     const GlobalTab B = T.dbl;
     double* o = out + (size_t)i * 8;
     const double pi = p[i], rsi = rs[i];
-    {
-        const GlobalTab W = B + D.water;  // p_ref, Bw_ref, c_w, mu_ref, c_v
-        const double X = W[2] * (pi - W[0]);
-        o[0] = (1.0 + X * (1.0 + X / 2.0)) / W[1];
-    }
+    o[0] = pvt_invBw(T, D, pi);
     const bool wetg = D.wg_n > 0;   // PVTG: the saturated curve
     o[1] = wetg ? tab1<double, GlobalTab>(B + D.wg_xs, B + D.wgs_invB, D.wg_n, pi) : tab1<double, GlobalTab>(B + D.gas_p, B + D.gas_invB, D.gas_n, pi);
     const double RsSat = rs_sat_value(T, pr, pi);
     o[3] = RsSat;
-    if (rsi >= RsSat) {
-        o[2] = tab1<double, GlobalTab>(B + D.sat_p, B + D.sat_invB, D.sat_n, pi);
-        o[6] = o[2] / tab1<double, GlobalTab>(B + D.sat_p, B + D.sat_invBMu, D.sat_n, pi);
-    } else {
-        o[2] = tab2<double, GlobalTab>(T, D, D.o_invB, rsi, pi);
-        o[6] = o[2] / tab2<double, GlobalTab>(T, D, D.o_invBMu, rsi, pi);
-    }
+    o[2] = pvt_invBo(T, pr, D, pi, rsi);
+    if (rsi >= RsSat) o[6] = o[2] / tab1<double, GlobalTab>(B + D.sat_p, B + D.sat_invBMu, D.sat_n, pi);
+    else o[6] = o[2] / tab2<double, GlobalTab>(T, D, D.o_invBMu, rsi, pi);
     const double Swco = B[Sd.swco];
     o[4] = pwlin<double, GlobalTab>(B + Sd.sw_x, B + Sd.pcow, Sd.nw, sw[i]);
     o[5] = pwlin<double, GlobalTab>(B + Sd.so_x, B + Sd.pcgo, Sd.ng, 1.0 - Swco - sg[i]);
@@ -857,18 +869,13 @@ __global__ __launch_bounds__(256) void k_gas_probe(Tables T, int pr, int n, cons
     const GlobalTab B = T.dbl;
     double* o = out + (size_t)i * 3;
     const double pi = p[i], rvi = rv[i];
+    o[0] = pvt_invBg(T, pr, D, pi, rvi);
     if (D.wg_n > 0) {
         const double RvSat = rv_sat_value(T, pr, pi);
         o[2] = RvSat;
-        if (rvi >= RvSat) {
-            o[0] = tab1<double, GlobalTab>(B + D.wg_xs, B + D.wgs_invB, D.wg_n, pi);
-            o[1] = o[0] / tab1<double, GlobalTab>(B + D.wg_xs, B + D.wgs_invBMu, D.wg_n, pi);
-        } else {
-            o[0] = tab2wg<double, GlobalTab>(T, D, D.wg_invB, pi, rvi);
-            o[1] = o[0] / tab2wg<double, GlobalTab>(T, D, D.wg_invBMu, pi, rvi);
-        }
+        if (rvi >= RvSat) o[1] = o[0] / tab1<double, GlobalTab>(B + D.wg_xs, B + D.wgs_invBMu, D.wg_n, pi);
+        else o[1] = o[0] / tab2wg<double, GlobalTab>(T, D, D.wg_invBMu, pi, rvi);
     } else {
-        o[0] = tab1<double, GlobalTab>(B + D.gas_p, B + D.gas_invB, D.gas_n, pi);
         o[1] = o[0] / tab1<double, GlobalTab>(B + D.gas_p, B + D.gas_invBMu, D.gas_n, pi);
         o[2] = 0.0;
     }
@@ -1593,6 +1600,8 @@ struct SwArrays {
     const int *vp, *cell, *wi;                  // perforation ranges, perforated cells (internal positions), per well: producer, injected phase, rate component
     const double *wd, *tw, *dz;                 // per well: rate target, bhp limit; per perforation
     double *head, *pr, *pack, *Dmat, *B, *C, *Dinv;
+    int wellbore, nperf;                        // the heads come from the well-bore density (k_std_wells_wellbore); all perforations of the list
+    double* wbstate;                            // then: p_perf [nperf] | the rates of the last assembly [nperf * 3]
 };
 // One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
 // global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
@@ -1610,7 +1619,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
     const int injPhase = W.wi[3 * w + 1], comp = W.wi[3 * w + 2];
     double* x = W.pack + (size_t)4 * w;
     double* flag = W.pack + (size_t)9 * W.num + w;
-    if (SOLVE)   // calculate_explicit_quantities: (rho_o g) dz, constant through the time step; lane l owns perforations pb + l + 64 k here and below
+    if (SOLVE && !W.wellbore)   // calculate_explicit_quantities: (rho_o g) dz, constant through the time step; lane l owns perforations pb + l + 64 k here and below
         for (int p = pb + lane; p < pe; p += 64) W.head[p] = (iq_at(iq, ncell, F_RHO + OIL, W.cell[p])[0] * GRAVITY) * W.dz[p];
     if (lane == 0) {
         for (int i = 0; i < 4; ++i) xs[i] = x[i];
@@ -1639,6 +1648,11 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
                         for (int v = 0; v < 3; ++v) { B[c * 3 + v] = -q[c * 5 + 1 + v]; C[c * 3 + v] = 0.0; }
                         B[9 + c] = 0.0;
                         C[9 + c] = -q[c * 5 + 4];
+                    }
+                    if (W.wellbore) {   // the well state the next time step's heads start from (StandardWell_impl.hpp:468 and the rates of computePerfRate)
+                        W.wbstate[p] = bhp + W.head[p];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) W.wbstate[(size_t)W.nperf + 3 * (size_t)p + c] = q[c * 5];
                     }
                 }
             }
@@ -1684,6 +1698,138 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
     }
     if (SOLVE && lane == 0)
         for (int i = 0; i < 4; ++i) x[i] = xs[i];
+}
+// ---- the heads from the well-bore density (opmhip_set_std_wells_head_model) ----------------------------------------------------
+// StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:899-1012, 1124-1210), StandardWellEval::computeConnectionDensities
+// (wells/StandardWellEval.cpp:814-960) and StandardWellGeneric::computeConnectionPressureDelta (wells/StandardWellGeneric.cpp:158-193) in
+// the statement order of wells.py StandardWells(head_model="wellbore", arithmetic="stated").  Components (the equations' order) oil,
+// water, gas; phases (the record's order) water, oil, gas: phase ph belongs to component (EQ_WATER, EQ_OIL, EQ_GAS)[ph].
+// (1/B_w, 1/B_o, 1/B_g: pvt_invBw / pvt_invBo / pvt_invBg, the one body the probes run too)
+__device__ __forceinline__ int wb_component(int phase) { return phase == GAS ? EQ_GAS : (phase == WATER ? EQ_WATER : EQ_OIL); }
+struct WbArrays {
+    const double *depth, *ref;   // per perforation: its depth; per well: the reference depth
+    const int* pref;             // per well: the preferred phase
+    double *out, *scratch;       // density [nperf] | p_avg [nperf] | mixture [nperf * 3]; 8 doubles per perforation
+};
+enum { WB_B = 0, WB_RSMAX = 3, WB_RVMAX = 4, WB_Q = 5, WB_REC = 8 };   // the record of a perforation between the passes: 1/B and q per component
+// One wavefront per well, in front of k_std_wells_eq<true>.  Lanes take the perforations 64 at a time for the gathers and the table
+// look-ups - p_avg, 1/B_w, RsSat, RvSat, 1/B_g, 1/B_o, the rates that count - and leave a record per perforation in LDS (a well of at
+// most 64 perforations) or in global scratch.  Lane 0 then runs the two dependent passes in perforation order: the flow past every
+// perforation from the last to the first, and from the first to the last the mixture, its corrected form x (which a perforation
+// without flow hands to the next), the density and the head's running sum.  No atomics, no transcendental functions; what a lane
+// computes depends on its perforation alone.  first: the bottom-hole pressure is the one k_std_wells_eq<true> is about to start from;
+// init: the perforation pressures are the perforated cells' oil pressures and the stored rates zero (wells/WellState.cpp:298).
+__global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays Q, Tables T, const int* __restrict__ pvtnum, int ncell,
+                                                           const double* __restrict__ iq, int first, int init) {
+    __shared__ double rec[64 * WB_REC];
+    __shared__ double s_tw;
+    const int w = blockIdx.x, lane = threadIdx.x;
+    const int pb = W.vp[w], pe = W.vp[w + 1];
+    const size_t np = W.nperf;
+    const bool producer = W.wi[3 * w] != 0;
+    const int injPhase = W.wi[3 * w + 1];
+    const double* x = W.pack + (size_t)4 * w;
+    double* pp = W.wbstate;
+    double* qs = W.wbstate + np;
+    double* sc = pe - pb <= 64 ? rec : Q.scratch + (size_t)WB_REC * pb;
+    if (init) {
+        for (int p = pb + lane; p < pe; p += 64) {
+            pp[p] = iq_at(iq, ncell, F_P + OIL, W.cell[p])[0];
+            qs[3 * (size_t)p] = 0.0; qs[3 * (size_t)p + 1] = 0.0; qs[3 * (size_t)p + 2] = 0.0;
+        }
+        __syncthreads();
+    }
+    const double bhp = first ? iq_at(iq, ncell, F_P + OIL, W.cell[pb])[0] + (producer ? -1e5 : 1e5) : x[3];
+    const double oilrate = fabs(x[EQ_OIL]), gasrate = fabs(x[EQ_GAS]);   // the well unknowns now present
+    // a producer all of whose stored rates are exactly zero: the mixture by mobility ratio, the perforations weighted by tw (:1154-1184)
+    int nonzero = 0;
+    for (int p = pb + lane; p < pe; p += 64) nonzero |= (qs[3 * (size_t)p] != 0.0 || qs[3 * (size_t)p + 1] != 0.0 || qs[3 * (size_t)p + 2] != 0.0) ? 1 : 0;
+    const bool fallback = !__syncthreads_or(nonzero) && producer;   // uniform
+    if (fallback) {
+        if (lane == 0) {
+            double t = 0.0;
+            for (int p = pb; p < pe; ++p) t += W.tw[p];
+            s_tw = t;
+        }
+        __syncthreads();
+    }
+    for (int p = pb + lane; p < pe; p += 64) {
+        const int c = W.cell[p];
+        const int pr = pvtnum ? pvtnum[c] : 0;
+        const PvtRegionDesc& D = T.pvt(pr);
+        const double pAbove = p == pb ? bhp : pp[p - 1];
+        const double pAvg = (pp[p] + pAbove) / 2.0;
+        double* s = sc + (size_t)WB_REC * (p - pb);
+        s[WB_B + EQ_WATER] = pvt_invBw(T, D, pAvg);
+        const double rvmax = D.wg_n > 0 ? rv_sat_value(T, pr, pAvg) : 0.0;
+        if (oilrate > 0.0) {
+            double rv = 0.0;
+            if (gasrate > 0.0) rv = oilrate / gasrate;
+            rv = rvmax < rv ? rvmax : rv;
+            s[WB_B + EQ_GAS] = pvt_invBg(T, pr, D, pAvg, rv);
+        } else s[WB_B + EQ_GAS] = pvt_invBg(T, pr, D, pAvg, rvmax);   // the saturated curve
+        const double rsmax = rs_sat_value(T, pr, pAvg);
+        if (gasrate > 0.0) {
+            double rs = 0.0;
+            if (oilrate > 0.0) rs = gasrate / oilrate;
+            rs = rsmax < rs ? rsmax : rs;
+            s[WB_B + EQ_OIL] = pvt_invBo(T, pr, D, pAvg, rs);
+        } else s[WB_B + EQ_OIL] = pvt_invBo(T, pr, D, pAvg, rsmax);
+        s[WB_RSMAX] = rsmax;
+        s[WB_RVMAX] = rvmax;
+        if (fallback) {
+            const double frac = W.tw[p] / s_tw;
+            double mob[3], tm = 0.0;
+            for (int ph = 0; ph < 3; ++ph) {
+                mob[ph] = iq_at(iq, ncell, F_MOB + ph, c)[0];
+                tm += iq_at(iq, ncell, F_B + ph, c)[0] * mob[ph];
+            }
+            for (int ph = 0; ph < 3; ++ph) s[WB_Q + wb_component(ph)] = frac * mob[ph] / tm;
+        } else {
+            for (int k = 0; k < 3; ++k) s[WB_Q + k] = qs[3 * (size_t)p + k];
+        }
+        Q.out[np + p] = pAvg;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    // 1. the flow up the well bore past every perforation, in place of the rates: from below minus what leaves through the perforation
+    for (int p = pe - 1; p >= pb; --p) {
+        double* s = sc + (size_t)WB_REC * (p - pb);
+        for (int k = 0; k < 3; ++k) {
+            double q = p == pe - 1 ? 0.0 : s[WB_REC + WB_Q + k];
+            q -= s[WB_Q + k];
+            s[WB_Q + k] = q;
+        }
+    }
+    // 2. mixture, volume ratio, density; the head
+    double xm[3] = {0.0, 0.0, 0.0}, head = 0.0;
+    for (int p = pb; p < pe; ++p) {
+        const double* s = sc + (size_t)WB_REC * (p - pb);
+        const double tot = ((0.0 + s[WB_Q]) + s[WB_Q + 1]) + s[WB_Q + 2];
+        double mix[3] = {0.0, 0.0, 0.0};
+        if (tot != 0.0) {
+            for (int k = 0; k < 3; ++k) mix[k] = fabs(s[WB_Q + k] / tot);
+        } else if (!producer) mix[wb_component(injPhase)] = 1.0;
+        else if (p == pb) mix[wb_component(Q.pref[w])] = 1.0;
+        else { mix[0] = xm[0]; mix[1] = xm[1]; mix[2] = xm[2]; }   // x, not mix, of the perforation above: as the reference has it
+        xm[0] = mix[0]; xm[1] = mix[1]; xm[2] = mix[2];
+        double rs = 0.0, rv = 0.0;
+        if (mix[EQ_OIL] > 1e-12) { const double r = mix[EQ_GAS] / mix[EQ_OIL]; rs = s[WB_RSMAX] < r ? s[WB_RSMAX] : r; }
+        if (mix[EQ_GAS] > 1e-12) { const double r = mix[EQ_OIL] / mix[EQ_GAS]; rv = s[WB_RVMAX] < r ? s[WB_RVMAX] : r; }
+        if (rs != 0.0) xm[EQ_GAS] = (mix[EQ_GAS] - mix[EQ_OIL] * rs) / (1.0 - rs * rv);
+        if (rv != 0.0) xm[EQ_OIL] = (mix[EQ_OIL] - mix[EQ_GAS] * rv) / (1.0 - rs * rv);
+        const GlobalTab rho = T.dbl + T.pvt(pvtnum ? pvtnum[W.cell[p]] : 0).density;   // surface densities: oil, water, gas
+        double volrat = 0.0, sd = 0.0;
+        for (int k = 0; k < 3; ++k) volrat += xm[k] / s[WB_B + k];
+        for (int k = 0; k < 3; ++k) sd += rho[k] * mix[k];
+        const double density = sd / volrat;
+        const double dz = Q.depth[p] - (p == pb ? Q.ref[w] : Q.depth[p - 1]);
+        const double dp = dz * density * GRAVITY;
+        head = p == pb ? dp : head + dp;
+        W.head[p] = head;
+        Q.out[p] = density;
+        for (int k = 0; k < 3; ++k) Q.out[2 * np + 3 * (size_t)p + k] = mix[k];
+    }
 }
 // update_well_controls, one lane per well
 __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ pack) {
@@ -1736,12 +1882,21 @@ __global__ __launch_bounds__(64) void k_std_wells_axpy(int n, double relax, cons
 }
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
-    return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.d_pack, S.d_Dmat, W.d_B, W.d_C, W.d_D};
+    return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.d_pack, S.d_Dmat, W.d_B, W.d_C, W.d_D,
+                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate};
 }
 // (booked under the profile's assembly class, one scope per function: a context with a list shows them in opmhip_profile_get)
 void launch_std_wells_solve(opmhip_ctx* c, bool first) {
     const int ps = prof_begin(c, PROF_ASSEMBLE);
     hipLaunchKernelGGL(k_std_wells_eq<true>, dim3(c->wells.sw.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
+    prof_end(c, ps);
+}
+void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(k_std_wells_wellbore, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells),
+                       WbArrays{S.d_wbdepth, S.d_wbref, S.d_wbpref, S.d_wbout, S.d_wbscratch}, tables_of(c), c->asmb.d_pvtnum, c->pat.Nloc, c->asmb.d_iq,
+                       first ? 1 : 0, init ? 1 : 0);
     prof_end(c, ps);
 }
 void launch_std_wells_controls(opmhip_ctx* c) {

@@ -501,6 +501,12 @@ int opmhip_advance_time_level(opmhip_ctx* c) {
         OPMHIP_HIP(c, hipMemcpyAsync(A.d_meaning_prev, A.d_meaning, (size_t)c->pat.Nloc, hipMemcpyDeviceToDevice, c->stream));
         if (c->wells.sw.num > 0)   // resident standard wells: the well state of the last accepted step (x | control)
             OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_saved, c->wells.sw.d_pack, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (c->wells.sw.wellbore) {   // ... and the perforation pressures and stored rates the next heads are formed from
+            StdWellsDev& S = c->wells.sw;
+            OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbsaved, S.d_wbstate, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            S.wb_state_saved = S.wb_state_set;
+            S.wb_initialised_saved = S.initialised;
+        }
         A.prev_set = true;
         return OPMHIP_SUCCESS;
     });
@@ -537,6 +543,12 @@ int opmhip_update_failed(opmhip_ctx* c) {
         if (c->wells.sw.num > 0) {
             OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_pack, c->wells.sw.d_saved, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             c->wells.sw.assembled = false;
+        }
+        if (c->wells.sw.wellbore) {
+            StdWellsDev& S = c->wells.sw;
+            OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbstate, S.d_wbsaved, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            S.wb_state_set = S.wb_state_saved;
+            S.initialised = S.wb_initialised_saved;   // a first step given up: the retry takes the bottom-hole pressures from the cells again, as a run that never tried it
         }
         A.assembled = false;
         return OPMHIP_SUCCESS;
@@ -1231,11 +1243,18 @@ int opmhip_get_aquifer_rates(opmhip_ctx* c, double* q4) {
 // ---- standard wells on the device --------------------------------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
+void std_wells_wellbore_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_wbdepth); dev_free(c, &S.d_wbref); dev_free(c, &S.d_wbpref); dev_free(c, &S.d_wbstate); dev_free(c, &S.d_wbsaved);
+    dev_free(c, &S.d_wbout); dev_free(c, &S.d_wbscratch);
+    S.wellbore = S.wb_state_set = S.wb_state_saved = S.wb_initialised_saved = false;
+}
 void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
     dev_free(c, &S.d_pack); dev_free(c, &S.d_saved); dev_free(c, &S.d_Dmat);
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
+    std_wells_wellbore_release(c);
     S.num = S.nperf = S.nd = 0;
     S.initialised = S.assembled = false;
     c->wells.num_wells = 0;   // no operator form of the list left behind for later products
@@ -1367,6 +1386,10 @@ int opmhip_std_wells_begin_iteration(opmhip_ctx* c, int iteration) {
         if (iteration < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "std_wells_begin_iteration: iteration = %d", iteration);
         OPMHIP_HIP(c, hipSetDevice(c->device));
         if (iteration == 0) {   // calculateExplicitQuantities, prepareTimeStep
+            if (S.wellbore) {   // computeWellConnectionPressures, from the well state the time step starts with
+                launch_std_wells_wellbore(c, !S.initialised, !S.wb_state_set);
+                S.wb_state_set = true;
+            }
             launch_std_wells_solve(c, !S.initialised);
             S.initialised = true;
         }
@@ -1482,6 +1505,94 @@ int opmhip_get_std_wells_blocks(opmhip_ctx* c, double* head, double* D, double* 
         if (C) OPMHIP_HIP(c, hipMemcpy(C, W.d_C, np * 12 * sizeof(double), hipMemcpyDeviceToHost));
         if (rates) OPMHIP_HIP(c, hipMemcpy(rates, S.d_pr, np * 15 * sizeof(double), hipMemcpyDeviceToHost));
         if (xw) OPMHIP_HIP(c, hipMemcpy(xw, W.d_xw, nw * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_head_model(opmhip_ctx* c, const opmhip_std_wells_wellbore* wb) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_head_model: no resident list (opmhip_set_std_wells)");
+        const size_t nw = S.num, np = S.nperf;
+        std::vector<int> wi;
+        if (wb) {   // everything is looked at before anything changes: a refused call leaves the model as it was
+            if (!wb->perf_depth || !wb->ref_depth || !wb->preferred_phase) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: null array");
+            for (size_t p = 0; p < np; ++p)
+                if (!std::isfinite(wb->perf_depth[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: perf_depth[%zu] is not finite", p);
+            for (size_t w = 0; w < nw; ++w)
+                if (!std::isfinite(wb->ref_depth[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: ref_depth[%zu] is not finite", w);
+        }
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if (wb) {
+            wi.resize(3 * nw);
+            OPMHIP_HIP(c, hipMemcpy(wi.data(), S.d_wi, wi.size() * sizeof(int), hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < nw; ++w)
+                if (wi[3 * w] && (wb->preferred_phase[w] < 0 || wb->preferred_phase[w] > 2))
+                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: unknown phase: preferred_phase[%zu] = %d (0 water, 1 oil, 2 gas)", w, wb->preferred_phase[w]);
+        }
+        std_wells_wellbore_release(c);
+        S.assembled = false;   // the heads the last assembly used are no longer the model's
+        if (!wb) return OPMHIP_SUCCESS;
+        const int rc = [&]() -> int {
+            int r;
+            std::vector<int> pref(nw);
+            for (size_t w = 0; w < nw; ++w) pref[w] = wi[3 * w] ? wb->preferred_phase[w] : 1;
+            const std::vector<double> depth(wb->perf_depth, wb->perf_depth + np), ref(wb->ref_depth, wb->ref_depth + nw);
+            if ((r = dev_upload(c, &S.d_wbdepth, depth)) || (r = dev_upload(c, &S.d_wbref, ref)) || (r = dev_upload(c, &S.d_wbpref, pref)) ||
+                (r = dev_upload(c, &S.d_wbstate, std::vector<double>(4 * np, 0.0))) || (r = dev_upload(c, &S.d_wbsaved, std::vector<double>(4 * np, 0.0))) ||
+                (r = dev_upload(c, &S.d_wbout, std::vector<double>(5 * np, 0.0))) || (r = dev_upload(c, &S.d_wbscratch, std::vector<double>(8 * np, 0.0))))
+                return r;
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+            return OPMHIP_SUCCESS;
+        }();
+        if (rc) { std_wells_wellbore_release(c); return rc; }
+        S.wellbore = true;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_wellbore(opmhip_ctx* c, double* density, double* p_avg, double* mixture, double* perf_pressure, double* perf_rates, int* perf_state_set) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (perf_state_set) *perf_state_set = S.wellbore && S.wb_state_set ? 1 : 0;
+        if (!S.wellbore) return OPMHIP_SUCCESS;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        const size_t np = S.nperf;
+        if (density) OPMHIP_HIP(c, hipMemcpy(density, S.d_wbout, np * sizeof(double), hipMemcpyDeviceToHost));
+        if (p_avg) OPMHIP_HIP(c, hipMemcpy(p_avg, S.d_wbout + np, np * sizeof(double), hipMemcpyDeviceToHost));
+        if (mixture) OPMHIP_HIP(c, hipMemcpy(mixture, S.d_wbout + 2 * np, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+        if (perf_pressure) OPMHIP_HIP(c, hipMemcpy(perf_pressure, S.d_wbstate, np * sizeof(double), hipMemcpyDeviceToHost));
+        if (perf_rates) OPMHIP_HIP(c, hipMemcpy(perf_rates, S.d_wbstate + np, 3 * np * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_perf_state(opmhip_ctx* c, const double* perf_pressure, const double* perf_rates) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (!S.wellbore) return fail(c, OPMHIP_NOT_READY, "set_std_wells_perf_state: the well-bore head model is not in force (opmhip_set_std_wells_head_model)");
+        const size_t np = S.nperf;
+        if (!perf_pressure && !perf_rates) return OPMHIP_SUCCESS;   // nothing handed in: nothing changes, the pressures still come from the cells if they have not yet
+        if (perf_pressure)
+            for (size_t p = 0; p < np; ++p)
+                if (!std::isfinite(perf_pressure[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: perf_pressure[%zu] is not finite", p);
+        if (perf_rates)
+            for (size_t i = 0; i < 3 * np; ++i)
+                if (!std::isfinite(perf_rates[i])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: perf_rates[%zu] is not finite", i);
+        if (!S.wb_state_set && !perf_pressure && perf_rates)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: rates alone before the perforation pressures exist (they are taken from the cells at the first begin_iteration(0))");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // rare: restarts
+        if (perf_pressure) OPMHIP_HIP(c, hipMemcpy(S.d_wbstate, perf_pressure, np * sizeof(double), hipMemcpyHostToDevice));
+        if (perf_rates) OPMHIP_HIP(c, hipMemcpy(S.d_wbstate + np, perf_rates, 3 * np * sizeof(double), hipMemcpyHostToDevice));
+        else if (!S.wb_state_set) OPMHIP_HIP(c, hipMemset(S.d_wbstate + np, 0, 3 * np * sizeof(double)));
+        OPMHIP_HIP(c, hipDeviceSynchronize());
+        S.wb_state_set = true;
         return OPMHIP_SUCCESS;
     });
 }

@@ -191,6 +191,14 @@ struct StdWellsDev {
     int *d_cpos = nullptr, *d_cptr = nullptr, *d_cperf = nullptr;   // distinct perforated cells: position, range into d_cperf, their perforations in perforation order
     double* d_save = nullptr;    // per distinct cell: the caller's 3 source and 9 dsource entries
     std::vector<double> h_flag;  // opmhip_solve_system: the flags' copy, queued in front of the synchronisation it does anyway
+    // the heads from the well-bore density (opmhip_set_std_wells_head_model).  d_wbstate: per perforation p_perf | q_o | q_w | q_g (4 nperf
+    // doubles, field-major), d_wbsaved its copy of the last opmhip_advance_time_level; d_wbout: density | p_avg | mixture (5 nperf, the
+    // mixture 3 per perforation); d_wbscratch: 8 doubles per perforation for the two dependent passes of wells that do not fit the LDS
+    bool wellbore = false;
+    bool wb_state_set = false, wb_state_saved = false;   // p_perf has been taken from the cells (or handed in); ... at the last advance_time_level
+    bool wb_initialised_saved = false;                   // `initialised` at the last advance_time_level: under this model the bottom-hole pressure is an input of the heads, so a given-up first step goes back to 'not yet set'
+    double *d_wbdepth = nullptr, *d_wbref = nullptr, *d_wbstate = nullptr, *d_wbsaved = nullptr, *d_wbout = nullptr, *d_wbscratch = nullptr;
+    int* d_wbpref = nullptr;     // per well: the preferred phase
     double* x() const { return d_pack; }
     double* control() const { return d_pack + (size_t)4 * num; }
     double* rw() const { return d_pack + (size_t)5 * num; }
@@ -708,6 +716,7 @@ void launch_aquifer_end(opmhip_ctx* c, double dt);
 // standard wells on the device (opmhip_set_std_wells; assemble.hip)
 int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_asm.cpp: the zero-pivot flags as the caller has just read them back; a singular D clears the list
 void launch_std_wells_solve(opmhip_ctx* c, bool first);   // heads, then the wells alone against the frozen reservoir (iteration 0)
+void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init);   // the heads from the well-bore density, in front of launch_std_wells_solve
 void launch_std_wells_controls(opmhip_ctx* c);            // updateWellControls
 void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
 void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)

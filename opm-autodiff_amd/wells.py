@@ -19,6 +19,17 @@ The device solves (A - C^T D^-1 B) x = r - C^T D^-1 r_w (opmhip_wells_apply_resi
 and returns x_w = D^-1 (r_w - B x) (opmhip_wells_recover_solution).
 
 The model object (capi.HipModel, or the oracle behind the same method names) supplies iq(): the cached intensive quantities of the cells.
+
+The head between a well's reference depth and a completion (head_model):
+  "cell_oil" (the default): (rho_o of the perforated cell * g) * dz - the minimal form;
+  "wellbore": the reference's, from the density of the mixture in the well bore above every completion -
+      StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:1195-1210): computePropertiesForWellConnectionPressures
+      (:899-1012), computeWellConnectionDensitesPressures (:1124-1189), StandardWellEval::computeConnectionDensities
+      (wells/StandardWellEval.cpp:814-960), StandardWellGeneric::computeConnectionPressureDelta (wells/StandardWellGeneric.cpp:158-193);
+      the state it reads - a pressure and three component rates per perforation - is WellState's (wells/WellState.cpp:298,
+      StandardWell_impl.hpp:468).  Left out: solvent, salt, temperature, distributed wells' global perforation order, InjectorType::MULTI.
+  Components are in the equations' order (oil, water, gas), phases in the record's (water, oil, gas): phase ph belongs to component
+  COMPONENT_OF_PHASE[ph].
 """
 import numpy as np
 
@@ -26,6 +37,11 @@ OIL, WATER, GAS = 0, 1, 2          # equation / component order of the blocks (c
 PH_W, PH_O, PH_G = 0, 1, 2         # phase order of the intensive-quantity record (opmhip_get_iq)
 F_S, F_P, F_B, F_MOB, F_RHO, F_RS = 0, 3, 6, 9, 12, 15
 GRAVITY = 9.80665
+COMPONENT_OF_PHASE = (WATER, OIL, GAS)      # indexed by PH_W, PH_O, PH_G
+PHASE_BY_NAME = {"water": PH_W, "oil": PH_O, "gas": PH_G}
+HEAD_MODELS = ("cell_oil", "wellbore")
+INVBW, INVBO, RSSAT = 0, 2, 3              # columns of props.probe (capi.HipFluid.COLUMNS)
+G_INVB, G_RVSAT = 0, 2                     # columns of props.probe_gas
 
 
 def peaceman_factor(perm, dx, dy, dz, diameter, skin=0.0):
@@ -92,12 +108,13 @@ def row_times_vector(M, r):
 
 
 class Well:
-    """name; cells: perforated cells (natural order); tw: connection transmissibility factors; ref_depth; producer or injector of `phase`;
-    control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit"""
+    """name; cells: perforated cells (natural order, from the top of the well down); tw: connection transmissibility factors; ref_depth;
+    producer or injector of `phase`; control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit"""
 
-    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None):
+    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil"):
         self.name, self.cells, self.tw = name, np.asarray(cells, np.int32), np.asarray(tw, float)
         self.ref_depth, self.producer, self.inj_phase = float(ref_depth), bool(producer), inj_phase
+        self.preferred_phase = preferred_phase     # a producer's (WELSPECS item 6): the well bore's content where nothing flows (head_model="wellbore")
         self.control, self.bhp_limit = control, float(bhp_limit)
         self.rate_control = control       # the deck's rate target, kept for switching back from the BHP limit
 
@@ -127,10 +144,18 @@ class StandardWells:
     arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
     bit; a singular D raises SingularWellEquations there."""
 
-    def __init__(self, wells, cell_depth, arithmetic="numpy"):
+    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None):
+        """head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
+        pvt_region=) - capi.HipFluid(fluid), the device's, or the CPU oracle's in tests, as equil.py takes them - with the deck-level
+        tables as props.fluid (the surface densities); pvtnum: PVT region per cell (None: region 0)"""
         if arithmetic not in ("numpy", "stated"):
             raise ValueError("arithmetic: 'numpy' or 'stated'")
+        if head_model not in HEAD_MODELS:
+            raise ValueError("head_model: 'cell_oil' or 'wellbore'")
+        if head_model == "wellbore" and props is None:
+            raise ValueError("head_model='wellbore' needs props (probe / probe_gas)")
         self.arithmetic = arithmetic
+        self.head_model, self.props = head_model, props
         self.wells = list(wells)
         self.nw = len(self.wells)
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
@@ -145,6 +170,16 @@ class StandardWells:
         self.x = np.zeros((self.nw, 4))            # q_oil, q_water, q_gas (into the reservoir), bhp
         self.head = None                           # per perforation: pressure in the well bore there - bhp (calculate_explicit_quantities)
         self.initialised = False
+        if head_model == "wellbore":
+            for w in self.wells:
+                if (w.producer and w.preferred_phase not in PHASE_BY_NAME) or (not w.producer and w.inj_phase not in PHASE_BY_NAME):
+                    raise ValueError("head_model='wellbore': well %s has no known preferred / injected phase" % w.name)
+            self.perf_depth = self.depth[self.cells]
+            self.pvt_of_perf = np.zeros(len(self.cells), int) if pvtnum is None else np.asarray(pvtnum, int)[self.cells]
+            self.surface_density = np.array([props.fluid.pvt[r]["density"] for r in self.pvt_of_perf], float)     # (nperf, 3): oil, water, gas
+            self.perf_pressure = None                      # per perforation; None: the perforated cells' oil pressures when first needed
+            self.perf_rates = np.zeros((len(self.cells), 3))   # the component rates of the last assemble()
+            self.wellbore = None                           # dict(density, p_avg, mixture, x, b, rsmax, rvmax) of the last calculate_explicit_quantities
 
     def records(self, model):
         """the perforated cells' intensive quantities from the model - the perforated cells only (updatePerforationIntensiveQuantities,
@@ -159,8 +194,175 @@ class StandardWells:
         StandardWell::computeWellConnectionPressures, wells/BlackoilWellModel_impl.hpp:824-827, wells/StandardWell_impl.hpp:1198-1245).
         Minimal form: the column between the reference depth and a completion weighs what the oil of the completion's cell weighs (the
         reference averages the well-bore mixture's phase densities segment by segment, StandardWellGeneric::computeConnectionPressureDelta)."""
+        if self.head_model == "wellbore":
+            return self._wellbore_heads(iq)
         q = _rows(iq, self.cells)
         self.head = q[:, F_RHO + PH_O, 0] * GRAVITY * (self.depth[self.cells] - self.ref_depth_of_perf)
+
+    def _initial_bhp(self, iq):
+        q = _rows(iq, [w.cells[0] for w in self.wells])
+        return q[:, F_P + PH_O, 0] + np.where([w.producer for w in self.wells], -1e5, 1e5)
+
+    def _wellbore_pvt(self, p_avg):
+        """computePropertiesForWellConnectionPressures (:931-1004) for all perforations: b (nperf, 3 components), rsmax, rvmax - elementwise,
+        every value out of the evaluator; the well rates are the well unknowns now present"""
+        n = len(self.cells)
+        oilrate, gasrate = np.abs(self.x[:, OIL])[self.well_of_perf], np.abs(self.x[:, GAS])[self.well_of_perf]
+        b, rsmax, rvmax = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+        for r in np.unique(self.pvt_of_perf):
+            sel = np.flatnonzero(self.pvt_of_perf == r)
+            p, qo, qg = p_avg[sel], oilrate[sel], gasrate[sel]
+            first = self.props.probe(p, pvt_region=int(r))
+            b[sel, WATER], rsmax[sel] = first[:, INVBW], first[:, RSSAT]
+            rvmax[sel] = self.props.probe_gas(p, pvt_region=int(r))[:, G_RVSAT]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rv = np.minimum(np.where(qg > 0.0, qo / qg, 0.0), rvmax[sel])
+                rs = np.minimum(np.where(qo > 0.0, qg / qo, 0.0), rsmax[sel])
+            rv = np.where(qo > 0.0, rv, rvmax[sel])           # no oil rate: the saturated curve (the probes take it where rv >= RvSat)
+            rs = np.where(qg > 0.0, rs, rsmax[sel])
+            b[sel, GAS] = self.props.probe_gas(p, rv, pvt_region=int(r))[:, G_INVB]
+            b[sel, OIL] = self.props.probe(p, rs, pvt_region=int(r))[:, INVBO]
+        return b, rsmax, rvmax
+
+    def _wellbore_heads(self, iq):
+        """computeWellConnectionPressures.  arithmetic="stated": loop by loop in the reference's statement order, every sum sequential;
+        "numpy": the same formulas vectorised, the sums by cumsum"""
+        q = _rows(iq, self.cells)
+        n = len(self.cells)
+        if self.perf_pressure is None:           # WellState::init: the perforated cell's pressure (wells/WellState.cpp:298)
+            self.perf_pressure = q[:, F_P + PH_O, 0].copy()
+            self.perf_rates = np.zeros((n, 3))
+        if not self.initialised:                 # ... and its bottom-hole pressure: the one solve_well_equations is about to start from
+            self.x[:, 3] = self._initial_bhp(iq)
+        first = self.vp[:-1]
+        p_above = np.concatenate([[0.0], self.perf_pressure[:-1]])
+        p_above[first] = self.x[:, 3]            # communicateAboveValues, serial: the bhp for the first perforation
+        p_avg = (self.perf_pressure + p_above) / 2
+        b, rsmax, rvmax = self._wellbore_pvt(p_avg)
+        producer = np.array([w.producer for w in self.wells])
+        rates = self.perf_rates.copy()
+        # for producers where all perforations have zero rate: the mixture by the mobility ratio, the perforations weighted by tw (:1154-1184)
+        # KNOWN DIFFERENCE FROM FLOW: every phase goes to its own component's place.  The reference writes the fractions in phase order
+        # (water, oil, gas) into the component slots (oil, water, gas), so that a producer at rest in oil-bearing cells starts with a column
+        # of water; a producer's first-step heads therefore differ from Flow's
+        for k in range(self.nw):
+            lo, hi = self.vp[k], self.vp[k + 1]
+            if producer[k] and np.all(rates[lo:hi] == 0.0):
+                if self.arithmetic == "stated":
+                    total_tw = 0.0
+                    for p in range(lo, hi):
+                        total_tw += float(self.tw[p])
+                    for p in range(lo, hi):
+                        frac = float(self.tw[p]) / total_tw
+                        total_mobility = 0.0
+                        for ph in (PH_W, PH_O, PH_G):
+                            total_mobility += float(q[p, F_B + ph, 0]) * float(q[p, F_MOB + ph, 0])
+                        for ph in (PH_W, PH_O, PH_G):
+                            rates[p, COMPONENT_OF_PHASE[ph]] = frac * float(q[p, F_MOB + ph, 0]) / total_mobility
+                else:
+                    frac = self.tw[lo:hi] / self.tw[lo:hi].sum()
+                    tm = (q[lo:hi, F_B:F_B + 3, 0] * q[lo:hi, F_MOB:F_MOB + 3, 0]).sum(axis=1)
+                    for ph in (PH_W, PH_O, PH_G):
+                        rates[lo:hi, COMPONENT_OF_PHASE[ph]] = frac * q[lo:hi, F_MOB + ph, 0] / tm
+        no_flow_mix = np.zeros((self.nw, 3))     # injector: the injected phase; producer: the preferred phase, for its first perforation
+        for k, w in enumerate(self.wells):
+            no_flow_mix[k, COMPONENT_OF_PHASE[PHASE_BY_NAME[w.preferred_phase if w.producer else w.inj_phase]]] = 1.0
+        dens_fn = self._connection_densities_stated if self.arithmetic == "stated" else self._connection_densities_numpy
+        density, mix, xcorr = dens_fn(rates, b, rsmax, rvmax, producer, no_flow_mix)
+        # computeConnectionPressureDelta: dz to the perforation above (the reference depth for the first), then the running sum per well
+        z_above = np.concatenate([[0.0], self.perf_depth[:-1]])
+        z_above[first] = [w.ref_depth for w in self.wells]
+        dp = (self.perf_depth - z_above) * density * GRAVITY
+        head = np.zeros(n)
+        for k in range(self.nw):
+            lo, hi = self.vp[k], self.vp[k + 1]
+            if self.arithmetic == "stated":
+                acc = float(dp[lo])
+                head[lo] = acc
+                for p in range(lo + 1, hi):
+                    acc = acc + float(dp[p])
+                    head[p] = acc
+            else:
+                head[lo:hi] = np.cumsum(dp[lo:hi])
+        self.head = head
+        self.wellbore = dict(density=density, p_avg=p_avg, mixture=mix, x=xcorr, b=b, rsmax=rsmax, rvmax=rvmax)
+
+    def _connection_densities_stated(self, rates, b, rsmax, rvmax, producer, no_flow_mix):
+        """StandardWellEval::computeConnectionDensities (wells/StandardWellEval.cpp:814-960), statement by statement"""
+        n = len(self.cells)
+        density, mixture, xs = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
+        rho = self.surface_density
+        for k in range(self.nw):
+            lo, hi = int(self.vp[k]), int(self.vp[k + 1])
+            # 1. the flow exiting up the well bore from each perforation, from the bottom to the top
+            q_out = [[0.0, 0.0, 0.0] for _ in range(hi - lo)]
+            for p in range(hi - 1, lo - 1, -1):
+                for c in range(3):
+                    v = 0.0 if p == hi - 1 else q_out[p + 1 - lo][c]
+                    v -= float(rates[p, c])
+                    q_out[p - lo][c] = v
+            # 2. the component mix, the volume ratio, the density of the segment above each perforation
+            x = [0.0, 0.0, 0.0]
+            for p in range(lo, hi):
+                qo = q_out[p - lo]
+                tot = ((0.0 + qo[0]) + qo[1]) + qo[2]              # std::accumulate
+                if tot != 0.0:
+                    mix = [abs(qo[c] / tot) for c in range(3)]
+                elif not producer[k] or p == lo:
+                    mix = [float(v) for v in no_flow_mix[k]]
+                else:
+                    mix = list(x)                                   # x, not mix, of the perforation above: as the reference has it
+                x = list(mix)
+                rs = rv = 0.0
+                if mix[OIL] > 1e-12:
+                    rs = min(mix[GAS] / mix[OIL], float(rsmax[p]))
+                if mix[GAS] > 1e-12:
+                    rv = min(mix[OIL] / mix[GAS], float(rvmax[p]))
+                if rs != 0.0:
+                    x[GAS] = (mix[GAS] - mix[OIL] * rs) / (1.0 - rs * rv)
+                if rv != 0.0:
+                    x[OIL] = (mix[OIL] - mix[GAS] * rv) / (1.0 - rs * rv)
+                volrat = 0.0
+                for c in range(3):
+                    volrat += x[c] / float(b[p, c])
+                sd = 0.0
+                for c in range(3):                                  # std::inner_product
+                    sd += float(rho[p, c]) * mix[c]
+                density[p] = sd / volrat
+                mixture[p], xs[p] = mix, x
+        return density, mixture, xs
+
+    def _connection_densities_numpy(self, rates, b, rsmax, rvmax, producer, no_flow_mix):
+        """the same formulas over all perforations at once; only a perforation without flow looks at the one above"""
+        n = len(self.cells)
+        q_out = np.zeros((n, 3))
+        for k in range(self.nw):
+            lo, hi = self.vp[k], self.vp[k + 1]
+            q_out[lo:hi] = -np.cumsum(rates[lo:hi][::-1], axis=0)[::-1]
+        tot = q_out.sum(axis=1)
+        flows = tot != 0.0
+        mix = np.zeros((n, 3))
+        mix[flows] = np.abs(q_out[flows] / tot[flows, None])
+        x = np.zeros((n, 3))
+        density = np.zeros(n)
+        rho = self.surface_density
+
+        def finish(sel):
+            m = mix[sel]
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                rs = np.where(m[:, OIL] > 1e-12, np.minimum(m[:, GAS] / m[:, OIL], rsmax[sel]), 0.0)
+                rv = np.where(m[:, GAS] > 1e-12, np.minimum(m[:, OIL] / m[:, GAS], rvmax[sel]), 0.0)
+            xs = m.copy()
+            xs[:, GAS] = np.where(rs != 0.0, (m[:, GAS] - m[:, OIL] * rs) / (1.0 - rs * rv), m[:, GAS])
+            xs[:, OIL] = np.where(rv != 0.0, (m[:, OIL] - m[:, GAS] * rv) / (1.0 - rs * rv), m[:, OIL])
+            x[sel] = xs
+            density[sel] = (rho[sel] * m).sum(axis=1) / (xs / b[sel]).sum(axis=1)
+        finish(np.flatnonzero(flows))
+        for p in np.flatnonzero(~flows):                            # ascending: the perforation above is done
+            k = self.well_of_perf[p]
+            mix[p] = no_flow_mix[k] if (not producer[k] or p == self.vp[k]) else x[p - 1]
+            finish(np.array([p]))
+        return density, mix, x
 
     # ---- connection rates of every perforation with their derivatives: (nperf, 3 components, 1 + 3 cell variables + bhp) ----------------
     def _perf_rates(self, iq, bhp):
@@ -275,8 +477,7 @@ class StandardWells:
         """the well equations alone at a frozen reservoir state (StandardWell::solveWellEqUntilConverged / prepareTimeStep): Newton on the
         4 unknowns of every well"""
         if not self.initialised:
-            q = _rows(iq, [w.cells[0] for w in self.wells])
-            self.x[:, 3] = q[:, F_P + PH_O, 0] + np.where([w.producer for w in self.wells], -1e5, 1e5)
+            self.x[:, 3] = self._initial_bhp(iq)
         active = np.ones(self.nw, bool)
         for _ in range(iterations):
             r, D, *_ = self._assemble_wells(iq)
@@ -298,6 +499,9 @@ class StandardWells:
         BlackoilWellModel::assemble at the present reservoir and well state.  ncells: also `source` / `dsource` as arrays over the whole grid
         (opmhip_set_source's form)."""
         rw, D, Bn, Cn, src, dsrc = self._assemble_wells(iq)
+        if self.head_model == "wellbore":        # the well state the next time step's heads start from (StandardWell_impl.hpp:468)
+            self.perf_pressure = self.x[:, 3][self.well_of_perf] + self.head
+            self.perf_rates = src.copy()
         Dinv = np.array([invert4_stated(d) for d in D]) if self.arithmetic == "stated" else np.linalg.inv(D)
         nu = len(self.ucells)
         source_cells, dsource_cells = np.zeros((nu, 3)), np.zeros((nu, 3, 3))
@@ -331,12 +535,23 @@ class StandardWells:
         return True
 
     def state(self):
-        return self.x.copy(), [w.control for w in self.wells]
+        """(x, controls) and, with head_model="wellbore", a third entry: (perforation pressures | None, stored rates, whether the bottom-hole
+        pressures have been set) - under that model the bottom-hole pressure is an input of the heads, so a state from before the first
+        time step says so and the retry of a given-up first step starts from the cells again"""
+        st = self.x.copy(), [w.control for w in self.wells]
+        if self.head_model == "wellbore":
+            st += ((None if self.perf_pressure is None else self.perf_pressure.copy(), self.perf_rates.copy(), self.initialised),)
+        return st
 
     def set_state(self, st):
         self.x = st[0].copy()
         for w, c in zip(self.wells, st[1]):
             w.control = c
+        if self.head_model == "wellbore" and len(st) > 2:
+            self.perf_pressure = None if st[2][0] is None else st[2][0].copy()
+            self.perf_rates = st[2][1].copy()
+            if len(st[2]) > 2:
+                self.initialised = bool(st[2][2])
 
 
 class DeviceStandardWells:
@@ -345,17 +560,24 @@ class DeviceStandardWells:
     (fetch).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
-    def __init__(self, wells, cell_depth, model):
+    def __init__(self, wells, cell_depth, model, head_model="cell_oil"):
+        """head_model="wellbore": the heads from the well-bore density (opmhip_set_std_wells_head_model), StandardWells(head_model="wellbore",
+        arithmetic="stated")'s with the device's own property functions"""
+        if head_model not in HEAD_MODELS:
+            raise ValueError("head_model: 'cell_oil' or 'wellbore'")
         self.wells = list(wells)
         self.nw = len(self.wells)
         self.m = model
-        phase = {"water": PH_W, "oil": PH_O, "gas": PH_G}
+        self.head_model = head_model
+        phase = PHASE_BY_NAME
         depth = np.asarray(cell_depth, float)
         for w in self.wells:
             if w.rate_control[0] != "rate" or (w.control[0] == "bhp" and w.control[1] != w.bhp_limit):
                 raise ValueError("DeviceStandardWells: well %s needs a rate target and, under BHP control, its limit as the target" % w.name)
             if not w.producer and w.inj_phase not in phase:
                 raise ValueError("DeviceStandardWells: injector %s with unknown phase %r" % (w.name, w.inj_phase))
+            if head_model == "wellbore" and w.producer and w.preferred_phase not in phase:
+                raise ValueError("DeviceStandardWells: producer %s with unknown preferred phase %r" % (w.name, w.preferred_phase))
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         model.set_std_wells(dict(
@@ -364,6 +586,10 @@ class DeviceStandardWells:
             producer=[int(w.producer) for w in self.wells], inj_phase=[0 if w.producer else phase[w.inj_phase] for w in self.wells],
             rate_component=[w.rate_control[1] for w in self.wells], rate_target=[w.rate_control[2] for w in self.wells],
             bhp_limit=[w.bhp_limit for w in self.wells], control=[int(w.control[0] == "bhp") for w in self.wells], x=None))
+        if head_model == "wellbore":
+            self._wellbore = dict(perf_depth=depth[self.cells], ref_depth=[w.ref_depth for w in self.wells],
+                                  preferred_phase=[phase[w.preferred_phase] if w.producer else PH_O for w in self.wells])
+            model.set_std_wells_head_model(self._wellbore)
         self.x = np.zeros((self.nw, 4))
         self.res_well = np.zeros((self.nw, 4))
 
@@ -394,9 +620,25 @@ class DeviceStandardWells:
         self.m.set_std_wells_state(self.x, [int(w.control[0] == "bhp") for w in self.wells], [w.rate_control[2] for w in self.wells])
 
     def state(self):
+        """as StandardWells.state(); the per-perforation state is read back where the device has one (None before the first heads).  The
+        third entry has no "bottom-hole pressures set" flag: the library keeps and rolls back its own (opmhip_update_failed)"""
         self.fetch()
-        return self.x.copy(), [w.control for w in self.wells]
+        st = self.x.copy(), [w.control for w in self.wells]
+        if self.head_model == "wellbore":
+            wb = self.m.std_wells_wellbore()
+            st += ((wb["perf_pressure"] if wb["perf_state_set"] else None, wb["perf_rates"]),)
+        return st
 
     def set_state(self, st):
-        StandardWells.set_state(self, st)
+        """a third entry whose pressures are None ("not yet taken from the cells") sets the head model anew: the library then takes them from
+        the cells at the next begin_iteration(0), as the host class does.  (Whether the bottom-hole pressures have been set is the library's
+        to keep: it cannot be handed in.)"""
+        self.x = st[0].copy()
+        for w, c in zip(self.wells, st[1]):
+            w.control = c
         self._send()
+        if self.head_model == "wellbore" and len(st) > 2:
+            if st[2][0] is None:
+                self.m.set_std_wells_head_model(self._wellbore)
+            else:
+                self.m.set_std_wells_perf_state(st[2][0], st[2][1])

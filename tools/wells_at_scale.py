@@ -8,7 +8,9 @@ producer with a BHP limit it never meets), under bench.py's time-step control, f
   device     the well equations resident on the device (opmhip_set_std_wells, wells.DeviceStandardWells): one read-back of 10 doubles per well
 Prints Newton iterations/s and linear iterations per Newton iteration of each.    python tools/wells_at_scale.py [--n 100] [--steps 20]
 --spe9: instead, the SPE9-shaped well case of the tests (decks.spe9_shaped_wells: 26 wells, 80 completions, 9 000 cells, producers'
-BHP limit 235 bar) with its wells per cell (host) and on the device, alternating, each form in a context of its own."""
+BHP limit 235 bar) with its wells per cell (host) and on the device, alternating, each form in a context of its own.
+--spe9 --heads: the resident wells alone, the head from the perforated cell's oil density against the head from the well-bore density
+(opmhip_set_std_wells_head_model), alternating, three times each."""
 import argparse, importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +21,10 @@ ap.add_argument("--n", type=int, default=100)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--spe9", action="store_true")
+ap.add_argument("--heads", action="store_true")
 a = ap.parse_args()
+if a.heads and not a.spe9:
+    ap.error("--heads compares the head models on the SPE9-shaped case: give --spe9 with it")
 pkg = importlib.import_module("opm-autodiff_amd")
 n = a.n
 if a.spe9:
@@ -54,14 +59,14 @@ class WholeGrid:
         return getattr(self._m, k)
 
 
-def run(name, with_wells, whole_grid=False, device=False):
+def run(name, with_wells, whole_grid=False, device=False, head_model="cell_oil"):
     m = pkg.capi.HipModel(case, tolerance=1e-2, maxit=200, ilu_relaxation=0.9)
     m.set_state(case["pv"], case["meaning"])
     wells = None
     if with_wells:
         wells = two_wells()
         if device:
-            wells = pkg.wells.DeviceStandardWells(wells.wells, case["depth"], m)
+            wells = pkg.wells.DeviceStandardWells(wells.wells, case["depth"], m, head_model=head_model)
     else:
         m.set_source(src)
     nm = pkg.newton.BlackoilModelHip(WholeGrid(m) if whole_grid else m, well_model=wells)
@@ -85,9 +90,14 @@ def run(name, with_wells, whole_grid=False, device=False):
 
 if a.spe9:
     print("SPE9-shaped: 24 x 25 x 15 cells, 26 wells, %d Newton iterations after %d of warm-up, each variant in a context of its own" % (a.steps, a.warmup), flush=True)
-    for rep in range(2):
-        run("26 wells, 80 completions: per cell", True)
-        run("26 wells, 80 completions: device", True, device=True)
+    if a.heads:
+        for rep in range(3):
+            run("26 wells on the device: head cell_oil", True, device=True)
+            run("26 wells on the device: head wellbore", True, device=True, head_model="wellbore")
+    else:
+        for rep in range(2):
+            run("26 wells, 80 completions: per cell", True)
+            run("26 wells, 80 completions: device", True, device=True)
     sys.exit(0)
 print("%d^3 cells, %d Newton iterations after %d of warm-up, each variant in a context of its own" % (n, a.steps, a.warmup), flush=True)
 for rep in range(2):
