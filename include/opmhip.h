@@ -749,16 +749,19 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
 
 /* ---- standard wells, resident on the device.  Additive to ABI 11 -----------------------------------------------------------
  * The well model the Python package states on the host (wells.py StandardWells: vertical standard wells, 4 unknowns per well - the
- * surface rates of oil, water and gas INTO the reservoir and the bottom-hole pressure -, rate or BHP control with one BHP limit, no
- * crossflow, no storage term, an explicit head per completion from the perforated cell's oil density), formed on the device from
+ * surface rates of oil, water and gas INTO the reservoir and the bottom-hole pressure -, rate or BHP control with one BHP limit,
+ * crossflow in producers on request (opmhip_set_std_wells_crossflow, below; off by default: a perforation that would flow against
+ * its well's kind is closed), no storage term, an explicit head per completion from the perforated cell's oil density), formed on the device from
  * the cached intensive quantities: nothing of a Newton iteration crosses to the host but one read-back of 10 doubles per well.
  * The arithmetic is wells.py's arithmetic="stated", operation by operation (the library is built without floating-point
  * contraction): the per-well sums run over the perforations in perforation order, D^-1 is Gauss-Jordan on [D | I] with partial
  * pivoting (largest |entry| of the column, lowest row on ties), D^-1 r a row-times-vector product in ascending column order.
  * The head is, on request, the reference's: from the density of the mixture in the well bore above every completion
  * (opmhip_set_std_wells_head_model, below).
- * NOT covered: groups, THP, VFP, crossflow, decomposed contexts (refused), the matrix-add form (opmhip_add_well_contributions stays
- * with host lists).
+ * NOT covered: groups, THP, VFP, crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
+ * because its composition - WFrac, GFrac - is an unknown while getQs pins the other components to zero; this parametrisation fixes
+ * the injected composition, and a half-measure would let oil leave through an injector's wellhead), decomposed contexts (refused),
+ * the matrix-add form (opmhip_add_well_contributions stays with host lists).
  * Phases: 0 water, 1 oil, 2 gas (the intensive-quantity record's order); components: 0 oil, 1 water, 2 gas (the equations' order). */
 typedef struct opmhip_std_wells {
     int num_wells;
@@ -806,6 +809,38 @@ int opmhip_set_std_wells_state(opmhip_ctx* ctx, const double* x, const int* cont
  * [num_wells * 16], B and C [nperf * 12] in opmhip_wells' layout, rates [nperf * 15] (3 components x value, d/dSw, d/dp, d/dX,
  * d/dbhp), x_w [num_wells * 4] */
 int opmhip_get_std_wells_blocks(opmhip_ctx* ctx, double* head, double* D, double* Dinv, double* B, double* C, double* rates, double* xw);
+/* ---- crossflow in producers.  Additive to ABI 11 ----------------------------------------------------------------------------
+ * replaces: the injecting branch of StandardWellEval::computePerfRate with allow_cf (wells/StandardWellEval.cpp:1023-1090; WELSPECS
+ * item 10, which Flow defaults to YES) for producers, in the operation order of wells.py StandardWells(arithmetic="stated").
+ * q = (q_o, q_w, q_g) are the well's rate unknowns; bhp, head, tw, b = 1/B, mob and rs those of the perforation as above.  A
+ * perforation of a producer with the switch whose drawdown dd = p_o - (bhp + head) is NOT > 0 flows
+ *   p_c = -q_c where q_c < 0, else 0;  P = (p_o + p_w) + p_g;  cmix_c = p_c / P      (wellSurfaceVolumeFraction, :233-243; the clamp
+ *   d cmix_c / d q_j = -((delta_cj - cmix_c) / P) where q_j < 0, else 0                is processFractions' on WFrac / GFrac)
+ *   cqt_i = -tw * (((mob_w + mob_o) + mob_g) * dd)
+ *   volumeRatio = (cmix_w / b_w + cmix_o / b_o) + (cmix_g - rs * cmix_o) / b_g
+ *   cqt_is = cqt_i / volumeRatio;  rate_c = cmix_c * cqt_is
+ * Every quantity carries its value and seven derivatives: d/dSw, d/dp, d/dX of the cell, d/dbhp, d/dq_o, d/dq_w, d/dq_g.  A product
+ * is (a0 b0; a0 b_i + b0 a_i), a quotient (v = a0 / b0; (a_i - v b_i) / b0), sums and differences entry by entry in the order
+ * written.  If P is not > 0 (a well that has not flowed yet: the first iteration of the wells alone) or volumeRatio is not > 0, the
+ * perforation stays closed for that evaluation: nothing is divided by zero or a negative, no NaN is formed.
+ * Assembly: r_w[c] = q_c - sum rate_c as before; D[c][j] = delta_cj - sum_p d rate_c / d q_j for j < 3, D[c][3] as before;
+ * C[j][c] = 0 - d rate_c / d q_j for j < 3 - the rows that are zero without crossflow; C[3][c], B, the source rows as before; every
+ * per-well sum is added by one lane in perforation order; the guard of a well none of whose completions flows keeps its condition.
+ * Perforations with dd > 0, and every perforation of a well without the switch, take the expressions of the list above in their
+ * order: a well with the switch and no reversed perforation gives the same bits as without.  With the well-bore heads the stored
+ * perforation rates are whatever the assembly formed, injecting signs included.
+ * Left out: vaporised oil in the rate model (rv = 0, d = 1, tmp_oil = cmix_o: the producing branch adds rs q_o to the gas and nothing
+ * to the oil, and crossflow keeps that); openCrossFlowAvoidSingularity.
+ * allow: per well, 0 or 1; NULL or all zeros: off.  Call it after opmhip_set_std_wells; replacing or clearing the list clears it.
+ * OPMHIP_NOT_READY without a list; OPMHIP_INVALID_ARGUMENT for a value other than 0 / 1 or for an injector (the text says so).  A
+ * refused call leaves the flags as they were.  What the last assemble formed is stale afterwards, as with
+ * opmhip_set_std_wells_state.  A list none of whose wells has the switch launches exactly the kernels it launched before; with a
+ * switch on, the wells alone and the assembly run a second instantiation of the same kernel in place of the first (15 sums per lane
+ * instead of 6): the number of launches does not change.  The switch adds no state to save or restore. */
+int opmhip_set_std_wells_crossflow(opmhip_ctx* ctx, const int* allow);
+/* for tests: dq [nperf * 9] = d rate_c / d q_j of the last assemble, [perforation][component c][unknown j]; zeros without the
+ * switch.  (opmhip_get_std_wells_blocks keeps its rates [nperf * 15] layout.) */
+int opmhip_get_std_wells_rate_dq(opmhip_ctx* ctx, double* dq);
 /* ---- the heads from the well-bore density.  Additive to ABI 11 -------------------------------------------------------------
  * replaces: StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:1195-1210), that is
  * computePropertiesForWellConnectionPressures (:899-1012), computeWellConnectionDensitesPressures (:1124-1189),

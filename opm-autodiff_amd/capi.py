@@ -655,6 +655,8 @@ def _bind_assembly(L):
     L.opmhip_set_std_wells_head_model.argtypes = [vp, C.POINTER(StdWellsWellbore)]
     L.opmhip_get_std_wells_wellbore.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.opmhip_set_std_wells_perf_state.argtypes = [vp, vp, vp]
+    L.opmhip_set_std_wells_crossflow.argtypes = [vp, vp]
+    L.opmhip_get_std_wells_rate_dq.argtypes = [vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -952,6 +954,26 @@ class HipModel(HipSolver):
         perforated cell's oil density.  A refused call leaves the model as it was."""
         wb, keep = make_std_wells_wellbore(wellbore, getattr(self, "_nsw", 0), getattr(self, "_nswperf", 0))
         self._check(lib().opmhip_set_std_wells_head_model(self._h, C.byref(wb) if wb else None))
+
+    def set_std_wells_crossflow(self, allow):
+        """opmhip_set_std_wells_crossflow: per well 0 / 1 - reversed perforations of that producer inject the well bore's mixture; None or
+        all zeros: off.  An injector with the switch is a ValueError; a refused call leaves the flags as they were."""
+        a = _i32(allow)
+        n = getattr(self, "_nsw", 0)
+        if a is not None and a.size != n:
+            raise ValueError("set_std_wells_crossflow: %d flags for the %d wells set" % (a.size, n))
+        try:
+            self._check(lib().opmhip_set_std_wells_crossflow(self._h, _ptr(a)))
+        except OpmHipError as e:
+            if e.code == INVALID_ARGUMENT and "injector" in str(e):
+                raise ValueError(str(e)) from e
+            raise
+
+    def std_wells_rate_dq(self):
+        """for tests: d rate_c / d q_j of the last assemble, (perforations, 3 components, 3 rate unknowns); zeros without crossflow"""
+        dq = np.zeros((getattr(self, "_nswperf", 0), 3, 3))
+        self._check(lib().opmhip_get_std_wells_rate_dq(self._h, _ptr(dq)))
+        return dq
 
     def std_wells_wellbore(self):
         """for tests and restart files: dict(density, p_avg, mixture (perforations, 3 components), perf_pressure, perf_rates (perforations, 3))

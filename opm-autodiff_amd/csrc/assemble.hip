@@ -1529,6 +1529,21 @@ void launch_aquifer_end(opmhip_ctx* c, double dt) {
 // operation order of wells.py StandardWells(arithmetic="stated") - the library is built with -ffp-contract=off, so that every
 // expression below rounds where its NumPy counterpart rounds.  A5: value, d/dSw, d/dp, d/dX of the perforated cell, d/dbhp.
 // Plain wave64 kernels; no atomics; every sum over perforations is added by one lane in perforation order.
+//
+// Crossflow in producers (opmhip_set_std_wells_crossflow, per well, off by default): the injecting branch of
+// StandardWellEval::computePerfRate with allow_cf (wells/StandardWellEval.cpp:1023-1090).  A perforation of such a producer whose
+// drawdown dd = p_o - (bhp + head) is not > 0 puts the well bore's mixture back into the formation.  q = the well's rate unknowns:
+//     p_c = -q_c where q_c < 0, else 0;  P = (p_o + p_w) + p_g;  cmix_c = p_c / P          (wellSurfaceVolumeFraction, :233-243)
+//     d cmix_c / d q_j = -((delta_cj - cmix_c) / P) where q_j < 0, else 0
+//     cqt_i = -tw * (((mob_w + mob_o) + mob_g) * dd)
+//     volumeRatio = (cmix_w / b_w + cmix_o / b_o) + (cmix_g - rs * cmix_o) / b_g            (b = 1/B of the perforated cell)
+//     cqt_is = cqt_i / volumeRatio;  rate_c = cmix_c * cqt_is
+// on A8 = value, d/dSw, d/dp, d/dX, d/dbhp, d/dq_o, d/dq_w, d/dq_g: a product is sw_mul (a0 b0; a0 b_i + b0 a_i), a quotient sw_div
+// (v = a0 / b0; (a_i - v b_i) / b0), sums and differences entry by entry, in the order written.  P not > 0 (the well has not flowed
+// yet) or volumeRatio not > 0: the perforation stays closed for that evaluation - nothing is divided by zero or a negative.  Then
+// D[c][j] = delta_cj - sum_p d rate_c / d q_j and C[j][c] = 0 - d rate_c / d q_j; perforations with dd > 0 and wells without the switch
+// take the expressions below unchanged.  Left out: vaporised oil (rv = 0, d = 1, tmp_oil = cmix_o), openCrossFlowAvoidSingularity.
+// Injectors are refused: this parametrisation fixes the injected composition, where the reference re-injects what crosses in.
 struct A5 { double v[5]; };
 __device__ __forceinline__ A5 sw_load(const double* __restrict__ p) { return A5{{p[0], p[1], p[2], p[3], 0.0}}; }
 __device__ __forceinline__ A5 sw_mul(const A5& a, const A5& b) {   // the product rule of wells.py's `mul`
@@ -1570,6 +1585,82 @@ __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int
         sw_store(out + comp * 5, sw_mul(sw_load(iq_at(iq, ncell, F_B + injPhase, c)), vol));
     }
 }
+struct A8 { double v[8]; };
+__device__ __forceinline__ A8 sw_load8(const double* __restrict__ p) { return A8{{p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0, 0.0}}; }
+__device__ __forceinline__ A8 sw_mul(const A8& a, const A8& b) {
+    A8 o;
+    o.v[0] = a.v[0] * b.v[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) o.v[i] = a.v[0] * b.v[i] + b.v[0] * a.v[i];
+    return o;
+}
+__device__ __forceinline__ A8 sw_div(const A8& a, const A8& b) {   // wells.py's `div`
+    A8 o;
+    o.v[0] = a.v[0] / b.v[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) o.v[i] = (a.v[i] - o.v[0] * b.v[i]) / b.v[0];
+    return o;
+}
+__device__ __forceinline__ A8 sw_scale(double s, const A8& a) {
+    A8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = s * a.v[i];
+    return o;
+}
+__device__ __forceinline__ A8 sw_add(const A8& a, const A8& b) {
+    A8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = a.v[i] + b.v[i];
+    return o;
+}
+__device__ __forceinline__ A8 sw_sub(const A8& a, const A8& b) {
+    A8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.v[i] = a.v[i] - b.v[i];
+    return o;
+}
+// the well bore's surface-volume fractions from the well's rate unknowns, mix[component * 4 + (value, d/dq_o, d/dq_w, d/dq_g)]
+// -> whether the well flows (P > 0)
+__device__ bool sw_wellbore_fractions(const double* x, double* mix) {
+    bool s[3];
+    double p[3];
+    for (int c = 0; c < 3; ++c) { s[c] = x[c] < 0.0; p[c] = s[c] ? -x[c] : 0.0; }
+    const double P = (p[EQ_OIL] + p[EQ_WATER]) + p[EQ_GAS];
+    for (int i = 0; i < 12; ++i) mix[i] = 0.0;
+    if (!(P > 0.0)) return false;
+    for (int c = 0; c < 3; ++c) {
+        const double m = p[c] / P;
+        mix[c * 4] = m;
+        for (int j = 0; j < 3; ++j)
+            if (s[j]) mix[c * 4 + 1 + j] = -(((c == j ? 1.0 : 0.0) - m) / P);
+    }
+    return true;
+}
+// a reversed perforation of a producer with crossflow: out as sw_perf_rates', dq[component * 3 + (d/dq_o, d/dq_w, d/dq_g)]; both are
+// left alone where the volume ratio is not positive
+__device__ __forceinline__ void sw_crossflow_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head,
+                                                   const double* mix, double* out, double* dq) {
+    A8 dd = sw_load8(iq_at(iq, ncell, F_P + OIL, c));
+    dd.v[0] = dd.v[0] - (bhp + head);
+    dd.v[4] = -1.0;
+    A8 cm[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cm[k] = A8{{mix[k * 4], 0.0, 0.0, 0.0, 0.0, mix[k * 4 + 1], mix[k * 4 + 2], mix[k * 4 + 3]}};
+    const A8 tot = sw_add(sw_add(sw_load8(iq_at(iq, ncell, F_MOB + WATER, c)), sw_load8(iq_at(iq, ncell, F_MOB + OIL, c))), sw_load8(iq_at(iq, ncell, F_MOB + GAS, c)));
+    const A8 cqt_i = sw_scale(-tw, sw_mul(tot, dd));
+    const A8 ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load8(iq_at(iq, ncell, F_B + WATER, c))), sw_div(cm[EQ_OIL], sw_load8(iq_at(iq, ncell, F_B + OIL, c)))),
+                            sw_div(sw_sub(cm[EQ_GAS], sw_mul(sw_load8(iq_at(iq, ncell, F_RS, c)), cm[EQ_OIL])), sw_load8(iq_at(iq, ncell, F_B + GAS, c))));
+    if (!(ratio.v[0] > 0.0)) return;
+    const A8 cqt_is = sw_div(cqt_i, ratio);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const A8 r = sw_mul(cm[k], cqt_is);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) out[k * 5 + i] = r.v[i];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dq[k * 3 + j] = r.v[5 + j];
+    }
+}
 // wells.py invert4_stated: Gauss-Jordan on [D | I], partial pivoting (largest |entry| of the column, lowest row on ties), the pivot row
 // divided by the pivot, every other row updated as a - f * b.  -> 0, or 1 + the column without a pivot (inv is then left alone)
 __device__ int sw_invert4(const double* D, double* inv) {
@@ -1602,17 +1693,24 @@ struct SwArrays {
     double *head, *pr, *pack, *Dmat, *B, *C, *Dinv;
     int wellbore, nperf;                        // the heads come from the well-bore density (k_std_wells_wellbore); all perforations of the list
     double* wbstate;                            // then: p_perf [nperf] | the rates of the last assembly [nperf * 3]
+    const int* cf;                              // per well: crossflow allowed (read by the CF instantiations only; NULL without a flag)
+    double* dq;                                 // then: d rate_c / d q_j of the last assembly [nperf * 9]
 };
 // One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
 // global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
 // without a flowing completion, and D^-1.  SOLVE: the well alone against the frozen reservoir (StandardWells.solve_well_equations) - the
 // heads first, then that body in a loop of at most 20 with the well's own stopping test, x -= D^-1 r_w in between; nothing but x, the
-// heads and the flag is written.
-template <bool SOLVE>
+// heads and the flag is written.  CF: the list has a well with crossflow (launched in place of the other instantiation, for all its
+// wells): 15 sums per lane - the 9 d rate / d q beside the 6 -, the full D, C's first three rows; the well bore's fractions are formed
+// by lane 0 once per evaluation from x in LDS.  A well without the switch, or without a reversed perforation, gets today's bits.
+template <bool SOLVE, bool CF>
 __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, const double* __restrict__ iq, int first) {
-    __shared__ double sums[64 * 6];
+    constexpr int NS = CF ? 15 : 6;
+    __shared__ double sums[64 * NS];
     __shared__ double xs[4];
-    __shared__ int s_active;
+    __shared__ double s_mix[12];
+    __shared__ int s_active, s_flows;
+    const bool crossflow = CF && W.cf[blockIdx.x] != 0;   // uniform: the well's
     const int w = blockIdx.x, lane = threadIdx.x;
     const int pb = W.vp[w], pe = W.vp[w + 1];
     const bool producer = W.wi[3 * w] != 0;
@@ -1628,15 +1726,29 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
     }
     __syncthreads();
     for (int it = 0; it < (SOLVE ? 20 : 1); ++it) {
+        if (crossflow) {
+            if (lane == 0) s_flows = sw_wellbore_fractions(xs, s_mix) ? 1 : 0;
+            __syncthreads();
+        }
         const double bhp = xs[3];
-        double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // lane 0: sums of the rates and of d/dbhp
+        double S[NS];   // lane 0: sums of the rates, of d/dbhp and (CF) of d/dq
+        for (int k = 0; k < NS; ++k) S[k] = 0.0;
         for (int p0 = pb; p0 < pe; p0 += 64) {
             const int p = p0 + lane;
             if (p < pe) {
                 double q[15];
                 sw_perf_rates(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, q);
+                double dq[CF ? 9 : 1];
+                if (CF) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { sums[lane * 6 + c] = q[c * 5]; sums[lane * 6 + 3 + c] = q[c * 5 + 4]; }
+                    for (int i = 0; i < 9; ++i) dq[i] = 0.0;
+                    if (crossflow && producer && s_flows && !(iq_at(iq, ncell, F_P + OIL, W.cell[p])[0] - (bhp + W.head[p]) > 0.0))
+                        sw_crossflow_rates(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], s_mix, q, dq);
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) sums[lane * NS + 6 + i] = dq[i];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { sums[lane * NS + c] = q[c * 5]; sums[lane * NS + 3 + c] = q[c * 5 + 4]; }
                 if (!SOLVE) {
                     double* pr = W.pr + (size_t)15 * p;
                     double* B = W.B + (size_t)12 * p;
@@ -1645,9 +1757,13 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
                     for (int i = 0; i < 15; ++i) pr[i] = q[i];
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        for (int v = 0; v < 3; ++v) { B[c * 3 + v] = -q[c * 5 + 1 + v]; C[c * 3 + v] = 0.0; }
+                        for (int v = 0; v < 3; ++v) { B[c * 3 + v] = -q[c * 5 + 1 + v]; C[c * 3 + v] = CF ? 0.0 - dq[v * 3 + c] : 0.0; }
                         B[9 + c] = 0.0;
                         C[9 + c] = -q[c * 5 + 4];
+                    }
+                    if (CF) {
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) W.dq[(size_t)9 * p + i] = dq[i];
                     }
                     if (W.wellbore) {   // the well state the next time step's heads start from (StandardWell_impl.hpp:468 and the rates of computePerfRate)
                         W.wbstate[p] = bhp + W.head[p];
@@ -1660,7 +1776,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
             if (lane == 0) {
                 const int m = pe - p0 < 64 ? pe - p0 : 64;
                 for (int j = 0; j < m; ++j)
-                    for (int k = 0; k < 6; ++k) S[k] = (p0 == pb && j == 0) ? sums[k] : S[k] + sums[j * 6 + k];
+                    for (int k = 0; k < NS; ++k) S[k] = (p0 == pb && j == 0) ? sums[k] : S[k] + sums[j * NS + k];
             }
             __syncthreads();
         }
@@ -1668,6 +1784,9 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
             double r[4], D[16], inv[16];
             for (int i = 0; i < 16; ++i) { D[i] = 0.0; inv[i] = 0.0; }
             for (int c = 0; c < 3; ++c) { r[c] = xs[c] - S[c]; D[c * 4 + c] = 1.0; D[c * 4 + 3] = -S[3 + c]; }
+            if (CF)
+                for (int c = 0; c < 3; ++c)
+                    for (int j = 0; j < 3; ++j) D[c * 4 + j] = D[c * 4 + j] - S[6 + c * 3 + j];
             if (W.pack[(size_t)4 * W.num + w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
             else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
             // a well none of whose completions flows has no rate that answers to its bottom-hole pressure: it keeps the pressure
@@ -1712,12 +1831,12 @@ struct WbArrays {
     double *out, *scratch;       // density [nperf] | p_avg [nperf] | mixture [nperf * 3]; 8 doubles per perforation
 };
 enum { WB_B = 0, WB_RSMAX = 3, WB_RVMAX = 4, WB_Q = 5, WB_REC = 8 };   // the record of a perforation between the passes: 1/B and q per component
-// One wavefront per well, in front of k_std_wells_eq<true>.  Lanes take the perforations 64 at a time for the gathers and the table
+// One wavefront per well, in front of the solving k_std_wells_eq.  Lanes take the perforations 64 at a time for the gathers and the table
 // look-ups - p_avg, 1/B_w, RsSat, RvSat, 1/B_g, 1/B_o, the rates that count - and leave a record per perforation in LDS (a well of at
 // most 64 perforations) or in global scratch.  Lane 0 then runs the two dependent passes in perforation order: the flow past every
 // perforation from the last to the first, and from the first to the last the mixture, its corrected form x (which a perforation
 // without flow hands to the next), the density and the head's running sum.  No atomics, no transcendental functions; what a lane
-// computes depends on its perforation alone.  first: the bottom-hole pressure is the one k_std_wells_eq<true> is about to start from;
+// computes depends on its perforation alone.  first: the bottom-hole pressure is the one the solving k_std_wells_eq is about to start from;
 // init: the perforation pressures are the perforated cells' oil pressures and the stored rates zero (wells/WellState.cpp:298).
 __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays Q, Tables T, const int* __restrict__ pvtnum, int ncell,
                                                            const double* __restrict__ iq, int first, int init) {
@@ -1883,12 +2002,14 @@ __global__ __launch_bounds__(64) void k_std_wells_axpy(int n, double relax, cons
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
     return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.d_pack, S.d_Dmat, W.d_B, W.d_C, W.d_D,
-                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate};
+                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate, S.d_cf, S.d_dq};
 }
 // (booked under the profile's assembly class, one scope per function: a context with a list shows them in opmhip_profile_get)
 void launch_std_wells_solve(opmhip_ctx* c, bool first) {
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(k_std_wells_eq<true>, dim3(c->wells.sw.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
+    // (a list with a crossflow well runs the CF instantiation in place of the other: the number of launches is the same)
+    const auto kernel = c->wells.sw.crossflow ? k_std_wells_eq<true, true> : k_std_wells_eq<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(c->wells.sw.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
     prof_end(c, ps);
 }
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
@@ -1908,7 +2029,8 @@ void launch_std_wells_controls(opmhip_ctx* c) {
 void launch_std_wells_assemble(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(k_std_wells_eq<false>, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, 0);
+    const auto kernel = S.crossflow ? k_std_wells_eq<false, true> : k_std_wells_eq<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, 0);
     hipLaunchKernelGGL(k_std_wells_source, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_cptr, S.d_cperf, S.d_pr, c->asmb.d_source,
                        c->asmb.d_dsource, S.d_save);
     prof_end(c, ps);

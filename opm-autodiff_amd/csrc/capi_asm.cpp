@@ -1254,6 +1254,8 @@ void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
     dev_free(c, &S.d_pack); dev_free(c, &S.d_saved); dev_free(c, &S.d_Dmat);
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
+    dev_free(c, &S.d_cf); dev_free(c, &S.d_dq);
+    S.crossflow = false;
     std_wells_wellbore_release(c);
     S.num = S.nperf = S.nd = 0;
     S.initialised = S.assembled = false;
@@ -1505,6 +1507,59 @@ int opmhip_get_std_wells_blocks(opmhip_ctx* c, double* head, double* D, double* 
         if (C) OPMHIP_HIP(c, hipMemcpy(C, W.d_C, np * 12 * sizeof(double), hipMemcpyDeviceToHost));
         if (rates) OPMHIP_HIP(c, hipMemcpy(rates, S.d_pr, np * 15 * sizeof(double), hipMemcpyDeviceToHost));
         if (xw) OPMHIP_HIP(c, hipMemcpy(xw, W.d_xw, nw * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_crossflow(opmhip_ctx* c, const int* allow) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_crossflow: no resident list (opmhip_set_std_wells)");
+        const size_t nw = S.num, np = S.nperf;
+        bool any = false;
+        if (allow)   // everything is looked at before anything changes: a refused call leaves the flags as they were
+            for (size_t w = 0; w < nw; ++w) {
+                if (allow[w] != 0 && allow[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_crossflow: allow[%zu] = %d (0 off, 1 on)", w, allow[w]);
+                any = any || allow[w] == 1;
+            }
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if (any) {
+            std::vector<int> wi(3 * nw);
+            OPMHIP_HIP(c, hipMemcpy(wi.data(), S.d_wi, wi.size() * sizeof(int), hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < nw; ++w)
+                if (allow[w] && !wi[3 * w])
+                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_crossflow: well %zu is an injector - crossflow is modelled for producers only (the injected composition is fixed)", w);
+        }
+        int* d_cf = nullptr;
+        double* d_dq = nullptr;
+        if (any) {
+            int r;
+            if ((r = dev_upload(c, &d_cf, std::vector<int>(allow, allow + nw))) || (r = dev_upload(c, &d_dq, std::vector<double>(9 * np, 0.0)))) {
+                dev_free(c, &d_cf); dev_free(c, &d_dq);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        dev_free(c, &S.d_cf); dev_free(c, &S.d_dq);
+        S.d_cf = d_cf; S.d_dq = d_dq;
+        S.crossflow = any;
+        S.assembled = false;   // the blocks of the last assembly are no longer the model's
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_rate_dq(opmhip_ctx* c, double* dq) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (S.num == 0 || !dq) return OPMHIP_SUCCESS;
+        const size_t np = S.nperf;
+        if (!S.crossflow) { std::memset(dq, 0, 9 * np * sizeof(double)); return OPMHIP_SUCCESS; }
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        OPMHIP_HIP(c, hipMemcpy(dq, S.d_dq, 9 * np * sizeof(double), hipMemcpyDeviceToHost));
         return OPMHIP_SUCCESS;
     });
 }

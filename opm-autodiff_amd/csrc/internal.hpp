@@ -199,6 +199,11 @@ struct StdWellsDev {
     bool wb_initialised_saved = false;                   // `initialised` at the last advance_time_level: under this model the bottom-hole pressure is an input of the heads, so a given-up first step goes back to 'not yet set'
     double *d_wbdepth = nullptr, *d_wbref = nullptr, *d_wbstate = nullptr, *d_wbsaved = nullptr, *d_wbout = nullptr, *d_wbscratch = nullptr;
     int* d_wbpref = nullptr;     // per well: the preferred phase
+    // crossflow in producers (opmhip_set_std_wells_crossflow): set only while some well of the list has the switch; d_cf: per well 0 / 1,
+    // d_dq: per perforation d rate_c / d q_j of the last assemble (9 doubles)
+    bool crossflow = false;
+    int* d_cf = nullptr;
+    double* d_dq = nullptr;
     double* x() const { return d_pack; }
     double* control() const { return d_pack + (size_t)4 * num; }
     double* rw() const { return d_pack + (size_t)5 * num; }

@@ -2,7 +2,7 @@
 the host (as in the reference: only the reservoir part of the linearisation and the Schur-complement operator are accelerated) and handed
 to the device as the blocks bda::WellContributions carries - B, C (4 x 3 per perforation), D^-1 (4 x 4 per well).
 
-What of the reference this restates, minimally (vertical wells, rate or BHP control, no crossflow, no well storage term):
+What of the reference this restates, minimally (vertical wells, rate or BHP control, crossflow in producers on request, no well storage term):
   wells/StandardWell_impl.hpp: computePerfRate (:195-420; producing perforations: phase rate = -Tw mob drawdown, surface rate through
       1/B, dissolved gas with the oil; injecting perforations: total mobility, the injected phase's 1/B), assembleWellEqWithoutIteration
       (:516-640: mass-balance equation per component = surface rate - sum of connection rates, one control equation), apply (:1254-1296),
@@ -30,6 +30,25 @@ The head between a well's reference depth and a completion (head_model):
       StandardWell_impl.hpp:468).  Left out: solvent, salt, temperature, distributed wells' global perforation order, InjectorType::MULTI.
   Components are in the equations' order (oil, water, gas), phases in the record's (water, oil, gas): phase ph belongs to component
   COMPONENT_OF_PHASE[ph].
+
+Crossflow (Well(allow_crossflow=True), off by default; WELSPECS item 10, which Flow defaults to YES): a producer's perforation whose
+drawdown dd = p_o - (bhp + head) is not > 0 puts the well bore's mixture back into the formation - the injecting branch of
+StandardWellEval::computePerfRate (wells/StandardWellEval.cpp:1023-1090) with allow_cf.  q = (q_o, q_w, q_g) are the well's rate unknowns:
+    p_c = -q_c where q_c < 0, else 0;  P = (p_o + p_w) + p_g;  cmix_c = p_c / P         (wellSurfaceVolumeFraction, :233-243; the clamp is
+    d cmix_c / d q_j = -((delta_cj - cmix_c) / P) where q_j < 0, else 0                   processFractions' on WFrac / GFrac)
+    cqt_i = -tw * (((mob_w + mob_o) + mob_g) * dd)
+    volumeRatio = (cmix_w / b_w + cmix_o / b_o) + (cmix_g - rs * cmix_o) / b_g           (b = 1/B of the perforated cell)
+    cqt_is = cqt_i / volumeRatio;  rate_c = cmix_c * cqt_is
+  Every quantity carries the value and seven derivatives (A8: value, d/dSw, d/dp, d/dX of the cell, d/dbhp, d/dq_o, d/dq_w, d/dq_g);
+  a product is `mul` (a0 b0; a0 b_i + b0 a_i), a quotient `div` (v = a0 / b0; (a_i - v b_i) / b0), sums and differences entry by entry,
+  in the order written above.  A well whose P is not > 0 (it has not flowed yet) and a perforation whose volumeRatio is not > 0 stay
+  closed for that evaluation: nothing is divided by zero or a negative.  Then D = I - sum_p d rate / d q beside its bhp column and C gains
+  its first three rows, C[j][c] = 0 - d rate_c / d q_j.  Perforations with dd > 0 and wells without the switch take the expressions above
+  unchanged.  Left out: vaporised oil (rv = 0, d = 1, tmp_oil = cmix_o: as the producing branch, which adds rs q_o to the gas and nothing
+  to the oil), openCrossFlowAvoidSingularity (the guard for a well without a flowing completion stays).
+  Injectors: refused (ValueError).  In the reference an injector re-injects what crosses into it, because its composition (WFrac, GFrac)
+  is an unknown while getQs pins the other components to zero; this parametrisation fixes the injected composition, and a half-measure
+  would let oil leave through an injector's wellhead.
 """
 import numpy as np
 
@@ -109,14 +128,17 @@ def row_times_vector(M, r):
 
 class Well:
     """name; cells: perforated cells (natural order, from the top of the well down); tw: connection transmissibility factors; ref_depth;
-    producer or injector of `phase`; control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit"""
+    producer or injector of `phase`; control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit;
+    allow_crossflow (WELSPECS item 10; producers only): perforations whose drawdown is reversed inject the well bore's mixture"""
 
-    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil"):
+    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil", allow_crossflow=False):
         self.name, self.cells, self.tw = name, np.asarray(cells, np.int32), np.asarray(tw, float)
         self.ref_depth, self.producer, self.inj_phase = float(ref_depth), bool(producer), inj_phase
         self.preferred_phase = preferred_phase     # a producer's (WELSPECS item 6): the well bore's content where nothing flows (head_model="wellbore")
         self.control, self.bhp_limit = control, float(bhp_limit)
         self.rate_control = control       # the deck's rate target, kept for switching back from the BHP limit
+        self.allow_crossflow = bool(allow_crossflow)
+        _crossflow_flags([self])
 
 
 class CellRecords:
@@ -132,6 +154,14 @@ class CellRecords:
 
 def _rows(iq, cells):
     return iq.rows(cells) if isinstance(iq, CellRecords) else np.asarray(iq)[np.asarray(cells, int)]
+
+
+def _crossflow_flags(wells):
+    """per well: allow_crossflow; an injector with the switch is refused (see the module's text)"""
+    for w in wells:
+        if getattr(w, "allow_crossflow", False) and not w.producer:
+            raise ValueError("well %s: allow_crossflow on an injector is not modelled (the injected composition is fixed)" % w.name)
+    return np.array([bool(getattr(w, "allow_crossflow", False)) for w in wells], bool)
 
 
 class StandardWells:
@@ -158,9 +188,12 @@ class StandardWells:
         self.head_model, self.props = head_model, props
         self.wells = list(wells)
         self.nw = len(self.wells)
+        self.allow_crossflow = _crossflow_flags(self.wells)
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         self.tw = np.concatenate([w.tw for w in self.wells])
+        self._rate_dq = None                       # d rate_c / d q_j of the last _perf_rates, (nperf, 3, 3); None: no perforation crossflows
+        self.rate_dq = np.zeros((len(self.cells), 3, 3))   # ... of the last _assemble_wells, zeros without crossflow
         self.well_of_perf = np.repeat(np.arange(self.nw), np.diff(self.vp))
         # the cells the model is asked about / told about: every perforated cell once
         self.ucells, self.perf_row = np.unique(self.cells, return_inverse=True)
@@ -366,7 +399,9 @@ class StandardWells:
 
     # ---- connection rates of every perforation with their derivatives: (nperf, 3 components, 1 + 3 cell variables + bhp) ----------------
     def _perf_rates(self, iq, bhp):
-        """bhp: per well"""
+        """bhp: per well.  With crossflow the rates also depend on the wells' rate unknowns self.x[:, :3]: those derivatives, (nperf, 3
+        components, 3 unknowns), are left in self._rate_dq (None where no perforation crossflows)"""
+        self._rate_dq = None
         if self.head is None:
             self.calculate_explicit_quantities(iq)
         q = _rows(iq, self.cells)
@@ -404,8 +439,58 @@ class StandardWells:
                 sel = inj & np.array([w.inj_phase == name for w in self.wells])[self.well_of_perf]
                 if sel.any():
                     out[sel, comp] = mul(b[ph], vol)[sel]
-        # a perforation that would flow against the well's kind is closed (no crossflow)
+        # a perforation that would flow against the well's kind is closed, unless it is a producer's and the well allows crossflow
+        cross = producer & self.allow_crossflow[self.well_of_perf] & ~(dd[:, 0] > 0.0)
+        if cross.any():
+            self._crossflow_rates(np.flatnonzero(cross), dd, b, mob, rs, out)
         return out
+
+    def _crossflow_rates(self, sel, dd, b, mob, rs, out):
+        """the perforations `sel` of producers with the switch: the module's formulas on A8 arrays, into out and self._rate_dq"""
+        mix = np.zeros((self.nw, 3, 8))            # cmix_c of every well: value and d/dq
+        flowing = np.zeros(self.nw, bool)
+        for k in np.flatnonzero(self.allow_crossflow):
+            s = [bool(self.x[k, c] < 0.0) for c in range(3)]
+            p = [-float(self.x[k, c]) if s[c] else 0.0 for c in range(3)]
+            P = (p[OIL] + p[WATER]) + p[GAS]
+            if not P > 0.0:
+                continue                           # a well that has not flowed yet: its reversed perforations stay closed
+            flowing[k] = True
+            for c in range(3):
+                mix[k, c, 0] = p[c] / P
+                for j in range(3):
+                    if s[j]:
+                        mix[k, c, 5 + j] = -(((1.0 if c == j else 0.0) - mix[k, c, 0]) / P)
+        sel = sel[flowing[self.well_of_perf[sel]]]
+        if not len(sel):
+            return
+        wide = lambda a: np.concatenate([a[sel], np.zeros((len(sel), 3))], axis=1)
+
+        def mul(x, y):
+            o = np.empty_like(x)
+            o[:, 0] = x[:, 0] * y[:, 0]
+            o[:, 1:] = x[:, :1] * y[:, 1:] + y[:, :1] * x[:, 1:]
+            return o
+
+        def div(x, y):
+            o = np.empty_like(x)
+            o[:, 0] = x[:, 0] / y[:, 0]
+            o[:, 1:] = (x[:, 1:] - o[:, :1] * y[:, 1:]) / y[:, :1]
+            return o
+        cmix = [mix[self.well_of_perf[sel], c] for c in range(3)]
+        d8, b8, mob8, rs8 = wide(dd), [wide(v) for v in b], [wide(v) for v in mob], wide(rs)
+        cqt_i = -self.tw[sel, None] * mul((mob8[PH_W] + mob8[PH_O]) + mob8[PH_G], d8)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):      # rows that end closed below
+            ratio = (div(cmix[WATER], b8[PH_W]) + div(cmix[OIL], b8[PH_O])) + div(cmix[GAS] - mul(rs8, cmix[OIL]), b8[PH_G])
+            cqt_is = div(cqt_i, ratio)
+            rates = [mul(cmix[c], cqt_is) for c in range(3)]
+        ok = ratio[:, 0] > 0.0                     # a volume ratio that is not positive: closed for this evaluation
+        if not ok.any():
+            return
+        self._rate_dq = np.zeros((len(self.cells), 3, 3))
+        for c in range(3):
+            out[sel[ok], c] = rates[c][ok, :5]
+            self._rate_dq[sel[ok], c] = rates[c][ok, 5:]
 
     def _control_rows(self):
         """(residual, d/d(q_o, q_w, q_g, bhp)) of every well's control equation"""
@@ -449,6 +534,7 @@ class StandardWells:
     def _assemble_wells(self, iq):
         """residuals r_w (nw x 4), D (nw x 4 x 4), per perforation B (4 x 3: d r_w / d cell variables), C (4 x 3: C^T = d r_cell / d x_w),
         source (3) and dsource (3 x 3)"""
+        self._rate_dq = None
         pr = self._perf_rates(iq, self.x[:, 3])
         nperf = len(self.cells)
         r = np.zeros((self.nw, 4))
@@ -461,6 +547,11 @@ class StandardWells:
         r[:, :3] = self.x[:, :3] - sums          # surface rate - sum of the connection rates
         D[:, [0, 1, 2], [0, 1, 2]] = 1.0
         D[:, :3, 3] = -dsums
+        dq = self._rate_dq                       # crossflow: the connection rates answer to the well's own rate unknowns
+        if dq is not None:
+            flat = dq.reshape(nperf, 9)
+            qsums = sequential_sums(flat, self.vp) if self.arithmetic == "stated" else np.add.reduceat(flat, seg, axis=0)
+            D[:, :3, :3] = D[:, :3, :3] - qsums.reshape(self.nw, 3, 3)
         r[:, 3], D[:, 3, :] = self._control_rows()
         # a well none of whose completions flows (its bottom-hole pressure on the wrong side of every completion's pressure) has no rate that
         # answers to its bottom-hole pressure: under a rate target its equations would be singular.  It keeps its bottom-hole pressure for
@@ -471,6 +562,9 @@ class StandardWells:
         B, C = np.zeros((nperf, 4, 3)), np.zeros((nperf, 4, 3))
         B[:, :3, :] = -pr[:, :, 1:4]                 # d r_w[c] / d (Sw, p, X) of the perforated cell
         C[:, 3, :] = -pr[:, :, 4]                    # d r_cell[c] / d bhp = - d(connection rate) / d bhp
+        if dq is not None:
+            C[:, :3, :] = 0.0 - dq.transpose(0, 2, 1)    # C[j][c]: d r_cell[c] / d q_j
+        self.rate_dq = np.zeros((nperf, 3, 3)) if dq is None else dq
         return r, D, B, C, pr[:, :, 0], pr[:, :, 1:4]
 
     def solve_well_equations(self, iq, iterations=20):
@@ -557,7 +651,7 @@ class StandardWells:
 class DeviceStandardWells:
     """The same wells resident on the device (opmhip_set_std_wells): model is a capi.HipModel whose state is set.  The well unknowns, the
     controls, the heads and the blocks B, C, D^-1 live there; what this object holds of them (x, controls, res_well) is the last read-back
-    (fetch).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
+    (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
     def __init__(self, wells, cell_depth, model, head_model="cell_oil"):
@@ -569,6 +663,7 @@ class DeviceStandardWells:
         self.nw = len(self.wells)
         self.m = model
         self.head_model = head_model
+        self.allow_crossflow = _crossflow_flags(self.wells)
         phase = PHASE_BY_NAME
         depth = np.asarray(cell_depth, float)
         for w in self.wells:
@@ -586,6 +681,8 @@ class DeviceStandardWells:
             producer=[int(w.producer) for w in self.wells], inj_phase=[0 if w.producer else phase[w.inj_phase] for w in self.wells],
             rate_component=[w.rate_control[1] for w in self.wells], rate_target=[w.rate_control[2] for w in self.wells],
             bhp_limit=[w.bhp_limit for w in self.wells], control=[int(w.control[0] == "bhp") for w in self.wells], x=None))
+        if self.allow_crossflow.any():           # (a list without the switch makes the calls it made before)
+            model.set_std_wells_crossflow(self.allow_crossflow.astype(np.int32))
         if head_model == "wellbore":
             self._wellbore = dict(perf_depth=depth[self.cells], ref_depth=[w.ref_depth for w in self.wells],
                                   preferred_phase=[phase[w.preferred_phase] if w.producer else PH_O for w in self.wells])
