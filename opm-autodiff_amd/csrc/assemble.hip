@@ -217,10 +217,9 @@ template <class E, class DP> __device__ __forceinline__ void cap_pressures(const
 // The cache is stored FIELD-MAJOR: field f of cell c = the four doubles at iq[(f * ncell + c) * 4].  Lanes that walk
 // consecutive cells (the per-cell kernels) write and read contiguous memory, and the neighbours a tile of k_assemble
 // gathers - runs of consecutive cells of a few z-lines - share cache lines: 3.6x fewer L1 accesses than with per-cell
-// records, whose 544-byte stride gave every lane of a gather its own lines.
+// records, whose 544-byte stride gave every lane of a gather its own lines.  (F_S .. F_RS, the phases, the equations: internal.hpp)
 __device__ __forceinline__ const double* iq_at(const double* iq, int ncell, int f, int c) { return iq + ((size_t)f * ncell + c) * 4; }
 __device__ __forceinline__ double* iq_at(double* iq, int ncell, int f, int c) { return iq + ((size_t)f * ncell + c) * 4; }
-enum { F_S = 0, F_P = 3, F_B = 6, F_MOB = 9, F_RHO = 12, F_RS = 15 };
 template <bool EXT> struct Lay {
     static constexpr int F_RV = 16, F_TMULT = 17;                    // EXT only
     static constexpr int F_PORO = EXT ? 18 : 16;
@@ -229,9 +228,6 @@ template <bool EXT> struct Lay {
     static constexpr int RQ_F0 = F_P;                                // neighbour fields of the flux: p, 1/B, mobility, density, Rs [, Rv, tmult]
     static constexpr int RQ_NF = (EXT ? F_TMULT : F_RS) - F_P + 1;
 };
-enum { WATER = 0, OIL = 1, GAS = 2 };
-enum { EQ_OIL = 0, EQ_WATER = 1, EQ_GAS = 2 };
-constexpr double GRAVITY = 9.80665;
 
 template <class E>
 struct Iq {
@@ -1527,7 +1523,7 @@ void launch_aquifer_end(opmhip_ctx* c, double dt) {
 // ============================== standard wells on the device (opmhip_set_std_wells) ===========================
 // computePerfRate and assembleWellEqWithoutIteration (wells/StandardWell_impl.hpp:195-420, 516-640) in the minimal form and in the
 // operation order of wells.py StandardWells(arithmetic="stated") - the library is built with -ffp-contract=off, so that every
-// expression below rounds where its NumPy counterpart rounds.  A5: value, d/dSw, d/dp, d/dX of the perforated cell, d/dbhp.
+// expression below rounds where its NumPy counterpart rounds.  SwAd<5>: value, d/dSw, d/dp, d/dX of the perforated cell, d/dbhp.
 // Plain wave64 kernels; no atomics; every sum over perforations is added by one lane in perforation order.
 //
 // Crossflow in producers (opmhip_set_std_wells_crossflow, per well, off by default): the injecting branch of
@@ -1538,86 +1534,61 @@ void launch_aquifer_end(opmhip_ctx* c, double dt) {
 //     cqt_i = -tw * (((mob_w + mob_o) + mob_g) * dd)
 //     volumeRatio = (cmix_w / b_w + cmix_o / b_o) + (cmix_g - rs * cmix_o) / b_g            (b = 1/B of the perforated cell)
 //     cqt_is = cqt_i / volumeRatio;  rate_c = cmix_c * cqt_is
-// on A8 = value, d/dSw, d/dp, d/dX, d/dbhp, d/dq_o, d/dq_w, d/dq_g: a product is sw_mul (a0 b0; a0 b_i + b0 a_i), a quotient sw_div
+// on SwAd<8> = value, d/dSw, d/dp, d/dX, d/dbhp, d/dq_o, d/dq_w, d/dq_g: a product is sw_mul (a0 b0; a0 b_i + b0 a_i), a quotient sw_div
 // (v = a0 / b0; (a_i - v b_i) / b0), sums and differences entry by entry, in the order written.  P not > 0 (the well has not flowed
 // yet) or volumeRatio not > 0: the perforation stays closed for that evaluation - nothing is divided by zero or a negative.  Then
 // D[c][j] = delta_cj - sum_p d rate_c / d q_j and C[j][c] = 0 - d rate_c / d q_j; perforations with dd > 0 and wells without the switch
 // take the expressions below unchanged.  Left out: vaporised oil (rv = 0, d = 1, tmp_oil = cmix_o), openCrossFlowAvoidSingularity.
 // Injectors are refused: this parametrisation fixes the injected composition, where the reference re-injects what crosses in.
-struct A5 { double v[5]; };
-__device__ __forceinline__ A5 sw_load(const double* __restrict__ p) { return A5{{p[0], p[1], p[2], p[3], 0.0}}; }
-__device__ __forceinline__ A5 sw_mul(const A5& a, const A5& b) {   // the product rule of wells.py's `mul`
-    A5 o;
-    o.v[0] = a.v[0] * b.v[0];
+template <int N> struct SwAd { double v[N]; };
+template <int N> __device__ __forceinline__ SwAd<N> sw_load(const double* __restrict__ p) {   // a field of the record: no d/dbhp, no d/dq
+    SwAd<N> o;
 #pragma unroll
-    for (int i = 1; i < 5; ++i) o.v[i] = a.v[0] * b.v[i] + b.v[0] * a.v[i];
+    for (int i = 0; i < N; ++i) o.v[i] = i < 4 ? p[i] : 0.0;
     return o;
 }
-__device__ __forceinline__ A5 sw_scale(double s, const A5& a) { return A5{{s * a.v[0], s * a.v[1], s * a.v[2], s * a.v[3], s * a.v[4]}}; }
-__device__ __forceinline__ A5 sw_add(const A5& a, const A5& b) { return A5{{a.v[0] + b.v[0], a.v[1] + b.v[1], a.v[2] + b.v[2], a.v[3] + b.v[3], a.v[4] + b.v[4]}}; }
-__device__ __forceinline__ void sw_store(double* o, const A5& a) {
+template <int N> __device__ __forceinline__ SwAd<N> sw_mul(const SwAd<N>& a, const SwAd<N>& b) {   // the product rule of wells.py's `mul`
+    SwAd<N> o;
+    o.v[0] = a.v[0] * b.v[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i) o.v[i] = a.v[0] * b.v[i] + b.v[0] * a.v[i];
+    return o;
+}
+template <int N> __device__ __forceinline__ SwAd<N> sw_div(const SwAd<N>& a, const SwAd<N>& b) {   // wells.py's `div`
+    SwAd<N> o;
+    o.v[0] = a.v[0] / b.v[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i) o.v[i] = (a.v[i] - o.v[0] * b.v[i]) / b.v[0];
+    return o;
+}
+template <int N> __device__ __forceinline__ SwAd<N> sw_scale(double s, const SwAd<N>& a) {
+    SwAd<N> o;
+#pragma unroll
+    for (int i = 0; i < N; ++i) o.v[i] = s * a.v[i];
+    return o;
+}
+template <int N> __device__ __forceinline__ SwAd<N> sw_add(const SwAd<N>& a, const SwAd<N>& b) {
+    SwAd<N> o;
+#pragma unroll
+    for (int i = 0; i < N; ++i) o.v[i] = a.v[i] + b.v[i];
+    return o;
+}
+template <int N> __device__ __forceinline__ SwAd<N> sw_sub(const SwAd<N>& a, const SwAd<N>& b) {
+    SwAd<N> o;
+#pragma unroll
+    for (int i = 0; i < N; ++i) o.v[i] = a.v[i] - b.v[i];
+    return o;
+}
+template <int N> __device__ __forceinline__ void sw_store5(double* o, const SwAd<N>& a) {
 #pragma unroll
     for (int i = 0; i < 5; ++i) o[i] = a.v[i];
 }
-// the connection rates of one perforation into the reservoir, out[component * 5 + (value, d/dSw, d/dp, d/dX, d/dbhp)]
-__device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head, bool producer, int injPhase,
-                                              double* out) {
-#pragma unroll
-    for (int i = 0; i < 15; ++i) out[i] = 0.0;
-    A5 dd = sw_load(iq_at(iq, ncell, F_P + OIL, c));
-    dd.v[0] = dd.v[0] - (bhp + head);   // the head between the reference depth and the completion is explicit
+// the drawdown p_o - (bhp + head) with its derivatives, from the cell's oil pressure and the value dd0
+template <int N> __device__ __forceinline__ SwAd<N> sw_drawdown(const double* __restrict__ po, double dd0) {
+    SwAd<N> dd = sw_load<N>(po);
+    dd.v[0] = dd0;
     dd.v[4] = -1.0;
-    const double ntw = -tw;
-    if (producer) {   // phase rate = -Tw mob drawdown, surface volumes through 1/B, dissolved gas with the oil
-        if (!(dd.v[0] > 0.0)) return;   // no crossflow
-        A5 surf[3];
-#pragma unroll
-        for (int ph = 0; ph < 3; ++ph)
-            surf[ph] = sw_mul(sw_load(iq_at(iq, ncell, F_B + ph, c)), sw_scale(ntw, sw_mul(sw_load(iq_at(iq, ncell, F_MOB + ph, c)), dd)));
-        sw_store(out + EQ_OIL * 5, surf[OIL]);
-        sw_store(out + EQ_WATER * 5, surf[WATER]);
-        sw_store(out + EQ_GAS * 5, sw_add(surf[GAS], sw_mul(sw_load(iq_at(iq, ncell, F_RS, c)), surf[OIL])));
-    } else {          // total mobility, the injected phase's 1/B
-        if (!(dd.v[0] < 0.0)) return;
-        const A5 tot = sw_add(sw_add(sw_load(iq_at(iq, ncell, F_MOB + 0, c)), sw_load(iq_at(iq, ncell, F_MOB + 1, c))), sw_load(iq_at(iq, ncell, F_MOB + 2, c)));
-        const A5 vol = sw_scale(ntw, sw_mul(tot, dd));
-        const int comp = injPhase == GAS ? EQ_GAS : (injPhase == WATER ? EQ_WATER : EQ_OIL);
-        sw_store(out + comp * 5, sw_mul(sw_load(iq_at(iq, ncell, F_B + injPhase, c)), vol));
-    }
-}
-struct A8 { double v[8]; };
-__device__ __forceinline__ A8 sw_load8(const double* __restrict__ p) { return A8{{p[0], p[1], p[2], p[3], 0.0, 0.0, 0.0, 0.0}}; }
-__device__ __forceinline__ A8 sw_mul(const A8& a, const A8& b) {
-    A8 o;
-    o.v[0] = a.v[0] * b.v[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) o.v[i] = a.v[0] * b.v[i] + b.v[0] * a.v[i];
-    return o;
-}
-__device__ __forceinline__ A8 sw_div(const A8& a, const A8& b) {   // wells.py's `div`
-    A8 o;
-    o.v[0] = a.v[0] / b.v[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) o.v[i] = (a.v[i] - o.v[0] * b.v[i]) / b.v[0];
-    return o;
-}
-__device__ __forceinline__ A8 sw_scale(double s, const A8& a) {
-    A8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = s * a.v[i];
-    return o;
-}
-__device__ __forceinline__ A8 sw_add(const A8& a, const A8& b) {
-    A8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = a.v[i] + b.v[i];
-    return o;
-}
-__device__ __forceinline__ A8 sw_sub(const A8& a, const A8& b) {
-    A8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = a.v[i] - b.v[i];
-    return o;
+    return dd;
 }
 // the well bore's surface-volume fractions from the well's rate unknowns, mix[component * 4 + (value, d/dq_o, d/dq_w, d/dq_g)]
 // -> whether the well flows (P > 0)
@@ -1636,29 +1607,57 @@ __device__ bool sw_wellbore_fractions(const double* x, double* mix) {
     }
     return true;
 }
-// a reversed perforation of a producer with crossflow: out as sw_perf_rates', dq[component * 3 + (d/dq_o, d/dq_w, d/dq_g)]; both are
-// left alone where the volume ratio is not positive
-__device__ __forceinline__ void sw_crossflow_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head,
-                                                   const double* mix, double* out, double* dq) {
-    A8 dd = sw_load8(iq_at(iq, ncell, F_P + OIL, c));
-    dd.v[0] = dd.v[0] - (bhp + head);
-    dd.v[4] = -1.0;
-    A8 cm[3];
+// The connection rates of one perforation into the reservoir, out[component * 5 + (value, d/dSw, d/dp, d/dX, d/dbhp)], and under CF
+// dq[component * 3 + (d/dq_o, d/dq_w, d/dq_g)].  The drawdown decides, once: a perforation that flows the way of its well takes the
+// N = 5 arithmetic (dq = 0); one that does not stays closed - unless it is a producer's and `reverse` holds (the well has the crossflow
+// switch and flows: mix are its fractions), which takes the N = 8 branch, closed still where the volume ratio is not positive.
+template <bool CF>
+__device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head, bool producer, int injPhase,
+                                              bool reverse, const double* mix, double* out, double* dq) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) cm[k] = A8{{mix[k * 4], 0.0, 0.0, 0.0, 0.0, mix[k * 4 + 1], mix[k * 4 + 2], mix[k * 4 + 3]}};
-    const A8 tot = sw_add(sw_add(sw_load8(iq_at(iq, ncell, F_MOB + WATER, c)), sw_load8(iq_at(iq, ncell, F_MOB + OIL, c))), sw_load8(iq_at(iq, ncell, F_MOB + GAS, c)));
-    const A8 cqt_i = sw_scale(-tw, sw_mul(tot, dd));
-    const A8 ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load8(iq_at(iq, ncell, F_B + WATER, c))), sw_div(cm[EQ_OIL], sw_load8(iq_at(iq, ncell, F_B + OIL, c)))),
-                            sw_div(sw_sub(cm[EQ_GAS], sw_mul(sw_load8(iq_at(iq, ncell, F_RS, c)), cm[EQ_OIL])), sw_load8(iq_at(iq, ncell, F_B + GAS, c))));
-    if (!(ratio.v[0] > 0.0)) return;
-    const A8 cqt_is = sw_div(cqt_i, ratio);
+    for (int i = 0; i < 15; ++i) out[i] = 0.0;
+    if (CF) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const A8 r = sw_mul(cm[k], cqt_is);
+        for (int i = 0; i < 9; ++i) dq[i] = 0.0;
+    }
+    const double* po = iq_at(iq, ncell, F_P + OIL, c);
+    const double dd0 = po[0] - (bhp + head);   // the head between the reference depth and the completion is explicit
+    const double ntw = -tw;
+    if (producer ? dd0 > 0.0 : dd0 < 0.0) {
+        const SwAd<5> dd = sw_drawdown<5>(po, dd0);
+        if (producer) {   // phase rate = -Tw mob drawdown, surface volumes through 1/B, dissolved gas with the oil
+            SwAd<5> surf[3];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) out[k * 5 + i] = r.v[i];
+            for (int ph = 0; ph < 3; ++ph)
+                surf[ph] = sw_mul(sw_load<5>(iq_at(iq, ncell, F_B + ph, c)), sw_scale(ntw, sw_mul(sw_load<5>(iq_at(iq, ncell, F_MOB + ph, c)), dd)));
+            sw_store5(out + EQ_OIL * 5, surf[OIL]);
+            sw_store5(out + EQ_WATER * 5, surf[WATER]);
+            sw_store5(out + EQ_GAS * 5, sw_add(surf[GAS], sw_mul(sw_load<5>(iq_at(iq, ncell, F_RS, c)), surf[OIL])));
+        } else {          // total mobility, the injected phase's 1/B
+            const SwAd<5> tot = sw_add(sw_add(sw_load<5>(iq_at(iq, ncell, F_MOB + 0, c)), sw_load<5>(iq_at(iq, ncell, F_MOB + 1, c))), sw_load<5>(iq_at(iq, ncell, F_MOB + 2, c)));
+            const SwAd<5> vol = sw_scale(ntw, sw_mul(tot, dd));
+            const int comp = injPhase == GAS ? EQ_GAS : (injPhase == WATER ? EQ_WATER : EQ_OIL);
+            sw_store5(out + comp * 5, sw_mul(sw_load<5>(iq_at(iq, ncell, F_B + injPhase, c)), vol));
+        }
+    } else if (CF && producer && reverse) {
+        typedef SwAd<8> A8;   // value, d/dSw, d/dp, d/dX, d/dbhp, d/dq_o, d/dq_w, d/dq_g
+        const A8 dd = sw_drawdown<8>(po, dd0);
+        A8 cm[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) dq[k * 3 + j] = r.v[5 + j];
+        for (int k = 0; k < 3; ++k) cm[k] = A8{{mix[k * 4], 0.0, 0.0, 0.0, 0.0, mix[k * 4 + 1], mix[k * 4 + 2], mix[k * 4 + 3]}};
+        const A8 tot = sw_add(sw_add(sw_load<8>(iq_at(iq, ncell, F_MOB + WATER, c)), sw_load<8>(iq_at(iq, ncell, F_MOB + OIL, c))), sw_load<8>(iq_at(iq, ncell, F_MOB + GAS, c)));
+        const A8 cqt_i = sw_scale(ntw, sw_mul(tot, dd));
+        const A8 ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load<8>(iq_at(iq, ncell, F_B + WATER, c))), sw_div(cm[EQ_OIL], sw_load<8>(iq_at(iq, ncell, F_B + OIL, c)))),
+                                sw_div(sw_sub(cm[EQ_GAS], sw_mul(sw_load<8>(iq_at(iq, ncell, F_RS, c)), cm[EQ_OIL])), sw_load<8>(iq_at(iq, ncell, F_B + GAS, c))));
+        if (!(ratio.v[0] > 0.0)) return;
+        const A8 cqt_is = sw_div(cqt_i, ratio);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const A8 r = sw_mul(cm[k], cqt_is);
+            sw_store5(out + k * 5, r);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dq[k * 3 + j] = r.v[5 + j];
+        }
     }
 }
 // wells.py invert4_stated: Gauss-Jordan on [D | I], partial pivoting (largest |entry| of the column, lowest row on ties), the pivot row
@@ -1690,11 +1689,12 @@ struct SwArrays {
     int num;
     const int *vp, *cell, *wi;                  // perforation ranges, perforated cells (internal positions), per well: producer, injected phase, rate component
     const double *wd, *tw, *dz;                 // per well: rate target, bhp limit; per perforation
-    double *head, *pr, *pack, *Dmat, *B, *C, *Dinv;
+    double *head, *pr, *x, *Dmat, *B, *C, *Dinv;   // x: the well unknowns, 4 per well
     int wellbore, nperf;                        // the heads come from the well-bore density (k_std_wells_wellbore); all perforations of the list
     double* wbstate;                            // then: p_perf [nperf] | the rates of the last assembly [nperf * 3]
     const int* cf;                              // per well: crossflow allowed (read by the CF instantiations only; NULL without a flag)
     double* dq;                                 // then: d rate_c / d q_j of the last assembly [nperf * 9]
+    double *control, *rw, *flag;                // d_pack's other fields: per well 0.0 rate / 1.0 bhp; r_w, 4 per well; the zero-pivot flag
 };
 // One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
 // global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
@@ -1715,8 +1715,8 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
     const int pb = W.vp[w], pe = W.vp[w + 1];
     const bool producer = W.wi[3 * w] != 0;
     const int injPhase = W.wi[3 * w + 1], comp = W.wi[3 * w + 2];
-    double* x = W.pack + (size_t)4 * w;
-    double* flag = W.pack + (size_t)9 * W.num + w;
+    double* x = W.x + (size_t)4 * w;
+    double* flag = W.flag + w;
     if (SOLVE && !W.wellbore)   // calculate_explicit_quantities: (rho_o g) dz, constant through the time step; lane l owns perforations pb + l + 64 k here and below
         for (int p = pb + lane; p < pe; p += 64) W.head[p] = (iq_at(iq, ncell, F_RHO + OIL, W.cell[p])[0] * GRAVITY) * W.dz[p];
     if (lane == 0) {
@@ -1736,14 +1736,9 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
         for (int p0 = pb; p0 < pe; p0 += 64) {
             const int p = p0 + lane;
             if (p < pe) {
-                double q[15];
-                sw_perf_rates(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, q);
-                double dq[CF ? 9 : 1];
+                double q[15], dq[CF ? 9 : 1];
+                sw_perf_rates<CF>(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, crossflow && s_flows, s_mix, q, dq);
                 if (CF) {
-#pragma unroll
-                    for (int i = 0; i < 9; ++i) dq[i] = 0.0;
-                    if (crossflow && producer && s_flows && !(iq_at(iq, ncell, F_P + OIL, W.cell[p])[0] - (bhp + W.head[p]) > 0.0))
-                        sw_crossflow_rates(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], s_mix, q, dq);
 #pragma unroll
                     for (int i = 0; i < 9; ++i) sums[lane * NS + 6 + i] = dq[i];
                 }
@@ -1787,7 +1782,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
             if (CF)
                 for (int c = 0; c < 3; ++c)
                     for (int j = 0; j < 3; ++j) D[c * 4 + j] = D[c * 4 + j] - S[6 + c * 3 + j];
-            if (W.pack[(size_t)4 * W.num + w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
+            if (W.control[w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
             else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
             // a well none of whose completions flows has no rate that answers to its bottom-hole pressure: it keeps the pressure
             if (D[3] == 0.0 && D[7] == 0.0 && D[11] == 0.0 && D[15] == 0.0) { r[3] = 0.0; D[12] = D[13] = D[14] = 0.0; D[15] = 1.0; }
@@ -1808,7 +1803,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
                     s_active = small ? 0 : 1;
                 }
             } else {
-                for (int i = 0; i < 4; ++i) W.pack[(size_t)5 * W.num + 4 * w + i] = r[i];
+                for (int i = 0; i < 4; ++i) W.rw[(size_t)4 * w + i] = r[i];
                 for (int i = 0; i < 16; ++i) { W.Dmat[(size_t)16 * w + i] = D[i]; W.Dinv[(size_t)16 * w + i] = inv[i]; }   // a singular D: zeros, never NaNs
             }
         }
@@ -1847,7 +1842,7 @@ __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays 
     const size_t np = W.nperf;
     const bool producer = W.wi[3 * w] != 0;
     const int injPhase = W.wi[3 * w + 1];
-    const double* x = W.pack + (size_t)4 * w;
+    const double* x = W.x + (size_t)4 * w;
     double* pp = W.wbstate;
     double* qs = W.wbstate + np;
     double* sc = pe - pb <= 64 ? rec : Q.scratch + (size_t)WB_REC * pb;
@@ -1951,14 +1946,15 @@ __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays 
     }
 }
 // update_well_controls, one lane per well
-__global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ pack) {
+__global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ xs,
+                                                           double* __restrict__ controls) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= num) return;
     const bool producer = wi[3 * w] != 0;
     const int comp = wi[3 * w + 2];
     const double target = wd[2 * w], limit = wd[2 * w + 1];
-    double* x = pack + (size_t)4 * w;
-    double* control = pack + (size_t)4 * num + w;
+    double* x = xs + (size_t)4 * w;
+    double* control = controls + w;
     if (*control == 0.0) {
         if ((producer && x[3] < limit) || (!producer && x[3] > limit)) { *control = 1.0; x[3] = limit; }
     } else if ((producer ? -1.0 : 1.0) * x[comp] > target) *control = 0.0;
@@ -2001,8 +1997,8 @@ __global__ __launch_bounds__(64) void k_std_wells_axpy(int n, double relax, cons
 }
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
-    return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.d_pack, S.d_Dmat, W.d_B, W.d_C, W.d_D,
-                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate, S.d_cf, S.d_dq};
+    return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.x(), S.d_Dmat, W.d_B, W.d_C, W.d_D,
+                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate, S.d_cf, S.d_dq, S.control(), S.rw(), S.flag()};
 }
 // (booked under the profile's assembly class, one scope per function: a context with a list shows them in opmhip_profile_get)
 void launch_std_wells_solve(opmhip_ctx* c, bool first) {
@@ -2023,7 +2019,7 @@ void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
 void launch_std_wells_controls(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(k_std_wells_controls, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.d_pack);
+    hipLaunchKernelGGL(k_std_wells_controls, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control());
     prof_end(c, ps);
 }
 void launch_std_wells_assemble(opmhip_ctx* c) {
@@ -2044,7 +2040,7 @@ void launch_std_wells_restore(opmhip_ctx* c) {
 void launch_std_wells_axpy(opmhip_ctx* c, double relax) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(k_std_wells_axpy, dim3((4 * S.num + 63) / 64), dim3(64), 0, c->stream, 4 * S.num, relax, c->wells.d_xw, S.d_pack);
+    hipLaunchKernelGGL(k_std_wells_axpy, dim3((4 * S.num + 63) / 64), dim3(64), 0, c->stream, 4 * S.num, relax, c->wells.d_xw, S.x());
     prof_end(c, ps);
 }
 

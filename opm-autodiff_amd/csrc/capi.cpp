@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstring>
 #include <new>
+#include <optional>
 
 #include "internal.hpp"
 
@@ -461,9 +462,10 @@ int opmhip_solve_system(opmhip_ctx* c, int N, int nnz, int dim, double* vals, co
         }
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         if ((rc = ms_wells_check(c))) return rc;   // a device-resident multisegment list whose D turned out singular
-        if (c->wells.sw.num > 0) {                 // the resident standard wells: B, C, D^-1 as the last assemble formed them, in operator form
+        std::optional<StdWellsOperatorForm> form;   // the resident standard wells: B, C, D^-1 as the last assemble formed them, in operator form
+        if (c->wells.sw.num > 0) {
             if ((rc = std_wells_check(c, c->wells.sw.h_flag.data()))) return rc;
-            c->wells.num_wells = c->wells.sw.num; c->wells.nperf = c->wells.sw.nperf; c->wells.distributed = false;
+            form.emplace(c->wells);
         }
         const double t1 = now();
         FactorRider rider;   // CPR: weights and level 0's values of the pressure hierarchy are formed while the rows are in LDS

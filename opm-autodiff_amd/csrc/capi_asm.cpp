@@ -5,14 +5,20 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "fluid_tables.hpp"
 #include "internal.hpp"
+#include "source_lists.hpp"
 
 using namespace opmhip;
 
 namespace {
+
+// the resident standard wells' part of opmhip_advance_time_level / opmhip_update_failed (beside the other well functions, below)
+int std_wells_save_state(opmhip_ctx* c);
+int std_wells_restore_state(opmhip_ctx* c);
 
 template <class F>
 int guarded(opmhip_ctx* c, F&& f) {
@@ -499,14 +505,7 @@ int opmhip_advance_time_level(opmhip_ctx* c) {
         // ghost cells included: a later update_failed needs no communication
         OPMHIP_HIP(c, hipMemcpyAsync(A.d_pv_prev, A.d_pv, (size_t)c->pat.Nloc * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         OPMHIP_HIP(c, hipMemcpyAsync(A.d_meaning_prev, A.d_meaning, (size_t)c->pat.Nloc, hipMemcpyDeviceToDevice, c->stream));
-        if (c->wells.sw.num > 0)   // resident standard wells: the well state of the last accepted step (x | control)
-            OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_saved, c->wells.sw.d_pack, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        if (c->wells.sw.wellbore) {   // ... and the perforation pressures and stored rates the next heads are formed from
-            StdWellsDev& S = c->wells.sw;
-            OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbsaved, S.d_wbstate, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            S.wb_state_saved = S.wb_state_set;
-            S.wb_initialised_saved = S.initialised;
-        }
+        if (int rc = std_wells_save_state(c)) return rc;
         A.prev_set = true;
         return OPMHIP_SUCCESS;
     });
@@ -540,16 +539,7 @@ int opmhip_update_failed(opmhip_ctx* c) {
         OPMHIP_HIP(c, hipMemsetAsync(A.d_wasSwitched, 0, c->pat.Nloc, c->stream));
         launch_iq_update(c);
         OPMHIP_HIP(c, hipGetLastError());
-        if (c->wells.sw.num > 0) {
-            OPMHIP_HIP(c, hipMemcpyAsync(c->wells.sw.d_pack, c->wells.sw.d_saved, (size_t)5 * c->wells.sw.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            c->wells.sw.assembled = false;
-        }
-        if (c->wells.sw.wellbore) {
-            StdWellsDev& S = c->wells.sw;
-            OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbstate, S.d_wbsaved, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            S.wb_state_set = S.wb_state_saved;
-            S.initialised = S.wb_initialised_saved;   // a first step given up: the retry takes the bottom-hole pressures from the cells again, as a run that never tried it
-        }
+        if (int rc = std_wells_restore_state(c)) return rc;
         A.assembled = false;
         return OPMHIP_SUCCESS;
     });
@@ -1009,20 +999,6 @@ void aquifers_release(opmhip_ctx* c) {   // the stream is idle
     Q.stepped = false;
     Q.h_ptr.clear(); Q.h_id.clear(); Q.h_tabptr.clear(); Q.h_par.clear(); Q.h_td.clear(); Q.h_pd.clear();
 }
-// opm-common's linearInterpolation / linearInterpolationDerivative (not in the reference tree: restated, UNVERIFIED): the interval
-// j with x[j] <= xv, the first / last interval outside the table (linear extrapolation); value = slope * (xv - x[j]) + y[j]
-int table_interval(const double* x, int n, double xv) {
-    const int j = (int)(std::upper_bound(x, x + n, xv) - x) - 1;
-    return std::min(std::max(j, 0), n - 2);
-}
-double table_slope(const double* x, const double* y, int n, double xv) {
-    const int j = table_interval(x, n, xv);
-    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]);
-}
-double table_value(const double* x, const double* y, int n, double xv) {
-    const int j = table_interval(x, n, xv);
-    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]) * (xv - x[j]) + y[j];
-}
 }  // namespace
 
 int opmhip_set_aquifers(opmhip_ctx* c, const opmhip_aquifers* aq) {
@@ -1040,84 +1016,21 @@ int opmhip_set_aquifers(opmhip_ctx* c, const opmhip_aquifers* aq) {
         if (c->comm.nranks > 1)
             return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: decomposed context (%d ranks) - alphai_, the equilibrium pressure and W_flux_ are sums over the ranks, which is not built", c->comm.nranks);
         const int na = aq->num_aquifers;
-        if (na < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: num_aquifers = %d", na);
-        if (!aq->type || !aq->id || !aq->conn_pointers || !aq->time_constant || !aq->water_density || !aq->datum_depth)
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (type, id, conn_pointers, time_constant, water_density, datum_depth are mandatory)");
-        if (aq->conn_pointers[0] != 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: conn_pointers[0] = %d, not 0", aq->conn_pointers[0]);
-        bool anyCT = false, anyFet = false;
-        for (int a = 0; a < na; ++a) {
-            if (aq->conn_pointers[a + 1] < aq->conn_pointers[a]) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: conn_pointers descend at aquifer %d", a);
-            if (aq->type[a] != 0 && aq->type[a] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: type[%d] = %d (0 Carter-Tracy, 1 Fetkovich)", a, aq->type[a]);
-            if (aq->type[a] == 0 && anyFet) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: Carter-Tracy aquifer %d behind a Fetkovich one (Carter-Tracy first: the order of addToSource)", a);
-            (aq->type[a] == 0 ? anyCT : anyFet) = true;
-        }
-        const int nc = aq->conn_pointers[na];
-        if (nc > 0 && (!aq->cell || !aq->alpha)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (cell / alpha)");
-        if (anyCT && (!aq->influx_constant || !aq->table_pointers || !aq->td || !aq->pd))
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (a Carter-Tracy aquifer needs influx_constant, table_pointers, td, pd)");
-        if (anyFet && (!aq->prod_index || !aq->total_compr || !aq->initial_watvolume))
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (a Fetkovich aquifer needs prod_index, total_compr, initial_watvolume)");
-        if (aq->has_restart && (!aq->restart_W_flux || (anyFet && !aq->restart_pressure)))
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (has_restart without restart_W_flux / restart_pressure)");
-        std::vector<double> par((size_t)na * AQ_PAR, 0.0), td, pd;
-        std::vector<int> tabptr(na + 1, 0), need_eq;
-        for (int a = 0; a < na; ++a) {
-            double* p = &par[(size_t)a * AQ_PAR];
-            if (!(aq->time_constant[a] > 0.0)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: aquifer %d has time constant Tc = %g, must be positive", a, aq->time_constant[a]);
-            const bool has_p = !aq->has_initial_pressure || aq->has_initial_pressure[a];
-            if (has_p && !aq->initial_pressure) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: null array (initial_pressure)");
-            const bool restart = aq->has_restart && aq->has_restart[a];
-            p[AQ_TYPE] = aq->type[a]; p[AQ_TC] = aq->time_constant[a]; p[AQ_RHOW] = aq->water_density[a]; p[AQ_DATUM] = aq->datum_depth[a];
-            p[AQ_PA0] = has_p ? aq->initial_pressure[a] : 0.0;
-            if (!has_p) need_eq.push_back(a);
-            tabptr[a + 1] = tabptr[a];
-            if (aq->type[a] == 0) {
-                if (restart) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: restart data for Carter-Tracy aquifer %d - restart-based initialisation is not supported for Carter-Tracy aquifers (as in the reference)", a);
-                p[AQ_BETA] = aq->influx_constant[a];
-                const int t0 = aq->table_pointers[a], t1 = aq->table_pointers[a + 1];
-                if (t0 < 0 || t1 - t0 < 2) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: the influence table of aquifer %d has fewer than two nodes", a);
-                for (int i = t0 + 1; i < t1; ++i)
-                    if (!(aq->td[i] > aq->td[i - 1])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: the influence table of aquifer %d is not ascending at node %d", a, i - t0);
-                td.insert(td.end(), aq->td + t0, aq->td + t1);
-                pd.insert(pd.end(), aq->pd + t0, aq->pd + t1);
-                tabptr[a + 1] = (int)td.size();
-            } else {
-                p[AQ_PI] = aq->prod_index[a];
-                p[AQ_CV] = aq->total_compr[a] * aq->initial_watvolume[a];
-                if (!(p[AQ_CV] > 0.0)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: Fetkovich aquifer %d has total_compr * initial_watvolume = %g, must be positive", a, p[AQ_CV]);
-            }
-        }
-        // connections; the distinct connected cells, each with its connections in aquifer order (= ascending connection number)
-        std::vector<int> of(nc), pos(nc), cpos, cptr, cconn(nc);
-        {
-            std::vector<int> seen(P.Nb, -1), slot(P.Nb, -1), count;
-            for (int a = 0; a < na; ++a)
-                for (int i = aq->conn_pointers[a]; i < aq->conn_pointers[a + 1]; ++i) {
-                    const int cell = aq->cell[i];
-                    if (cell < 0 || cell >= P.Nb) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: connection %d of aquifer %d names cell %d, outside [0, %d)", i - aq->conn_pointers[a], a, cell, P.Nb);
-                    if (seen[cell] == a) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_aquifers: cell %d is repeated within aquifer %d (one connection per cell)", cell, a);
-                    seen[cell] = a;
-                    of[i] = a;
-                    pos[i] = P.toOrder[cell];
-                    if (slot[cell] < 0) { slot[cell] = (int)cpos.size(); cpos.push_back(pos[i]); count.push_back(0); }
-                    count[slot[cell]]++;
-                }
-            cptr.assign(cpos.size() + 1, 0);
-            for (size_t t = 0; t < cpos.size(); ++t) cptr[t + 1] = cptr[t] + count[t];
-            std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-            for (int i = 0; i < nc; ++i) cconn[fill[slot[aq->cell[i]]]++] = i;
-        }
+        AquiferLists H;
+        std::string msg;
+        if (int r = aquifer_lists(aq, P.Nb, P.toOrder.data(), H, msg)) return fail(c, r, "%s", msg.c_str());
+        const int nc = H.nc;
         // calculateReservoirEquilibrium (AquiferInterface.hpp:330-373) for the aquifers without an initial pressure
-        if (!need_eq.empty()) {
+        if (!H.need_eq.empty()) {
             const int IQS = iq_doubles_per_cell(c);
             std::vector<double> depth(P.Nloc), rec;
             OPMHIP_HIP(c, hipMemcpy(depth.data(), A.d_depth, depth.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (int a : need_eq) {
+            for (int a : H.need_eq) {
                 const int i0 = aq->conn_pointers[a], n = aq->conn_pointers[a + 1] - i0;
                 std::vector<int> order(n), p(n);
                 for (int i = 0; i < n; ++i) order[i] = i0 + i;
                 std::sort(order.begin(), order.end(), [&](int x, int y) { return aq->cell[x] < aq->cell[y]; });   // the element loop
-                for (int i = 0; i < n; ++i) p[i] = pos[order[i]];
+                for (int i = 0; i < n; ++i) p[i] = H.pos[order[i]];
                 rec.resize((size_t)n * IQS);
                 if (n > 0) {
                     int rc = stage_cell_positions(c, p);
@@ -1127,32 +1040,20 @@ int opmhip_set_aquifers(opmhip_ctx* c, const opmhip_aquifers* aq) {
                     OPMHIP_HIP(c, hipMemcpyAsync(rec.data(), A.d_stage_cell, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
                     OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
                 }
-                const double datum = aq->datum_depth[a];
-                double sumAlpha = 0.0, sumPw = 0.0;
-                for (int i = i0; i < i0 + n; ++i) sumAlpha += aq->alpha[i];
-                for (int i = 0; i < n; ++i) {
-                    const double pw = rec[(size_t)i * IQS + 4 * 3], rho = rec[(size_t)i * IQS + 4 * 12];   // fields p_w, rho_w of the record
-                    const double gdz = 9.80665 * (depth[p[i]] - datum);   // the assembly's gravity constant (assemble.hip GRAVITY)
-                    sumPw += aq->alpha[order[i]] * (pw - rho * gdz);
-                }
-                par[(size_t)a * AQ_PAR + AQ_PA0] = sumPw / sumAlpha;
+                H.par[(size_t)a * AQ_PAR + AQ_PA0] = aquifer_equilibrium_pressure(aq->alpha, i0, n, order.data(), rec.data(), IQS, depth.data(), p.data(), aq->datum_depth[a]);
             }
         }
-        std::vector<double> state((size_t)na * AQ_STATE, 0.0);
-        for (int a = 0; a < na; ++a) {
-            const bool restart = aq->has_restart && aq->has_restart[a];
-            state[(size_t)a * AQ_STATE + AQ_WFLUX] = restart ? aq->restart_W_flux[a] : 0.0;
-            state[(size_t)a * AQ_STATE + AQ_AUX] = aq->type[a] == 0 ? 0.0 : (restart ? aq->restart_pressure[a] : par[(size_t)a * AQ_PAR + AQ_PA0]);
-        }
+        std::vector<double> state;
+        aquifer_initial_state(aq, H.par, state);
         const int rc = [&]() -> int {
             int r;
             const std::vector<int> ptr(aq->conn_pointers, aq->conn_pointers + na + 1);
             const std::vector<double> alpha(aq->alpha, aq->alpha + nc), zc((size_t)4 * std::max(nc, 1), 0.0);
-            if ((r = dev_upload(c, &Q.d_ptr, ptr)) || (r = dev_upload(c, &Q.d_of, of)) || (r = dev_upload(c, &Q.d_pos, pos)) || (r = dev_upload(c, &Q.d_alpha, alpha)) ||
-                (r = dev_upload(c, &Q.d_par, par)) || (r = dev_upload(c, &Q.d_state, state)) || (r = dev_upload(c, &Q.d_q, zc)) ||
-                (r = dev_upload(c, &Q.d_cpos, cpos)) || (r = dev_upload(c, &Q.d_cptr, cptr)) || (r = dev_upload(c, &Q.d_cconn, cconn)))
+            if ((r = dev_upload(c, &Q.d_ptr, ptr)) || (r = dev_upload(c, &Q.d_of, H.of)) || (r = dev_upload(c, &Q.d_pos, H.pos)) || (r = dev_upload(c, &Q.d_alpha, alpha)) ||
+                (r = dev_upload(c, &Q.d_par, H.par)) || (r = dev_upload(c, &Q.d_state, state)) || (r = dev_upload(c, &Q.d_q, zc)) ||
+                (r = dev_upload(c, &Q.d_cpos, H.cpos)) || (r = dev_upload(c, &Q.d_cptr, H.cptr)) || (r = dev_upload(c, &Q.d_cconn, H.cconn)))
                 return r;
-            if ((r = dev_alloc(c, &Q.d_pprev, (size_t)nc)) || (r = dev_alloc(c, &Q.d_step, (size_t)na * AQ_STEP)) || (r = dev_alloc(c, &Q.d_save, cpos.size() * 4))) return r;
+            if ((r = dev_alloc(c, &Q.d_pprev, (size_t)nc)) || (r = dev_alloc(c, &Q.d_step, (size_t)na * AQ_STEP)) || (r = dev_alloc(c, &Q.d_save, H.cpos.size() * 4))) return r;
             OPMHIP_HIP(c, hipMemset(Q.d_pprev, 0, (size_t)std::max(nc, 1) * sizeof(double)));
             OPMHIP_HIP(c, hipMemset(Q.d_step, 0, (size_t)na * AQ_STEP * sizeof(double)));
             OPMHIP_HIP(c, hipHostMalloc((void**)&Q.h_step, (size_t)na * AQ_STEP * sizeof(double), hipHostMallocDefault));
@@ -1161,10 +1062,10 @@ int opmhip_set_aquifers(opmhip_ctx* c, const opmhip_aquifers* aq) {
             return OPMHIP_SUCCESS;
         }();
         if (rc) { aquifers_release(c); return rc; }
-        Q.num = na; Q.nc = nc; Q.nd = (int)cpos.size();
+        Q.num = na; Q.nc = nc; Q.nd = (int)H.cpos.size();
         Q.h_ptr.assign(aq->conn_pointers, aq->conn_pointers + na + 1);
         Q.h_id.assign(aq->id, aq->id + na);
-        Q.h_par = par; Q.h_tabptr = tabptr; Q.h_td = td; Q.h_pd = pd;
+        Q.h_par = H.par; Q.h_tabptr = H.tabptr; Q.h_td = H.td; Q.h_pd = H.pd;
         return OPMHIP_SUCCESS;
     });
 }
@@ -1177,21 +1078,7 @@ int opmhip_aquifers_begin_time_step(opmhip_ctx* c, double time, double dt) {
         if (!(dt > 0.0) || !std::isfinite(time)) return fail(c, OPMHIP_INVALID_ARGUMENT, "aquifers_begin_time_step: dt must be positive, time finite");
         OPMHIP_HIP(c, hipSetDevice(c->device));
         if (Q.stepped) OPMHIP_HIP(c, hipEventSynchronize(Q.ev_step));   // the last call's copy has read the staging area
-        for (int a = 0; a < Q.num; ++a) {
-            const double* p = &Q.h_par[(size_t)a * AQ_PAR];
-            double* s = Q.h_step + (size_t)a * AQ_STEP;
-            s[AQ_TD] = s[AQ_PITD] = s[AQ_PITDPRIME] = s[AQ_COEF] = 0.0;
-            if (p[AQ_TYPE] == 0.0) {   // calculateEqnConstants (AquiferCarterTracy.hpp:150-153)
-                const double td_plus_dt = (dt + time) / p[AQ_TC];
-                const int t0 = Q.h_tabptr[a], n = Q.h_tabptr[a + 1] - t0;
-                s[AQ_TD] = time / p[AQ_TC];
-                s[AQ_PITD] = table_value(&Q.h_td[t0], &Q.h_pd[t0], n, td_plus_dt);
-                s[AQ_PITDPRIME] = table_slope(&Q.h_td[t0], &Q.h_pd[t0], n, td_plus_dt);
-            } else {                   // AquiferFetkovich.hpp:143-144
-                const double td_Tc = dt / p[AQ_TC];
-                s[AQ_COEF] = (1 - std::exp(-td_Tc)) / td_Tc;
-            }
-        }
+        aquifer_step_scalars(Q.num, Q.h_par, Q.h_tabptr, Q.h_td, Q.h_pd, time, dt, Q.h_step);
         OPMHIP_HIP(c, hipMemcpyAsync(Q.d_step, Q.h_step, (size_t)Q.num * AQ_STEP * sizeof(double), hipMemcpyHostToDevice, c->stream));
         OPMHIP_HIP(c, hipEventRecord(Q.ev_step, c->stream));
         if (Q.nc > 0) launch_aquifer_begin(c);
@@ -1212,17 +1099,7 @@ int opmhip_get_aquifers(opmhip_ctx* c, double* W_flux, double* pressure, double*
         std::vector<double> state((size_t)Q.num * AQ_STATE), q((size_t)4 * std::max(Q.nc, 1));
         OPMHIP_HIP(c, hipMemcpy(state.data(), Q.d_state, state.size() * sizeof(double), hipMemcpyDeviceToHost));
         if (flux_rate) OPMHIP_HIP(c, hipMemcpy(q.data(), Q.d_q, q.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int a = 0; a < Q.num; ++a) {
-            const double* p = &Q.h_par[(size_t)a * AQ_PAR];
-            if (W_flux) W_flux[a] = state[(size_t)a * AQ_STATE + AQ_WFLUX];
-            if (pressure) pressure[a] = p[AQ_TYPE] == 0.0 ? p[AQ_PA0] : state[(size_t)a * AQ_STATE + AQ_AUX];
-            if (init_pressure) init_pressure[a] = p[AQ_PA0];
-            if (flux_rate) {
-                double f = 0.0;
-                for (int i = Q.h_ptr[a]; i < Q.h_ptr[a + 1]; ++i) f += q[(size_t)4 * i];
-                flux_rate[a] = f;
-            }
-        }
+        aquifer_report(Q.num, Q.h_par, Q.h_ptr, state.data(), q.data(), W_flux, pressure, flux_rate, init_pressure);
         return OPMHIP_SUCCESS;
     });
 }
@@ -1257,9 +1134,35 @@ void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     dev_free(c, &S.d_cf); dev_free(c, &S.d_dq);
     S.crossflow = false;
     std_wells_wellbore_release(c);
+    S.h_wi.clear(); S.h_wd.clear();
     S.num = S.nperf = S.nd = 0;
     S.initialised = S.assembled = false;
     c->wells.num_wells = 0;   // no operator form of the list left behind for later products
+}
+// On the context's stream, in the order of the callers' other copies.  The well state of the last accepted step (x | control) and, under
+// the well-bore head model, the perforation pressures and stored rates the next heads are formed from
+int std_wells_save_state(opmhip_ctx* c) {
+    StdWellsDev& S = c->wells.sw;
+    if (S.num > 0) OPMHIP_HIP(c, hipMemcpyAsync(S.d_saved, S.d_pack, (size_t)SW_SAVED * S.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (S.wellbore) {
+        OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbsaved, S.d_wbstate, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        S.wb_state_saved = S.wb_state_set;
+        S.wb_initialised_saved = S.initialised;
+    }
+    return OPMHIP_SUCCESS;
+}
+int std_wells_restore_state(opmhip_ctx* c) {
+    StdWellsDev& S = c->wells.sw;
+    if (S.num > 0) {
+        OPMHIP_HIP(c, hipMemcpyAsync(S.d_pack, S.d_saved, (size_t)SW_SAVED * S.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        S.assembled = false;
+    }
+    if (S.wellbore) {
+        OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbstate, S.d_wbsaved, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        S.wb_state_set = S.wb_state_saved;
+        S.initialised = S.wb_initialised_saved;   // a first step given up: the retry takes the bottom-hole pressures from the cells again, as a run that never tried it
+    }
+    return OPMHIP_SUCCESS;
 }
 }  // namespace
 
@@ -1295,47 +1198,10 @@ int opmhip_set_std_wells(opmhip_ctx* c, const opmhip_std_wells* sw) {
         if (!sw || sw->num_wells == 0) return OPMHIP_SUCCESS;
         if (c->comm.nranks > 1)
             return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: decomposed context (%d ranks) - the per-well sums over the ranks are not built; hand the wells over as a host list (opmhip_wells.distributed)", c->comm.nranks);
-        const int nw = sw->num_wells;
-        if (nw < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: num_wells = %d", nw);
-        if (!sw->perf_pointers || !sw->cell || !sw->tw || !sw->dz || !sw->producer || !sw->inj_phase || !sw->rate_component || !sw->rate_target || !sw->bhp_limit || !sw->control)
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: null array (only x is optional)");
-        if (sw->perf_pointers[0] != 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: inconsistent pointers (perf_pointers[0] = %d, not 0)", sw->perf_pointers[0]);
-        for (int w = 0; w < nw; ++w) {
-            if (sw->perf_pointers[w + 1] <= sw->perf_pointers[w]) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: inconsistent pointers (well %d has no perforation)", w);
-            if (sw->producer[w] != 0 && sw->producer[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: producer[%d] = %d (1 producer, 0 injector)", w, sw->producer[w]);
-            if (!sw->producer[w] && (sw->inj_phase[w] < 0 || sw->inj_phase[w] > 2))
-                return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: unknown phase: inj_phase[%d] = %d (0 water, 1 oil, 2 gas)", w, sw->inj_phase[w]);
-            if (sw->rate_component[w] < 0 || sw->rate_component[w] > 2)
-                return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: unknown component: rate_component[%d] = %d (0 oil, 1 water, 2 gas)", w, sw->rate_component[w]);
-            if (sw->control[w] != 0 && sw->control[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: control[%d] = %d (0 rate, 1 bhp)", w, sw->control[w]);
-            if (!std::isfinite(sw->rate_target[w]) || !std::isfinite(sw->bhp_limit[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: rate target / bhp limit of well %d is not finite", w);
-        }
-        const int np = sw->perf_pointers[nw];
-        // the perforated cells in the internal order; the distinct ones, each with its perforations in perforation order
-        std::vector<int> pos(np), cpos, cptr, cperf(np);
-        {
-            std::vector<int> slot(P.Nb, -1), count;
-            for (int p = 0; p < np; ++p) {
-                const int cell = sw->cell[p];
-                if (cell < 0 || cell >= P.Nb) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: perforation %d names cell %d, outside [0, %d)", p, cell, P.Nb);
-                if (!std::isfinite(sw->tw[p]) || !std::isfinite(sw->dz[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells: tw / dz of perforation %d is not finite", p);
-                pos[p] = P.toOrder[cell];
-                if (slot[cell] < 0) { slot[cell] = (int)cpos.size(); cpos.push_back(pos[p]); count.push_back(0); }
-                count[slot[cell]]++;
-            }
-            cptr.assign(cpos.size() + 1, 0);
-            for (size_t t = 0; t < cpos.size(); ++t) cptr[t + 1] = cptr[t] + count[t];
-            std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-            for (int p = 0; p < np; ++p) cperf[fill[slot[sw->cell[p]]]++] = p;
-        }
-        std::vector<int> wi((size_t)3 * nw);
-        std::vector<double> wd((size_t)2 * nw), pack((size_t)10 * nw, 0.0);
-        for (int w = 0; w < nw; ++w) {
-            wi[3 * w] = sw->producer[w]; wi[3 * w + 1] = sw->producer[w] ? 0 : sw->inj_phase[w]; wi[3 * w + 2] = sw->rate_component[w];
-            wd[2 * w] = sw->rate_target[w]; wd[2 * w + 1] = sw->bhp_limit[w];
-            for (int i = 0; i < 4; ++i) pack[(size_t)4 * w + i] = sw->x ? sw->x[(size_t)4 * w + i] : 0.0;
-            pack[(size_t)4 * nw + w] = sw->control[w];
-        }
+        StdWellsLists H;
+        std::string msg;
+        if (int r = std_wells_lists(sw, P.Nb, P.toOrder.data(), H, msg)) return fail(c, r, "%s", msg.c_str());
+        const int nw = sw->num_wells, np = sw->perf_pointers[nw];
         const int rc = [&]() -> int {
             int r;
             // WellsDev's arrays sized for the list: written by kernels from now on.  What they held of a host list is gone: the record of it
@@ -1358,24 +1224,25 @@ int opmhip_set_std_wells(opmhip_ctx* c, const opmhip_std_wells* sw) {
             }
             W.h_vp.clear(); W.h_D.clear(); W.h_cc.clear(); W.h_bc.clear(); W.h_C.clear(); W.h_B.clear();
             OPMHIP_HIP(c, hipMemcpy(W.d_val_pointers, sw->perf_pointers, ((size_t)nw + 1) * sizeof(int), hipMemcpyHostToDevice));
-            OPMHIP_HIP(c, hipMemcpy(W.d_Ccols, pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
-            OPMHIP_HIP(c, hipMemcpy(W.d_Bcols, pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemcpy(W.d_Ccols, H.pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemcpy(W.d_Bcols, H.pos.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice));
             OPMHIP_HIP(c, hipMemset(W.d_D, 0, (size_t)nw * 16 * sizeof(double)));
             OPMHIP_HIP(c, hipMemset(W.d_B, 0, (size_t)np * 12 * sizeof(double)));
             OPMHIP_HIP(c, hipMemset(W.d_C, 0, (size_t)np * 12 * sizeof(double)));
             OPMHIP_HIP(c, hipMemset(W.d_xw, 0, (size_t)nw * 4 * sizeof(double)));
             const std::vector<double> tw(sw->tw, sw->tw + np), dz(sw->dz, sw->dz + np), zp((size_t)15 * np, 0.0), zw((size_t)16 * nw, 0.0);
-            if ((r = dev_upload(c, &S.d_wi, wi)) || (r = dev_upload(c, &S.d_wd, wd)) || (r = dev_upload(c, &S.d_tw, tw)) || (r = dev_upload(c, &S.d_dz, dz)) ||
-                (r = dev_upload(c, &S.d_head, std::vector<double>(np, 0.0))) || (r = dev_upload(c, &S.d_pr, zp)) || (r = dev_upload(c, &S.d_pack, pack)) ||
-                (r = dev_upload(c, &S.d_saved, std::vector<double>((size_t)5 * nw, 0.0))) || (r = dev_upload(c, &S.d_Dmat, zw)) || (r = dev_upload(c, &S.d_cpos, cpos)) ||
-                (r = dev_upload(c, &S.d_cptr, cptr)) || (r = dev_upload(c, &S.d_cperf, cperf)) || (r = dev_alloc(c, &S.d_save, cpos.size() * 12)))
+            if ((r = dev_upload(c, &S.d_wi, H.wi)) || (r = dev_upload(c, &S.d_wd, H.wd)) || (r = dev_upload(c, &S.d_tw, tw)) || (r = dev_upload(c, &S.d_dz, dz)) ||
+                (r = dev_upload(c, &S.d_head, std::vector<double>(np, 0.0))) || (r = dev_upload(c, &S.d_pr, zp)) || (r = dev_upload(c, &S.d_pack, H.pack)) ||
+                (r = dev_upload(c, &S.d_saved, std::vector<double>((size_t)SW_SAVED * nw, 0.0))) || (r = dev_upload(c, &S.d_Dmat, zw)) || (r = dev_upload(c, &S.d_cpos, H.cpos)) ||
+                (r = dev_upload(c, &S.d_cptr, H.cptr)) || (r = dev_upload(c, &S.d_cperf, H.cperf)) || (r = dev_alloc(c, &S.d_save, H.cpos.size() * 12)))
                 return r;
-            OPMHIP_HIP(c, hipMemcpy(S.d_saved, pack.data(), (size_t)5 * nw * sizeof(double), hipMemcpyHostToDevice));
+            OPMHIP_HIP(c, hipMemcpy(S.d_saved, H.pack.data(), (size_t)SW_SAVED * nw * sizeof(double), hipMemcpyHostToDevice));
             OPMHIP_HIP(c, hipDeviceSynchronize());
             return OPMHIP_SUCCESS;
         }();
         if (rc) { std_wells_release(c); return rc; }
-        S.num = nw; S.nperf = np; S.nd = (int)cpos.size();
+        S.num = nw; S.nperf = np; S.nd = (int)H.cpos.size();
+        S.h_wi = std::move(H.wi); S.h_wd = std::move(H.wd);
         return OPMHIP_SUCCESS;
     });
 }
@@ -1409,9 +1276,8 @@ int opmhip_std_wells_apply_residual(opmhip_ctx* c) {
         if (W.sw.num == 0) return fail(c, OPMHIP_NOT_READY, "std_wells_apply_residual: no resident list (opmhip_set_std_wells)");
         if (!W.sw.assembled || !c->asmb.assembled) return fail(c, OPMHIP_NOT_READY, "std_wells_apply_residual before opmhip_assemble: there is no r_w");
         OPMHIP_HIP(c, hipSetDevice(c->device));
-        W.num_wells = W.sw.num; W.nperf = W.sw.nperf; W.distributed = false;
+        const StdWellsOperatorForm form(W);
         launch_wells_residual(c, W.sw.rw(), c->d_b);   // wellModel().apply(r): r -= C^T D^-1 r_w
-        W.num_wells = 0;                               // the operator form is set per solve_system call
         OPMHIP_HIP(c, hipGetLastError());
         return OPMHIP_SUCCESS;
     });
@@ -1425,10 +1291,11 @@ int opmhip_std_wells_update(opmhip_ctx* c, double relax) {
         if (!c->have_result) return fail(c, OPMHIP_NOT_READY, "std_wells_update before a solve");
         if (!W.sw.assembled) return fail(c, OPMHIP_NOT_READY, "std_wells_update before opmhip_assemble: there is no r_w");
         OPMHIP_HIP(c, hipSetDevice(c->device));
-        W.num_wells = W.sw.num; W.nperf = W.sw.nperf; W.distributed = false;
-        const int rc = launch_wells_recover(c, W.sw.rw(), c->d_x, W.d_xw);   // x_w = D^-1 (r_w - B x)
-        W.num_wells = 0;
-        if (rc) return rc;
+        {
+            const StdWellsOperatorForm form(W);
+            const int rc = launch_wells_recover(c, W.sw.rw(), c->d_x, W.d_xw);   // x_w = D^-1 (r_w - B x)
+            if (rc) return rc;
+        }
         launch_std_wells_axpy(c, relax);
         OPMHIP_HIP(c, hipGetLastError());
         return OPMHIP_SUCCESS;
@@ -1442,15 +1309,15 @@ int opmhip_get_std_wells(opmhip_ctx* c, double* x, int* control, double* res_wel
         if (S.num == 0) return OPMHIP_SUCCESS;
         OPMHIP_HIP(c, hipSetDevice(c->device));
         const size_t nw = S.num;
-        std::vector<double> h(10 * nw);
+        std::vector<double> h(SW_PACK * nw);
         OPMHIP_HIP(c, hipMemcpyAsync(h.data(), S.d_pack, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-        const int rc = std_wells_check(c, &h[9 * nw]);
+        const int rc = std_wells_check(c, &h[SW_FLAG * nw]);
         if (rc) return rc;
-        if (x) std::memcpy(x, &h[0], 4 * nw * sizeof(double));
+        if (x) std::memcpy(x, &h[SW_X * nw], 4 * nw * sizeof(double));
         if (control)
-            for (size_t w = 0; w < nw; ++w) control[w] = h[4 * nw + w] != 0.0;
-        if (res_well) std::memcpy(res_well, &h[5 * nw], 4 * nw * sizeof(double));
+            for (size_t w = 0; w < nw; ++w) control[w] = h[SW_CONTROL * nw + w] != 0.0;
+        if (res_well) std::memcpy(res_well, &h[SW_RW * nw], 4 * nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
 }
@@ -1461,15 +1328,8 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
         StdWellsDev& S = c->wells.sw;
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_state: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num;
-        if (control)
-            for (size_t w = 0; w < nw; ++w)
-                if (control[w] != 0 && control[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: control[%zu] = %d (0 rate, 1 bhp)", w, control[w]);
-        if (rate_target)
-            for (size_t w = 0; w < nw; ++w)
-                if (!std::isfinite(rate_target[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: rate_target[%zu] is not finite", w);
-        if (x)
-            for (size_t i = 0; i < 4 * nw; ++i)
-                if (!std::isfinite(x[i])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_state: x[%zu] is not finite", i);
+        std::string msg;
+        if (int r = std_wells_check_state(nw, x, control, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
         S.assembled = false;   // from here on the device state changes: nothing a refusal above could have left half done
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // rare: events and restarts
@@ -1480,10 +1340,8 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
             OPMHIP_HIP(c, hipMemcpy(S.control(), h.data(), nw * sizeof(double), hipMemcpyHostToDevice));
         }
         if (rate_target) {
-            std::vector<double> wd(2 * nw);
-            OPMHIP_HIP(c, hipMemcpy(wd.data(), S.d_wd, wd.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t w = 0; w < nw; ++w) wd[2 * w] = rate_target[w];
-            OPMHIP_HIP(c, hipMemcpy(S.d_wd, wd.data(), wd.size() * sizeof(double), hipMemcpyHostToDevice));
+            for (size_t w = 0; w < nw; ++w) S.h_wd[2 * w] = rate_target[w];
+            OPMHIP_HIP(c, hipMemcpy(S.d_wd, S.h_wd.data(), S.h_wd.size() * sizeof(double), hipMemcpyHostToDevice));
         }
         OPMHIP_HIP(c, hipDeviceSynchronize());
         S.assembled = false;
@@ -1518,20 +1376,10 @@ int opmhip_set_std_wells_crossflow(opmhip_ctx* c, const int* allow) {
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_crossflow: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num, np = S.nperf;
         bool any = false;
-        if (allow)   // everything is looked at before anything changes: a refused call leaves the flags as they were
-            for (size_t w = 0; w < nw; ++w) {
-                if (allow[w] != 0 && allow[w] != 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_crossflow: allow[%zu] = %d (0 off, 1 on)", w, allow[w]);
-                any = any || allow[w] == 1;
-            }
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the flags as they were
+        if (int r = std_wells_check_crossflow(nw, allow, S.h_wi.data(), any, msg)) return fail(c, r, "%s", msg.c_str());
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-        if (any) {
-            std::vector<int> wi(3 * nw);
-            OPMHIP_HIP(c, hipMemcpy(wi.data(), S.d_wi, wi.size() * sizeof(int), hipMemcpyDeviceToHost));
-            for (size_t w = 0; w < nw; ++w)
-                if (allow[w] && !wi[3 * w])
-                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_crossflow: well %zu is an injector - crossflow is modelled for producers only (the injected composition is fixed)", w);
-        }
         int* d_cf = nullptr;
         double* d_dq = nullptr;
         if (any) {
@@ -1570,30 +1418,17 @@ int opmhip_set_std_wells_head_model(opmhip_ctx* c, const opmhip_std_wells_wellbo
         StdWellsDev& S = c->wells.sw;
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_head_model: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num, np = S.nperf;
-        std::vector<int> wi;
-        if (wb) {   // everything is looked at before anything changes: a refused call leaves the model as it was
-            if (!wb->perf_depth || !wb->ref_depth || !wb->preferred_phase) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: null array");
-            for (size_t p = 0; p < np; ++p)
-                if (!std::isfinite(wb->perf_depth[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: perf_depth[%zu] is not finite", p);
-            for (size_t w = 0; w < nw; ++w)
-                if (!std::isfinite(wb->ref_depth[w])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: ref_depth[%zu] is not finite", w);
-        }
+        std::vector<int> pref;
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the model as it was
+        if (wb)
+            if (int r = std_wells_head_model(wb, nw, np, S.h_wi.data(), pref, msg)) return fail(c, r, "%s", msg.c_str());
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-        if (wb) {
-            wi.resize(3 * nw);
-            OPMHIP_HIP(c, hipMemcpy(wi.data(), S.d_wi, wi.size() * sizeof(int), hipMemcpyDeviceToHost));
-            for (size_t w = 0; w < nw; ++w)
-                if (wi[3 * w] && (wb->preferred_phase[w] < 0 || wb->preferred_phase[w] > 2))
-                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_head_model: unknown phase: preferred_phase[%zu] = %d (0 water, 1 oil, 2 gas)", w, wb->preferred_phase[w]);
-        }
         std_wells_wellbore_release(c);
         S.assembled = false;   // the heads the last assembly used are no longer the model's
         if (!wb) return OPMHIP_SUCCESS;
         const int rc = [&]() -> int {
             int r;
-            std::vector<int> pref(nw);
-            for (size_t w = 0; w < nw; ++w) pref[w] = wi[3 * w] ? wb->preferred_phase[w] : 1;
             const std::vector<double> depth(wb->perf_depth, wb->perf_depth + np), ref(wb->ref_depth, wb->ref_depth + nw);
             if ((r = dev_upload(c, &S.d_wbdepth, depth)) || (r = dev_upload(c, &S.d_wbref, ref)) || (r = dev_upload(c, &S.d_wbpref, pref)) ||
                 (r = dev_upload(c, &S.d_wbstate, std::vector<double>(4 * np, 0.0))) || (r = dev_upload(c, &S.d_wbsaved, std::vector<double>(4 * np, 0.0))) ||
@@ -1633,14 +1468,8 @@ int opmhip_set_std_wells_perf_state(opmhip_ctx* c, const double* perf_pressure, 
         if (!S.wellbore) return fail(c, OPMHIP_NOT_READY, "set_std_wells_perf_state: the well-bore head model is not in force (opmhip_set_std_wells_head_model)");
         const size_t np = S.nperf;
         if (!perf_pressure && !perf_rates) return OPMHIP_SUCCESS;   // nothing handed in: nothing changes, the pressures still come from the cells if they have not yet
-        if (perf_pressure)
-            for (size_t p = 0; p < np; ++p)
-                if (!std::isfinite(perf_pressure[p])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: perf_pressure[%zu] is not finite", p);
-        if (perf_rates)
-            for (size_t i = 0; i < 3 * np; ++i)
-                if (!std::isfinite(perf_rates[i])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: perf_rates[%zu] is not finite", i);
-        if (!S.wb_state_set && !perf_pressure && perf_rates)
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_perf_state: rates alone before the perforation pressures exist (they are taken from the cells at the first begin_iteration(0))");
+        std::string msg;
+        if (int r = std_wells_check_perf_state(np, perf_pressure, perf_rates, S.wb_state_set, msg)) return fail(c, r, "%s", msg.c_str());
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // rare: restarts
         if (perf_pressure) OPMHIP_HIP(c, hipMemcpy(S.d_wbstate, perf_pressure, np * sizeof(double), hipMemcpyHostToDevice));

@@ -179,13 +179,17 @@ struct MsWellsDev {
 // into WellsDev's d_B / d_C / d_D (= D^-1) / d_val_pointers / d_Ccols / d_Bcols, which the existing operator kernels then read.
 // d_pack, one array so that a Newton iteration reads back once: x [4 num] | control [num] (0.0 rate, 1.0 bhp) | r_w [4 num] |
 // flag [num] (0.0, or 1 + the column whose pivot was zero; sticky until the host has looked).  d_saved: x | control of the last
-// opmhip_advance_time_level.
+// opmhip_advance_time_level.  h_wi / h_wd: what d_wi / d_wd hold.
+constexpr int SW_X = 0, SW_CONTROL = 4, SW_RW = 5, SW_FLAG = 9, SW_PACK = 10;   // where d_pack's fields begin and its length, in doubles per well
+constexpr int SW_SAVED = SW_RW;                                                 // d_saved's length: the fields in front of r_w
 struct StdWellsDev {
     int num = 0, nperf = 0, nd = 0;
     bool initialised = false;    // the first begin_iteration(0) has set the bottom-hole pressures
     bool assembled = false;      // B, C, D^-1, r_w belong to the well unknowns now present
     int* d_wi = nullptr;         // per well: producer, injected phase, rate component
     double* d_wd = nullptr;      // per well: rate target, bhp limit
+    std::vector<int> h_wi;
+    std::vector<double> h_wd;
     double *d_tw = nullptr, *d_dz = nullptr, *d_head = nullptr, *d_pr = nullptr;   // per perforation; d_pr: 15 doubles, [component][value, d/dSw, d/dp, d/dX, d/dbhp]
     double *d_pack = nullptr, *d_saved = nullptr, *d_Dmat = nullptr;
     int *d_cpos = nullptr, *d_cptr = nullptr, *d_cperf = nullptr;   // distinct perforated cells: position, range into d_cperf, their perforations in perforation order
@@ -204,10 +208,10 @@ struct StdWellsDev {
     bool crossflow = false;
     int* d_cf = nullptr;
     double* d_dq = nullptr;
-    double* x() const { return d_pack; }
-    double* control() const { return d_pack + (size_t)4 * num; }
-    double* rw() const { return d_pack + (size_t)5 * num; }
-    double* flag() const { return d_pack + (size_t)9 * num; }
+    double* x() const { return d_pack + (size_t)SW_X * num; }
+    double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
+    double* rw() const { return d_pack + (size_t)SW_RW * num; }
+    double* flag() const { return d_pack + (size_t)SW_FLAG * num; }
 };
 
 struct WellsDev {
@@ -233,6 +237,21 @@ struct WellsDev {
     MsWellsDev ms;   // ... or on the device, in the same place (opmhip_set_ms_wells)
     bool any() const { return num_wells > 0 || num_ms > 0 || ms.num > 0; }
 };
+// The resident standard wells in operator form - B, C, D^-1 as the last assemble formed them, read by the wells kernels of the solver -
+// for as long as this lives: the form is set per call, none is left behind for later products
+struct StdWellsOperatorForm {
+    WellsDev& W;
+    explicit StdWellsOperatorForm(WellsDev& w) : W(w) { W.num_wells = W.sw.num; W.nperf = W.sw.nperf; W.distributed = false; }
+    ~StdWellsOperatorForm() { W.num_wells = 0; }
+    StdWellsOperatorForm(const StdWellsOperatorForm&) = delete;
+    StdWellsOperatorForm& operator=(const StdWellsOperatorForm&) = delete;
+};
+
+// The intensive-quantity record (assemble.hip): fields of value + 3 derivatives, the first of each group; phases, equations, gravity
+enum { F_S = 0, F_P = 3, F_B = 6, F_MOB = 9, F_RHO = 12, F_RS = 15 };
+enum { WATER = 0, OIL = 1, GAS = 2 };
+enum { EQ_OIL = 0, EQ_WATER = 1, EQ_GAS = 2 };
+constexpr double GRAVITY = 9.80665;
 
 // Analytic aquifers on the device (opmhip_set_aquifers).  nc connections (aquifers concatenated, Carter-Tracy first), nd distinct connected
 // cells.  Per aquifer: AQ_PAR constants, AQ_STEP scalars of the time step under way (host-computed, opmhip_aquifers_begin_time_step), AQ_STATE

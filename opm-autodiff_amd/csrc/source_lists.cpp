@@ -1,0 +1,272 @@
+// Host set-up of the resident standard wells and analytic aquifers (source_lists.hpp).  No HIP call: capi_asm.cpp uploads what is
+// built here.
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <utility>
+
+#include "internal.hpp"
+#include "source_lists.hpp"
+
+namespace opmhip {
+
+namespace {
+// the text as fail() will cut it
+int refuse(std::string& msg, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    msg = buf;
+    return OPMHIP_INVALID_ARGUMENT;
+}
+}  // namespace
+
+void group_by_cell(const int* cell, int n, int Nb, const int* toOrder, std::vector<int>& pos, std::vector<int>& cpos, std::vector<int>& cptr,
+                   std::vector<int>& items) {
+    pos.assign(n, 0); items.assign(n, 0); cpos.clear();
+    std::vector<int> slot(Nb, -1), count;
+    for (int i = 0; i < n; ++i) {
+        pos[i] = toOrder[cell[i]];
+        if (slot[cell[i]] < 0) { slot[cell[i]] = (int)cpos.size(); cpos.push_back(pos[i]); count.push_back(0); }
+        count[slot[cell[i]]]++;
+    }
+    cptr.assign(cpos.size() + 1, 0);
+    for (size_t t = 0; t < cpos.size(); ++t) cptr[t + 1] = cptr[t] + count[t];
+    std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+    for (int i = 0; i < n; ++i) items[fill[slot[cell[i]]]++] = i;
+}
+
+// ---- standard wells ----
+int std_wells_lists(const opmhip_std_wells* sw, int Nb, const int* toOrder, StdWellsLists& out, std::string& msg) {
+    const int nw = sw->num_wells;
+    if (nw < 0) return refuse(msg, "set_std_wells: num_wells = %d", nw);
+    if (!sw->perf_pointers || !sw->cell || !sw->tw || !sw->dz || !sw->producer || !sw->inj_phase || !sw->rate_component || !sw->rate_target || !sw->bhp_limit || !sw->control)
+        return refuse(msg, "set_std_wells: null array (only x is optional)");
+    if (sw->perf_pointers[0] != 0) return refuse(msg, "set_std_wells: inconsistent pointers (perf_pointers[0] = %d, not 0)", sw->perf_pointers[0]);
+    for (int w = 0; w < nw; ++w) {
+        if (sw->perf_pointers[w + 1] <= sw->perf_pointers[w]) return refuse(msg, "set_std_wells: inconsistent pointers (well %d has no perforation)", w);
+        if (sw->producer[w] != 0 && sw->producer[w] != 1) return refuse(msg, "set_std_wells: producer[%d] = %d (1 producer, 0 injector)", w, sw->producer[w]);
+        if (!sw->producer[w] && (sw->inj_phase[w] < 0 || sw->inj_phase[w] > 2))
+            return refuse(msg, "set_std_wells: unknown phase: inj_phase[%d] = %d (0 water, 1 oil, 2 gas)", w, sw->inj_phase[w]);
+        if (sw->rate_component[w] < 0 || sw->rate_component[w] > 2)
+            return refuse(msg, "set_std_wells: unknown component: rate_component[%d] = %d (0 oil, 1 water, 2 gas)", w, sw->rate_component[w]);
+        if (sw->control[w] != 0 && sw->control[w] != 1) return refuse(msg, "set_std_wells: control[%d] = %d (0 rate, 1 bhp)", w, sw->control[w]);
+        if (!std::isfinite(sw->rate_target[w]) || !std::isfinite(sw->bhp_limit[w])) return refuse(msg, "set_std_wells: rate target / bhp limit of well %d is not finite", w);
+    }
+    const int np = sw->perf_pointers[nw];
+    for (int p = 0; p < np; ++p) {
+        const int cell = sw->cell[p];
+        if (cell < 0 || cell >= Nb) return refuse(msg, "set_std_wells: perforation %d names cell %d, outside [0, %d)", p, cell, Nb);
+        if (!std::isfinite(sw->tw[p]) || !std::isfinite(sw->dz[p])) return refuse(msg, "set_std_wells: tw / dz of perforation %d is not finite", p);
+    }
+    // the perforated cells in the internal order; the distinct ones, each with its perforations in perforation order
+    group_by_cell(sw->cell, np, Nb, toOrder, out.pos, out.cpos, out.cptr, out.cperf);
+    out.wi.assign((size_t)3 * nw, 0);
+    out.wd.assign((size_t)2 * nw, 0.0);
+    out.pack.assign((size_t)SW_PACK * nw, 0.0);
+    for (int w = 0; w < nw; ++w) {
+        out.wi[3 * w] = sw->producer[w]; out.wi[3 * w + 1] = sw->producer[w] ? 0 : sw->inj_phase[w]; out.wi[3 * w + 2] = sw->rate_component[w];
+        out.wd[2 * w] = sw->rate_target[w]; out.wd[2 * w + 1] = sw->bhp_limit[w];
+        for (int i = 0; i < 4; ++i) out.pack[(size_t)SW_X * nw + 4 * w + i] = sw->x ? sw->x[(size_t)4 * w + i] : 0.0;
+        out.pack[(size_t)SW_CONTROL * nw + w] = sw->control[w];
+    }
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_check_state(size_t nw, const double* x, const int* control, const double* rate_target, std::string& msg) {
+    if (control)
+        for (size_t w = 0; w < nw; ++w)
+            if (control[w] != 0 && control[w] != 1) return refuse(msg, "set_std_wells_state: control[%zu] = %d (0 rate, 1 bhp)", w, control[w]);
+    if (rate_target)
+        for (size_t w = 0; w < nw; ++w)
+            if (!std::isfinite(rate_target[w])) return refuse(msg, "set_std_wells_state: rate_target[%zu] is not finite", w);
+    if (x)
+        for (size_t i = 0; i < 4 * nw; ++i)
+            if (!std::isfinite(x[i])) return refuse(msg, "set_std_wells_state: x[%zu] is not finite", i);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_check_crossflow(size_t nw, const int* allow, const int* wi, bool& any, std::string& msg) {
+    bool some = false;
+    if (allow)
+        for (size_t w = 0; w < nw; ++w) {
+            if (allow[w] != 0 && allow[w] != 1) return refuse(msg, "set_std_wells_crossflow: allow[%zu] = %d (0 off, 1 on)", w, allow[w]);
+            some = some || allow[w] == 1;
+        }
+    if (some)
+        for (size_t w = 0; w < nw; ++w)
+            if (allow[w] && !wi[3 * w])
+                return refuse(msg, "set_std_wells_crossflow: well %zu is an injector - crossflow is modelled for producers only (the injected composition is fixed)", w);
+    any = some;
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_head_model(const opmhip_std_wells_wellbore* wb, size_t nw, size_t np, const int* wi, std::vector<int>& pref, std::string& msg) {
+    if (!wb->perf_depth || !wb->ref_depth || !wb->preferred_phase) return refuse(msg, "set_std_wells_head_model: null array");
+    for (size_t p = 0; p < np; ++p)
+        if (!std::isfinite(wb->perf_depth[p])) return refuse(msg, "set_std_wells_head_model: perf_depth[%zu] is not finite", p);
+    for (size_t w = 0; w < nw; ++w)
+        if (!std::isfinite(wb->ref_depth[w])) return refuse(msg, "set_std_wells_head_model: ref_depth[%zu] is not finite", w);
+    for (size_t w = 0; w < nw; ++w)
+        if (wi[3 * w] && (wb->preferred_phase[w] < 0 || wb->preferred_phase[w] > 2))
+            return refuse(msg, "set_std_wells_head_model: unknown phase: preferred_phase[%zu] = %d (0 water, 1 oil, 2 gas)", w, wb->preferred_phase[w]);
+    pref.resize(nw);
+    for (size_t w = 0; w < nw; ++w) pref[w] = wi[3 * w] ? wb->preferred_phase[w] : 1;
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_check_perf_state(size_t np, const double* perf_pressure, const double* perf_rates, bool state_set, std::string& msg) {
+    if (perf_pressure)
+        for (size_t p = 0; p < np; ++p)
+            if (!std::isfinite(perf_pressure[p])) return refuse(msg, "set_std_wells_perf_state: perf_pressure[%zu] is not finite", p);
+    if (perf_rates)
+        for (size_t i = 0; i < 3 * np; ++i)
+            if (!std::isfinite(perf_rates[i])) return refuse(msg, "set_std_wells_perf_state: perf_rates[%zu] is not finite", i);
+    if (!state_set && !perf_pressure && perf_rates)
+        return refuse(msg, "set_std_wells_perf_state: rates alone before the perforation pressures exist (they are taken from the cells at the first begin_iteration(0))");
+    return OPMHIP_SUCCESS;
+}
+
+// ---- analytic aquifers ----
+int aquifer_lists(const opmhip_aquifers* aq, int Nb, const int* toOrder, AquiferLists& out, std::string& msg) {
+    const int na = aq->num_aquifers;
+    if (na < 0) return refuse(msg, "set_aquifers: num_aquifers = %d", na);
+    if (!aq->type || !aq->id || !aq->conn_pointers || !aq->time_constant || !aq->water_density || !aq->datum_depth)
+        return refuse(msg, "set_aquifers: null array (type, id, conn_pointers, time_constant, water_density, datum_depth are mandatory)");
+    if (aq->conn_pointers[0] != 0) return refuse(msg, "set_aquifers: conn_pointers[0] = %d, not 0", aq->conn_pointers[0]);
+    bool anyCT = false, anyFet = false;
+    for (int a = 0; a < na; ++a) {
+        if (aq->conn_pointers[a + 1] < aq->conn_pointers[a]) return refuse(msg, "set_aquifers: conn_pointers descend at aquifer %d", a);
+        if (aq->type[a] != 0 && aq->type[a] != 1) return refuse(msg, "set_aquifers: type[%d] = %d (0 Carter-Tracy, 1 Fetkovich)", a, aq->type[a]);
+        if (aq->type[a] == 0 && anyFet) return refuse(msg, "set_aquifers: Carter-Tracy aquifer %d behind a Fetkovich one (Carter-Tracy first: the order of addToSource)", a);
+        (aq->type[a] == 0 ? anyCT : anyFet) = true;
+    }
+    const int nc = aq->conn_pointers[na];
+    if (nc > 0 && (!aq->cell || !aq->alpha)) return refuse(msg, "set_aquifers: null array (cell / alpha)");
+    if (anyCT && (!aq->influx_constant || !aq->table_pointers || !aq->td || !aq->pd))
+        return refuse(msg, "set_aquifers: null array (a Carter-Tracy aquifer needs influx_constant, table_pointers, td, pd)");
+    if (anyFet && (!aq->prod_index || !aq->total_compr || !aq->initial_watvolume))
+        return refuse(msg, "set_aquifers: null array (a Fetkovich aquifer needs prod_index, total_compr, initial_watvolume)");
+    if (aq->has_restart && (!aq->restart_W_flux || (anyFet && !aq->restart_pressure)))
+        return refuse(msg, "set_aquifers: null array (has_restart without restart_W_flux / restart_pressure)");
+    AquiferLists L;
+    L.nc = nc;
+    L.par.assign((size_t)na * AQ_PAR, 0.0);
+    L.tabptr.assign(na + 1, 0);
+    for (int a = 0; a < na; ++a) {
+        double* p = &L.par[(size_t)a * AQ_PAR];
+        if (!(aq->time_constant[a] > 0.0)) return refuse(msg, "set_aquifers: aquifer %d has time constant Tc = %g, must be positive", a, aq->time_constant[a]);
+        const bool has_p = !aq->has_initial_pressure || aq->has_initial_pressure[a];
+        if (has_p && !aq->initial_pressure) return refuse(msg, "set_aquifers: null array (initial_pressure)");
+        const bool restart = aq->has_restart && aq->has_restart[a];
+        p[AQ_TYPE] = aq->type[a]; p[AQ_TC] = aq->time_constant[a]; p[AQ_RHOW] = aq->water_density[a]; p[AQ_DATUM] = aq->datum_depth[a];
+        p[AQ_PA0] = has_p ? aq->initial_pressure[a] : 0.0;
+        if (!has_p) L.need_eq.push_back(a);
+        L.tabptr[a + 1] = L.tabptr[a];
+        if (aq->type[a] == 0) {
+            if (restart) return refuse(msg, "set_aquifers: restart data for Carter-Tracy aquifer %d - restart-based initialisation is not supported for Carter-Tracy aquifers (as in the reference)", a);
+            p[AQ_BETA] = aq->influx_constant[a];
+            const int t0 = aq->table_pointers[a], t1 = aq->table_pointers[a + 1];
+            if (t0 < 0 || t1 - t0 < 2) return refuse(msg, "set_aquifers: the influence table of aquifer %d has fewer than two nodes", a);
+            for (int i = t0 + 1; i < t1; ++i)
+                if (!(aq->td[i] > aq->td[i - 1])) return refuse(msg, "set_aquifers: the influence table of aquifer %d is not ascending at node %d", a, i - t0);
+            L.td.insert(L.td.end(), aq->td + t0, aq->td + t1);
+            L.pd.insert(L.pd.end(), aq->pd + t0, aq->pd + t1);
+            L.tabptr[a + 1] = (int)L.td.size();
+        } else {
+            p[AQ_PI] = aq->prod_index[a];
+            p[AQ_CV] = aq->total_compr[a] * aq->initial_watvolume[a];
+            if (!(p[AQ_CV] > 0.0)) return refuse(msg, "set_aquifers: Fetkovich aquifer %d has total_compr * initial_watvolume = %g, must be positive", a, p[AQ_CV]);
+        }
+    }
+    // connections; the distinct connected cells, each with its connections in aquifer order (= ascending connection number)
+    L.of.assign(nc, 0);
+    {
+        std::vector<int> seen(Nb, -1);
+        for (int a = 0; a < na; ++a)
+            for (int i = aq->conn_pointers[a]; i < aq->conn_pointers[a + 1]; ++i) {
+                const int cell = aq->cell[i];
+                if (cell < 0 || cell >= Nb) return refuse(msg, "set_aquifers: connection %d of aquifer %d names cell %d, outside [0, %d)", i - aq->conn_pointers[a], a, cell, Nb);
+                if (seen[cell] == a) return refuse(msg, "set_aquifers: cell %d is repeated within aquifer %d (one connection per cell)", cell, a);
+                seen[cell] = a;
+                L.of[i] = a;
+            }
+    }
+    group_by_cell(aq->cell, nc, Nb, toOrder, L.pos, L.cpos, L.cptr, L.cconn);
+    out = std::move(L);
+    return OPMHIP_SUCCESS;
+}
+
+double aquifer_equilibrium_pressure(const double* alpha, int i0, int n, const int* order, const double* rec, int IQS, const double* depth, const int* p,
+                                    double datum) {
+    double sumAlpha = 0.0, sumPw = 0.0;
+    for (int i = i0; i < i0 + n; ++i) sumAlpha += alpha[i];
+    for (int i = 0; i < n; ++i) {
+        const double pw = rec[(size_t)i * IQS + 4 * (F_P + WATER)], rho = rec[(size_t)i * IQS + 4 * (F_RHO + WATER)];
+        const double gdz = GRAVITY * (depth[p[i]] - datum);
+        sumPw += alpha[order[i]] * (pw - rho * gdz);
+    }
+    return sumPw / sumAlpha;
+}
+
+void aquifer_initial_state(const opmhip_aquifers* aq, const std::vector<double>& par, std::vector<double>& state) {
+    const int na = aq->num_aquifers;
+    state.assign((size_t)na * AQ_STATE, 0.0);
+    for (int a = 0; a < na; ++a) {
+        const bool restart = aq->has_restart && aq->has_restart[a];
+        state[(size_t)a * AQ_STATE + AQ_WFLUX] = restart ? aq->restart_W_flux[a] : 0.0;
+        state[(size_t)a * AQ_STATE + AQ_AUX] = aq->type[a] == 0 ? 0.0 : (restart ? aq->restart_pressure[a] : par[(size_t)a * AQ_PAR + AQ_PA0]);
+    }
+}
+
+int table_interval(const double* x, int n, double xv) {
+    const int j = (int)(std::upper_bound(x, x + n, xv) - x) - 1;
+    return std::min(std::max(j, 0), n - 2);
+}
+double table_slope(const double* x, const double* y, int n, double xv) {
+    const int j = table_interval(x, n, xv);
+    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]);
+}
+double table_value(const double* x, const double* y, int n, double xv) {
+    const int j = table_interval(x, n, xv);
+    return (y[j + 1] - y[j]) / (x[j + 1] - x[j]) * (xv - x[j]) + y[j];
+}
+
+void aquifer_step_scalars(int num, const std::vector<double>& par, const std::vector<int>& tabptr, const std::vector<double>& td, const std::vector<double>& pd,
+                          double time, double dt, double* step) {
+    for (int a = 0; a < num; ++a) {
+        const double* p = &par[(size_t)a * AQ_PAR];
+        double* s = step + (size_t)a * AQ_STEP;
+        s[AQ_TD] = s[AQ_PITD] = s[AQ_PITDPRIME] = s[AQ_COEF] = 0.0;
+        if (p[AQ_TYPE] == 0.0) {   // calculateEqnConstants (AquiferCarterTracy.hpp:150-153)
+            const double td_plus_dt = (dt + time) / p[AQ_TC];
+            const int t0 = tabptr[a], n = tabptr[a + 1] - t0;
+            s[AQ_TD] = time / p[AQ_TC];
+            s[AQ_PITD] = table_value(&td[t0], &pd[t0], n, td_plus_dt);
+            s[AQ_PITDPRIME] = table_slope(&td[t0], &pd[t0], n, td_plus_dt);
+        } else {                   // AquiferFetkovich.hpp:143-144
+            const double td_Tc = dt / p[AQ_TC];
+            s[AQ_COEF] = (1 - std::exp(-td_Tc)) / td_Tc;
+        }
+    }
+}
+
+void aquifer_report(int num, const std::vector<double>& par, const std::vector<int>& ptr, const double* state, const double* q4, double* W_flux,
+                    double* pressure, double* flux_rate, double* init_pressure) {
+    for (int a = 0; a < num; ++a) {
+        const double* p = &par[(size_t)a * AQ_PAR];
+        if (W_flux) W_flux[a] = state[(size_t)a * AQ_STATE + AQ_WFLUX];
+        if (pressure) pressure[a] = p[AQ_TYPE] == 0.0 ? p[AQ_PA0] : state[(size_t)a * AQ_STATE + AQ_AUX];
+        if (init_pressure) init_pressure[a] = p[AQ_PA0];
+        if (flux_rate) {
+            double f = 0.0;
+            for (int i = ptr[a]; i < ptr[a + 1]; ++i) f += q4[(size_t)4 * i];
+            flux_rate[a] = f;
+        }
+    }
+}
+
+}  // namespace opmhip

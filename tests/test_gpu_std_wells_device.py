@@ -422,6 +422,17 @@ def test_refusals(pkg):
     m.assemble(DAY, 0, fetch=False)
     m.wells_apply_residual(wa["wells"], wa["res_well"])  # ... and once it is cleared a host list is taken (and copied) again
     assert m.solve_jacobian_system(wells=wa["wells"]).converged
+    # a second list with the producers and injectors swapped: the setters that ask which wells produce go by the list now set
+    m.set_std_wells(good)
+    m.set_std_wells(dict(good, producer=[0, 1]))
+    with pytest.raises(ValueError, match="injector"):
+        m.set_std_wells_crossflow([1, 0])
+    m.set_std_wells_crossflow([0, 1])
+    depths = dict(perf_depth=[2000.0, 2001.0, 2000.0], ref_depth=[2000.0, 2000.0])
+    with pytest.raises(C.OpmHipError, match="unknown phase"):
+        m.set_std_wells_head_model(dict(depths, preferred_phase=[1, 7]))
+    m.set_std_wells_head_model(dict(depths, preferred_phase=[7, 1]))   # an injector's is not looked at
+    m.set_std_wells(None)
     # a decomposed context (loopback, two ranks): out of scope
     sub = pkg.ras.cartesian_subdomain_case(6, 2, 0, state="mixed", heterogeneous=False)
     dd = C.HipModel(sub, comm=("loopback", 2, 0, "sw" + uuid.uuid4().hex), reorder="level_scheduling")

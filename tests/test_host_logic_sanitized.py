@@ -4,7 +4,9 @@ decomposed subdomains with ghost columns, irregular patterns with rows of up to 
 (tests/san/host_logic_san.cpp, which also checks the invariants every ordering must keep).  No GPU: the harness serves the three HIP
 runtime calls of reorder.cpp from the host heap.  The GPU sanitizers are not available on the pool; this is the CPU build the brief asks
 to run them on.  The CPR pressure-AMG set-up (csrc/cpr_setup.cpp) is built the same way, linked alone (tests/san/cpr_setup_san.cpp: level
-invariants on every hierarchy, the oracle's hierarchy alongside)."""
+invariants on every hierarchy, the oracle's hierarchy alongside).  So is the host set-up of the resident standard wells and analytic
+aquifers (csrc/source_lists.cpp, linked alone; tests/san/source_lists_san.cpp: the grouping by distinct cell against a quadratic restatement,
+every refusal with its code and its text, the aquifers' tables, step scalars and sums)."""
 import os
 import shutil
 import subprocess
@@ -52,3 +54,23 @@ def test_cpr_setup_under_asan_ubsan(tmp_path):
     assert out.count("; oracle agrees: levels, n, nc, agg, coarsest matrix\n") == 104   # every set-up of the list, each against the oracle
     for stop in ("rows", "stall", "width"):   # every rule that ends a hierarchy was met
         assert "(last: %s)" % stop in out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_source_lists_under_asan_ubsan(tmp_path):
+    # source_lists.cpp alone, no HIP stand-ins: the link fails if the set-up of the resident wells and aquifers calls the HIP runtime
+    exe = str(tmp_path / "source_lists_san")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           "-D_GLIBCXX_ASSERTIONS", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           os.path.join(ROOT, "tests", "san", "source_lists_san.cpp"), os.path.join(CSRC, "source_lists.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "all checks passed" in out and "FAILED" not in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-4000:]
+    lines = out.splitlines()   # every case of the lists ran
+    assert sum(l.startswith("ok  group_by_cell: ") for l in lines) == 30 and sum(l.startswith("ok  refused: ") for l in lines) == 50
+    assert sum(l.startswith("ok  ") for l in lines) == 93
