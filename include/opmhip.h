@@ -758,7 +758,10 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * pivoting (largest |entry| of the column, lowest row on ties), D^-1 r a row-times-vector product in ascending column order.
  * The head is, on request, the reference's: from the density of the mixture in the well bore above every completion
  * (opmhip_set_std_wells_head_model, below).
- * NOT covered: groups, THP, VFP, crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
+ * A tubing-head-pressure limit through VFPPROD / VFPINJ tables is a third control (opmhip_set_vfp_tables, opmhip_set_std_wells_thp, below).
+ * NOT covered: groups and GRUP control; gas lift (ALQ is a constant per well); bhpwithflo and the robust BHP-THP intersection of
+ * computeBhpAtThpLimitProd; well potentials; THP for multisegment wells; the deck-level parsing and unit conversion of VFPPROD / VFPINJ
+ * (opm-common's: it stays with the caller); crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
  * because its composition - WFrac, GFrac - is an unknown while getQs pins the other components to zero; this parametrisation fixes
  * the injected composition, and a half-measure would let oil leave through an injector's wellhead), decomposed contexts (refused),
  * the matrix-add form (opmhip_add_well_contributions stays with host lists).
@@ -893,6 +896,91 @@ int opmhip_set_std_wells_perf_state(opmhip_ctx* ctx, const double* perf_pressure
  * opmhip_std_wells_begin_iteration(0) takes them from the cells again and yields the heads of a context that never tried the step.
  * Without it no call launches, copies or decides anything else than before. */
 
+/* ---- VFP tables and the THP limit of the resident standard wells.  Additive to ABI 11 --------------------------------------------
+ * replaces: VFPProdProperties / VFPInjProperties with wells/VFPHelpers.cpp - findInterpData (:81-145), interpolate (:181-287 VFPPROD,
+ * :289-341 VFPINJ), bhp (:343-385), findTHP (:387-499) with findX (:40-66), getFlo / getWFR / getGFR (:501-590) -, the AD forms of bhp
+ * (VFPProdProperties.cpp:142-172, VFPInjProperties.cpp:88-112) and the inverse look-ups thp (VFPProdProperties.cpp:37-82,
+ * VFPInjProperties.cpp:47-74), in the statement order of the Python package's vfp.py, operation by operation and without contraction.
+ * Everything is SI: rates m^3/s (positive on the flo axis; the rates handed to the functions are INTO the reservoir, a producer's are
+ * negative - the reference's sign), pressures Pa.
+ * UNVERIFIED (opm-material is not in the reference tree): the derivative of Opm::max on evaluations, stated as "a chop max(0, .) or a
+ * threshold max(1e-12, .) that binds, ties included, has derivative zero".  Where the reference leaves the result undefined it is defined:
+ * a NaN looked up on an axis takes the last interval, an inverse look-up that finds nothing returns the -1e100 it starts from.  An
+ * injector's dwfr, dgfr, dalq are not carried (0).
+ * Per table: kind (0 VFPPROD, 1 VFPINJ); the deck's table number (> 0, unique per kind); flo type (VFPPROD 0 OIL, 1 LIQ, 2 GAS; VFPINJ
+ * 0 OIL, 1 WAT, 2 GAS), wfr type (0 WOR, 1 WCT, 2 WGR) and gfr type (0 GOR, 1 GLR, 2 OGR; both ignored for VFPINJ); the datum depth; five
+ * axis sizes in the order flo, thp, wfr, gfr, alq (an injector's last three are ignored) and the axes themselves in that order (an
+ * injector has the first two), non-decreasing; the BHP values with flo fastest: [thp][wfr][gfr][alq][flo], [thp][flo]. */
+typedef struct opmhip_vfp_tables {
+    int num_tables;
+    const int* kind;               /* per table */
+    const int* table_num;          /* per table */
+    const int* flo_type;           /* per table */
+    const int* wfr_type;           /* per table */
+    const int* gfr_type;           /* per table */
+    const double* datum_depth;     /* per table */
+    const int* axis_sizes;         /* [num_tables * 5] */
+    const int* axis_pointers;      /* [num_tables + 1] ranges into axes: a table's axes one after the other */
+    const double* axes;
+    const int* value_pointers;     /* [num_tables + 1] ranges into values */
+    const double* values;
+} opmhip_vfp_tables;
+/* The tables are packed once into one double array and an int descriptor per table and stay resident for the context's life.  NULL or
+ * num_tables == 0 clears the set.  Needs no fluid, static data or state.
+ * OPMHIP_INVALID_ARGUMENT (the text names the reason) for a null array, an empty axis, an axis that decreases or is not finite, a value
+ * that is not finite, an unknown kind or type, a table number <= 0, a duplicate number, inconsistent pointers.  A refused call leaves the
+ * previous set in force.  Replacing or clearing the set while wells hold THP limits (which name its tables) is refused likewise: switch
+ * the limits off first. */
+int opmhip_set_vfp_tables(opmhip_ctx* ctx, const opmhip_vfp_tables* tables);
+/* The counterpart of opmhip_fluid_probe: the functions the well kernels call, ON THE DEVICE, to the bit.  For each of n points (host
+ * arrays; one lane per point): out[10 i + 0..9] = bhp, d/dthp, d/dwfr, d/dgfr, d/dalq, d/dflo of the table at (aqua, liquid, vapour, thp,
+ * alq) - producers search the flo axis with -flo, injectors with flo -; d bhp / d aqua, d liquid, d vapour = (dwfr * wfr') + (dgfr * gfr')
+ * - (dflo * flo') (injectors: dflo * flo'), wfr' and gfr' by the quotient rule (a' - v * b') / b with v = a / b; and
+ * thp(aqua, liquid, vapour, bhp_target, alq), the inverse look-up (a producer with all-zero rates takes the first entry of the flo axis
+ * and zero fractions; 0 for a table whose THP axis has fewer than two entries).  alq is ignored for an injector (NULL allowed);
+ * bhp_target NULL leaves the tenth slot 0.  OPMHIP_NOT_READY without tables, OPMHIP_INVALID_ARGUMENT for a table that does not exist. */
+int opmhip_vfp_probe(opmhip_ctx* ctx, int kind, int table_num, int n, const double* aqua, const double* liquid, const double* vapour, const double* thp,
+                     const double* alq, const double* bhp_target, double* out);
+/* The THP limit of the resident wells.  Per well: vfp_table, the deck number of a VFPPROD (producer) / VFPINJ (injector) table, 0: the
+ * well has no THP limit; thp_limit; alq; dh = the table's datum depth - the well's reference depth. */
+typedef struct opmhip_std_wells_thp {
+    const int* vfp_table;
+    const double* thp_limit;
+    const double* alq;
+    const double* dh;
+} opmhip_std_wells_thp;
+/* Call it after opmhip_set_std_wells; NULL switches it off; replacing or clearing the list clears it, as with the crossflow flags.
+ * OPMHIP_NOT_READY without a list or without tables; OPMHIP_INVALID_ARGUMENT for a null array, a table number that does not exist for
+ * the well's kind, a THP axis of fewer than two entries, a limit, alq or dh that is not finite, and for taking the limit from a well
+ * that is under THP control.  A refused call leaves the previous values in force.  With limits in force:
+ *   control value 2 (THP) exists beside 0 and 1 in opmhip_set_std_wells_state and opmhip_get_std_wells; 2 for a well without a limit is
+ *     refused.  opmhip_set_std_wells' own control field keeps refusing anything but 0 / 1: a well starts under its deck mode and reaches
+ *     THP through the state call or by switching;
+ *   opmhip_std_wells_begin_iteration(0) sets, after the heads, dp = (rho * g) * dh per well (wells/WellHelpers.hpp:149-155), rho what the
+ *     head model uses for the first perforation: the well-bore density there under the well-bore head model (perf_densities_[0], getRho()),
+ *     the perforated cell's oil density otherwise; constant through the Newton iterations, as the heads are;
+ *   the control equation under control 2, in the wells alone and in opmhip_assemble (replaces control_eq = bhp - bhp_from_thp,
+ *     wells/WellInterfaceEval.cpp:351-354, 433-436, calculateBhpFromThp :463-504): V = bhp(table, q_w, q_o, q_g, thp_limit, alq);
+ *     r_w[3] = bhp - (V - dp); D[3][j] = 0.0 - dV/dq_j for the three rate unknowns in their order (oil, water, gas); D[3][3] = 1.0.  The
+ *     guard of a well without a flowing completion keeps its condition and cannot fire with D[3][3] = 1;
+ *   updateWellControls (every opmhip_std_wells_begin_iteration) checks the limits in the reference's order
+ *     (wells/WellInterfaceFluidSystem.cpp:170-268 producers, :100-166 injectors); the first that is violated and is not the control in
+ *     force wins: 1. BHP (bhp beyond bhp_limit) -> control 1, bhp = bhp_limit; 2. the rate target exceeded -> control 0; 3. THP: current =
+ *     thp(table, q_w, q_o, q_g, bhp + dp, alq) (wells/StandardWellGeneric.cpp:116-156, wells/StandardWellEval.cpp:546-583); a producer
+ *     switches when thp_limit > current, an injector when thp_limit < current, to control 2 with bhp = V - dp at the rates at hand
+ *     (updateWellStateWithTarget's THP case, wells/WellInterface_impl.hpp:659-667 injectors, :882-890 producers: the bhp from
+ *     calculateBhpFromThp).  A well without a limit
+ *     takes exactly the two branches it took before.
+ * The control rides along in what opmhip_advance_time_level / opmhip_update_failed save and restore; dp is formed anew at the next
+ * opmhip_std_wells_begin_iteration(0): no new state.  A list without a limit launches the kernels it launched before; with a limit the
+ * wells alone, the assembly and the controls run another instantiation of the same kernels in place of the first: the number of launches
+ * of a Newton iteration does not change. */
+int opmhip_set_std_wells_thp(opmhip_ctx* ctx, const opmhip_std_wells_thp* thp);
+/* Per well (any pointer may be NULL; waits for the stream): the tubing-head pressure the last opmhip_std_wells_begin_iteration formed
+ * from the well's state (before it switched anything), this time step's hydrostatic correction dp, and V - dp of the last
+ * opmhip_assemble (formed for every well with a limit, whatever its control).  Zeros for wells without a limit. */
+int opmhip_get_std_wells_thp(opmhip_ctx* ctx, double* thp, double* dp, double* bhp_from_thp);
+
 /* With a list set:
  * opmhip_assemble forms, in front of the assembly kernel and of the aquifers' influx (the host order: wells' rates first), the
  * perforation rates with their five derivatives, r_w, D, D^-1, B and C (computePerfRate, assembleWellEqWithoutIteration:
@@ -904,7 +992,7 @@ int opmhip_set_std_wells_perf_state(opmhip_ctx* ctx, const double* perf_pressure
  * column are named) and the list is cleared - its D^-1 is stored as zeros, never as NaNs.
  * opmhip_solve_system(wells = NULL) takes the resident B / C / D^-1 as its operator form; a host list with num_wells > 0 is
  * refused by every call that takes one (the operator would be applied twice); OPMHIP_NOT_READY before the first assemble.
- * opmhip_advance_time_level / opmhip_update_failed also save / restore the well unknowns and the controls.
+ * opmhip_advance_time_level / opmhip_update_failed also save / restore the well unknowns and the controls (control 2, THP, included).
  * Two wells in one cell: the new kernels add in perforation order, but the existing operator kernels (y -= C^T D^-1 B x, r -= C^T D^-1
  * r_w) add two wells' contributions to a shared cell atomically, in either order - with a host list as with the resident one.  A run
  * with such a cell is therefore not reproducible to the bit from run to run, nor against the host path; every other run is.

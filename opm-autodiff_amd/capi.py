@@ -101,6 +101,56 @@ class StdWellsWellbore(C.Structure):
     _fields_ = [("perf_depth", C.c_void_p), ("ref_depth", C.c_void_p), ("preferred_phase", C.c_void_p)]
 
 
+class VfpTables(C.Structure):
+    """opmhip_vfp_tables: VFPPROD / VFPINJ tables, SI (opmhip_set_vfp_tables)"""
+    _fields_ = [("num_tables", C.c_int), ("kind", C.c_void_p), ("table_num", C.c_void_p), ("flo_type", C.c_void_p), ("wfr_type", C.c_void_p),
+                ("gfr_type", C.c_void_p), ("datum_depth", C.c_void_p), ("axis_sizes", C.c_void_p), ("axis_pointers", C.c_void_p), ("axes", C.c_void_p),
+                ("value_pointers", C.c_void_p), ("values", C.c_void_p)]
+
+
+class StdWellsThp(C.Structure):
+    """opmhip_std_wells_thp: the THP limits of the resident standard wells (opmhip_set_std_wells_thp)"""
+    _fields_ = [("vfp_table", C.c_void_p), ("thp_limit", C.c_void_p), ("alq", C.c_void_p), ("dh", C.c_void_p)]
+
+
+def make_vfp_tables(tables):
+    """list of vfp.VFPTable (or objects with its attributes: kind, table_num, flo_type, wfr_type, gfr_type, datum_depth, axes in the order flo,
+    thp[, wfr, gfr, alq], values with flo fastest) -> (VfpTables struct, keep-alive dict); empty / None -> (None, {})"""
+    if not tables:
+        return None, {}
+    ap, vp, sizes, axes, values = [0], [0], [], [], []
+    for t in tables:
+        ax = [np.asarray(a, float).reshape(-1) for a in t.axes]
+        sizes.append(([len(a) for a in ax] + [1, 1, 1])[:5])
+        axes.extend(ax)
+        v = np.asarray(t.values, float).reshape(-1)
+        values.append(v)
+        ap.append(ap[-1] + sum(len(a) for a in ax))
+        vp.append(vp[-1] + len(v))
+    arr = dict(kind=_i32([t.kind for t in tables]), table_num=_i32([t.table_num for t in tables]), flo_type=_i32([t.flo_type for t in tables]),
+               wfr_type=_i32([t.wfr_type for t in tables]), gfr_type=_i32([t.gfr_type for t in tables]), datum_depth=_f64([t.datum_depth for t in tables]),
+               axis_sizes=_i32(np.asarray(sizes).reshape(-1)), axis_pointers=_i32(ap), axes=_f64(np.concatenate(axes)), value_pointers=_i32(vp),
+               values=_f64(np.concatenate(values)))
+    s = VfpTables(len(tables))
+    for name, _ in VfpTables._fields_[1:]:
+        setattr(s, name, arr[name].ctypes.data)
+    return s, arr
+
+
+def make_std_wells_thp(t, num_wells):
+    """dict(vfp_table, thp_limit, alq, dh per well; vfp_table 0: no limit) -> (StdWellsThp struct, keep-alive dict); None -> (None, {})"""
+    if t is None:
+        return None, {}
+    arr = dict(vfp_table=_i32(np.asarray(t["vfp_table"]).reshape(-1)), thp_limit=_f64(np.asarray(t["thp_limit"], float).reshape(-1)),
+               alq=_f64(np.asarray(t["alq"], float).reshape(-1)), dh=_f64(np.asarray(t["dh"], float).reshape(-1)))
+    if any(len(a) != num_wells for a in arr.values()):
+        raise ValueError("make_std_wells_thp: array lengths do not fit the %d wells set" % num_wells)
+    s = StdWellsThp()
+    for name, _ in StdWellsThp._fields_:
+        setattr(s, name, arr[name].ctypes.data)
+    return s, arr
+
+
 def make_std_wells_wellbore(w, num_wells, nperf):
     """dict(perf_depth per perforation; ref_depth, preferred_phase (0 water, 1 oil, 2 gas) per well) for a list of num_wells wells and nperf
     perforations -> (StdWellsWellbore struct, keep-alive dict); None -> (None, {}).  Ragged input raises ValueError."""
@@ -287,6 +337,8 @@ def lib():
         L.opmhip_synchronize.argtypes = [vp]
         L.opmhip_comm_info.argtypes = [vp, ip]
         L.opmhip_comm_selftest.argtypes = [vp, dp]
+        L.opmhip_set_vfp_tables.argtypes = [vp, C.POINTER(VfpTables)]
+        L.opmhip_vfp_probe.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -382,6 +434,23 @@ class HipSolver:
         if rc < 0:
             raise OpmHipError(rc, lib().opmhip_last_error(self._h).decode())
         return rc
+
+    def set_vfp_tables(self, tables):
+        """opmhip_set_vfp_tables: the VFPPROD / VFPINJ tables (list of vfp.VFPTable, SI) resident on the device; None or empty clears them.  A
+        refused call leaves the previous set in force."""
+        vt, keep = make_vfp_tables(tables)
+        self._check(lib().opmhip_set_vfp_tables(self._h, C.byref(vt) if vt else None))
+
+    def vfp_probe(self, kind, table_num, aqua, liquid, vapour, thp, alq=0.0, bhp_target=None):
+        """opmhip_vfp_probe: the device's VFP functions at given points -> (n, 10): bhp, dthp, dwfr, dgfr, dalq, dflo, d/daqua, d/dliquid, d/dvapour
+        and thp(..., bhp_target) (0 without a target) - vfp.probe's columns, bit for bit"""
+        vals = (aqua, liquid, vapour, thp, alq) + (() if bhp_target is None else (bhp_target,))
+        a = [np.ascontiguousarray(v) for v in np.broadcast_arrays(*(np.atleast_1d(np.asarray(v, np.float64)) for v in vals))]
+        n = len(a[0])
+        tgt = a.pop() if bhp_target is not None else None
+        out = np.zeros((n, 10))
+        self._check(lib().opmhip_vfp_probe(self._h, int(kind), int(table_num), n, *[_ptr(v) for v in a], _ptr(tgt), _ptr(out)))
+        return out
 
     def set_pattern(self, Nb, rows, cols):
         rows, cols = _i32(rows), _i32(cols)
@@ -657,6 +726,8 @@ def _bind_assembly(L):
     L.opmhip_set_std_wells_perf_state.argtypes = [vp, vp, vp]
     L.opmhip_set_std_wells_crossflow.argtypes = [vp, vp]
     L.opmhip_get_std_wells_rate_dq.argtypes = [vp, vp]
+    L.opmhip_set_std_wells_thp.argtypes = [vp, C.POINTER(StdWellsThp)]
+    L.opmhip_get_std_wells_thp.argtypes = [vp, vp, vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -969,6 +1040,20 @@ class HipModel(HipSolver):
                 raise ValueError(str(e)) from e
             raise
 
+    def set_std_wells_thp(self, thp):
+        """opmhip_set_std_wells_thp: the THP limits (dict, see make_std_wells_thp); None switches them off.  A refused call leaves the previous
+        values in force."""
+        t, keep = make_std_wells_thp(thp, getattr(self, "_nsw", 0))
+        self._check(lib().opmhip_set_std_wells_thp(self._h, C.byref(t) if t else None))
+
+    def std_wells_thp(self):
+        """opmhip_get_std_wells_thp: dict(thp: what the last begin_iteration formed from the well's state, dp: this time step's hydrostatic
+        correction, bhp_from_thp: V - dp of the last assemble) per well; zeros for wells without a limit"""
+        n = getattr(self, "_nsw", 0)
+        out = dict(thp=np.zeros(n), dp=np.zeros(n), bhp_from_thp=np.zeros(n))
+        self._check(lib().opmhip_get_std_wells_thp(self._h, _ptr(out["thp"]), _ptr(out["dp"]), _ptr(out["bhp_from_thp"])))
+        return out
+
     def std_wells_rate_dq(self):
         """for tests: d rate_c / d q_j of the last assemble, (perforations, 3 components, 3 rate unknowns); zeros without crossflow"""
         dq = np.zeros((getattr(self, "_nswperf", 0), 3, 3))
@@ -1009,7 +1094,7 @@ class HipModel(HipSolver):
         self._check(lib().opmhip_std_wells_update(self._h, float(relax)))
 
     def get_std_wells(self):
-        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp, r_w (wells, 4))"""
+        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp / 2 thp, r_w (wells, 4))"""
         n = getattr(self, "_nsw", 0)
         x, ctl, rw = np.zeros((n, 4)), np.zeros(n, np.int32), np.zeros((n, 4))
         self._check(lib().opmhip_get_std_wells(self._h, _ptr(x), _ptr(ctl), _ptr(rw)))

@@ -1520,6 +1520,213 @@ void launch_aquifer_end(opmhip_ctx* c, double dt) {
     hipLaunchKernelGGL(k_aquifer_end, dim3((Q.num + 63) / 64), dim3(64), 0, c->stream, Q.num, dt, Q.d_ptr, Q.d_par, Q.d_q, Q.d_state);
 }
 
+// ============================== VFP tables (opmhip_set_vfp_tables) ==============================================
+// wells/VFPHelpers.cpp - findInterpData (:81-145), interpolate (:181-287, :289-341), bhp (:343-385), findTHP (:387-499), findX (:40-66),
+// getFlo / getWFR / getGFR (:501-590) -, the AD forms of bhp (VFPProdProperties.cpp:142-172, VFPInjProperties.cpp:88-112) and thp
+// (VFPProdProperties.cpp:37-82, VFPInjProperties.cpp:47-74) in the statement order of vfp.py: one body for opmhip_vfp_probe and for the
+// wells' THP control.  No contraction (the library's build), plain loads: the 32 corners are a gather from a table of a few tens of KB
+// that lives in L2.  UNVERIFIED, as vfp.py says: a chop or a threshold that binds, ties included, has derivative zero.
+struct VfpTab { const int* desc; const double* dbl; };   // one table's descriptor (vfp_tables.hpp), the set's doubles
+struct VfpInterp { int i0, i1; double inv, fac; };
+struct VfpVar { double v, d[3]; };                        // a value and its derivatives by (aqua, liquid, vapour)
+__device__ __forceinline__ const double* vfp_axis(const VfpTab T, int a) { return T.dbl + T.desc[VFP_AXIS + a]; }
+__device__ VfpInterp vfp_find_interp(double value_in, const double* __restrict__ axis, int n) {
+    VfpInterp r{0, 0, 0.0, 0.0};
+    const double value = value_in < 0.0 ? 0.0 : value_in;   // no extrapolation towards negative ranges
+    if (n == 1) return r;
+    if (value < axis[0]) r.i1 = 1;
+    else if (value >= axis[n - 1]) r.i1 = n - 1;
+    else {
+        r.i1 = n - 1;   // (a NaN finds nothing: the last interval)
+        for (int i = 1; i < n; ++i)
+            if (axis[i] >= value) { r.i1 = i; break; }
+    }
+    r.i0 = r.i1 - 1;
+    const double start = axis[r.i0], end = axis[r.i1];
+    if (end > start) { r.inv = 1.0 / (end - start); r.fac = (value - start) * r.inv; }
+    if (r.fac > 3.0) r.fac = 3.0;
+    return r;
+}
+// c[2^N], the corner of the axis reduced first in the lowest bit: N reductions (t1 * a) + (t2 * b), t2 = fac[s], t1 = 1.0 - t2
+template <int N>
+__device__ __forceinline__ double vfp_reduce(double* c, const double* fac) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        const double t2 = fac[s], t1 = 1.0 - t2;
+#pragma unroll
+        for (int k = 0; k < (1 << (N - 1 - s)); ++k) c[k] = (t1 * c[2 * k]) + (t2 * c[2 * k + 1]);
+    }
+    return c[0];
+}
+// VFPPROD: out[0] = value and, DERIV, out[1..5] = dthp, dwfr, dgfr, dalq, dflo.  Corner index t * 16 + w * 8 + g * 4 + a * 2 + f; every
+// derivative (hi - lo) * inv_dist per corner pair, the same at both ends; all fields reduced along flo, alq, gfr, wfr, thp
+template <bool DERIV>
+__device__ void vfp_interp_prod(const VfpTab T, const VfpInterp& fl, const VfpInterp& th, const VfpInterp& wf, const VfpInterp& gf, const VfpInterp& al, double* out) {
+    const int* d = T.desc;
+    const double* __restrict__ val = T.dbl + d[VFP_VALUES];
+    const size_t nf = d[VFP_N], nw = d[VFP_N + 2], ng = d[VFP_N + 3], na = d[VFP_N + 4];
+    double v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const size_t ti = (i & 16) ? th.i1 : th.i0, wi = (i & 8) ? wf.i1 : wf.i0, gi = (i & 4) ? gf.i1 : gf.i0, ai = (i & 2) ? al.i1 : al.i0, fi = (i & 1) ? fl.i1 : fl.i0;
+        v[i] = val[(((ti * nw + wi) * ng + gi) * na + ai) * nf + fi];
+    }
+    const double fac[5] = {fl.fac, al.fac, gf.fac, wf.fac, th.fac};
+    if (DERIV) {
+        const double inv[5] = {th.inv, wf.inv, gf.inv, al.inv, fl.inv};
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int b = 16 >> k;
+            double dd[32];
+#pragma unroll
+            for (int i = 0; i < 32; ++i) dd[i] = (v[i | b] - v[i & ~b]) * inv[k];
+            out[1 + k] = vfp_reduce<5>(dd, fac);
+        }
+    }
+    out[0] = vfp_reduce<5>(v, fac);
+}
+// VFPINJ: out[0] = value and, DERIV, out[1] = dthp, out[2] = dflo.  Corner index t * 2 + f; reduced along flo, then thp
+template <bool DERIV>
+__device__ void vfp_interp_inj(const VfpTab T, const VfpInterp& fl, const VfpInterp& th, double* out) {
+    const double* __restrict__ val = T.dbl + T.desc[VFP_VALUES];
+    const size_t nf = T.desc[VFP_N];
+    double v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = val[(size_t)((i & 2) ? th.i1 : th.i0) * nf + ((i & 1) ? fl.i1 : fl.i0)];
+    const double fac[2] = {fl.fac, th.fac};
+    if (DERIV) {
+        const double inv[2] = {th.inv, fl.inv};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int b = 2 >> k;
+            double dd[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dd[i] = (v[i | b] - v[i & ~b]) * inv[k];
+            out[1 + k] = vfp_reduce<2>(dd, fac);
+        }
+    }
+    out[0] = vfp_reduce<2>(v, fac);
+}
+__device__ __forceinline__ VfpVar vfp_var(double v, double da, double dl, double dv) { return VfpVar{v, {da, dl, dv}}; }
+__device__ __forceinline__ VfpVar vfp_chop(VfpVar x) {   // chopNegativeValues: max(0, x), std::max's way
+    if (!(0.0 < x.v)) x = vfp_var(0.0, 0.0, 0.0, 0.0);
+    return x;
+}
+// chop(a) / max(1e-12, chop(c)); the quotient rule as (a' - v * b') / b with v = a / b
+__device__ VfpVar vfp_quotient(VfpVar a, VfpVar c) {
+    a = vfp_chop(a);
+    c = vfp_chop(c);
+    if (!(1e-12 < c.v)) c = vfp_var(1e-12, 0.0, 0.0, 0.0);
+    VfpVar o;
+    o.v = a.v / c.v;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o.d[j] = (a.d[j] - o.v * c.d[j]) / c.v;
+    return o;
+}
+__device__ VfpVar vfp_flo(const int* desc, double aq, double li, double va) {   // getFlo: the sign of the rates kept
+    const int type = desc[VFP_FLO_TYPE];
+    if (type == 0) return vfp_var(li, 0.0, 1.0, 0.0);
+    if (type == 2) return vfp_var(va, 0.0, 0.0, 1.0);
+    return desc[VFP_KIND] == 0 ? vfp_var(aq + li, 1.0, 1.0, 0.0) : vfp_var(aq, 1.0, 0.0, 0.0);   // LIQ / WAT
+}
+__device__ VfpVar vfp_wfr(const int* desc, double aq, double li, double va) {
+    const int type = desc[VFP_WFR_TYPE];
+    const VfpVar num = vfp_var(-aq, -1.0, 0.0, 0.0);
+    if (type == 0) return vfp_quotient(num, vfp_var(-li, 0.0, -1.0, 0.0));          // WOR
+    if (type == 1) return vfp_quotient(num, vfp_var(-aq - li, -1.0, -1.0, 0.0));    // WCT
+    return vfp_quotient(num, vfp_var(-va, 0.0, 0.0, -1.0));                         // WGR
+}
+__device__ VfpVar vfp_gfr(const int* desc, double aq, double li, double va) {
+    const int type = desc[VFP_GFR_TYPE];
+    if (type == 0) return vfp_quotient(vfp_var(-va, 0.0, 0.0, -1.0), vfp_var(-li, 0.0, -1.0, 0.0));          // GOR
+    if (type == 1) return vfp_quotient(vfp_var(-va, 0.0, 0.0, -1.0), vfp_var(-li - aq, -1.0, -1.0, 0.0));    // GLR
+    return vfp_quotient(vfp_var(-li, 0.0, -1.0, 0.0), vfp_var(-va, 0.0, 0.0, -1.0));                         // OGR
+}
+// out[9]: bhp, dthp, dwfr, dgfr, dalq, dflo, d/daqua, d/dliquid, d/dvapour (an injector's dwfr, dgfr, dalq: 0)
+__device__ void vfp_bhp(const VfpTab T, double aq, double li, double va, double thp, double alq, double* out) {
+    const int* d = T.desc;
+    const VfpVar f = vfp_flo(d, aq, li, va);
+    const VfpInterp th = vfp_find_interp(thp, vfp_axis(T, 1), d[VFP_N + 1]);
+    if (d[VFP_KIND] == 0) {
+        const VfpVar w = vfp_wfr(d, aq, li, va), g = vfp_gfr(d, aq, li, va);
+        const VfpInterp fl = vfp_find_interp(-f.v, vfp_axis(T, 0), d[VFP_N]), wf = vfp_find_interp(w.v, vfp_axis(T, 2), d[VFP_N + 2]),
+                        gf = vfp_find_interp(g.v, vfp_axis(T, 3), d[VFP_N + 3]), al = vfp_find_interp(alq, vfp_axis(T, 4), d[VFP_N + 4]);
+        vfp_interp_prod<true>(T, fl, th, wf, gf, al, out);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[6 + j] = ((out[2] * w.d[j]) + (out[3] * g.d[j])) - (out[5] * f.d[j]);
+    } else {
+        double r[3];
+        vfp_interp_inj<true>(T, vfp_find_interp(f.v, vfp_axis(T, 0), d[VFP_N]), th, r);
+        out[0] = r[0]; out[1] = r[1]; out[2] = 0.0; out[3] = 0.0; out[4] = 0.0; out[5] = r[2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[6 + j] = r[2] * f.d[j];
+    }
+}
+__device__ __forceinline__ double vfp_find_x(double x0, double x1, double y0, double y1, double y) {
+    const double dx = x1 - x0, dy = y1 - y0;
+    return dy != 0.0 ? x0 + (y - y0) * (dx / dy) : x1;
+}
+// The inverse look-up: the table's BHP at every entry of its THP axis for these rates, then findTHP - in one pass over the axis, which
+// keeps what findTHP can ask for: whether the values are sorted, the first and the last interval, the first interval with y0 < bhp <= y1.
+// -1e100 where the reference throws; 0 for a THP axis of fewer than two entries (refused where it matters: opmhip_set_std_wells_thp)
+__device__ double vfp_thp(const VfpTab T, double aq, double li, double va, double bhp, double alq) {
+    const int* d = T.desc;
+    const int nthp = d[VFP_N + 1];
+    if (nthp < 2) return 0.0;
+    const bool prod = d[VFP_KIND] == 0;
+    const double* __restrict__ taxis = vfp_axis(T, 1);
+    double flo = vfp_flo(d, aq, li, va).v;
+    VfpInterp wf{0, 0, 0.0, 0.0}, gf = wf, al = wf;
+    if (prod) {
+        double wfr = 0.0, gfr = 0.0;
+        if (aq == 0.0 && li == 0.0 && va == 0.0) flo = vfp_axis(T, 0)[0];   // likely the initial state: no extrapolation, zero fractions
+        else { flo = -flo; wfr = vfp_wfr(d, aq, li, va).v; gfr = vfp_gfr(d, aq, li, va).v; }
+        wf = vfp_find_interp(wfr, vfp_axis(T, 2), d[VFP_N + 2]);
+        gf = vfp_find_interp(gfr, vfp_axis(T, 3), d[VFP_N + 3]);
+        al = vfp_find_interp(alq, vfp_axis(T, 4), d[VFP_N + 4]);
+    }
+    const VfpInterp fl = vfp_find_interp(flo, vfp_axis(T, 0), d[VFP_N]);
+    bool sorted = true;
+    int in = -1;
+    double b0 = 0.0, b1 = 0.0, bm = 0.0, bl = 0.0, iy0 = 0.0, iy1 = 0.0;   // the first two, the last two, the interval found
+    for (int i = 0; i < nthp; ++i) {
+        const VfpInterp th = vfp_find_interp(taxis[i], taxis, nthp);
+        double b;
+        if (prod) vfp_interp_prod<false>(T, fl, th, wf, gf, al, &b);
+        else vfp_interp_inj<false>(T, fl, th, &b);
+        if (i == 0) b0 = b;
+        else {
+            if (i == 1) b1 = b;
+            if (b < bl) sorted = false;
+            if (in < 0 && bl < bhp && bhp <= b) { in = i - 1; iy0 = bl; iy1 = b; }
+        }
+        bm = bl;
+        bl = b;
+    }
+    const int where = bhp <= b0 ? 0 : (bhp > bl ? 1 : 2);   // below, above, neither
+    if (in >= 0 && (!sorted || where == 2)) return vfp_find_x(taxis[in], taxis[in + 1], iy0, iy1, bhp);
+    if (where == 0) return vfp_find_x(taxis[0], taxis[1], b0, b1, bhp);
+    if (where == 1) return vfp_find_x(taxis[nthp - 2], taxis[nthp - 1], bm, bl, bhp);
+    return -1e100;
+}
+// opmhip_vfp_probe: one lane per point; in: aqua | liquid | vapour | thp | alq | bhp_target, n each
+__global__ __launch_bounds__(64) void k_vfp_probe(VfpTab T, int n, const double* __restrict__ in, int has_target, double* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const size_t N = n;
+    const double aq = in[i], li = in[N + i], va = in[2 * N + i], alq = in[4 * N + i];
+    double o[10];
+    vfp_bhp(T, aq, li, va, in[3 * N + i], alq, o);
+    o[9] = has_target ? vfp_thp(T, aq, li, va, in[5 * N + i], alq) : 0.0;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) out[(size_t)10 * i + k] = o[k];
+}
+int launch_vfp_probe(opmhip_ctx* c, int table, int n, const double* d_in, bool has_target, double* d_out) {
+    const VfpDev& V = c->asmb.vfp;
+    hipLaunchKernelGGL(k_vfp_probe, dim3((n + 63) / 64), dim3(64), 0, c->stream, VfpTab{V.d_desc + (size_t)table * VFP_DESC, V.d_dbl}, n, d_in, has_target ? 1 : 0, d_out);
+    return OPMHIP_SUCCESS;
+}
+
 // ============================== standard wells on the device (opmhip_set_std_wells) ===========================
 // computePerfRate and assembleWellEqWithoutIteration (wells/StandardWell_impl.hpp:195-420, 516-640) in the minimal form and in the
 // operation order of wells.py StandardWells(arithmetic="stated") - the library is built with -ffp-contract=off, so that every
@@ -1694,8 +1901,20 @@ struct SwArrays {
     double* wbstate;                            // then: p_perf [nperf] | the rates of the last assembly [nperf * 3]
     const int* cf;                              // per well: crossflow allowed (read by the CF instantiations only; NULL without a flag)
     double* dq;                                 // then: d rate_c / d q_j of the last assembly [nperf * 9]
-    double *control, *rw, *flag;                // d_pack's other fields: per well 0.0 rate / 1.0 bhp; r_w, 4 per well; the zero-pivot flag
+    double *control, *rw, *flag;                // d_pack's other fields: per well 0.0 rate / 1.0 bhp / 2.0 thp; r_w, 4 per well; the zero-pivot flag
 };
+// THP limits (opmhip_set_std_wells_thp; read by the THP instantiations only).  table: per well the index of its VFP table, -1: no limit; wd:
+// per well limit, alq, dh; out: thp of the last controls [num] | dp of this time step [num] | V - dp of the last assembly [num]; wbdens: the
+// well-bore densities per perforation under that head model
+struct SwThp {
+    const int* table;
+    const double* wd;
+    double* out;
+    const int* desc;
+    const double* dbl;
+    const double* wbdens;
+};
+__device__ __forceinline__ VfpTab sw_thp_table(const SwThp& H, int w) { return VfpTab{H.desc + (size_t)H.table[w] * VFP_DESC, H.dbl}; }
 // One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
 // global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
 // without a flowing completion, and D^-1.  SOLVE: the well alone against the frozen reservoir (StandardWells.solve_well_equations) - the
@@ -1703,8 +1922,12 @@ struct SwArrays {
 // heads and the flag is written.  CF: the list has a well with crossflow (launched in place of the other instantiation, for all its
 // wells): 15 sums per lane - the 9 d rate / d q beside the 6 -, the full D, C's first three rows; the well bore's fractions are formed
 // by lane 0 once per evaluation from x in LDS.  A well without the switch, or without a reversed perforation, gets today's bits.
-template <bool SOLVE, bool CF>
-__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, const double* __restrict__ iq, int first) {
+// THP: the list has a well with a THP limit (launched in place of the other instantiation, for all its wells).  SOLVE then sets, after the
+// heads, dp = (rho g) dh of every such well - rho what the head model uses for the first perforation (WellHelpers.hpp:149-155) -; under
+// control 2 the control row is bhp - (V - dp) with V = vfp_bhp at the limit (control_eq = bhp - bhp_from_thp, WellInterfaceEval.cpp:351-354,
+// 433-436, 463-504); the assembling form also leaves V - dp of every well with a limit.  Every other well gets today's bits.
+template <bool SOLVE, bool CF, bool THP>
+__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, int ncell, const double* __restrict__ iq, int first) {
     constexpr int NS = CF ? 15 : 6;
     __shared__ double sums[64 * NS];
     __shared__ double xs[4];
@@ -1719,10 +1942,19 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
     double* flag = W.flag + w;
     if (SOLVE && !W.wellbore)   // calculate_explicit_quantities: (rho_o g) dz, constant through the time step; lane l owns perforations pb + l + 64 k here and below
         for (int p = pb + lane; p < pe; p += 64) W.head[p] = (iq_at(iq, ncell, F_RHO + OIL, W.cell[p])[0] * GRAVITY) * W.dz[p];
+    const bool limited = THP && H.table[w] >= 0;   // uniform: the well's
+    double dp = 0.0;                               // lane 0's
     if (lane == 0) {
         for (int i = 0; i < 4; ++i) xs[i] = x[i];
         if (SOLVE && first) xs[3] = iq_at(iq, ncell, F_P + OIL, W.cell[pb])[0] + (producer ? -1e5 : 1e5);
         s_active = 1;
+        if (limited) {
+            if (SOLVE) {
+                const double rho = W.wellbore ? H.wbdens[pb] : iq_at(iq, ncell, F_RHO + OIL, W.cell[pb])[0];
+                dp = (rho * GRAVITY) * H.wd[3 * w + 2];
+                H.out[(size_t)W.num + w] = dp;
+            } else dp = H.out[(size_t)W.num + w];
+        }
     }
     __syncthreads();
     for (int it = 0; it < (SOLVE ? 20 : 1); ++it) {
@@ -1782,7 +2014,19 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, int ncell, cons
             if (CF)
                 for (int c = 0; c < 3; ++c)
                     for (int j = 0; j < 3; ++j) D[c * 4 + j] = D[c * 4 + j] - S[6 + c * 3 + j];
-            if (W.control[w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
+            const bool thp = limited && W.control[w] == 2.0;
+            double V[9] = {0.0}, fromThp = 0.0;
+            if (limited && (thp || !SOLVE)) {   // the table's bhp at the limit and the rates now present, brought to the reference depth
+                vfp_bhp(sw_thp_table(H, w), xs[EQ_WATER], xs[EQ_OIL], xs[EQ_GAS], H.wd[3 * w], H.wd[3 * w + 1], V);
+                fromThp = V[0] - dp;
+                if (!SOLVE) H.out[(size_t)2 * W.num + w] = fromThp;
+            }
+            if (thp) {
+                r[3] = xs[3] - fromThp;
+                D[12 + EQ_OIL] = 0.0 - V[7]; D[12 + EQ_WATER] = 0.0 - V[6]; D[12 + EQ_GAS] = 0.0 - V[8];
+                D[15] = 1.0;
+            }
+            else if (W.control[w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
             else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
             // a well none of whose completions flows has no rate that answers to its bottom-hole pressure: it keeps the pressure
             if (D[3] == 0.0 && D[7] == 0.0 && D[11] == 0.0 && D[15] == 0.0) { r[3] = 0.0; D[12] = D[13] = D[14] = 0.0; D[15] = 1.0; }
@@ -1945,9 +2189,14 @@ __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays 
         for (int k = 0; k < 3; ++k) Q.out[2 * np + 3 * (size_t)p + k] = mix[k];
     }
 }
-// update_well_controls, one lane per well
+// update_well_controls, one lane per well.  THP (the list has a well with a THP limit): the limits in the reference's order
+// (WellInterfaceFluidSystem.cpp:170-268, :100-166), the first that is violated and is not the control in force wins - BHP, the rate
+// target, THP: current = thp(table, q_w, q_o, q_g, bhp + dp, alq) (StandardWellGeneric.cpp:116-156, StandardWellEval.cpp:546-583), a
+// producer switches when its limit > current, an injector when its limit < current, to control 2 with bhp = V - dp at the rates at hand
+// (updateWellStateWithTarget's THP case, WellInterface_impl.hpp:659-667, 882-890).  A well without a limit takes today's two branches.
+template <bool THP>
 __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ xs,
-                                                           double* __restrict__ controls) {
+                                                           double* __restrict__ controls, SwThp H) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= num) return;
     const bool producer = wi[3 * w] != 0;
@@ -1955,9 +2204,20 @@ __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* _
     const double target = wd[2 * w], limit = wd[2 * w + 1];
     double* x = xs + (size_t)4 * w;
     double* control = controls + w;
-    if (*control == 0.0) {
-        if ((producer && x[3] < limit) || (!producer && x[3] > limit)) { *control = 1.0; x[3] = limit; }
-    } else if ((producer ? -1.0 : 1.0) * x[comp] > target) *control = 0.0;
+    const bool limited = THP && H.table[w] >= 0;
+    double current = 0.0;
+    if (THP) {
+        if (limited) current = vfp_thp(sw_thp_table(H, w), x[EQ_WATER], x[EQ_OIL], x[EQ_GAS], x[3] + H.out[(size_t)num + w], H.wd[3 * w + 1]);
+        H.out[w] = current;
+    }
+    if (*control != 1.0 && ((producer && x[3] < limit) || (!producer && x[3] > limit))) { *control = 1.0; x[3] = limit; }
+    else if (*control != 0.0 && (producer ? -1.0 : 1.0) * x[comp] > target) *control = 0.0;
+    else if (limited && *control != 2.0 && (producer ? H.wd[3 * w] > current : H.wd[3 * w] < current)) {
+        double V[9];
+        vfp_bhp(sw_thp_table(H, w), x[EQ_WATER], x[EQ_OIL], x[EQ_GAS], H.wd[3 * w], H.wd[3 * w + 1], V);
+        *control = 2.0;
+        x[3] = V[0] - H.out[(size_t)num + w];
+    }
 }
 // In front of k_assemble (and of k_aquifer_apply), one lane per DISTINCT perforated cell: the caller's source and dsource rows are kept in
 // `save`, the rates of the cell's perforations are added in perforation order (computeTotalRatesForDof)
@@ -1995,6 +2255,11 @@ __global__ __launch_bounds__(64) void k_std_wells_axpy(int n, double relax, cons
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n) x[i] = x[i] - relax * xw[i];
 }
+static SwThp std_wells_thp(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    const VfpDev& V = c->asmb.vfp;
+    return SwThp{S.d_thp_table, S.d_thp_wd, S.d_thp_out, V.d_desc, V.d_dbl, S.d_wbout};
+}
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
     return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.x(), S.d_Dmat, W.d_B, W.d_C, W.d_D,
@@ -2004,8 +2269,11 @@ static SwArrays std_wells_arrays(const WellsDev& W) {
 void launch_std_wells_solve(opmhip_ctx* c, bool first) {
     const int ps = prof_begin(c, PROF_ASSEMBLE);
     // (a list with a crossflow well runs the CF instantiation in place of the other: the number of launches is the same)
-    const auto kernel = c->wells.sw.crossflow ? k_std_wells_eq<true, true> : k_std_wells_eq<true, false>;
-    hipLaunchKernelGGL(kernel, dim3(c->wells.sw.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
+    // (... and one with a THP limit the THP instantiation)
+    const StdWellsDev& S = c->wells.sw;
+    const auto kernel = S.thp ? (S.crossflow ? k_std_wells_eq<true, true, true> : k_std_wells_eq<true, false, true>)
+                              : (S.crossflow ? k_std_wells_eq<true, true, false> : k_std_wells_eq<true, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
     prof_end(c, ps);
 }
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
@@ -2019,14 +2287,16 @@ void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
 void launch_std_wells_controls(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(k_std_wells_controls, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control());
+    const auto kernel = S.thp ? k_std_wells_controls<true> : k_std_wells_controls<false>;
+    hipLaunchKernelGGL(kernel, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control(), std_wells_thp(c));
     prof_end(c, ps);
 }
 void launch_std_wells_assemble(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    const auto kernel = S.crossflow ? k_std_wells_eq<false, true> : k_std_wells_eq<false, false>;
-    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), c->pat.Nloc, c->asmb.d_iq, 0);
+    const auto kernel = S.thp ? (S.crossflow ? k_std_wells_eq<false, true, true> : k_std_wells_eq<false, false, true>)
+                              : (S.crossflow ? k_std_wells_eq<false, true, false> : k_std_wells_eq<false, false, false>);
+    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), c->pat.Nloc, c->asmb.d_iq, 0);
     hipLaunchKernelGGL(k_std_wells_source, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_cptr, S.d_cperf, S.d_pr, c->asmb.d_source,
                        c->asmb.d_dsource, S.d_save);
     prof_end(c, ps);

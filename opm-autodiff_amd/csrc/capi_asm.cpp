@@ -11,6 +11,7 @@
 #include "fluid_tables.hpp"
 #include "internal.hpp"
 #include "source_lists.hpp"
+#include "vfp_tables.hpp"
 
 using namespace opmhip;
 
@@ -1126,6 +1127,12 @@ void std_wells_wellbore_release(opmhip_ctx* c) {   // the stream is idle
     dev_free(c, &S.d_wbout); dev_free(c, &S.d_wbscratch);
     S.wellbore = S.wb_state_set = S.wb_state_saved = S.wb_initialised_saved = false;
 }
+void std_wells_thp_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_thp_table); dev_free(c, &S.d_thp_wd); dev_free(c, &S.d_thp_out);
+    S.h_thp_table.clear();
+    S.thp = false;
+}
 void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
@@ -1133,6 +1140,7 @@ void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
     dev_free(c, &S.d_cf); dev_free(c, &S.d_dq);
     S.crossflow = false;
+    std_wells_thp_release(c);
     std_wells_wellbore_release(c);
     S.h_wi.clear(); S.h_wd.clear();
     S.num = S.nperf = S.nd = 0;
@@ -1316,7 +1324,7 @@ int opmhip_get_std_wells(opmhip_ctx* c, double* x, int* control, double* res_wel
         if (rc) return rc;
         if (x) std::memcpy(x, &h[SW_X * nw], 4 * nw * sizeof(double));
         if (control)
-            for (size_t w = 0; w < nw; ++w) control[w] = h[SW_CONTROL * nw + w] != 0.0;
+            for (size_t w = 0; w < nw; ++w) control[w] = (int)h[SW_CONTROL * nw + w];   // 0 rate, 1 bhp, 2 thp
         if (res_well) std::memcpy(res_well, &h[SW_RW * nw], 4 * nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
@@ -1329,7 +1337,10 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_state: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num;
         std::string msg;
-        if (int r = std_wells_check_state(nw, x, control, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
+        if (S.thp) {   // control 2 exists, for the wells that have a limit; everything else is looked at as before
+            if (int r = std_wells_thp_check_controls(nw, control, S.h_thp_table.data(), msg)) return fail(c, r, "%s", msg.c_str());
+            if (int r = std_wells_check_state(nw, x, nullptr, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
+        } else if (int r = std_wells_check_state(nw, x, control, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
         S.assembled = false;   // from here on the device state changes: nothing a refusal above could have left half done
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // rare: events and restarts
@@ -1477,6 +1488,127 @@ int opmhip_set_std_wells_perf_state(opmhip_ctx* c, const double* perf_pressure, 
         else if (!S.wb_state_set) OPMHIP_HIP(c, hipMemset(S.d_wbstate + np, 0, 3 * np * sizeof(double)));
         OPMHIP_HIP(c, hipDeviceSynchronize());
         S.wb_state_set = true;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+// ---- VFP tables, the THP limit of the resident wells ---------------------------------------------------------------------------------------
+int opmhip_set_vfp_tables(opmhip_ctx* c, const opmhip_vfp_tables* tables) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        VfpDev& V = c->asmb.vfp;
+        if (c->wells.sw.thp)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_vfp_tables: the resident wells hold THP limits that name the tables in force; switch them off first (opmhip_set_std_wells_thp(NULL))");
+        VfpPacked P;
+        if (tables && tables->num_tables != 0) {   // everything is looked at before anything changes: a refused call leaves the previous set in force
+            std::string msg;
+            if (int r = vfp_pack(tables, P, msg)) return fail(c, r, "%s", msg.c_str());
+        }
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        int* d_desc = nullptr;
+        double* d_dbl = nullptr;
+        if (P.num > 0) {
+            int r;
+            if ((r = dev_upload(c, &d_desc, P.desc)) || (r = dev_upload(c, &d_dbl, P.dbl))) {
+                dev_free(c, &d_desc); dev_free(c, &d_dbl);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        dev_free(c, &V.d_desc); dev_free(c, &V.d_dbl);
+        V.d_desc = d_desc; V.d_dbl = d_dbl;
+        V.h = std::move(P);
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_vfp_probe(opmhip_ctx* c, int kind, int table_num, int n, const double* aqua, const double* liquid, const double* vapour, const double* thp,
+                     const double* alq, const double* bhp_target, double* out) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const VfpDev& V = c->asmb.vfp;
+        if (V.h.num == 0) return fail(c, OPMHIP_NOT_READY, "vfp_probe before set_vfp_tables");
+        const int table = vfp_find(V.h, kind, table_num);
+        if (table < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "vfp_probe: there is no table %d of kind %d (0 VFPPROD, 1 VFPINJ)", table_num, kind);
+        if (n < 0 || (n > 0 && (!aqua || !liquid || !vapour || !thp || !out || (kind == 0 && !alq)))) return fail(c, OPMHIP_INVALID_ARGUMENT, "vfp_probe: null array");
+        if (n == 0) return OPMHIP_SUCCESS;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        struct Scratch { double *in = nullptr, *out = nullptr; ~Scratch() { if (in) (void)hipFree(in); if (out) (void)hipFree(out); } } S;
+        OPMHIP_HIP(c, hipMalloc((void**)&S.in, (size_t)6 * n * sizeof(double)));
+        OPMHIP_HIP(c, hipMalloc((void**)&S.out, (size_t)10 * n * sizeof(double)));
+        const double* src[6] = {aqua, liquid, vapour, thp, kind == 0 ? alq : nullptr, bhp_target};
+        for (int k = 0; k < 6; ++k) {
+            if (src[k]) OPMHIP_HIP(c, hipMemcpyAsync(S.in + (size_t)k * n, src[k], (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            else OPMHIP_HIP(c, hipMemsetAsync(S.in + (size_t)k * n, 0, (size_t)n * sizeof(double), c->stream));
+        }
+        launch_vfp_probe(c, table, n, S.in, bhp_target != nullptr, S.out);
+        OPMHIP_HIP(c, hipGetLastError());
+        OPMHIP_HIP(c, hipMemcpyAsync(out, S.out, (size_t)10 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_thp(opmhip_ctx* c, const opmhip_std_wells_thp* thp) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        const VfpDev& V = c->asmb.vfp;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_thp: no resident list (opmhip_set_std_wells)");
+        if (thp && V.h.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_thp: no VFP tables (opmhip_set_vfp_tables)");
+        const size_t nw = S.num;
+        std::vector<int> table(nw, -1);
+        std::vector<double> wd;
+        bool any = false;
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the previous values in force
+        if (thp)
+            if (int r = std_wells_thp_lists(thp, nw, S.h_wi.data(), V.h, table, wd, any, msg)) return fail(c, r, "%s", msg.c_str());
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if (S.thp) {   // a well under THP control keeps its limit: the control row would have no table to read
+            std::vector<double> ctl(nw);
+            OPMHIP_HIP(c, hipMemcpy(ctl.data(), S.control(), nw * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < nw; ++w)
+                if (ctl[w] == 2.0 && table[w] < 0)
+                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_thp: well %zu is under THP control and would lose its limit; put it under another control first (opmhip_set_std_wells_state)", w);
+        }
+        int* d_table = nullptr;
+        double *d_wd = nullptr, *d_out = nullptr;
+        if (any) {
+            int r;
+            if ((r = dev_upload(c, &d_table, table)) || (r = dev_upload(c, &d_wd, wd)) || (r = dev_upload(c, &d_out, std::vector<double>(3 * nw, 0.0)))) {
+                dev_free(c, &d_table); dev_free(c, &d_wd); dev_free(c, &d_out);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        std_wells_thp_release(c);
+        S.d_thp_table = d_table; S.d_thp_wd = d_wd; S.d_thp_out = d_out;
+        if (any) S.h_thp_table = std::move(table);
+        S.thp = any;
+        S.assembled = false;   // the control rows of the last assembly are no longer the model's
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_thp(opmhip_ctx* c, double* thp, double* dp, double* bhp_from_thp) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        const size_t nw = S.num;
+        std::vector<double> h(3 * nw, 0.0);
+        if (S.thp) {
+            OPMHIP_HIP(c, hipSetDevice(c->device));
+            OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+            OPMHIP_HIP(c, hipMemcpy(h.data(), S.d_thp_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t w = 0; w < nw; ++w)
+                if (S.h_thp_table[w] < 0) h[w] = h[nw + w] = h[2 * nw + w] = 0.0;
+        }
+        if (thp) std::memcpy(thp, &h[0], nw * sizeof(double));
+        if (dp) std::memcpy(dp, &h[nw], nw * sizeof(double));
+        if (bhp_from_thp) std::memcpy(bhp_from_thp, &h[2 * nw], nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
 }

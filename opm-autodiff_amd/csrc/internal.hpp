@@ -14,6 +14,7 @@
 
 #include "../../include/opmhip.h"
 #include "cpr_setup.hpp"
+#include "vfp_tables.hpp"
 
 namespace opmhip {
 
@@ -208,6 +209,13 @@ struct StdWellsDev {
     bool crossflow = false;
     int* d_cf = nullptr;
     double* d_dq = nullptr;
+    // THP limits (opmhip_set_std_wells_thp): set only while some well of the list has one.  d_thp_table: per well the index of its VFP
+    // table (-1: no limit), h_thp_table its host copy; d_thp_wd: per well limit, alq, dh; d_thp_out: thp of the last controls | dp of this
+    // time step | V - dp of the last assemble (3 num doubles, field-major)
+    bool thp = false;
+    std::vector<int> h_thp_table;
+    int* d_thp_table = nullptr;
+    double *d_thp_wd = nullptr, *d_thp_out = nullptr;
     double* x() const { return d_pack + (size_t)SW_X * num; }
     double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
     double* rw() const { return d_pack + (size_t)SW_RW * num; }
@@ -274,9 +282,17 @@ struct AquifersDev {
     hipEvent_t ev_step = nullptr;                                     // "h_step has been read"
 };
 
+// VFP tables (opmhip_set_vfp_tables): the packed host form (vfp_tables.hpp) and its two device arrays, resident for the context's life
+struct VfpDev {
+    VfpPacked h;
+    int* d_desc = nullptr;
+    double* d_dbl = nullptr;
+};
+
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
 struct AsmDev {
     AquifersDev aq;
+    VfpDev vfp;
     bool fluid_set = false, static_set = false, state_set = false, assembled = false;
     double *d_tab_dbl = nullptr;
     int* d_tab_idx = nullptr;
@@ -762,6 +778,8 @@ void launch_source_scatter(opmhip_ctx* c, int n, const int* d_pos, const double*
 int iq_doubles_per_cell(const opmhip_ctx* c);
 int asm_max_rows();
 int launch_fluid_probe(opmhip_ctx* c, int pr, int sr, int n, const double* d_in, double* d_out);
+// opmhip_vfp_probe: table = the index into the packed set; d_in = aqua | liquid | vapour | thp | alq | bhp_target (n each), d_out 10 per point
+int launch_vfp_probe(opmhip_ctx* c, int table, int n, const double* d_in, bool has_target, double* d_out);
 int launch_gas_probe(opmhip_ctx* c, int pr, int n, const double* d_in, double* d_out);
 int launch_sat_probe(opmhip_ctx* c, int sr, int cfg, const double* d_eps, int n, const double* d_in, double* d_out);
 int asm_threads();

@@ -49,8 +49,24 @@ StandardWellEval::computePerfRate (wells/StandardWellEval.cpp:1023-1090) with al
   Injectors: refused (ValueError).  In the reference an injector re-injects what crosses into it, because its composition (WFrac, GFrac)
   is an unknown while getQs pins the other components to zero; this parametrisation fixes the injected composition, and a half-measure
   would let oil leave through an injector's wellhead.
+
+A tubing-head-pressure limit (Well(thp_limit=, vfp_table=, alq=), StandardWells(vfp=[tables])): a third control beside the rate target and
+the BHP limit, through the VFPPROD (producers) / VFPINJ (injectors) tables of vfp.py.
+  dp = (rho * g) * dh, dh = the table's datum depth - the well's reference depth (wells/WellHelpers.hpp:149-155), rho what the head model
+      uses for the first perforation (the well-bore density there under "wellbore" - the reference's perf_densities_[0], getRho() -, the
+      perforated cell's oil density otherwise); set with the heads, constant through the time step's Newton iterations;
+  under ("thp", limit) the control equation is bhp - (V - dp) with V = vfp.bhp(table, q_w, q_o, q_g, limit, alq) and its derivatives by the
+      three rates (control_eq = bhp - bhp_from_thp, wells/WellInterfaceEval.cpp:351-354, 433-436; calculateBhpFromThp :463-504);
+  update_well_controls checks the limits in the reference's order (wells/WellInterfaceFluidSystem.cpp:170-268, injectors :100-166): the
+      first that is violated and is not the control in force wins - BHP, the rate target, then THP: current = vfp.thp(table, q_w, q_o, q_g,
+      bhp + dp, alq) (wells/StandardWellGeneric.cpp:116-156, wells/StandardWellEval.cpp:546-583); a producer switches when its limit >
+      current, an injector when its limit < current, and its bhp becomes V - dp at the rates at hand (updateWellStateWithTarget's THP case,
+      wells/WellInterface_impl.hpp:659-667, 882-890).
+  Left out: groups, gas lift (alq is a constant), bhpwithflo and the robust BHP-THP intersection (computeBhpAtThpLimitProd), well potentials.
 """
 import numpy as np
+
+from . import vfp as vfp_mod
 
 OIL, WATER, GAS = 0, 1, 2          # equation / component order of the blocks (csrc/assemble.hip: EQ_OIL, EQ_WATER, EQ_GAS)
 PH_W, PH_O, PH_G = 0, 1, 2         # phase order of the intensive-quantity record (opmhip_get_iq)
@@ -129,16 +145,25 @@ def row_times_vector(M, r):
 class Well:
     """name; cells: perforated cells (natural order, from the top of the well down); tw: connection transmissibility factors; ref_depth;
     producer or injector of `phase`; control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit;
-    allow_crossflow (WELSPECS item 10; producers only): perforations whose drawdown is reversed inject the well bore's mixture"""
+    allow_crossflow (WELSPECS item 10; producers only): perforations whose drawdown is reversed inject the well bore's mixture;
+    thp_limit (pascal) with vfp_table (the deck number of a VFPPROD / VFPINJ table handed to StandardWells) and alq: the tubing-head-pressure
+    limit - lower (producer) / upper (injector); control may then also be ("thp", thp_limit)"""
 
-    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil", allow_crossflow=False):
+    def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil", allow_crossflow=False,
+                 thp_limit=None, vfp_table=None, alq=0.0):
         self.name, self.cells, self.tw = name, np.asarray(cells, np.int32), np.asarray(tw, float)
         self.ref_depth, self.producer, self.inj_phase = float(ref_depth), bool(producer), inj_phase
         self.preferred_phase = preferred_phase     # a producer's (WELSPECS item 6): the well bore's content where nothing flows (head_model="wellbore")
         self.control, self.bhp_limit = control, float(bhp_limit)
-        self.rate_control = control       # the deck's rate target, kept for switching back from the BHP limit
+        self.rate_control = control       # the deck's rate target, kept for switching back from the BHP / THP limit
         self.allow_crossflow = bool(allow_crossflow)
         _crossflow_flags([self])
+        if (thp_limit is None) != (vfp_table is None):
+            raise ValueError("well %s: thp_limit and vfp_table come together" % name)
+        self.thp_limit = None if thp_limit is None else float(thp_limit)
+        self.vfp_table, self.alq = None if vfp_table is None else int(vfp_table), float(alq)
+        if control[0] == "thp" and (self.thp_limit is None or float(control[1]) != self.thp_limit):
+            raise ValueError("well %s: THP control needs thp_limit, and the limit as its target" % name)
 
 
 class CellRecords:
@@ -164,6 +189,26 @@ def _crossflow_flags(wells):
     return np.array([bool(getattr(w, "allow_crossflow", False)) for w in wells], bool)
 
 
+CONTROL_CODE = {"rate": 0, "bhp": 1, "thp": 2}     # opmhip_get_std_wells / opmhip_set_std_wells_state
+
+
+def _thp_tables(wells, tables):
+    """per well: the vfp.VFPTable of its THP limit (VFPPROD for a producer, VFPINJ for an injector, by deck number) or None"""
+    out = []
+    for w in wells:
+        if getattr(w, "thp_limit", None) is None:
+            out.append(None)
+            continue
+        kind = vfp_mod.PROD if w.producer else vfp_mod.INJ
+        t = [t for t in (tables or []) if t.kind == kind and t.table_num == w.vfp_table]
+        if len(t) != 1:
+            raise ValueError("well %s: %d %s tables with the number %d" % (w.name, len(t), "VFPPROD" if w.producer else "VFPINJ", w.vfp_table))
+        if len(t[0].thp_axis) < 2:
+            raise ValueError("well %s: the THP axis of table %d has fewer than two entries" % (w.name, w.vfp_table))
+        out.append(t[0])
+    return out
+
+
 class StandardWells:
     """All wells at once: every step below is one pass of array arithmetic over the perforations (nperf x 5: value, d/dSw, d/dp, d/dX of the
     perforated cell, d/dbhp), per-well sums in the order of the perforations.
@@ -174,10 +219,11 @@ class StandardWells:
     arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
     bit; a singular D raises SingularWellEquations there."""
 
-    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None):
+    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None):
         """head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
         pvt_region=) - capi.HipFluid(fluid), the device's, or the CPU oracle's in tests, as equil.py takes them - with the deck-level
-        tables as props.fluid (the surface densities); pvtnum: PVT region per cell (None: region 0)"""
+        tables as props.fluid (the surface densities); pvtnum: PVT region per cell (None: region 0); vfp: the vfp.VFPTable list the wells' THP
+        limits name (a list without limits computes what it computes with vfp=None)"""
         if arithmetic not in ("numpy", "stated"):
             raise ValueError("arithmetic: 'numpy' or 'stated'")
         if head_model not in HEAD_MODELS:
@@ -189,6 +235,11 @@ class StandardWells:
         self.wells = list(wells)
         self.nw = len(self.wells)
         self.allow_crossflow = _crossflow_flags(self.wells)
+        self.thp_tables = _thp_tables(self.wells, vfp)
+        self.thp_dp = np.zeros(self.nw)            # per well with a limit: (rho g) dh of this time step
+        self.thp_current = np.zeros(self.nw)       # ... the tubing-head pressure the last update_well_controls formed from the well's state
+        self.bhp_from_thp = np.zeros(self.nw)      # ... V - dp of the last assemble()
+        self._from_thp = np.zeros(self.nw)
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         self.tw = np.concatenate([w.tw for w in self.wells])
@@ -228,9 +279,20 @@ class StandardWells:
         Minimal form: the column between the reference depth and a completion weighs what the oil of the completion's cell weighs (the
         reference averages the well-bore mixture's phase densities segment by segment, StandardWellGeneric::computeConnectionPressureDelta)."""
         if self.head_model == "wellbore":
-            return self._wellbore_heads(iq)
-        q = _rows(iq, self.cells)
-        self.head = q[:, F_RHO + PH_O, 0] * GRAVITY * (self.depth[self.cells] - self.ref_depth_of_perf)
+            self._wellbore_heads(iq)
+            rho = self.wellbore["density"]
+        else:
+            q = _rows(iq, self.cells)
+            rho = q[:, F_RHO + PH_O, 0]
+            self.head = rho * GRAVITY * (self.depth[self.cells] - self.ref_depth_of_perf)
+        for k, t in enumerate(self.thp_tables):      # the hydrostatic correction between the table's datum and the reference depth
+            if t is not None:
+                self.thp_dp[k] = (rho[self.vp[k]] * GRAVITY) * (t.datum_depth - self.wells[k].ref_depth)
+
+    def _bhp_at_thp_limit(self, k):
+        """vfp.bhp at well k's rates and limit: (9,) - value, the five partials, d/d(aqua, liquid, vapour)"""
+        w, x = self.wells[k], self.x[k]
+        return vfp_mod.bhp(self.thp_tables[k], float(x[WATER]), float(x[OIL]), float(x[GAS]), w.thp_limit, w.alq)
 
     def _initial_bhp(self, iq):
         q = _rows(iq, [w.cells[0] for w in self.wells])
@@ -496,7 +558,13 @@ class StandardWells:
         """(residual, d/d(q_o, q_w, q_g, bhp)) of every well's control equation"""
         r, g = np.zeros(self.nw), np.zeros((self.nw, 4))
         for k, (w, x) in enumerate(zip(self.wells, self.x)):
-            if w.control[0] == "bhp":
+            if self.thp_tables[k] is not None:
+                V = self._bhp_at_thp_limit(k)
+                self._from_thp[k] = V[0] - self.thp_dp[k]
+            if w.control[0] == "thp":
+                r[k] = x[3] - self._from_thp[k]
+                g[k, OIL], g[k, WATER], g[k, GAS], g[k, 3] = 0.0 - V[7], 0.0 - V[6], 0.0 - V[8], 1.0
+            elif w.control[0] == "bhp":
                 r[k], g[k, 3] = x[3] - w.control[1], 1.0
             else:
                 comp, target = w.control[1], w.control[2]
@@ -504,18 +572,23 @@ class StandardWells:
         return r, g
 
     def update_well_controls(self):
-        """BlackoilWellModel::updateWellControls, for the two controls a well here has: a rate target whose BHP leaves its limit goes under
-        BHP control; under BHP control it returns to the rate target once the rate exceeds it"""
-        for w, x in zip(self.wells, self.x):
+        """BlackoilWellModel::updateWellControls: the limits in the reference's order, the first that is violated and is not the control in
+        force wins.  A well leaves its rate target (or its THP limit) for BHP control when its BHP leaves the limit; it returns to the rate
+        target once the rate exceeds it; with a THP limit it goes under THP control when the tubing-head pressure its state implies is
+        beyond the limit (the module's text)"""
+        for k, (w, x) in enumerate(zip(self.wells, self.x)):
             sign = -1.0 if w.producer else 1.0
-            if w.control[0] == "rate":
-                if (w.producer and x[3] < w.bhp_limit) or (not w.producer and x[3] > w.bhp_limit):
-                    w.control = ("bhp", w.bhp_limit)
-                    x[3] = w.bhp_limit
-            else:
-                comp, target = w.rate_control[1], w.rate_control[2]
-                if sign * x[comp] > target:
-                    w.control = w.rate_control
+            t = self.thp_tables[k]
+            if t is not None:
+                self.thp_current[k] = vfp_mod.thp(t, float(x[WATER]), float(x[OIL]), float(x[GAS]), float(x[3] + self.thp_dp[k]), w.alq)
+            if w.control[0] != "bhp" and ((w.producer and x[3] < w.bhp_limit) or (not w.producer and x[3] > w.bhp_limit)):
+                w.control = ("bhp", w.bhp_limit)
+                x[3] = w.bhp_limit
+            elif w.control[0] != "rate" and sign * x[w.rate_control[1]] > w.rate_control[2]:
+                w.control = w.rate_control
+            elif t is not None and w.control[0] != "thp" and (w.thp_limit > self.thp_current[k] if w.producer else w.thp_limit < self.thp_current[k]):
+                w.control = ("thp", w.thp_limit)
+                x[3] = self._bhp_at_thp_limit(k)[0] - self.thp_dp[k]
 
     def set_rate_target(self, k, target):
         """a WCONPROD / WCONINJE record at a report step (ScheduleEvents::PRODUCTION_UPDATE / INJECTION_UPDATE, wells/WellState.hpp:57): the
@@ -593,6 +666,7 @@ class StandardWells:
         BlackoilWellModel::assemble at the present reservoir and well state.  ncells: also `source` / `dsource` as arrays over the whole grid
         (opmhip_set_source's form)."""
         rw, D, Bn, Cn, src, dsrc = self._assemble_wells(iq)
+        self.bhp_from_thp = self._from_thp.copy()
         if self.head_model == "wellbore":        # the well state the next time step's heads start from (StandardWell_impl.hpp:468)
             self.perf_pressure = self.x[:, 3][self.well_of_perf] + self.head
             self.perf_rates = src.copy()
@@ -624,7 +698,7 @@ class StandardWells:
             if np.abs(rw[k, :3]).max() > tol_rate * scale:
                 return False
             ctl = abs(rw[k, 3])
-            if ctl > (tol_bhp if w.control[0] == "bhp" else tol_rate * scale):
+            if ctl > (tol_bhp if w.control[0] in ("bhp", "thp") else tol_rate * scale):
                 return False
         return True
 
@@ -654,9 +728,10 @@ class DeviceStandardWells:
     (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
-    def __init__(self, wells, cell_depth, model, head_model="cell_oil"):
+    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None):
         """head_model="wellbore": the heads from the well-bore density (opmhip_set_std_wells_head_model), StandardWells(head_model="wellbore",
-        arithmetic="stated")'s with the device's own property functions"""
+        arithmetic="stated")'s with the device's own property functions; vfp: the vfp.VFPTable list the wells' THP limits name - sent to the
+        context (opmhip_set_vfp_tables) with the limits (opmhip_set_std_wells_thp) when some well has one"""
         if head_model not in HEAD_MODELS:
             raise ValueError("head_model: 'cell_oil' or 'wellbore'")
         self.wells = list(wells)
@@ -669,10 +744,13 @@ class DeviceStandardWells:
         for w in self.wells:
             if w.rate_control[0] != "rate" or (w.control[0] == "bhp" and w.control[1] != w.bhp_limit):
                 raise ValueError("DeviceStandardWells: well %s needs a rate target and, under BHP control, its limit as the target" % w.name)
+            if w.control[0] == "thp" and w.control[1] != w.thp_limit:
+                raise ValueError("DeviceStandardWells: well %s under THP control needs its limit as the target" % w.name)
             if not w.producer and w.inj_phase not in phase:
                 raise ValueError("DeviceStandardWells: injector %s with unknown phase %r" % (w.name, w.inj_phase))
             if head_model == "wellbore" and w.producer and w.preferred_phase not in phase:
                 raise ValueError("DeviceStandardWells: producer %s with unknown preferred phase %r" % (w.name, w.preferred_phase))
+        self.thp_tables = _thp_tables(self.wells, vfp)
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         model.set_std_wells(dict(
@@ -687,6 +765,14 @@ class DeviceStandardWells:
             self._wellbore = dict(perf_depth=depth[self.cells], ref_depth=[w.ref_depth for w in self.wells],
                                   preferred_phase=[phase[w.preferred_phase] if w.producer else PH_O for w in self.wells])
             model.set_std_wells_head_model(self._wellbore)
+        if any(t is not None for t in self.thp_tables):     # (a list without a limit makes the calls it made before)
+            model.set_vfp_tables(list(vfp))
+            model.set_std_wells_thp(dict(vfp_table=[0 if t is None else w.vfp_table for w, t in zip(self.wells, self.thp_tables)],
+                                         thp_limit=[0.0 if t is None else w.thp_limit for w, t in zip(self.wells, self.thp_tables)],
+                                         alq=[w.alq if t is not None else 0.0 for w, t in zip(self.wells, self.thp_tables)],
+                                         dh=[0.0 if t is None else t.datum_depth - w.ref_depth for w, t in zip(self.wells, self.thp_tables)]))
+            if any(w.control[0] == "thp" for w in self.wells):   # the list itself starts under the deck's modes: THP through the state call
+                model.set_std_wells_state(None, [CONTROL_CODE[w.control[0]] for w in self.wells], None)
         self.x = np.zeros((self.nw, 4))
         self.res_well = np.zeros((self.nw, 4))
 
@@ -697,7 +783,7 @@ class DeviceStandardWells:
         """opmhip_get_std_wells: x, the controls in force (onto the Well objects) and r_w of the last assemble"""
         self.x, ctl, self.res_well = self.m.get_std_wells()
         for w, k in zip(self.wells, ctl):
-            w.control = ("bhp", w.bhp_limit) if k else w.rate_control
+            w.control = (w.rate_control, ("bhp", w.bhp_limit), ("thp", w.thp_limit))[int(k)]
         return self.x
 
     def update(self, relax=1.0):
@@ -714,7 +800,11 @@ class DeviceStandardWells:
         self._send()
 
     def _send(self):
-        self.m.set_std_wells_state(self.x, [int(w.control[0] == "bhp") for w in self.wells], [w.rate_control[2] for w in self.wells])
+        self.m.set_std_wells_state(self.x, [CONTROL_CODE[w.control[0]] for w in self.wells], [w.rate_control[2] for w in self.wells])
+
+    def thp(self):
+        """opmhip_get_std_wells_thp: dict(thp, dp, bhp_from_thp) per well - StandardWells' thp_current, thp_dp, bhp_from_thp"""
+        return self.m.std_wells_thp()
 
     def state(self):
         """as StandardWells.state(); the per-perforation state is read back where the device has one (None before the first heads).  The
