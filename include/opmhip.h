@@ -759,7 +759,8 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * The head is, on request, the reference's: from the density of the mixture in the well bore above every completion
  * (opmhip_set_std_wells_head_model, below).
  * A tubing-head-pressure limit through VFPPROD / VFPINJ tables is a third control (opmhip_set_vfp_tables, opmhip_set_std_wells_thp, below).
- * NOT covered: groups and GRUP control; gas lift (ALQ is a constant per well); bhpwithflo and the robust BHP-THP intersection of
+ * Further rate limits - ORAT, WRAT, GRAT, LRAT, RESV beside the list's own target - are controls 3 .. 7 (opmhip_set_std_wells_limits, below).
+ * NOT covered: groups and GRUP control; CRAT; history-mode RESV; gas lift (ALQ is a constant per well); bhpwithflo and the robust BHP-THP intersection of
  * computeBhpAtThpLimitProd; well potentials; THP for multisegment wells; the deck-level parsing and unit conversion of VFPPROD / VFPINJ
  * (opm-common's: it stays with the caller); crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
  * because its composition - WFrac, GFrac - is an unknown while getQs pins the other components to zero; this parametrisation fixes
@@ -981,6 +982,55 @@ int opmhip_set_std_wells_thp(opmhip_ctx* ctx, const opmhip_std_wells_thp* thp);
  * opmhip_assemble (formed for every well with a limit, whatever its control).  Zeros for wells without a limit. */
 int opmhip_get_std_wells_thp(opmhip_ctx* ctx, double* thp, double* dp, double* bhp_from_thp);
 
+/* ---- several rate limits per resident well: ORAT, WRAT, GRAT, LRAT, RESV (WCONPROD), RESV (WCONINJE).  Additive to ABI 11 ------------
+ * Per well, beside the list's own (rate_component, rate_target), its bhp_limit and its THP limit: positive surface volume rates [m^3/s],
+ * resv_rate a reservoir volume rate; +infinity: no such limit; a NULL array: none of that kind.  use_list_target per well (NULL: all 1):
+ * with 0 the list's own (rate_component, rate_target) is not a limit of that well - a deck record without a limit on a single component.
+ * For an injector only resv_rate is read; the others must be absent. */
+typedef struct opmhip_std_wells_limits {
+    const double* oil_rate;
+    const double* water_rate;
+    const double* gas_rate;
+    const double* liquid_rate;
+    const double* resv_rate;
+    const int* use_list_target;
+} opmhip_std_wells_limits;
+/* Call it after opmhip_set_std_wells; NULL switches it off; replacing or clearing the list clears it.  OPMHIP_NOT_READY without a list;
+ * OPMHIP_INVALID_ARGUMENT, the text naming the reason, for: a limit that is NaN, -infinity or not > 0; a finite limit on the component
+ * the list's own target names while use_list_target is 1; use_list_target = 0 for a well under control 0; taking away the limit a well is
+ * under control of; a producer's limit on an injector; use_list_target other than 0 / 1.  A refused call leaves the previous values in
+ * force.  With limits in force:
+ *   control values 3 ORAT, 4 WRAT, 5 GRAT, 6 LRAT, 7 RESV exist beside 0 (the list's own target), 1 (BHP), 2 (THP) in
+ *     opmhip_set_std_wells_state and opmhip_get_std_wells; a value whose limit the well does not have is refused.  opmhip_set_std_wells
+ *     keeps refusing anything but 0 / 1: a well reaches the new modes by switching or through the state call;
+ *   the control row, unknowns being rates into the reservoir (a producer's are negative), components in the order oil, water, gas:
+ *     3 - 5: r_w[3] = x[c] + limit, D[3][c] = 1;  6: r_w[3] = (x_o + x_w) + limit, D[3][o] = D[3][w] = 1;
+ *     7, producer (prediction mode, wells/WellInterfaceEval.cpp:320-331): r_w[3] = ((c_w x_w + c_o x_o) + c_g x_g) + limit, D[3][j] = c_j,
+ *        c = RateConverter::calcCoeff (wells/RateConverter.hpp:592-646);
+ *     7, injector (:215-228): r_w[3] = c_inj x[inj] - limit, D[3][inj] = c_inj, c = calcInjCoeff (:648-683);
+ *     the guard of a well without a flowing completion keeps its condition;
+ *   opmhip_std_wells_begin_iteration(0) forms, only when some well has a RESV limit, the field's averages (opmhip_reservoir_averages'
+ *     kernels) and every such well's coefficients at the PVT region of its first perforated cell (wells/BlackoilWellModel_impl.hpp:748-759),
+ *     1/B through the functions opmhip_fluid_probe / opmhip_gas_probe run: constant through the time step's Newton iterations, as the
+ *     heads are; a field without pore volume leaves zeros and is reported by opmhip_reservoir_averages;
+ *   updateWellControls (every opmhip_std_wells_begin_iteration) in the reference's order (wells/WellInterfaceFluidSystem.cpp:100-268):
+ *     producers BHP, ORAT, WRAT, GRAT, LRAT, RESV, THP; injectors BHP, RATE, RESV, THP; the list's own target at its component's place;
+ *     the first limit that is violated and is not the control in force wins.  RESV's current rate is the sum of
+ *     calcReservoirVoidageRates (:702-777) at the well's present rates (:66-81, 217-231).  On a switch to a rate-type mode the well's
+ *     state is left as it is (updateWellStateWithTarget's rescaling is left out, as under control 0).
+ * KNOWN DIFFERENCE FROM FLOW: the reference's injector RESV and THP branches assign a local copy of the control and return true without
+ * changing the well state (:140-166); here the well switches.
+ * A list without limits launches the instantiations it launched before; with limits another instantiation runs in their place: the
+ * number of launches of a Newton iteration does not change, and a time step gains the averages and coefficients only with a RESV limit.
+ * Left out: groups / GRUP, CRAT, history-mode RESV (form WCONHIST's target from the averages and hand it in as resv_rate), FIP regions
+ * other than the whole field, salt and temperature in the converter, decomposed contexts. */
+int opmhip_set_std_wells_limits(opmhip_ctx* ctx, const opmhip_std_wells_limits* limits);
+/* averages[5] as opmhip_reservoir_averages gives them, of the last opmhip_std_wells_begin_iteration(0) that formed them; coeff[num_wells * 3]
+ * (oil, water, gas): the control equation's coefficients of every well with a RESV limit (calcCoeff for a producer, calcInjCoeff for an
+ * injector), zeros otherwise; resv_current[num_wells]: the voidage rate the last controls pass formed.  Any pointer may be NULL; waits for
+ * the stream.  Zeros without limits. */
+int opmhip_get_std_wells_resv(opmhip_ctx* ctx, double* averages, double* coeff, double* resv_current);
+
 /* With a list set:
  * opmhip_assemble forms, in front of the assembly kernel and of the aquifers' influx (the host order: wells' rates first), the
  * perforation rates with their five derivatives, r_w, D, D^-1, B and C (computePerfRate, assembleWellEqWithoutIteration:
@@ -1020,6 +1070,18 @@ int opmhip_get_iq_cells(opmhip_ctx* ctx, int n, const int* cells, double* out);
  * getReservoirConvergence (flow/BlackoilModelEbos.hpp:628-904).  out[17]: R_sum[3], maxCoeff[3], B_avg[3], pvSum,
  * cnvErrorPv, CNV[3], MB[3]; component order oil, water, gas. */
 int opmhip_convergence(opmhip_ctx* ctx, double dt, double tol_cnv, double* out);
+
+/* replaces: RateConverter::SurfaceToReservoirVoidage::defineState (wells/RateConverter.hpp:433-554) for the one region Flow's well model
+ * uses (every cell in region 0, wells/BlackoilWellModel_impl.hpp:206-208, 460): the averages the surface-to-reservoir conversion of a
+ * RESV limit is evaluated at, from the intensive quantities of the state now present.  Per cell pv_cell = V * porosity (the record's,
+ * at the cell's pressure), hpv = pv_cell * (1 - S_w); sums of hpv, p_o hpv, Rs hpv, Rv hpv over the cells with hpv > 0, the same with
+ * pv_cell over the cells with pv_cell > 0 (Rv = 0 in the 17-field record).  out[5] = pressure, rs, rv, pv, weights: the hydrocarbon
+ * sums divided by sum hpv where that is > 0 (weights = 1.0, pv = sum hpv), otherwise the pore-volume sums divided by sum pv_cell
+ * (weights = 0.0, pv = sum pv_cell).  Two kernels on the context's stream, no floating-point atomics: the same state gives the same
+ * bits from call to call; the call waits for the stream to read the result back.
+ * OPMHIP_NOT_READY before set_state; OPMHIP_INVALID_ARGUMENT for out == NULL, for a decomposed context (comm.sum over the ranks is
+ * not part of this) and for a field whose pore volume is not > 0 (nothing is divided; out stays untouched).  Additive to ABI 11 */
+int opmhip_reservoir_averages(opmhip_ctx* ctx, double* out);
 
 /* replaces: BlackoilModelEbos::updateSolution (flow/BlackoilModelEbos.hpp:549-563) = BlackOilNewtonMethod::update_
  * (dp <= 0.3 p, dS <= 0.2, primary-variable switching) + invalidateAndUpdateIntensiveQuantities, preceded by

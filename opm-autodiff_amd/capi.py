@@ -113,6 +113,30 @@ class StdWellsThp(C.Structure):
     _fields_ = [("vfp_table", C.c_void_p), ("thp_limit", C.c_void_p), ("alq", C.c_void_p), ("dh", C.c_void_p)]
 
 
+class StdWellsLimits(C.Structure):
+    """opmhip_std_wells_limits: the further rate limits of the resident standard wells (opmhip_set_std_wells_limits)"""
+    _fields_ = [("oil_rate", C.c_void_p), ("water_rate", C.c_void_p), ("gas_rate", C.c_void_p), ("liquid_rate", C.c_void_p), ("resv_rate", C.c_void_p),
+                ("use_list_target", C.c_void_p)]
+
+
+def make_std_wells_limits(t, num_wells):
+    """dict(any of oil_rate, water_rate, gas_rate, liquid_rate, resv_rate per well, +infinity: no such limit; use_list_target per well) ->
+    (StdWellsLimits struct, keep-alive dict); None -> (None, {}).  An absent or None entry is a NULL array."""
+    if t is None:
+        return None, {}
+    arr = {}
+    for name, _ in StdWellsLimits._fields_:
+        v = t.get(name)
+        if v is not None:
+            arr[name] = _i32(np.asarray(v).reshape(-1)) if name == "use_list_target" else _f64(np.asarray(v, float).reshape(-1))
+            if len(arr[name]) != num_wells:
+                raise ValueError("make_std_wells_limits: %s has %d entries for the %d wells set" % (name, len(arr[name]), num_wells))
+    s = StdWellsLimits()
+    for name, a in arr.items():
+        setattr(s, name, a.ctypes.data)
+    return s, arr
+
+
 def make_vfp_tables(tables):
     """list of vfp.VFPTable (or objects with its attributes: kind, table_num, flo_type, wfr_type, gfr_type, datum_depth, axes in the order flo,
     thp[, wfr, gfr, alq], values with flo fastest) -> (VfpTables struct, keep-alive dict); empty / None -> (None, {})"""
@@ -685,6 +709,7 @@ def _bind_assembly(L):
     L.opmhip_set_source_cells.argtypes = [vp, C.c_int, vp, vp, vp]
     L.opmhip_convergence.argtypes = [vp, C.c_double, C.c_double, vp]
     L.opmhip_update.argtypes = [vp, vp, C.c_double, C.POINTER(C.c_int)]
+    L.opmhip_reservoir_averages.argtypes = [vp, vp]
     L.opmhip_set_pattern_dd.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.opmhip_comm_unique_id.argtypes = [C.c_char_p]
     L.opmhip_comm_init_rccl.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
@@ -728,6 +753,8 @@ def _bind_assembly(L):
     L.opmhip_get_std_wells_rate_dq.argtypes = [vp, vp]
     L.opmhip_set_std_wells_thp.argtypes = [vp, C.POINTER(StdWellsThp)]
     L.opmhip_get_std_wells_thp.argtypes = [vp, vp, vp, vp]
+    L.opmhip_set_std_wells_limits.argtypes = [vp, C.POINTER(StdWellsLimits)]
+    L.opmhip_get_std_wells_resv.argtypes = [vp, vp, vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -1054,6 +1081,20 @@ class HipModel(HipSolver):
         self._check(lib().opmhip_get_std_wells_thp(self._h, _ptr(out["thp"]), _ptr(out["dp"]), _ptr(out["bhp_from_thp"])))
         return out
 
+    def set_std_wells_limits(self, limits):
+        """opmhip_set_std_wells_limits: the further rate limits (dict, see make_std_wells_limits); None switches them off.  A refused call
+        leaves the previous values in force."""
+        t, keep = make_std_wells_limits(limits, getattr(self, "_nsw", 0))
+        self._check(lib().opmhip_set_std_wells_limits(self._h, C.byref(t) if t else None))
+
+    def std_wells_resv(self):
+        """opmhip_get_std_wells_resv: dict(averages (5): the field's, as the last begin_iteration(0) with a RESV limit formed them; coeff
+        (wells, 3): the RESV control equation's coefficients (oil, water, gas); resv_current: the voidage rate of the last controls pass)"""
+        n = getattr(self, "_nsw", 0)
+        out = dict(averages=np.zeros(5), coeff=np.zeros((n, 3)), resv_current=np.zeros(n))
+        self._check(lib().opmhip_get_std_wells_resv(self._h, _ptr(out["averages"]), _ptr(out["coeff"]), _ptr(out["resv_current"])))
+        return out
+
     def std_wells_rate_dq(self):
         """for tests: d rate_c / d q_j of the last assemble, (perforations, 3 components, 3 rate unknowns); zeros without crossflow"""
         dq = np.zeros((getattr(self, "_nswperf", 0), 3, 3))
@@ -1094,7 +1135,8 @@ class HipModel(HipSolver):
         self._check(lib().opmhip_std_wells_update(self._h, float(relax)))
 
     def get_std_wells(self):
-        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp / 2 thp, r_w (wells, 4))"""
+        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp / 2 thp / 3 - 7 orat, wrat, grat, lrat, resv,
+        r_w (wells, 4))"""
         n = getattr(self, "_nsw", 0)
         x, ctl, rw = np.zeros((n, 4)), np.zeros(n, np.int32), np.zeros((n, 4))
         self._check(lib().opmhip_get_std_wells(self._h, _ptr(x), _ptr(ctl), _ptr(rw)))
@@ -1149,6 +1191,13 @@ class HipModel(HipSolver):
     def convergence(self, dt, tol_cnv=1e-2):
         out = np.empty(17)
         self._check(lib().opmhip_convergence(self._h, dt, tol_cnv, _ptr(out)))
+        return out
+
+    def reservoir_averages(self):
+        """opmhip_reservoir_averages: (pressure, rs, rv, pv, 1.0 hydrocarbon weights | 0.0 pore-volume fallback) of the whole field at the
+        state now present - RateConverter's defineState, what wells.reservoir_averages(iq, volume) forms by a sequential loop"""
+        out = np.empty(5)
+        self._check(lib().opmhip_reservoir_averages(self._h, _ptr(out)))
         return out
 
     def solve_jacobian_system(self, wells=None):

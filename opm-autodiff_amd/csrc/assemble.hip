@@ -1307,6 +1307,72 @@ __global__ __launch_bounds__(256) void k_conv_final2(int nblocks, const double* 
     if (threadIdx.x == 0) out[10] = sh[0];
 }
 
+// ============================== reservoir averages ============================================================
+// RateConverter::SurfaceToReservoirVoidage::defineState (wells/RateConverter.hpp:433-554) for the one region Flow uses (every cell in
+// region 0): pore-volume-weighted sums of p_o, Rs, Rv over the cells, once weighted by the hydrocarbon pore volume, once by the pore volume.
+// Eight sums: [0..4) = sum hpv, sum p_o hpv, sum Rs hpv, sum Rv hpv over the cells with hpv > 0; [4..8) the same with pv_cell over the cells
+// with pv_cell > 0.  Two stages in the manner of k_conv_pass1 / k_conv_final1, no atomics: a lane adds its cells (grid stride) in ascending
+// order, the wave's lanes by shuffles, the four waves in order, one final workgroup the partials in a fixed order - the grid depends on the
+// cell count alone, so two runs over one state give the same bits.  Value loads only (element 0 of the AD records).
+constexpr int RESV_SUMS = 8;
+template <bool EXT>
+__global__ __launch_bounds__(256) void k_resv_avg_part(int Nb, int ncell, const double* __restrict__ iq, const double* __restrict__ volume,
+                                                       double* __restrict__ part) {
+    __shared__ double sh[RESV_SUMS][4];
+    double a[RESV_SUMS];
+    for (int i = 0; i < RESV_SUMS; ++i) a[i] = 0.0;
+    for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)Nb; c += (size_t)gridDim.x * 256) {
+        const int ci = (int)c;
+        const double pv_cell = volume[ci] * iq_at(iq, ncell, Lay<EXT>::F_PORO, ci)[0];
+        double hydrocarbon = 1.0;
+        hydrocarbon -= iq_at(iq, ncell, F_S + WATER, ci)[0];
+        const double po = iq_at(iq, ncell, F_P + OIL, ci)[0], Rs = iq_at(iq, ncell, F_RS, ci)[0];
+        const double Rv = EXT ? iq_at(iq, ncell, Lay<EXT>::F_RV, ci)[0] : 0.0;
+        const double hpv = pv_cell * hydrocarbon;
+        if (hpv > 0.0) { a[0] += hpv; a[1] += po * hpv; a[2] += Rs * hpv; a[3] += Rv * hpv; }
+        if (pv_cell > 0.0) { a[4] += pv_cell; a[5] += po * pv_cell; a[6] += Rs * pv_cell; a[7] += Rv * pv_cell; }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int i = 0; i < RESV_SUMS; ++i) {
+        double v = a[i];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) sh[i][wv] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < RESV_SUMS) {
+        const int i = threadIdx.x;
+        part[(size_t)blockIdx.x * RESV_SUMS + i] = ((sh[i][0] + sh[i][1]) + sh[i][2]) + sh[i][3];
+    }
+}
+// one workgroup: the partials in a fixed order, then the averages - out[0..5) = pressure, rs, rv, pv, 1.0 where the hydrocarbon weights
+// were used / 0.0 for the pore-volume fallback; out[5] = sum pv (the host refuses a field without pore volume instead of dividing)
+__global__ __launch_bounds__(RESV_FINAL_THREADS) void k_resv_avg_final(int nblocks, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double sh[RESV_SUMS][RESV_FINAL_THREADS];
+    double a[RESV_SUMS];
+    for (int i = 0; i < RESV_SUMS; ++i) a[i] = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += RESV_FINAL_THREADS)
+        for (int i = 0; i < RESV_SUMS; ++i) a[i] += part[(size_t)b * RESV_SUMS + i];
+    for (int i = 0; i < RESV_SUMS; ++i) sh[i][threadIdx.x] = a[i];
+    __syncthreads();
+    for (int o = RESV_FINAL_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int i = 0; i < RESV_SUMS; ++i) sh[i][threadIdx.x] += sh[i][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double hpv_sum = sh[0][0], pv_sum = sh[4][0];
+        const int k = hpv_sum > 0.0 ? 0 : 4;
+        const double w = sh[k][0];
+        const bool ok = hpv_sum > 0.0 || pv_sum > 0.0;
+        out[0] = ok ? sh[k + 1][0] / w : 0.0;
+        out[1] = ok ? sh[k + 2][0] / w : 0.0;
+        out[2] = ok ? sh[k + 3][0] / w : 0.0;
+        out[3] = w;
+        out[4] = k == 0 ? 1.0 : 0.0;
+        out[5] = pv_sum;
+    }
+}
+
 // EclProblem::endTimeStep, drift part (ebos/eclproblem.hh:1126-1135): drift = residual * dt of the accepted step
 __global__ void k_drift_update(int n, const double* __restrict__ resid, double dt, double* __restrict__ drift) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1915,6 +1981,85 @@ struct SwThp {
     const double* wbdens;
 };
 __device__ __forceinline__ VfpTab sw_thp_table(const SwThp& H, int w) { return VfpTab{H.desc + (size_t)H.table[w] * VFP_DESC, H.dbl}; }
+__device__ __forceinline__ int wb_component(int phase);   // the component of a phase (below, with the well-bore heads)
+// Further rate limits (opmhip_set_std_wells_limits; read by the LIM instantiations only).  lim: per well oil, water, gas, liquid, resv
+// (+infinity: no such limit) - control value 3 + k names lim[5 w + k]; use: per well, the list's own target is a limit; out: coeff [3 num] |
+// resv_current [num] | the averages of this time step [5]
+struct SwLim {
+    const double* lim;
+    const int* use;
+    double* out;
+};
+// RateConverter::calcCoeff / calcInjCoeff / calcReservoirVoidageRates (wells/RateConverter.hpp:592-777) in the statement order of wells.py
+// calc_coeff / calc_inj_coeff / calc_reservoir_voidage_rates; components oil, water, gas; avg: pressure, rs, rv
+__device__ __forceinline__ void rc_calc_coeff(const Tables& T, int pr, const double* avg, double* coeff) {
+    const PvtRegionDesc& D = T.pvt(pr);
+    const double p = avg[0], Rs = avg[1], Rv = avg[2];
+    const double bw = pvt_invBw(T, D, p), bo = pvt_invBo(T, pr, D, p, Rs), bg = pvt_invBg(T, pr, D, p, Rv);
+    coeff[EQ_OIL] = 0.0; coeff[EQ_WATER] = 0.0; coeff[EQ_GAS] = 0.0;
+    coeff[EQ_WATER] = 1.0 / bw;
+    const double detR = 1.0 - (Rs * Rv);
+    double den = bo * detR;
+    coeff[EQ_OIL] += 1.0 / den;
+    coeff[EQ_GAS] -= Rv / den;
+    den = bg * detR;
+    coeff[EQ_GAS] += 1.0 / den;
+    coeff[EQ_OIL] -= Rs / den;
+}
+__device__ __forceinline__ void rc_calc_inj_coeff(const Tables& T, int pr, const double* avg, double* coeff) {
+    const PvtRegionDesc& D = T.pvt(pr);
+    const double p = avg[0];
+    const double bw = pvt_invBw(T, D, p), bo = pvt_invBo(T, pr, D, p, 0.0), bg = pvt_invBg(T, pr, D, p, 0.0);
+    coeff[EQ_OIL] = 0.0; coeff[EQ_WATER] = 0.0; coeff[EQ_GAS] = 0.0;
+    coeff[EQ_WATER] = 1.0 / bw;
+    coeff[EQ_OIL] += 1.0 / bo;
+    coeff[EQ_GAS] += 1.0 / bg;
+}
+// the sum of the voidage rates of the surface rates x (oil, water, gas): positive for what a producer takes out / an injector puts in
+// (wells/WellInterfaceFluidSystem.cpp:145-152, 217-226)
+__device__ __forceinline__ double rc_resv_current(const Tables& T, int pr, const double* avg, const double* x, bool producer) {
+    const PvtRegionDesc& D = T.pvt(pr);
+    const double p = avg[0];
+    const double qo = x[EQ_OIL], qw = x[EQ_WATER], qg = x[EQ_GAS];
+    double a = avg[1];
+    double b = qg / (qo + 1.0e-15);
+    const double Rs = b < a ? b : a;
+    a = avg[2];
+    b = qo / (qg + 1.0e-15);
+    const double Rv = b < a ? b : a;
+    const double bw = pvt_invBw(T, D, p), bo = pvt_invBo(T, pr, D, p, Rs), bg = pvt_invBg(T, pr, D, p, Rv);
+    const double vw = qw / bw;
+    const double detR = 1.0 - (Rs * Rv);
+    double den = bo * detR;
+    double v = qo;
+    v -= Rv * qg;
+    const double vo = v / den;
+    den = bg * detR;
+    v = qg;
+    v -= Rs * qo;
+    const double vg = v / den;
+    double cur = 0.0;
+    if (producer) { cur -= vw; cur -= vo; cur -= vg; }
+    else { cur += vw; cur += vo; cur += vg; }
+    return cur;
+}
+// At opmhip_std_wells_begin_iteration(0), behind k_resv_avg_final, one lane per well: this time step's averages are kept beside the
+// coefficients (a later opmhip_reservoir_averages does not change them); the coefficients of every well with a RESV limit, at the PVT
+// region of its first perforated cell
+__global__ __launch_bounds__(64) void k_std_wells_resv_coeff(int num, const int* __restrict__ wi, const int* __restrict__ vp, const int* __restrict__ cell,
+                                                             const int* __restrict__ pvtnum, Tables T, SwLim M, const double* __restrict__ avg) {
+    const int w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= num) return;
+    if (w == 0)
+        for (int i = 0; i < 5; ++i) M.out[(size_t)4 * num + i] = avg[i];
+    double coeff[3] = {0.0, 0.0, 0.0};
+    if (M.lim[5 * w + 4] < INFINITY && avg[5] > 0.0) {   // (a field without pore volume: zeros, nothing is divided)
+        const int pr = pvtnum ? pvtnum[cell[vp[w]]] : 0;
+        if (wi[3 * w] != 0) rc_calc_coeff(T, pr, avg, coeff);
+        else rc_calc_inj_coeff(T, pr, avg, coeff);
+    }
+    for (int i = 0; i < 3; ++i) M.out[(size_t)3 * w + i] = coeff[i];
+}
 // One wavefront per well.  Lanes take the well's perforations 64 at a time: rates with their five derivatives, B, C and the rates to
 // global memory, what the per-well sums need to LDS; lane 0 adds the sums in perforation order and forms r_w, D, the guard of a well
 // without a flowing completion, and D^-1.  SOLVE: the well alone against the frozen reservoir (StandardWells.solve_well_equations) - the
@@ -1926,8 +2071,10 @@ __device__ __forceinline__ VfpTab sw_thp_table(const SwThp& H, int w) { return V
 // heads, dp = (rho g) dh of every such well - rho what the head model uses for the first perforation (WellHelpers.hpp:149-155) -; under
 // control 2 the control row is bhp - (V - dp) with V = vfp_bhp at the limit (control_eq = bhp - bhp_from_thp, WellInterfaceEval.cpp:351-354,
 // 433-436, 463-504); the assembling form also leaves V - dp of every well with a limit.  Every other well gets today's bits.
-template <bool SOLVE, bool CF, bool THP>
-__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, int ncell, const double* __restrict__ iq, int first) {
+// LIM: the list has further rate limits (launched in place of the other instantiation, for all its wells): under control 3 .. 7 the control
+// row is that limit's (include/opmhip.h, opmhip_set_std_wells_limits); every other control gets today's bits.
+template <bool SOLVE, bool CF, bool THP, bool LIM>
+__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim M, int ncell, const double* __restrict__ iq, int first) {
     constexpr int NS = CF ? 15 : 6;
     __shared__ double sums[64 * NS];
     __shared__ double xs[4];
@@ -2025,6 +2172,23 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, int nc
                 r[3] = xs[3] - fromThp;
                 D[12 + EQ_OIL] = 0.0 - V[7]; D[12 + EQ_WATER] = 0.0 - V[6]; D[12 + EQ_GAS] = 0.0 - V[8];
                 D[15] = 1.0;
+            }
+            else if (LIM && W.control[w] >= 3.0) {
+                const int k = (int)W.control[w] - 3;
+                const double L = M.lim[5 * w + k];
+                if (k < 3) { r[3] = xs[k] + L; D[12 + k] = 1.0; }   // ORAT, WRAT, GRAT: the components' order is the equations'
+                else if (k == 3) { r[3] = (xs[EQ_OIL] + xs[EQ_WATER]) + L; D[12 + EQ_OIL] = 1.0; D[12 + EQ_WATER] = 1.0; }
+                else {
+                    const double* cf = M.out + (size_t)3 * w;
+                    if (producer) {
+                        r[3] = ((cf[EQ_WATER] * xs[EQ_WATER] + cf[EQ_OIL] * xs[EQ_OIL]) + cf[EQ_GAS] * xs[EQ_GAS]) + L;
+                        for (int j = 0; j < 3; ++j) D[12 + j] = cf[j];
+                    } else {
+                        const int ic = wb_component(injPhase);
+                        r[3] = cf[ic] * xs[ic] - L;
+                        D[12 + ic] = cf[ic];
+                    }
+                }
             }
             else if (W.control[w] != 0.0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
             else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
@@ -2194,9 +2358,12 @@ __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays 
 // target, THP: current = thp(table, q_w, q_o, q_g, bhp + dp, alq) (StandardWellGeneric.cpp:116-156, StandardWellEval.cpp:546-583), a
 // producer switches when its limit > current, an injector when its limit < current, to control 2 with bhp = V - dp at the rates at hand
 // (updateWellStateWithTarget's THP case, WellInterface_impl.hpp:659-667, 882-890).  A well without a limit takes today's two branches.
-template <bool THP>
+// LIM (the list has further rate limits): producers BHP, ORAT, WRAT, GRAT, LRAT, RESV, THP; injectors BHP, RATE, RESV, THP; the list's own
+// target at its component's place; RESV's current rate from rc_resv_current at the rates at hand.  A switch to a rate-type mode leaves x.
+template <bool THP, bool LIM>
 __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ xs,
-                                                           double* __restrict__ controls, SwThp H) {
+                                                           double* __restrict__ controls, SwThp H, SwLim M, Tables T, const int* __restrict__ vp,
+                                                           const int* __restrict__ cell, const int* __restrict__ pvtnum) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= num) return;
     const bool producer = wi[3 * w] != 0;
@@ -2209,6 +2376,41 @@ __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* _
     if (THP) {
         if (limited) current = vfp_thp(sw_thp_table(H, w), x[EQ_WATER], x[EQ_OIL], x[EQ_GAS], x[3] + H.out[(size_t)num + w], H.wd[3 * w + 1]);
         H.out[w] = current;
+    }
+    if (LIM) {
+        const double* lim = M.lim + (size_t)5 * w;
+        double resv = 0.0;
+        if (lim[4] < INFINITY) {
+            resv = rc_resv_current(T, pvtnum ? pvtnum[cell[vp[w]]] : 0, M.out + (size_t)4 * num, x, producer);
+            M.out[(size_t)3 * num + w] = resv;
+        }
+        if (*control != 1.0 && ((producer && x[3] < limit) || (!producer && x[3] > limit))) { *control = 1.0; x[3] = limit; return; }
+        const double ctl = *control;
+        const int own = M.use[w] ? comp : -1;
+        if (producer) {
+            for (int k = 0; k < 5; ++k) {
+                if (k < 3 && k == own) {
+                    if (ctl != 0.0 && -1.0 * x[k] > target) { *control = 0.0; return; }
+                    continue;
+                }
+                if (!(lim[k] < INFINITY) || ctl == 3.0 + k) continue;
+                double cur;
+                if (k < 3) cur = -x[k];
+                else if (k == 3) { cur = -x[EQ_OIL]; cur -= x[EQ_WATER]; }
+                else cur = resv;
+                if (lim[k] < cur) { *control = 3.0 + k; return; }
+            }
+        } else {
+            if (own >= 0 && ctl != 0.0 && 1.0 * x[comp] > target) { *control = 0.0; return; }
+            if (lim[4] < INFINITY && ctl != 7.0 && lim[4] < resv) { *control = 7.0; return; }
+        }
+        if (limited && ctl != 2.0 && (producer ? H.wd[3 * w] > current : H.wd[3 * w] < current)) {
+            double V[9];
+            vfp_bhp(sw_thp_table(H, w), x[EQ_WATER], x[EQ_OIL], x[EQ_GAS], H.wd[3 * w], H.wd[3 * w + 1], V);
+            *control = 2.0;
+            x[3] = V[0] - H.out[(size_t)num + w];
+        }
+        return;
     }
     if (*control != 1.0 && ((producer && x[3] < limit) || (!producer && x[3] > limit))) { *control = 1.0; x[3] = limit; }
     else if (*control != 0.0 && (producer ? -1.0 : 1.0) * x[comp] > target) *control = 0.0;
@@ -2260,6 +2462,20 @@ static SwThp std_wells_thp(opmhip_ctx* c) {
     const VfpDev& V = c->asmb.vfp;
     return SwThp{S.d_thp_table, S.d_thp_wd, S.d_thp_out, V.d_desc, V.d_dbl, S.d_wbout};
 }
+static SwLim std_wells_lim(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    return SwLim{S.d_lim, S.d_lim_use, S.d_lim_out};
+}
+// the instantiation of k_std_wells_eq a list runs: one per combination of crossflow, THP limits and further rate limits (a list without the
+// feature runs the code it ran before; the number of launches is the same)
+template <bool SOLVE>
+static auto std_wells_eq_kernel(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false>) {
+    if (S.limits)
+        return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, true> : k_std_wells_eq<SOLVE, false, true, true>)
+                     : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, true> : k_std_wells_eq<SOLVE, false, false, true>);
+    return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, false> : k_std_wells_eq<SOLVE, false, true, false>)
+                 : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, false> : k_std_wells_eq<SOLVE, false, false, false>);
+}
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
     return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.x(), S.d_Dmat, W.d_B, W.d_C, W.d_D,
@@ -2271,9 +2487,8 @@ void launch_std_wells_solve(opmhip_ctx* c, bool first) {
     // (a list with a crossflow well runs the CF instantiation in place of the other: the number of launches is the same)
     // (... and one with a THP limit the THP instantiation)
     const StdWellsDev& S = c->wells.sw;
-    const auto kernel = S.thp ? (S.crossflow ? k_std_wells_eq<true, true, true> : k_std_wells_eq<true, false, true>)
-                              : (S.crossflow ? k_std_wells_eq<true, true, false> : k_std_wells_eq<true, false, false>);
-    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), c->pat.Nloc, c->asmb.d_iq, first ? 1 : 0);
+    hipLaunchKernelGGL(std_wells_eq_kernel<true>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), c->pat.Nloc,
+                       c->asmb.d_iq, first ? 1 : 0);
     prof_end(c, ps);
 }
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
@@ -2287,16 +2502,17 @@ void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
 void launch_std_wells_controls(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    const auto kernel = S.thp ? k_std_wells_controls<true> : k_std_wells_controls<false>;
-    hipLaunchKernelGGL(kernel, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control(), std_wells_thp(c));
+    const auto kernel = S.limits ? (S.thp ? k_std_wells_controls<true, true> : k_std_wells_controls<false, true>)
+                                 : (S.thp ? k_std_wells_controls<true, false> : k_std_wells_controls<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control(), std_wells_thp(c), std_wells_lim(c),
+                       tables_of(c), c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum);
     prof_end(c, ps);
 }
 void launch_std_wells_assemble(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    const auto kernel = S.thp ? (S.crossflow ? k_std_wells_eq<false, true, true> : k_std_wells_eq<false, false, true>)
-                              : (S.crossflow ? k_std_wells_eq<false, true, false> : k_std_wells_eq<false, false, false>);
-    hipLaunchKernelGGL(kernel, dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), c->pat.Nloc, c->asmb.d_iq, 0);
+    hipLaunchKernelGGL(std_wells_eq_kernel<false>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), c->pat.Nloc,
+                       c->asmb.d_iq, 0);
     hipLaunchKernelGGL(k_std_wells_source, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_cptr, S.d_cperf, S.d_pr, c->asmb.d_source,
                        c->asmb.d_dsource, S.d_save);
     prof_end(c, ps);
@@ -2529,6 +2745,31 @@ int launch_convergence(opmhip_ctx* c, double dt, double tol_cnv) {
     }
     prof_end(c, ps);
     return OPMHIP_SUCCESS;
+}
+// the two kernels of the reservoir averages: asmb.d_resv = the partials, then the RESV_OUT results
+static double* resv_avg_kernels(opmhip_ctx* c) {
+    const int Nb = c->pat.Nb, nb = cdiv(Nb, 256) < RESV_MAX_PARTS ? cdiv(Nb, 256) : RESV_MAX_PARTS;
+    double* part = c->asmb.d_resv;
+    double* avg = part + (size_t)RESV_MAX_PARTS * RESV_SUMS;
+    OPMHIP_LAYOUT(c,
+        hipLaunchKernelGGL(k_resv_avg_part<false>, dim3(nb), dim3(256), 0, c->stream, Nb, c->pat.Nloc, c->asmb.d_iq, c->asmb.d_volume, part),
+        hipLaunchKernelGGL(k_resv_avg_part<true>, dim3(nb), dim3(256), 0, c->stream, Nb, c->pat.Nloc, c->asmb.d_iq, c->asmb.d_volume, part));
+    hipLaunchKernelGGL(k_resv_avg_final, dim3(1), dim3(RESV_FINAL_THREADS), 0, c->stream, nb, part, avg);
+    return avg;
+}
+// (one scope: a time step of a list with a RESV limit shows one more entry of the assembly class than one without)
+void launch_std_wells_resv(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    const double* avg = resv_avg_kernels(c);
+    hipLaunchKernelGGL(k_std_wells_resv_coeff, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum,
+                       tables_of(c), std_wells_lim(c), avg);
+    prof_end(c, ps);
+}
+void launch_reservoir_averages(opmhip_ctx* c) {
+    const int ps = prof_begin(c, PROF_ASSEMBLE);   // (the well model's, as the standard wells' launches: one span per call)
+    resv_avg_kernels(c);
+    prof_end(c, ps);
 }
 void launch_u8_to_internal(opmhip_ctx* c, const unsigned char* nat, unsigned char* internal) {
     hipLaunchKernelGGL(k_cellvec_to_internal_u8, dim3(cdiv(c->pat.Nloc, 256)), dim3(256), 0, c->stream, c->pat.Nloc, c->pat.d_fromOrder, nat, internal);

@@ -1133,8 +1133,15 @@ void std_wells_thp_release(opmhip_ctx* c) {   // the stream is idle
     S.h_thp_table.clear();
     S.thp = false;
 }
+void std_wells_limits_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_lim); dev_free(c, &S.d_lim_use); dev_free(c, &S.d_lim_out);
+    S.h_lim.clear(); S.h_lim_use.clear();
+    S.limits = S.resv = false;
+}
 void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
+    std_wells_limits_release(c);
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
     dev_free(c, &S.d_pack); dev_free(c, &S.d_saved); dev_free(c, &S.d_Dmat);
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
@@ -1267,6 +1274,7 @@ int opmhip_std_wells_begin_iteration(opmhip_ctx* c, int iteration) {
                 launch_std_wells_wellbore(c, !S.initialised, !S.wb_state_set);
                 S.wb_state_set = true;
             }
+            if (S.resv) launch_std_wells_resv(c);   // RateConverter::defineState and the coefficients, from the state the time step starts with
             launch_std_wells_solve(c, !S.initialised);
             S.initialised = true;
         }
@@ -1324,7 +1332,7 @@ int opmhip_get_std_wells(opmhip_ctx* c, double* x, int* control, double* res_wel
         if (rc) return rc;
         if (x) std::memcpy(x, &h[SW_X * nw], 4 * nw * sizeof(double));
         if (control)
-            for (size_t w = 0; w < nw; ++w) control[w] = (int)h[SW_CONTROL * nw + w];   // 0 rate, 1 bhp, 2 thp
+            for (size_t w = 0; w < nw; ++w) control[w] = (int)h[SW_CONTROL * nw + w];   // 0 rate, 1 bhp, 2 thp, 3 .. 7 orat, wrat, grat, lrat, resv
         if (res_well) std::memcpy(res_well, &h[SW_RW * nw], 4 * nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
@@ -1337,7 +1345,10 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_state: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num;
         std::string msg;
-        if (S.thp) {   // control 2 exists, for the wells that have a limit; everything else is looked at as before
+        if (S.limits) {   // controls 3 .. 7 exist, for the wells that have that limit
+            if (int r = std_wells_limits_check_controls(nw, control, S.thp ? S.h_thp_table.data() : nullptr, S.h_lim.data(), S.h_lim_use.data(), msg)) return fail(c, r, "%s", msg.c_str());
+            if (int r = std_wells_check_state(nw, x, nullptr, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
+        } else if (S.thp) {   // control 2 exists, for the wells that have a limit; everything else is looked at as before
             if (int r = std_wells_thp_check_controls(nw, control, S.h_thp_table.data(), msg)) return fail(c, r, "%s", msg.c_str());
             if (int r = std_wells_check_state(nw, x, nullptr, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
         } else if (int r = std_wells_check_state(nw, x, control, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
@@ -1613,6 +1624,60 @@ int opmhip_get_std_wells_thp(opmhip_ctx* c, double* thp, double* dp, double* bhp
     });
 }
 
+int opmhip_set_std_wells_limits(opmhip_ctx* c, const opmhip_std_wells_limits* limits) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_limits: no resident list (opmhip_set_std_wells)");
+        const size_t nw = S.num;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        std::vector<double> hc(nw);   // the controls in force: a limit a well is under control of stays
+        OPMHIP_HIP(c, hipMemcpy(hc.data(), S.control(), nw * sizeof(double), hipMemcpyDeviceToHost));
+        std::vector<int> control(nw);
+        for (size_t w = 0; w < nw; ++w) control[w] = (int)hc[w];
+        StdWellsLimitsLists H;
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the previous values in force
+        if (int r = std_wells_limits(limits, nw, S.h_wi.data(), control.data(), H, msg)) return fail(c, r, "%s", msg.c_str());
+        double *d_lim = nullptr, *d_out = nullptr;
+        int* d_use = nullptr;
+        if (H.any) {
+            int r;
+            if ((r = dev_upload(c, &d_lim, H.lim)) || (r = dev_upload(c, &d_use, H.use)) || (r = dev_upload(c, &d_out, std::vector<double>(4 * nw + 5, 0.0))) ||
+                (H.any_resv && !c->asmb.d_resv && (r = dev_alloc(c, &c->asmb.d_resv, (size_t)RESV_MAX_PARTS * 8 + RESV_OUT)))) {
+                dev_free(c, &d_lim); dev_free(c, &d_use); dev_free(c, &d_out);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        std_wells_limits_release(c);
+        S.d_lim = d_lim; S.d_lim_use = d_use; S.d_lim_out = d_out;
+        S.limits = H.any; S.resv = H.any_resv;
+        if (H.any) { S.h_lim = std::move(H.lim); S.h_lim_use = std::move(H.use); }
+        S.assembled = false;   // the blocks of the last assembly are no longer the model's
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_resv(opmhip_ctx* c, double* averages, double* coeff, double* resv_current) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        const size_t nw = S.num;
+        std::vector<double> h(4 * nw + 5, 0.0);
+        if (S.limits) {
+            OPMHIP_HIP(c, hipSetDevice(c->device));
+            OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+            OPMHIP_HIP(c, hipMemcpy(h.data(), S.d_lim_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (averages) std::memcpy(averages, &h[4 * nw], 5 * sizeof(double));
+        if (coeff) std::memcpy(coeff, &h[0], 3 * nw * sizeof(double));
+        if (resv_current) std::memcpy(resv_current, &h[3 * nw], nw * sizeof(double));
+        return OPMHIP_SUCCESS;
+    });
+}
+
 int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double* residual) {
     if (!c) return OPMHIP_INVALID_ARGUMENT;
     return guarded(c, [&]() -> int {
@@ -1710,6 +1775,28 @@ int opmhip_convergence(opmhip_ctx* c, double dt, double tol_cnv, double* out) {
             out[11 + e] = h[6 + e] * dt * h[3 + e];
             out[14 + e] = std::fabs(h[6 + e] * h[e]) * dt / h[9];
         }
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_reservoir_averages(opmhip_ctx* c, double* out) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        AsmDev& A = c->asmb;
+        if (!A.state_set) return fail(c, OPMHIP_NOT_READY, "reservoir_averages before set_state");
+        if (!out) return fail(c, OPMHIP_INVALID_ARGUMENT, "reservoir_averages: out == NULL");
+        if (c->comm.nranks > 1 || c->pat.Nghost > 0)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "reservoir_averages: a decomposed context (the sums over the ranks are not formed)");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        int rc;
+        if (!A.d_resv && (rc = dev_alloc(c, &A.d_resv, (size_t)RESV_MAX_PARTS * 8 + RESV_OUT))) return rc;
+        launch_reservoir_averages(c);
+        OPMHIP_HIP(c, hipGetLastError());
+        double h[RESV_OUT];
+        OPMHIP_HIP(c, hipMemcpyAsync(h, A.d_resv + (size_t)RESV_MAX_PARTS * 8, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if (!(h[5] > 0.0)) return fail(c, OPMHIP_INVALID_ARGUMENT, "reservoir_averages: the field's pore volume is %.17g, not > 0", h[5]);
+        for (int i = 0; i < 5; ++i) out[i] = h[i];
         return OPMHIP_SUCCESS;
     });
 }

@@ -216,6 +216,14 @@ struct StdWellsDev {
     std::vector<int> h_thp_table;
     int* d_thp_table = nullptr;
     double *d_thp_wd = nullptr, *d_thp_out = nullptr;
+    // further rate limits (opmhip_set_std_wells_limits): set only while some well of the list has one (or use_list_target = 0).  d_lim: per
+    // well oil, water, gas, liquid, resv (+infinity: none), h_lim its host copy; d_lim_use / h_lim_use: per well use_list_target; d_lim_out:
+    // coeff [3 num] | resv_current [num] | the averages the coefficients were formed at [5]; resv: some well has a RESV limit
+    bool limits = false, resv = false;
+    std::vector<double> h_lim;
+    std::vector<int> h_lim_use;
+    double *d_lim = nullptr, *d_lim_out = nullptr;
+    int* d_lim_use = nullptr;
     double* x() const { return d_pack + (size_t)SW_X * num; }
     double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
     double* rw() const { return d_pack + (size_t)SW_RW * num; }
@@ -289,6 +297,11 @@ struct VfpDev {
     double* d_dbl = nullptr;
 };
 
+// opmhip_reservoir_averages (assemble.hip, k_resv_avg_part / k_resv_avg_final): the first stage runs cdiv(cells, 256) workgroups of 256 lanes,
+// at most RESV_MAX_PARTS (beyond that its lanes stride over the grid); the one workgroup of the final stage has RESV_FINAL_THREADS lanes,
+// so more than RESV_FINAL_THREADS x 256 cells take a second pass over the partials
+constexpr int RESV_MAX_PARTS = 1024, RESV_FINAL_THREADS = 256, RESV_OUT = 6;
+
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
 struct AsmDev {
     AquifersDev aq;
@@ -324,6 +337,7 @@ struct AsmDev {
     int* d_imbnum = nullptr;
     double* d_eps_imb = nullptr;
     double* d_rc = nullptr;                               // relativeChange: 2 x 256 partial sums + (delta, denominator)
+    double* d_resv = nullptr;                             // opmhip_reservoir_averages: RESV_MAX_PARTS x 8 partial sums + the 6 results (allocated at the first call)
     int num_wc = 0, h_rocknum_max = -1;                   // water-compaction tables; largest rock-table index handed in (-1: none)
     int* d_wcdesc = nullptr;                              // per table {np, nsw, pressure at, S_w at, pore-volume multipliers at, transmissibility multipliers at | -1}
     double* d_wcdata = nullptr;
@@ -758,6 +772,7 @@ int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_asm.cpp: the 
 void launch_std_wells_solve(opmhip_ctx* c, bool first);   // heads, then the wells alone against the frozen reservoir (iteration 0)
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init);   // the heads from the well-bore density, in front of launch_std_wells_solve
 void launch_std_wells_controls(opmhip_ctx* c);            // updateWellControls
+void launch_std_wells_resv(opmhip_ctx* c);                // the field's averages and the RESV wells' coefficients (iteration 0, lists with a RESV limit)
 void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
 void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)
 void launch_std_wells_axpy(opmhip_ctx* c, double relax);  // x -= relax * x_w
@@ -770,6 +785,7 @@ void launch_max_water_saturation(opmhip_ctx* c, bool init);
 void launch_hyst_update(opmhip_ctx* c, const double* d_sw_ow = nullptr, const double* d_sw_go = nullptr);
 int launch_relative_change(opmhip_ctx* c);   // -> asmb.d_rc[512 .. 514)
 int launch_convergence(opmhip_ctx* c, double dt, double tol_cnv);
+void launch_reservoir_averages(opmhip_ctx* c);   // -> asmb.d_resv[RESV_MAX_PARTS * 8 .. + RESV_OUT)
 void launch_u8_to_internal(opmhip_ctx* c, const unsigned char* nat, unsigned char* internal);
 void launch_u8_to_natural(opmhip_ctx* c, const unsigned char* internal, unsigned char* nat);
 void launch_iq_to_natural(opmhip_ctx* c, double* d_nat);

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <limits>
 #include <utility>
 
 #include "internal.hpp"
@@ -86,6 +87,57 @@ int std_wells_check_state(size_t nw, const double* x, const int* control, const 
     if (x)
         for (size_t i = 0; i < 4 * nw; ++i)
             if (!std::isfinite(x[i])) return refuse(msg, "set_std_wells_state: x[%zu] is not finite", i);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_limits(const opmhip_std_wells_limits* L, size_t nw, const int* wi, const int* control, StdWellsLimitsLists& out, std::string& msg) {
+    static const char* const name[5] = {"oil_rate", "water_rate", "gas_rate", "liquid_rate", "resv_rate"};
+    const double inf = std::numeric_limits<double>::infinity();
+    StdWellsLimitsLists H;
+    H.lim.assign(5 * nw, inf);
+    H.use.assign(nw, 1);
+    if (L) {
+        const double* arr[5] = {L->oil_rate, L->water_rate, L->gas_rate, L->liquid_rate, L->resv_rate};
+        for (size_t w = 0; w < nw; ++w) {
+            const bool producer = wi[3 * w] != 0;
+            const int use = L->use_list_target ? L->use_list_target[w] : 1;
+            if (use != 0 && use != 1) return refuse(msg, "set_std_wells_limits: use_list_target[%zu] = %d (0 / 1)", w, use);
+            H.use[w] = use;
+            if (!use) H.any = true;
+            for (int k = 0; k < 5; ++k) {
+                if (!arr[k]) continue;
+                const double v = arr[k][w];
+                if (!(v > 0.0)) return refuse(msg, "set_std_wells_limits: %s[%zu] = %g is not > 0 (+infinity: no such limit)", name[k], w, v);
+                if (v == inf) continue;
+                if (!producer && k != 4) return refuse(msg, "set_std_wells_limits: %s[%zu] is a producer's limit, well %zu is an injector (its limits: the list's rate target and resv_rate)", name[k], w, w);
+                if (producer && use && k < 3 && wi[3 * w + 2] == k)
+                    return refuse(msg, "set_std_wells_limits: %s[%zu] limits the component the list's own target already names (use_list_target = 0 takes that one out)", name[k], w);
+                H.lim[5 * w + k] = v;
+                H.any = true;
+                if (k == 4) H.any_resv = true;
+            }
+        }
+    }
+    for (size_t w = 0; w < nw; ++w) {
+        if (control[w] == 0 && !H.use[w]) return refuse(msg, "set_std_wells_limits: use_list_target[%zu] = 0 for a well under control 0, the list's own target", w);
+        if (control[w] >= 3 && control[w] <= 7 && !(H.lim[5 * w + control[w] - 3] < inf))
+            return refuse(msg, "set_std_wells_limits: well %zu is under control %d (%s): that limit cannot be taken away", w, control[w], name[control[w] - 3]);
+    }
+    out = std::move(H);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_limits_check_controls(size_t nw, const int* control, const int* thp_table, const double* lim, const int* use, std::string& msg) {
+    if (!control) return OPMHIP_SUCCESS;
+    for (size_t w = 0; w < nw; ++w) {
+        const int k = control[w];
+        if (k < 0 || k > 7) return refuse(msg, "set_std_wells_state: control[%zu] = %d (0 rate, 1 bhp, 2 thp, 3 orat, 4 wrat, 5 grat, 6 lrat, 7 resv)", w, k);
+        if (k == 0 && !use[w]) return refuse(msg, "set_std_wells_state: control[%zu] = 0 for a well whose own target is not a limit (use_list_target = 0)", w);
+        if (k == 2 && (!thp_table || thp_table[w] < 0))
+            return refuse(msg, "set_std_wells_state: control[%zu] = 2 (thp) for a well without a THP limit (opmhip_set_std_wells_thp)", w);
+        if (k >= 3 && !(lim[5 * w + k - 3] < std::numeric_limits<double>::infinity()))
+            return refuse(msg, "set_std_wells_state: control[%zu] = %d for a well without that limit (opmhip_set_std_wells_limits)", w, k);
+    }
     return OPMHIP_SUCCESS;
 }
 

@@ -27,6 +27,17 @@ int std_wells_lists(const opmhip_std_wells* sw, int Nb, const int* toOrder, StdW
 int std_wells_check_state(size_t nw, const double* x, const int* control, const double* rate_target, std::string& msg);
 // wi: the list's; any: some well has the switch
 int std_wells_check_crossflow(size_t nw, const int* allow, const int* wi, bool& any, std::string& msg);
+// opmhip_set_std_wells_limits.  wi: the list's; control: the controls in force (nw); lim: per well oil, water, gas, liquid, resv (+infinity:
+// none); use: per well use_list_target; any / any_resv: some well has a limit (or use_list_target = 0) / a RESV limit
+struct StdWellsLimitsLists {
+    std::vector<double> lim;
+    std::vector<int> use;
+    bool any = false, any_resv = false;
+};
+int std_wells_limits(const opmhip_std_wells_limits* L, size_t nw, const int* wi, const int* control, StdWellsLimitsLists& out, std::string& msg);
+// the controls opmhip_set_std_wells_state hands in, with limits in force: 0 .. 7, 2 only with a THP limit (thp_table NULL: none has one), 3 .. 7
+// only with that limit, 0 only with use_list_target
+int std_wells_limits_check_controls(size_t nw, const int* control, const int* thp_table, const double* lim, const int* use, std::string& msg);
 // pref: per well the preferred phase the kernel reads (an injector's is never looked at: oil)
 int std_wells_head_model(const opmhip_std_wells_wellbore* wb, size_t nw, size_t np, const int* wi, std::vector<int>& pref, std::string& msg);
 // state_set: the perforation pressures exist already

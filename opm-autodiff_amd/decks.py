@@ -174,13 +174,15 @@ SPE9_PRODUCERS_IJ = [(5, 1), (8, 2), (11, 3), (10, 4), (12, 5), (4, 6), (8, 7), 
 
 
 def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, producer_bhp_limit=1000.0 * PSIA, injector_bhp_limit=400e5,
-                      diameter=0.1524):
+                      diameter=0.1524, liquid_rate_stb_day=None, resv_rate=None):
     """BASELINE.json configs[2] with wells that are wells (wells.StandardWells) on a 24 x 25 x 15 cartesian_case: SPE9's water injector at
     (24, 25), completed in layers 11-15, on a surface-rate target with an upper BHP limit, and its 25 oil producers, completed in layers
     2-4, on an oil-rate target (1500 stb/day; the SPE9 schedule cuts it to 100 stb/day for a while) with a lower BHP limit of 1000 psia;
     reference depth = the centre of the topmost completion; connection factors by Peaceman's formula from the cell's own permeability,
     so that on the log-normal field some producers cannot hold their target and fall to the BHP limit.  A stand-in like the grid itself:
-    the SPE9 deck is not in the reference tree, its fluid and its dipping layers are not reproduced."""
+    the SPE9 deck is not in the reference tree, its fluid and its dipping layers are not reproduced.
+    liquid_rate_stb_day / resv_rate (reservoir m^3/s): every producer also gets an LRAT / a RESV limit (wells.Well(limits=)); a RESV limit
+    needs the fluid's property functions: build wells.StandardWells(.wells, depth, props=, volume=) from the list returned."""
     from . import wells as _wells
     nx, ny, nz = case["nx"], case["ny"], case["nz"]
     if (nx, ny) != (24, 25) or nz < 15:
@@ -194,7 +196,13 @@ def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, 
                        inj_phase="water")]
     for n, (i, j) in enumerate(SPE9_PRODUCERS_IJ):
         cells, tw = column(i, j, 2, 4)
-        out.append(_wells.Well("PRODU%d" % (n + 2), cells, tw, case["depth"][cells[0]], True, ("rate", _wells.OIL, oil_rate_stb_day * STB_PER_DAY), producer_bhp_limit))
+        limits = {}
+        if liquid_rate_stb_day is not None:
+            limits["lrat"] = liquid_rate_stb_day * STB_PER_DAY
+        if resv_rate is not None:
+            limits["resv"] = resv_rate
+        out.append(_wells.Well("PRODU%d" % (n + 2), cells, tw, case["depth"][cells[0]], True, ("rate", _wells.OIL, oil_rate_stb_day * STB_PER_DAY), producer_bhp_limit,
+                               **({"limits": limits} if limits else {})))
     return _wells.StandardWells(out, case["depth"])
 
 

@@ -2,7 +2,8 @@
 the host (as in the reference: only the reservoir part of the linearisation and the Schur-complement operator are accelerated) and handed
 to the device as the blocks bda::WellContributions carries - B, C (4 x 3 per perforation), D^-1 (4 x 4 per well).
 
-What of the reference this restates, minimally (vertical wells, rate or BHP control, crossflow in producers on request, no well storage term):
+What of the reference this restates, minimally (vertical wells, rate, BHP or THP control and several rate limits per well, crossflow in producers on request,
+no well storage term):
   wells/StandardWell_impl.hpp: computePerfRate (:195-420; producing perforations: phase rate = -Tw mob drawdown, surface rate through
       1/B, dissolved gas with the oil; injecting perforations: total mobility, the injected phase's 1/B), assembleWellEqWithoutIteration
       (:516-640: mass-balance equation per component = surface rate - sum of connection rates, one control equation), apply (:1254-1296),
@@ -63,6 +64,33 @@ the BHP limit, through the VFPPROD (producers) / VFPINJ (injectors) tables of vf
       current, an injector when its limit < current, and its bhp becomes V - dp at the rates at hand (updateWellStateWithTarget's THP case,
       wells/WellInterface_impl.hpp:659-667, 882-890).
   Left out: groups, gas lift (alq is a constant), bhpwithflo and the robust BHP-THP intersection (computeBhpAtThpLimitProd), well potentials.
+
+Several rate limits per well (Well(limits={"orat": , "wrat": , "grat": , "lrat": , "resv": }); WCONPROD's ORAT, WRAT, GRAT, LRAT, RESV and
+WCONINJE's RESV): positive surface volume rates, "resv" a reservoir volume rate; a limit that is absent does not exist.  They stand beside
+the well's own ("rate", component, target), which keeps its place among them (an oil target is the well's ORAT limit, and so on; for an
+injector it is WCONINJE's RATE); Well(use_list_target=False) takes it out of the limits - a deck record without a limit on a single
+component.  The control tuples ("orat", v) ... ("resv", v) name the limit in force.
+  control rows, in this module's sign (the unknowns are rates into the reservoir, a producer's are negative):
+      ORAT / WRAT / GRAT   x[c] + limit                                      D[3][c] = 1
+      LRAT                 (x_o + x_w) + limit                               D[3][o] = D[3][w] = 1
+      RESV, producer       ((c_w x_w + c_o x_o) + c_g x_g) + limit           D[3][j] = c_j, c = calc_coeff (prediction mode,
+                                                                             wells/WellInterfaceEval.cpp:320-331)
+      RESV, injector       c_inj x[inj] - limit                              D[3][inj] = c_inj, c = calc_inj_coeff (:215-228)
+  the rate converter (wells/RateConverter.hpp): reservoir_averages is defineState (:433-554) for the one region Flow's well model uses -
+      hydrocarbon-pore-volume-weighted averages of p_o, Rs, Rv over all cells, the pore-volume-weighted ones where there is no hydrocarbon
+      pore volume; calc_coeff, calc_inj_coeff, calc_reservoir_voidage_rates are calcCoeff, calcInjCoeff, calcReservoirVoidageRates
+      (:592-777) operation by operation in the reference's statement order, 1/B through props.probe / probe_gas at the PVT region of the
+      well's first perforated cell (wells/BlackoilWellModel_impl.hpp:748-759).  The averages are the model's (records()), frozen with the
+      coefficients in calculate_explicit_quantities: constant through a time step's Newton iterations, as the heads are.
+  update_well_controls, in the reference's order (wells/WellInterfaceFluidSystem.cpp:100-268): producers BHP, ORAT, WRAT, GRAT, LRAT, RESV,
+      THP; injectors BHP, RATE, RESV, THP; the first limit that is violated and is not the control in force wins.  For RESV the current
+      rate is the sum of calc_reservoir_voidage_rates at the well's present rates (:66-81, 217-231), not the coefficient form.
+  KNOWN DIFFERENCES FROM FLOW: on a switch to a rate-type mode the well's state is left as it is (updateWellStateWithTarget's rescaling is
+      left out, as under control 0).  The reference's injector RESV and THP branches assign a local copy of the control and return true
+      without changing the well state (:140-166); here the well switches.  props.probe takes the saturated curve where Rs >= RsSat(p)
+      (probe_gas where Rv >= RvSat); the reference's converter evaluates the undersaturated function at the averages as they are.
+  Left out: groups / GRUP, CRAT, history-mode RESV (prediction_mode == false; a caller forms WCONHIST's target from the averages and hands it
+      in as "resv"), FIP regions other than the whole field, salt and temperature in the converter.
 """
 import numpy as np
 
@@ -147,15 +175,20 @@ class Well:
     producer or injector of `phase`; control: ("rate", component, target > 0 surface m^3/s) or ("bhp", pascal); bhp_limit: lower (producer) / upper (injector) limit;
     allow_crossflow (WELSPECS item 10; producers only): perforations whose drawdown is reversed inject the well bore's mixture;
     thp_limit (pascal) with vfp_table (the deck number of a VFPPROD / VFPINJ table handed to StandardWells) and alq: the tubing-head-pressure
-    limit - lower (producer) / upper (injector); control may then also be ("thp", thp_limit)"""
+    limit - lower (producer) / upper (injector); control may then also be ("thp", thp_limit);
+    limits: dict of further rate limits, any of "orat", "wrat", "grat", "lrat" (surface m^3/s) and "resv" (reservoir m^3/s), all > 0 - an
+    injector's only "resv" - and control may be (kind, that limit); use_list_target=False: the rate target of `rate_control` is not a limit
+    of this well (the control must then be another one); rate_control: the well's own rate target where control is not the "rate" tuple"""
 
     def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil", allow_crossflow=False,
-                 thp_limit=None, vfp_table=None, alq=0.0):
+                 thp_limit=None, vfp_table=None, alq=0.0, limits=None, use_list_target=True, rate_control=None):
         self.name, self.cells, self.tw = name, np.asarray(cells, np.int32), np.asarray(tw, float)
         self.ref_depth, self.producer, self.inj_phase = float(ref_depth), bool(producer), inj_phase
         self.preferred_phase = preferred_phase     # a producer's (WELSPECS item 6): the well bore's content where nothing flows (head_model="wellbore")
         self.control, self.bhp_limit = control, float(bhp_limit)
-        self.rate_control = control       # the deck's rate target, kept for switching back from the BHP / THP limit
+        self.rate_control = control if rate_control is None else rate_control   # the deck's rate target, kept for switching back from another limit
+        self.use_list_target = bool(use_list_target)
+        self.limits = _check_limits(name, self.producer, self.rate_control, limits, self.use_list_target, control)
         self.allow_crossflow = bool(allow_crossflow)
         _crossflow_flags([self])
         if (thp_limit is None) != (vfp_table is None):
@@ -189,7 +222,130 @@ def _crossflow_flags(wells):
     return np.array([bool(getattr(w, "allow_crossflow", False)) for w in wells], bool)
 
 
-CONTROL_CODE = {"rate": 0, "bhp": 1, "thp": 2}     # opmhip_get_std_wells / opmhip_set_std_wells_state
+CONTROL_CODE = {"rate": 0, "bhp": 1, "thp": 2, "orat": 3, "wrat": 4, "grat": 5, "lrat": 6, "resv": 7}     # opmhip_get_std_wells / opmhip_set_std_wells_state (0 - 2)
+LIMIT_KINDS = ("orat", "wrat", "grat", "lrat", "resv")       # in the order update_well_controls looks at them
+LIMIT_OF_COMPONENT = {OIL: "orat", WATER: "wrat", GAS: "grat"}
+COMPONENT_OF_LIMIT = {"orat": OIL, "wrat": WATER, "grat": GAS}
+
+
+def reservoir_averages(iq, volume):
+    """RateConverter::SurfaceToReservoirVoidage::defineState (wells/RateConverter.hpp:433-554) over all cells, by a sequential loop in cell
+    order: iq (cells, 17 | 19 fields, 4) as model.iq() returns it, volume per cell -> array (pressure, rs, rv, pv, 1.0 | 0.0): the
+    hydrocarbon-pore-volume-weighted averages where the field has hydrocarbon pore volume (last entry 1.0), else the pore-volume-weighted
+    ones (0.0).  What capi.HipModel.reservoir_averages() forms on the device (there in a reduction's order: equal to rounding)."""
+    iq = np.asarray(iq, float)
+    nf = iq.shape[1]
+    f_rv, f_poro = (16, 18) if nf == 19 else (None, 16)
+    hpv_s = [0.0, 0.0, 0.0, 0.0]           # pv, pressure, rs, rv
+    pv_s = [0.0, 0.0, 0.0, 0.0]
+    for c in range(iq.shape[0]):
+        pv_cell = float(volume[c]) * float(iq[c, f_poro, 0])
+        hydrocarbon = 1.0
+        hydrocarbon -= float(iq[c, F_S + PH_W, 0])
+        po, rs = float(iq[c, F_P + PH_O, 0]), float(iq[c, F_RS, 0])
+        rv = 0.0 if f_rv is None else float(iq[c, f_rv, 0])
+        hpv = pv_cell * hydrocarbon
+        if hpv > 0.0:
+            hpv_s[0] += hpv
+            hpv_s[1] += po * hpv
+            hpv_s[2] += rs * hpv
+            hpv_s[3] += rv * hpv
+        if pv_cell > 0.0:
+            pv_s[0] += pv_cell
+            pv_s[1] += po * pv_cell
+            pv_s[2] += rs * pv_cell
+            pv_s[3] += rv * pv_cell
+    if hpv_s[0] > 0.0:
+        return np.array([hpv_s[1] / hpv_s[0], hpv_s[2] / hpv_s[0], hpv_s[3] / hpv_s[0], hpv_s[0], 1.0])
+    if not pv_s[0] > 0.0:
+        raise ValueError("reservoir_averages: the field's pore volume is %r, not > 0" % pv_s[0])
+    return np.array([pv_s[1] / pv_s[0], pv_s[2] / pv_s[0], pv_s[3] / pv_s[0], pv_s[0], 0.0])
+
+
+def _inv_b(props, averages_p, rs, rv, region):
+    """(1/B_w(p), 1/B_o(p, rs), 1/B_g(p, rv)) out of the evaluator, as the well-bore heads take them"""
+    p = np.array([float(averages_p)])
+    bw = float(props.probe(p, pvt_region=int(region))[0, INVBW])
+    bo = float(props.probe(p, float(rs), pvt_region=int(region))[0, INVBO])
+    bg = float(props.probe_gas(p, float(rv), pvt_region=int(region))[0, G_INVB])
+    return bw, bo, bg
+
+
+def calc_coeff(props, averages, pvt_region=0):
+    """RateConverter::calcCoeff (wells/RateConverter.hpp:592-646): coeff (oil, water, gas) with sum_c coeff[c] q_c = the reservoir voidage
+    rate of the surface rates q at the averages (pressure, rs, rv, ...)"""
+    p, Rs, Rv = float(averages[0]), float(averages[1]), float(averages[2])
+    bw, bo, bg = _inv_b(props, p, Rs, Rv, pvt_region)
+    coeff = [0.0, 0.0, 0.0]
+    coeff[WATER] = 1.0 / bw
+    detR = 1.0 - (Rs * Rv)
+    den = bo * detR
+    coeff[OIL] += 1.0 / den
+    coeff[GAS] -= Rv / den
+    den = bg * detR
+    coeff[GAS] += 1.0 / den
+    coeff[OIL] -= Rs / den
+    return np.array(coeff)
+
+
+def calc_inj_coeff(props, averages, pvt_region=0):
+    """RateConverter::calcInjCoeff (:648-683): every phase alone, nothing dissolved or vaporised in what is injected"""
+    bw, bo, bg = _inv_b(props, float(averages[0]), 0.0, 0.0, pvt_region)
+    coeff = [0.0, 0.0, 0.0]
+    coeff[WATER] = 1.0 / bw
+    coeff[OIL] += 1.0 / bo
+    coeff[GAS] += 1.0 / bg
+    return np.array(coeff)
+
+
+def calc_reservoir_voidage_rates(props, averages, surface_rates, pvt_region=0):
+    """RateConverter::calcReservoirVoidageRates (:702-777): the reservoir volume rates (oil, water, gas) of the surface rates (oil, water,
+    gas), with Rs = min(average, q_g / (q_o + 1e-15)) and Rv = min(average, q_o / (q_g + 1e-15))"""
+    p = float(averages[0])
+    qo, qw, qg = np.float64(surface_rates[OIL]), np.float64(surface_rates[WATER]), np.float64(surface_rates[GAS])
+    with np.errstate(all="ignore"):                # (a rate of exactly -1e-15 divides by zero, as in the reference: IEEE's answer, no exception)
+        a = np.float64(averages[1])
+        b = qg / (qo + 1.0e-15)
+        Rs = b if b < a else a                     # std::min(a, b)
+        a = np.float64(averages[2])
+        b = qo / (qg + 1.0e-15)
+        Rv = b if b < a else a
+    bw, bo, bg = _inv_b(props, p, Rs, Rv, pvt_region)
+    out = [0.0, 0.0, 0.0]
+    out[WATER] = qw / bw
+    detR = 1.0 - (Rs * Rv)
+    den = bo * detR
+    v = qo
+    v -= Rv * qg
+    out[OIL] = v / den
+    den = bg * detR
+    v = qg
+    v -= Rs * qo
+    out[GAS] = v / den
+    return np.array(out)
+
+
+def _check_limits(name, producer, rate_control, limits, use_list_target, control):
+    """the limits of one well as a dict kind -> float; ValueError with the reason for what opmhip_set_std_wells_limits refuses"""
+    out = {}
+    for kind, v in (limits or {}).items():
+        if kind not in LIMIT_KINDS:
+            raise ValueError("well %s: unknown limit %r (one of %s)" % (name, kind, ", ".join(LIMIT_KINDS)))
+        if v is None or v == np.inf:
+            continue                              # no such limit
+        v = float(v)
+        if not v > 0.0 or v != v:
+            raise ValueError("well %s: the %s limit %r is not > 0" % (name, kind, v))
+        if not producer and kind != "resv":
+            raise ValueError("well %s: the %s limit is a producer's; an injector has its rate target and RESV" % (name, kind))
+        if use_list_target and producer and rate_control[0] == "rate" and LIMIT_OF_COMPONENT[rate_control[1]] == kind:
+            raise ValueError("well %s: a %s limit beside the well's own target on the same component" % (name, kind))
+        out[kind] = v
+    if not use_list_target and control[0] == "rate":
+        raise ValueError("well %s: use_list_target=False for a well under its own rate target" % name)
+    if control[0] in LIMIT_KINDS and (control[0] not in out or float(control[1]) != out[control[0]]):
+        raise ValueError("well %s: %s control needs that limit, and the limit as its target" % (name, control[0].upper()))
+    return out
 
 
 def _thp_tables(wells, tables):
@@ -219,8 +375,9 @@ class StandardWells:
     arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
     bit; a singular D raises SingularWellEquations there."""
 
-    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None):
-        """head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
+    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None, volume=None):
+        """volume: the cells' volumes, for the reservoir averages of a RESV limit where the model has no reservoir_averages() of its own
+        (a RESV limit also needs props).  head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
         pvt_region=) - capi.HipFluid(fluid), the device's, or the CPU oracle's in tests, as equil.py takes them - with the deck-level
         tables as props.fluid (the surface densities); pvtnum: PVT region per cell (None: region 0); vfp: the vfp.VFPTable list the wells' THP
         limits name (a list without limits computes what it computes with vfp=None)"""
@@ -240,6 +397,13 @@ class StandardWells:
         self.thp_current = np.zeros(self.nw)       # ... the tubing-head pressure the last update_well_controls formed from the well's state
         self.bhp_from_thp = np.zeros(self.nw)      # ... V - dp of the last assemble()
         self._from_thp = np.zeros(self.nw)
+        self.has_resv = any("resv" in getattr(w, "limits", {}) for w in self.wells)
+        self.volume = None if volume is None else np.asarray(volume, float)
+        self.pvt_of_well = np.array([0 if pvtnum is None else int(np.asarray(pvtnum)[w.cells[0]]) for w in self.wells], int)
+        self._model_averages = None                # what records() / set_reservoir_averages last took
+        self.resv_averages = np.zeros(5)           # frozen by calculate_explicit_quantities: pressure, rs, rv, pv, hydrocarbon weights used
+        self.resv_coeff = np.zeros((self.nw, 3))   # per well with a RESV limit: calc_coeff (producer) / calc_inj_coeff (injector), (oil, water, gas)
+        self.resv_current = np.zeros(self.nw)      # ... the voidage rate the last update_well_controls formed from the well's rates
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         self.tw = np.concatenate([w.tw for w in self.wells])
@@ -268,9 +432,23 @@ class StandardWells:
     def records(self, model):
         """the perforated cells' intensive quantities from the model - the perforated cells only (updatePerforationIntensiveQuantities,
         wells/BlackoilWellModel_impl.hpp:1606-1630); a model without iq_cells hands over its whole array"""
+        if self.has_resv:                          # (a list without a RESV limit asks the model for what it asked before)
+            if hasattr(model, "reservoir_averages"):
+                self._model_averages = np.array(model.reservoir_averages(), float)
+            else:
+                if self.volume is None:
+                    raise ValueError("a RESV limit needs the cells' volumes (StandardWells(volume=)) with a model that has no reservoir_averages()")
+                self._model_averages = reservoir_averages(model.iq(), self.volume)
         if hasattr(model, "iq_cells"):
             return CellRecords(self.ucells, model.iq_cells(self.ucells))
         return model.iq()
+
+    def set_reservoir_averages(self, averages):
+        """the averages the next calculate_explicit_quantities freezes, handed in (pressure, rs, rv[, pv, weights]) instead of taken from a
+        model in records() - e.g. the device's own, read back"""
+        a = np.zeros(5)
+        a[:len(averages)] = np.asarray(averages, float)
+        self._model_averages = a
 
     def calculate_explicit_quantities(self, iq):
         """The pressure differences between the reference depth and the completions, once per time step from the state it starts with and
@@ -288,6 +466,28 @@ class StandardWells:
         for k, t in enumerate(self.thp_tables):      # the hydrostatic correction between the table's datum and the reference depth
             if t is not None:
                 self.thp_dp[k] = (rho[self.vp[k]] * GRAVITY) * (t.datum_depth - self.wells[k].ref_depth)
+        if self.has_resv:                            # RateConverter::defineState at the start of the time step (BlackoilWellModel::beginTimeStep)
+            if self._model_averages is None or self.props is None:
+                raise ValueError("a RESV limit needs props (probe / probe_gas) and the reservoir averages: records(model) or set_reservoir_averages")
+            self.resv_averages = self._model_averages.copy()
+            for k, w in enumerate(self.wells):
+                if "resv" in w.limits:
+                    self.resv_coeff[k] = (calc_coeff if w.producer else calc_inj_coeff)(self.props, self.resv_averages, self.pvt_of_well[k])
+
+    def _resv_current(self, k):
+        """the voidage rate of well k at its present rates: the sum of calc_reservoir_voidage_rates, positive for what a producer takes out /
+        an injector puts in (wells/WellInterfaceFluidSystem.cpp:145-152, 217-226)"""
+        v = calc_reservoir_voidage_rates(self.props, self.resv_averages, self.x[k, :3], self.pvt_of_well[k])
+        cur = 0.0
+        if self.wells[k].producer:
+            cur -= float(v[WATER])
+            cur -= float(v[OIL])
+            cur -= float(v[GAS])
+        else:
+            cur += float(v[WATER])
+            cur += float(v[OIL])
+            cur += float(v[GAS])
+        return cur
 
     def _bhp_at_thp_limit(self, k):
         """vfp.bhp at well k's rates and limit: (9,) - value, the five partials, d/d(aqua, liquid, vapour)"""
@@ -566,6 +766,19 @@ class StandardWells:
                 g[k, OIL], g[k, WATER], g[k, GAS], g[k, 3] = 0.0 - V[7], 0.0 - V[6], 0.0 - V[8], 1.0
             elif w.control[0] == "bhp":
                 r[k], g[k, 3] = x[3] - w.control[1], 1.0
+            elif w.control[0] in COMPONENT_OF_LIMIT:
+                comp = COMPONENT_OF_LIMIT[w.control[0]]
+                r[k], g[k, comp] = x[comp] + w.control[1], 1.0
+            elif w.control[0] == "lrat":
+                r[k], g[k, OIL], g[k, WATER] = (x[OIL] + x[WATER]) + w.control[1], 1.0, 1.0
+            elif w.control[0] == "resv":
+                c = self.resv_coeff[k]
+                if w.producer:
+                    r[k] = ((c[WATER] * x[WATER] + c[OIL] * x[OIL]) + c[GAS] * x[GAS]) + w.control[1]
+                    g[k, :3] = c
+                else:
+                    comp = COMPONENT_OF_PHASE[PHASE_BY_NAME[w.inj_phase]]
+                    r[k], g[k, comp] = c[comp] * x[comp] - w.control[1], c[comp]
             else:
                 comp, target = w.control[1], w.control[2]
                 r[k], g[k, comp] = x[comp] - (-1.0 if w.producer else 1.0) * target, 1.0
@@ -575,18 +788,46 @@ class StandardWells:
         """BlackoilWellModel::updateWellControls: the limits in the reference's order, the first that is violated and is not the control in
         force wins.  A well leaves its rate target (or its THP limit) for BHP control when its BHP leaves the limit; it returns to the rate
         target once the rate exceeds it; with a THP limit it goes under THP control when the tubing-head pressure its state implies is
-        beyond the limit (the module's text)"""
+        beyond the limit; the further rate limits (Well(limits=)) stand between BHP and THP in the order ORAT, WRAT, GRAT, LRAT, RESV, the
+        well's own target at its component's place (the module's text).  On a switch to a rate-type mode the state stays as it is."""
         for k, (w, x) in enumerate(zip(self.wells, self.x)):
             sign = -1.0 if w.producer else 1.0
             t = self.thp_tables[k]
             if t is not None:
                 self.thp_current[k] = vfp_mod.thp(t, float(x[WATER]), float(x[OIL]), float(x[GAS]), float(x[3] + self.thp_dp[k]), w.alq)
+            limits = getattr(w, "limits", {})
+            if "resv" in limits:
+                self.resv_current[k] = self._resv_current(k)
+            own = w.rate_control if w.rate_control[0] == "rate" and getattr(w, "use_list_target", True) else None
             if w.control[0] != "bhp" and ((w.producer and x[3] < w.bhp_limit) or (not w.producer and x[3] > w.bhp_limit)):
                 w.control = ("bhp", w.bhp_limit)
                 x[3] = w.bhp_limit
-            elif w.control[0] != "rate" and sign * x[w.rate_control[1]] > w.rate_control[2]:
-                w.control = w.rate_control
-            elif t is not None and w.control[0] != "thp" and (w.thp_limit > self.thp_current[k] if w.producer else w.thp_limit < self.thp_current[k]):
+                continue
+            switched = False
+            for kind in LIMIT_KINDS if w.producer else ("rate", "resv"):
+                comp = COMPONENT_OF_LIMIT.get(kind, own[1] if own else None)
+                if own is not None and comp == own[1] and kind != "lrat" and kind != "resv":     # the well's own target, at its component's place
+                    hit = w.control[0] != "rate" and sign * x[comp] > own[2]
+                    target = own
+                elif kind not in limits or w.control[0] == kind:
+                    continue
+                else:
+                    target = (kind, limits[kind])
+                    if kind == "lrat":
+                        current = -x[OIL]
+                        current -= x[WATER]
+                    elif kind == "resv":
+                        current = self.resv_current[k]
+                    else:
+                        current = -x[comp]
+                    hit = limits[kind] < current
+                if hit:
+                    w.control = target
+                    switched = True
+                    break
+            if switched:
+                continue
+            if t is not None and w.control[0] != "thp" and (w.thp_limit > self.thp_current[k] if w.producer else w.thp_limit < self.thp_current[k]):
                 w.control = ("thp", w.thp_limit)
                 x[3] = self._bhp_at_thp_limit(k)[0] - self.thp_dp[k]
 
@@ -725,7 +966,8 @@ class StandardWells:
 class DeviceStandardWells:
     """The same wells resident on the device (opmhip_set_std_wells): model is a capi.HipModel whose state is set.  The well unknowns, the
     controls, the heads and the blocks B, C, D^-1 live there; what this object holds of them (x, controls, res_well) is the last read-back
-    (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow).  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
+    (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow), further rate limits (Well(limits=)) sent
+    with opmhip_set_std_wells_limits.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
     def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None):
@@ -746,6 +988,8 @@ class DeviceStandardWells:
                 raise ValueError("DeviceStandardWells: well %s needs a rate target and, under BHP control, its limit as the target" % w.name)
             if w.control[0] == "thp" and w.control[1] != w.thp_limit:
                 raise ValueError("DeviceStandardWells: well %s under THP control needs its limit as the target" % w.name)
+            if w.control[0] in LIMIT_KINDS and w.control[1] != getattr(w, "limits", {}).get(w.control[0]):
+                raise ValueError("DeviceStandardWells: well %s under %s control needs that limit as the target" % (w.name, w.control[0].upper()))
             if not w.producer and w.inj_phase not in phase:
                 raise ValueError("DeviceStandardWells: injector %s with unknown phase %r" % (w.name, w.inj_phase))
             if head_model == "wellbore" and w.producer and w.preferred_phase not in phase:
@@ -771,8 +1015,19 @@ class DeviceStandardWells:
                                          thp_limit=[0.0 if t is None else w.thp_limit for w, t in zip(self.wells, self.thp_tables)],
                                          alq=[w.alq if t is not None else 0.0 for w, t in zip(self.wells, self.thp_tables)],
                                          dh=[0.0 if t is None else t.datum_depth - w.ref_depth for w, t in zip(self.wells, self.thp_tables)]))
-            if any(w.control[0] == "thp" for w in self.wells):   # the list itself starts under the deck's modes: THP through the state call
-                model.set_std_wells_state(None, [CONTROL_CODE[w.control[0]] for w in self.wells], None)
+        self.has_limits = any(getattr(w, "limits", None) or not getattr(w, "use_list_target", True) for w in self.wells)
+        if self.has_limits:                                  # (a list without further limits makes the calls it made before)
+            inf = float("inf")
+            kinds = dict(oil_rate="orat", water_rate="wrat", gas_rate="grat", liquid_rate="lrat", resv_rate="resv")
+            # a well that starts under one of the new modes is under BHP control until the state call below: its own target may not be a limit
+            lim = {field: [w.limits.get(kind, inf) for w in self.wells] for field, kind in kinds.items()}
+            lim["use_list_target"] = [int(w.use_list_target) for w in self.wells]
+            start = [1 if (w.control[0] in LIMIT_KINDS or w.control[0] == "thp") else CONTROL_CODE[w.control[0]] for w in self.wells]
+            if any(s != int(w.control[0] == "bhp") for s, w in zip(start, self.wells)):
+                model.set_std_wells_state(None, start, None)
+            model.set_std_wells_limits(lim)
+        if any(w.control[0] not in ("rate", "bhp") for w in self.wells):   # the list itself starts under the deck's modes: the others through the state call
+            model.set_std_wells_state(None, [CONTROL_CODE[w.control[0]] for w in self.wells], None)
         self.x = np.zeros((self.nw, 4))
         self.res_well = np.zeros((self.nw, 4))
 
@@ -783,7 +1038,8 @@ class DeviceStandardWells:
         """opmhip_get_std_wells: x, the controls in force (onto the Well objects) and r_w of the last assemble"""
         self.x, ctl, self.res_well = self.m.get_std_wells()
         for w, k in zip(self.wells, ctl):
-            w.control = (w.rate_control, ("bhp", w.bhp_limit), ("thp", w.thp_limit))[int(k)]
+            k = int(k)
+            w.control = (w.rate_control, ("bhp", w.bhp_limit), ("thp", w.thp_limit))[k] if k < 3 else (LIMIT_KINDS[k - 3], w.limits[LIMIT_KINDS[k - 3]])
         return self.x
 
     def update(self, relax=1.0):
@@ -801,6 +1057,10 @@ class DeviceStandardWells:
 
     def _send(self):
         self.m.set_std_wells_state(self.x, [CONTROL_CODE[w.control[0]] for w in self.wells], [w.rate_control[2] for w in self.wells])
+
+    def resv(self):
+        """opmhip_get_std_wells_resv: dict(averages, coeff, resv_current) - StandardWells' resv_averages, resv_coeff, resv_current"""
+        return self.m.std_wells_resv()
 
     def thp(self):
         """opmhip_get_std_wells_thp: dict(thp, dp, bhp_from_thp) per well - StandardWells' thp_current, thp_dp, bhp_from_thp"""
