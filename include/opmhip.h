@@ -833,8 +833,9 @@ int opmhip_get_std_wells_blocks(opmhip_ctx* ctx, double* head, double* D, double
  * Perforations with dd > 0, and every perforation of a well without the switch, take the expressions of the list above in their
  * order: a well with the switch and no reversed perforation gives the same bits as without.  With the well-bore heads the stored
  * perforation rates are whatever the assembly formed, injecting signs included.
- * Left out: vaporised oil in the rate model (rv = 0, d = 1, tmp_oil = cmix_o: the producing branch adds rs q_o to the gas and nothing
- * to the oil, and crossflow keeps that); openCrossFlowAvoidSingularity.
+ * By default the rate model is the dry-gas one (rv = 0, d = 1, tmp_oil = cmix_o: the producing branch adds rs q_o to the gas and nothing
+ * to the oil, and crossflow keeps that); opmhip_set_std_wells_vaporised_oil switches the wet-gas model on.  Left out:
+ * openCrossFlowAvoidSingularity.
  * allow: per well, 0 or 1; NULL or all zeros: off.  Call it after opmhip_set_std_wells; replacing or clearing the list clears it.
  * OPMHIP_NOT_READY without a list; OPMHIP_INVALID_ARGUMENT for a value other than 0 / 1 or for an injector (the text says so).  A
  * refused call leaves the flags as they were.  What the last assemble formed is stale afterwards, as with
@@ -845,6 +846,35 @@ int opmhip_set_std_wells_crossflow(opmhip_ctx* ctx, const int* allow);
 /* for tests: dq [nperf * 9] = d rate_c / d q_j of the last assemble, [perforation][component c][unknown j]; zeros without the
  * switch.  (opmhip_get_std_wells_blocks keeps its rates [nperf * 15] layout.) */
 int opmhip_get_std_wells_rate_dq(opmhip_ctx* ctx, double* dq);
+/* ---- vaporised oil in the connection rates.  Additive to ABI 11 ------------------------------------------------------------------
+ * replaces: the rs / rv terms of StandardWellEval::computePerfRate (wells/StandardWellEval.cpp:999-1021 the producing branch, :1055-1073
+ * the injecting / crossflow branch with d = 1 - rv rs, :1092-1112 the split into dissolved gas and vaporised oil), the per-well sums of
+ * wells/StandardWell_impl.hpp:313-336 and the rates of wells/WellState.cpp:562-563, in the operation order of wells.py
+ * StandardWells(arithmetic="stated", vaporised_oil=True).  Per list, off by default: the default is the dry-gas model above, on a wet-gas
+ * context too - a producer in a gas cap then reports no oil for the condensate its gas carries.  With the switch on,
+ * surf[ph] = b_ph * (-tw * (mob_ph * dd)), rs and rv the record's Rs and Rv with their three cell derivatives:
+ *   producing perforation (dd > 0):  rate_o = surf_o + rv * surf_g;  rate_g = surf_g + rs * surf_o;  rate_w = surf_w  (both products
+ *     from the surf values before either sum); for a producer perf_dis_gas = (rs * surf_o).value, perf_vap_oil = (rv * surf_g).value;
+ *   reversed perforation of a producer with the crossflow switch:  d = 1 - rv * rs;  tmp_oil = (cmix_o - rv * cmix_g) / d;
+ *     tmp_gas = (cmix_g - rs * cmix_o) / d;  volumeRatio = (cmix_w / b_w + tmp_oil / b_o) + tmp_gas / b_g;  cqt_is and rate_c as above.
+ *     A perforation whose d is not > 0 stays closed for that evaluation, like one whose volumeRatio is not > 0 (the reference throws a
+ *     NumericalIssue where d == 0).  On values only: perf_vap_oil = rv * (q_g - rs * q_o) / d, perf_dis_gas = rs * (q_o - rv * q_g) / d
+ *     with q = rate_c;
+ *   injectors: unchanged - the injected composition is fixed and nothing of rv enters.
+ * The two split values are added per well by one lane in perforation order, like every other sum.
+ * on: 0 or 1.  Call it after opmhip_set_std_wells; replacing or clearing the list clears it.  OPMHIP_NOT_READY without a list;
+ * OPMHIP_INVALID_ARGUMENT (the text names the reason) for another value and for a context whose fluid has no PVTG.  A refused call
+ * leaves the switch as it was.  What the last assemble formed is stale afterwards, as with opmhip_set_std_wells_crossflow.  A list
+ * without the switch launches exactly the kernels it launched before; with it, the wells alone and the assembly run another
+ * instantiation of the same kernel in place of the first (two more sums per lane): the number of launches does not change.  The switch
+ * adds no state to save or restore.
+ * UNVERIFIED in the usual sense: the reference tree holds no number for a well's rates. */
+int opmhip_set_std_wells_vaporised_oil(opmhip_ctx* ctx, int on);
+/* per well [num_wells] each, either pointer may be NULL: the sums of perf_dis_gas and perf_vap_oil over a producer's perforations that
+ * the last opmhip_assemble formed, in the module's sign - rates into the reservoir, production negative.  Zeros for injectors, without
+ * a list and with the switch off - dissolved_gas too: the default model runs the kernels it ran before, which form neither.  Waits for
+ * the stream. */
+int opmhip_get_std_wells_solution_rates(opmhip_ctx* ctx, double* dissolved_gas, double* vaporised_oil);
 /* ---- the heads from the well-bore density.  Additive to ABI 11 -------------------------------------------------------------
  * replaces: StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:1195-1210), that is
  * computePropertiesForWellConnectionPressures (:899-1012), computeWellConnectionDensitesPressures (:1124-1189),

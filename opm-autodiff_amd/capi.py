@@ -751,6 +751,8 @@ def _bind_assembly(L):
     L.opmhip_set_std_wells_perf_state.argtypes = [vp, vp, vp]
     L.opmhip_set_std_wells_crossflow.argtypes = [vp, vp]
     L.opmhip_get_std_wells_rate_dq.argtypes = [vp, vp]
+    L.opmhip_set_std_wells_vaporised_oil.argtypes = [vp, C.c_int]
+    L.opmhip_get_std_wells_solution_rates.argtypes = [vp, vp, vp]
     L.opmhip_set_std_wells_thp.argtypes = [vp, C.POINTER(StdWellsThp)]
     L.opmhip_get_std_wells_thp.argtypes = [vp, vp, vp, vp]
     L.opmhip_set_std_wells_limits.argtypes = [vp, C.POINTER(StdWellsLimits)]
@@ -1094,6 +1096,24 @@ class HipModel(HipSolver):
         out = dict(averages=np.zeros(5), coeff=np.zeros((n, 3)), resv_current=np.zeros(n))
         self._check(lib().opmhip_get_std_wells_resv(self._h, _ptr(out["averages"]), _ptr(out["coeff"]), _ptr(out["resv_current"])))
         return out
+
+    def set_std_wells_vaporised_oil(self, on=True):
+        """opmhip_set_std_wells_vaporised_oil: the wet-gas rate model of the resident list - the oil the produced gas carries counts as oil.
+        A context whose fluid has no PVTG is a ValueError; a refused call leaves the switch as it was."""
+        try:
+            self._check(lib().opmhip_set_std_wells_vaporised_oil(self._h, int(on)))
+        except OpmHipError as e:
+            if e.code == INVALID_ARGUMENT and "no PVTG" in str(e):
+                raise ValueError(str(e)) from e
+            raise
+
+    def std_wells_solution_rates(self):
+        """opmhip_get_std_wells_solution_rates: (dissolved_gas, vaporised_oil) per well of the last assemble - rates into the reservoir,
+        production negative; zeros for injectors and with the switch off"""
+        n = getattr(self, "_nsw", 0)
+        dis, vap = np.zeros(n), np.zeros(n)
+        self._check(lib().opmhip_get_std_wells_solution_rates(self._h, _ptr(dis), _ptr(vap)))
+        return dis, vap
 
     def std_wells_rate_dq(self):
         """for tests: d rate_c / d q_j of the last assemble, (perforations, 3 components, 3 rate unknowns); zeros without crossflow"""

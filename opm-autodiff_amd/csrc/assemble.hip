@@ -1811,8 +1811,18 @@ int launch_vfp_probe(opmhip_ctx* c, int table, int n, const double* d_in, bool h
 // (v = a0 / b0; (a_i - v b_i) / b0), sums and differences entry by entry, in the order written.  P not > 0 (the well has not flowed
 // yet) or volumeRatio not > 0: the perforation stays closed for that evaluation - nothing is divided by zero or a negative.  Then
 // D[c][j] = delta_cj - sum_p d rate_c / d q_j and C[j][c] = 0 - d rate_c / d q_j; perforations with dd > 0 and wells without the switch
-// take the expressions below unchanged.  Left out: vaporised oil (rv = 0, d = 1, tmp_oil = cmix_o), openCrossFlowAvoidSingularity.
-// Injectors are refused: this parametrisation fixes the injected composition, where the reference re-injects what crosses in.
+// take the expressions below unchanged.  By default the rate model is the dry-gas one (rv = 0, d = 1, tmp_oil = cmix_o).  Left out:
+// openCrossFlowAvoidSingularity.  Injectors are refused: this parametrisation fixes the injected composition, where the reference
+// re-injects what crosses in.
+//
+// Vaporised oil (opmhip_set_std_wells_vaporised_oil, per list, off by default; the VO instantiations): the rs / rv terms of computePerfRate
+// (wells/StandardWellEval.cpp:999-1021, 1055-1073, 1092-1112) with rv = the record's F_RV.  surf[ph] = b_ph * (-tw * (mob_ph * dd)):
+//     dd > 0 (N = 5):  rate_o = surf_o + rv * surf_g;  rate_g = surf_g + rs * surf_o;  rate_w = surf_w
+//                      a producer's perf_dis_gas = (rs * surf_o).value, perf_vap_oil = (rv * surf_g).value
+//     reversed, CF (N = 8):  d = 1 - rv * rs;  tmp_oil = (cmix_o - rv * cmix_g) / d;  tmp_gas = (cmix_g - rs * cmix_o) / d
+//                      volumeRatio = (cmix_w / b_w + tmp_oil / b_o) + tmp_gas / b_g;  d not > 0: closed, like volumeRatio not > 0
+//                      on values: perf_vap_oil = rv * (q_g - rs * q_o) / d;  perf_dis_gas = rs * (q_o - rv * q_g) / d
+// Injectors keep their branch.  The two split values join the per-well sums in LDS (NS + 2); lane 0 leaves their sums per well.
 template <int N> struct SwAd { double v[N]; };
 template <int N> __device__ __forceinline__ SwAd<N> sw_load(const double* __restrict__ p) {   // a field of the record: no d/dbhp, no d/dq
     SwAd<N> o;
@@ -1884,11 +1894,13 @@ __device__ bool sw_wellbore_fractions(const double* x, double* mix) {
 // dq[component * 3 + (d/dq_o, d/dq_w, d/dq_g)].  The drawdown decides, once: a perforation that flows the way of its well takes the
 // N = 5 arithmetic (dq = 0); one that does not stays closed - unless it is a producer's and `reverse` holds (the well has the crossflow
 // switch and flows: mix are its fractions), which takes the N = 8 branch, closed still where the volume ratio is not positive.
-template <bool CF>
+// VO: the wet-gas rate model (the extended record: F_RV); sol[0] = perf_dis_gas, sol[1] = perf_vap_oil of a producer's perforation.
+template <bool CF, bool VO>
 __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int ncell, int c, double tw, double bhp, double head, bool producer, int injPhase,
-                                              bool reverse, const double* mix, double* out, double* dq) {
+                                              bool reverse, const double* mix, double* out, double* dq, double* sol) {
 #pragma unroll
     for (int i = 0; i < 15; ++i) out[i] = 0.0;
+    if (VO) { sol[0] = 0.0; sol[1] = 0.0; }
     if (CF) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) dq[i] = 0.0;
@@ -1903,9 +1915,19 @@ __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int
 #pragma unroll
             for (int ph = 0; ph < 3; ++ph)
                 surf[ph] = sw_mul(sw_load<5>(iq_at(iq, ncell, F_B + ph, c)), sw_scale(ntw, sw_mul(sw_load<5>(iq_at(iq, ncell, F_MOB + ph, c)), dd)));
-            sw_store5(out + EQ_OIL * 5, surf[OIL]);
-            sw_store5(out + EQ_WATER * 5, surf[WATER]);
-            sw_store5(out + EQ_GAS * 5, sw_add(surf[GAS], sw_mul(sw_load<5>(iq_at(iq, ncell, F_RS, c)), surf[OIL])));
+            if (VO) {     // the oil the gas carries counts as oil; both products from the surf values before either sum
+                const SwAd<5> dis = sw_mul(sw_load<5>(iq_at(iq, ncell, F_RS, c)), surf[OIL]);
+                const SwAd<5> vap = sw_mul(sw_load<5>(iq_at(iq, ncell, Lay<true>::F_RV, c)), surf[GAS]);
+                sw_store5(out + EQ_OIL * 5, sw_add(surf[OIL], vap));
+                sw_store5(out + EQ_WATER * 5, surf[WATER]);
+                sw_store5(out + EQ_GAS * 5, sw_add(surf[GAS], dis));
+                sol[0] = dis.v[0];
+                sol[1] = vap.v[0];
+            } else {
+                sw_store5(out + EQ_OIL * 5, surf[OIL]);
+                sw_store5(out + EQ_WATER * 5, surf[WATER]);
+                sw_store5(out + EQ_GAS * 5, sw_add(surf[GAS], sw_mul(sw_load<5>(iq_at(iq, ncell, F_RS, c)), surf[OIL])));
+            }
         } else {          // total mobility, the injected phase's 1/B
             const SwAd<5> tot = sw_add(sw_add(sw_load<5>(iq_at(iq, ncell, F_MOB + 0, c)), sw_load<5>(iq_at(iq, ncell, F_MOB + 1, c))), sw_load<5>(iq_at(iq, ncell, F_MOB + 2, c)));
             const SwAd<5> vol = sw_scale(ntw, sw_mul(tot, dd));
@@ -1920,8 +1942,20 @@ __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int
         for (int k = 0; k < 3; ++k) cm[k] = A8{{mix[k * 4], 0.0, 0.0, 0.0, 0.0, mix[k * 4 + 1], mix[k * 4 + 2], mix[k * 4 + 3]}};
         const A8 tot = sw_add(sw_add(sw_load<8>(iq_at(iq, ncell, F_MOB + WATER, c)), sw_load<8>(iq_at(iq, ncell, F_MOB + OIL, c))), sw_load<8>(iq_at(iq, ncell, F_MOB + GAS, c)));
         const A8 cqt_i = sw_scale(ntw, sw_mul(tot, dd));
-        const A8 ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load<8>(iq_at(iq, ncell, F_B + WATER, c))), sw_div(cm[EQ_OIL], sw_load<8>(iq_at(iq, ncell, F_B + OIL, c)))),
-                                sw_div(sw_sub(cm[EQ_GAS], sw_mul(sw_load<8>(iq_at(iq, ncell, F_RS, c)), cm[EQ_OIL])), sw_load<8>(iq_at(iq, ncell, F_B + GAS, c))));
+        A8 ratio;
+        double rs0 = 0.0, rv0 = 0.0, d0 = 1.0;
+        if (VO) {
+            const A8 rs = sw_load<8>(iq_at(iq, ncell, F_RS, c)), rv = sw_load<8>(iq_at(iq, ncell, Lay<true>::F_RV, c));
+            const A8 d = sw_sub(A8{{1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}}, sw_mul(rv, rs));
+            if (!(d.v[0] > 0.0)) return;   // (the reference throws where d == 0)
+            const A8 tmp_oil = sw_div(sw_sub(cm[EQ_OIL], sw_mul(rv, cm[EQ_GAS])), d);
+            const A8 tmp_gas = sw_div(sw_sub(cm[EQ_GAS], sw_mul(rs, cm[EQ_OIL])), d);
+            ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load<8>(iq_at(iq, ncell, F_B + WATER, c))), sw_div(tmp_oil, sw_load<8>(iq_at(iq, ncell, F_B + OIL, c)))),
+                           sw_div(tmp_gas, sw_load<8>(iq_at(iq, ncell, F_B + GAS, c))));
+            rs0 = rs.v[0]; rv0 = rv.v[0]; d0 = d.v[0];
+        } else
+            ratio = sw_add(sw_add(sw_div(cm[EQ_WATER], sw_load<8>(iq_at(iq, ncell, F_B + WATER, c))), sw_div(cm[EQ_OIL], sw_load<8>(iq_at(iq, ncell, F_B + OIL, c)))),
+                           sw_div(sw_sub(cm[EQ_GAS], sw_mul(sw_load<8>(iq_at(iq, ncell, F_RS, c)), cm[EQ_OIL])), sw_load<8>(iq_at(iq, ncell, F_B + GAS, c))));
         if (!(ratio.v[0] > 0.0)) return;
         const A8 cqt_is = sw_div(cqt_i, ratio);
 #pragma unroll
@@ -1930,6 +1964,10 @@ __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int
             sw_store5(out + k * 5, r);
 #pragma unroll
             for (int j = 0; j < 3; ++j) dq[k * 3 + j] = r.v[5 + j];
+        }
+        if (VO) {   // the split, on values only (:1105-1111)
+            sol[1] = rv0 * (out[EQ_GAS * 5] - rs0 * out[EQ_OIL * 5]) / d0;
+            sol[0] = rs0 * (out[EQ_OIL * 5] - rv0 * out[EQ_GAS * 5]) / d0;
         }
     }
 }
@@ -1967,6 +2005,7 @@ struct SwArrays {
     double* wbstate;                            // then: p_perf [nperf] | the rates of the last assembly [nperf * 3]
     const int* cf;                              // per well: crossflow allowed (read by the CF instantiations only; NULL without a flag)
     double* dq;                                 // then: d rate_c / d q_j of the last assembly [nperf * 9]
+    double* sol;                                // the VO instantiations': per well dissolved gas [num] | vaporised oil [num] of the last assembly
     double *control, *rw, *flag;                // d_pack's other fields: per well 0.0 rate / 1.0 bhp / 2.0 thp; r_w, 4 per well; the zero-pivot flag
 };
 // THP limits (opmhip_set_std_wells_thp; read by the THP instantiations only).  table: per well the index of its VFP table, -1: no limit; wd:
@@ -2073,9 +2112,11 @@ __global__ __launch_bounds__(64) void k_std_wells_resv_coeff(int num, const int*
 // 433-436, 463-504); the assembling form also leaves V - dp of every well with a limit.  Every other well gets today's bits.
 // LIM: the list has further rate limits (launched in place of the other instantiation, for all its wells): under control 3 .. 7 the control
 // row is that limit's (include/opmhip.h, opmhip_set_std_wells_limits); every other control gets today's bits.
-template <bool SOLVE, bool CF, bool THP, bool LIM>
+// VO: the list has the vaporised-oil switch (launched in place of the other instantiation): the wet-gas rate model of sw_perf_rates, two
+// more sums per lane - a perforation's dissolved gas and vaporised oil -, which the assembling form leaves per well in W.sol.
+template <bool SOLVE, bool CF, bool THP, bool LIM, bool VO>
 __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim M, int ncell, const double* __restrict__ iq, int first) {
-    constexpr int NS = CF ? 15 : 6;
+    constexpr int NS = (CF ? 15 : 6) + (VO ? 2 : 0), SOL = CF ? 15 : 6;   // SOL: where the two split values sit
     __shared__ double sums[64 * NS];
     __shared__ double xs[4];
     __shared__ double s_mix[12];
@@ -2115,8 +2156,9 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim 
         for (int p0 = pb; p0 < pe; p0 += 64) {
             const int p = p0 + lane;
             if (p < pe) {
-                double q[15], dq[CF ? 9 : 1];
-                sw_perf_rates<CF>(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, crossflow && s_flows, s_mix, q, dq);
+                double q[15], dq[CF ? 9 : 1], sol[VO ? 2 : 1];
+                sw_perf_rates<CF, VO>(iq, ncell, W.cell[p], W.tw[p], bhp, W.head[p], producer, injPhase, crossflow && s_flows, s_mix, q, dq, sol);
+                if (VO) { sums[lane * NS + SOL] = sol[0]; sums[lane * NS + SOL + 1] = sol[1]; }
                 if (CF) {
 #pragma unroll
                     for (int i = 0; i < 9; ++i) sums[lane * NS + 6 + i] = dq[i];
@@ -2212,6 +2254,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim 
                 }
             } else {
                 for (int i = 0; i < 4; ++i) W.rw[(size_t)4 * w + i] = r[i];
+                if (VO) { W.sol[w] = S[SOL]; W.sol[(size_t)W.num + w] = S[SOL + 1]; }
                 for (int i = 0; i < 16; ++i) { W.Dmat[(size_t)16 * w + i] = D[i]; W.Dinv[(size_t)16 * w + i] = inv[i]; }   // a singular D: zeros, never NaNs
             }
         }
@@ -2466,20 +2509,24 @@ static SwLim std_wells_lim(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     return SwLim{S.d_lim, S.d_lim_use, S.d_lim_out};
 }
-// the instantiation of k_std_wells_eq a list runs: one per combination of crossflow, THP limits and further rate limits (a list without the
-// feature runs the code it ran before; the number of launches is the same)
-template <bool SOLVE>
-static auto std_wells_eq_kernel(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false>) {
+// the instantiation of k_std_wells_eq a list runs: one per combination of crossflow, THP limits, further rate limits and the vaporised-oil
+// switch (a list without the feature runs the code it ran before; the number of launches is the same)
+template <bool SOLVE, bool VO>
+static auto std_wells_eq_kernel_of(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, VO>) {
     if (S.limits)
-        return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, true> : k_std_wells_eq<SOLVE, false, true, true>)
-                     : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, true> : k_std_wells_eq<SOLVE, false, false, true>);
-    return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, false> : k_std_wells_eq<SOLVE, false, true, false>)
-                 : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, false> : k_std_wells_eq<SOLVE, false, false, false>);
+        return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, true, VO> : k_std_wells_eq<SOLVE, false, true, true, VO>)
+                     : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, true, VO> : k_std_wells_eq<SOLVE, false, false, true, VO>);
+    return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, false, VO> : k_std_wells_eq<SOLVE, false, true, false, VO>)
+                 : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, false, VO> : k_std_wells_eq<SOLVE, false, false, false, VO>);
+}
+template <bool SOLVE>
+static auto std_wells_eq_kernel(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, false>) {
+    return S.vaporised_oil ? std_wells_eq_kernel_of<SOLVE, true>(S) : std_wells_eq_kernel_of<SOLVE, false>(S);
 }
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
     return SwArrays{S.num, W.d_val_pointers, W.d_Ccols, S.d_wi, S.d_wd, S.d_tw, S.d_dz, S.d_head, S.d_pr, S.x(), S.d_Dmat, W.d_B, W.d_C, W.d_D,
-                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate, S.d_cf, S.d_dq, S.control(), S.rw(), S.flag()};
+                    S.wellbore ? 1 : 0, S.nperf, S.d_wbstate, S.d_cf, S.d_dq, S.d_sol, S.control(), S.rw(), S.flag()};
 }
 // (booked under the profile's assembly class, one scope per function: a context with a list shows them in opmhip_profile_get)
 void launch_std_wells_solve(opmhip_ctx* c, bool first) {

@@ -1147,6 +1147,8 @@ void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
     dev_free(c, &S.d_cf); dev_free(c, &S.d_dq);
     S.crossflow = false;
+    dev_free(c, &S.d_sol);
+    S.vaporised_oil = false;
     std_wells_thp_release(c);
     std_wells_wellbore_release(c);
     S.h_wi.clear(); S.h_wd.clear();
@@ -1430,6 +1432,50 @@ int opmhip_get_std_wells_rate_dq(opmhip_ctx* c, double* dq) {
         OPMHIP_HIP(c, hipSetDevice(c->device));
         OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
         OPMHIP_HIP(c, hipMemcpy(dq, S.d_dq, 9 * np * sizeof(double), hipMemcpyDeviceToHost));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_vaporised_oil(opmhip_ctx* c, int on) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_vaporised_oil: no resident list (opmhip_set_std_wells)");
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the switch as it was
+        if (int r = std_wells_check_vaporised_oil(on, c->asmb.wet_gas, msg)) return fail(c, r, "%s", msg.c_str());
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        double* d_sol = nullptr;
+        if (on) {
+            if (int r = dev_upload(c, &d_sol, std::vector<double>(2 * (size_t)S.num, 0.0))) {
+                dev_free(c, &d_sol);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        dev_free(c, &S.d_sol);
+        S.d_sol = d_sol;
+        S.vaporised_oil = on != 0;
+        S.assembled = false;   // the blocks of the last assembly are no longer the model's
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_solution_rates(opmhip_ctx* c, double* dissolved_gas, double* vaporised_oil) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return OPMHIP_SUCCESS;
+        const size_t nw = S.num;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        if (!S.vaporised_oil) {   // the default model's kernels form neither
+            if (dissolved_gas) std::memset(dissolved_gas, 0, nw * sizeof(double));
+            if (vaporised_oil) std::memset(vaporised_oil, 0, nw * sizeof(double));
+            return OPMHIP_SUCCESS;
+        }
+        if (dissolved_gas) OPMHIP_HIP(c, hipMemcpy(dissolved_gas, S.d_sol, nw * sizeof(double), hipMemcpyDeviceToHost));
+        if (vaporised_oil) OPMHIP_HIP(c, hipMemcpy(vaporised_oil, S.d_sol + nw, nw * sizeof(double), hipMemcpyDeviceToHost));
         return OPMHIP_SUCCESS;
     });
 }

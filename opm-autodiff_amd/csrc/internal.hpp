@@ -209,6 +209,10 @@ struct StdWellsDev {
     bool crossflow = false;
     int* d_cf = nullptr;
     double* d_dq = nullptr;
+    // vaporised oil in the rate model (opmhip_set_std_wells_vaporised_oil): d_sol: per well the dissolved gas [num] | the vaporised oil
+    // [num] of the last assemble; allocated while the switch is on
+    bool vaporised_oil = false;
+    double* d_sol = nullptr;
     // THP limits (opmhip_set_std_wells_thp): set only while some well of the list has one.  d_thp_table: per well the index of its VFP
     // table (-1: no limit), h_thp_table its host copy; d_thp_wd: per well limit, alq, dh; d_thp_out: thp of the last controls | dp of this
     // time step | V - dp of the last assemble (3 num doubles, field-major)

@@ -156,6 +156,13 @@ int std_wells_check_crossflow(size_t nw, const int* allow, const int* wi, bool& 
     return OPMHIP_SUCCESS;
 }
 
+int std_wells_check_vaporised_oil(int on, bool has_pvtg, std::string& msg) {
+    if (on != 0 && on != 1) return refuse(msg, "set_std_wells_vaporised_oil: on = %d (0 off, 1 on)", on);
+    if (!has_pvtg)
+        return refuse(msg, "set_std_wells_vaporised_oil: the context's fluid has no PVTG - its intensive-quantity records hold no Rv for the rate model to read");
+    return OPMHIP_SUCCESS;
+}
+
 int std_wells_head_model(const opmhip_std_wells_wellbore* wb, size_t nw, size_t np, const int* wi, std::vector<int>& pref, std::string& msg) {
     if (!wb->perf_depth || !wb->ref_depth || !wb->preferred_phase) return refuse(msg, "set_std_wells_head_model: null array");
     for (size_t p = 0; p < np; ++p)

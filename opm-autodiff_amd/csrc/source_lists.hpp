@@ -27,6 +27,8 @@ int std_wells_lists(const opmhip_std_wells* sw, int Nb, const int* toOrder, StdW
 int std_wells_check_state(size_t nw, const double* x, const int* control, const double* rate_target, std::string& msg);
 // wi: the list's; any: some well has the switch
 int std_wells_check_crossflow(size_t nw, const int* allow, const int* wi, bool& any, std::string& msg);
+// opmhip_set_std_wells_vaporised_oil.  has_pvtg: the context's fluid has PVTG, so that its records hold Rv
+int std_wells_check_vaporised_oil(int on, bool has_pvtg, std::string& msg);
 // opmhip_set_std_wells_limits.  wi: the list's; control: the controls in force (nw); lim: per well oil, water, gas, liquid, resv (+infinity:
 // none); use: per well use_list_target; any / any_resv: some well has a limit (or use_list_target = 0) / a RESV limit
 struct StdWellsLimitsLists {

@@ -206,6 +206,34 @@ def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, 
     return _wells.StandardWells(out, case["depth"])
 
 
+def gas_condensate_wells(case, allow_crossflow=False, oil_rate=40.0 / 86400.0, gas_rate=4000.0 / 86400.0, orat=0.1 / 86400.0, injection_rate=5000.0 / 86400.0,
+                         scale=0.2, diameter=0.15, limits=None, thp_limit=None, vfp_table=None):
+    """Three wells that share no cell on a column grid whose top is a gas cap holding vaporised oil (tests/helpers.py wetgas_case: gas cap,
+    three-phase zone, oil leg; nx, ny >= 3), as a list of wells.Well for wells.StandardWells / DeviceStandardWells(vaporised_oil=):
+      PLONG  a producer through every layer of column (0, 0) on an oil-rate target; its connection factors are scaled down (scale) so that
+             its drawdown is of the size of the pressure scatter of the synthetic cases: solved alone it keeps a few reversed perforations
+             in all three zones; allow_crossflow, limits (wells.Well(limits=)) and thp_limit / vfp_table are this well's;
+      PCAP   a producer of one completion in the gas cap, column (nx - 1, ny - 1) in the second layer, on a gas-rate target (GRAT) with an
+             ORAT limit: all its oil is the oil its gas carries, so the limit binds under the wet-gas rate model and never under the default;
+      GINJ   a gas injector into the top five layers of column (nx - 1, 0).
+    Surface rates in m^3/s; reference depth = the centre of the topmost completion; connection factors by Peaceman's formula."""
+    from . import wells as _wells
+    nx, ny, nz = case["nx"], case["ny"], case["nz"]
+    if nx < 3 or ny < 3 or nz < 6:
+        raise ValueError("gas_condensate_wells: at least 3 x 3 x 6 cells are expected")
+
+    def well(name, i, j, ks, producer, control, bhp_limit, factor=1.0, **kw):
+        cells = [i + nx * (j + ny * k) for k in ks]
+        tw = [factor * _wells.peaceman_factor(case["perm"][c], case["dx"], case["dy"], case["dz"], diameter) for c in cells]
+        return _wells.Well(name, cells, tw, case["depth"][cells[0]], producer, control, bhp_limit, **kw)
+    long_kw = dict(allow_crossflow=allow_crossflow, limits=limits)
+    if thp_limit is not None:
+        long_kw.update(thp_limit=thp_limit, vfp_table=vfp_table)
+    return [well("PLONG", 0, 0, range(nz), True, ("rate", _wells.OIL, oil_rate), 200e5, scale, **long_kw),
+            well("PCAP", nx - 1, ny - 1, [1], True, ("rate", _wells.GAS, gas_rate), 200e5, limits={"orat": orat}),
+            well("GINJ", nx - 1, 0, range(5), False, ("rate", _wells.GAS, injection_rate), 400e5, inj_phase="gas")]
+
+
 # Field rate of the five-spot pair on a 100 x 100 x 100 grid (scaled with the areal cell count elsewhere): 0.4 % of a well
 # cell's pore volume per day.  Fixed-rate sources do not see the mobility of the cell they drain, so rates ten times
 # higher desaturate the producer column within weeks and the Newton method then fails on 10-day steps.

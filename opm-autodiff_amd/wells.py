@@ -2,8 +2,8 @@
 the host (as in the reference: only the reservoir part of the linearisation and the Schur-complement operator are accelerated) and handed
 to the device as the blocks bda::WellContributions carries - B, C (4 x 3 per perforation), D^-1 (4 x 4 per well).
 
-What of the reference this restates, minimally (vertical wells, rate, BHP or THP control and several rate limits per well, crossflow in producers on request,
-no well storage term):
+What of the reference this restates, minimally (vertical wells, rate, BHP or THP control and several rate limits per well, crossflow in producers and vaporised oil in
+the connection rates on request, no well storage term):
   wells/StandardWell_impl.hpp: computePerfRate (:195-420; producing perforations: phase rate = -Tw mob drawdown, surface rate through
       1/B, dissolved gas with the oil; injecting perforations: total mobility, the injected phase's 1/B), assembleWellEqWithoutIteration
       (:516-640: mass-balance equation per component = surface rate - sum of connection rates, one control equation), apply (:1254-1296),
@@ -45,11 +45,32 @@ StandardWellEval::computePerfRate (wells/StandardWellEval.cpp:1023-1090) with al
   in the order written above.  A well whose P is not > 0 (it has not flowed yet) and a perforation whose volumeRatio is not > 0 stay
   closed for that evaluation: nothing is divided by zero or a negative.  Then D = I - sum_p d rate / d q beside its bhp column and C gains
   its first three rows, C[j][c] = 0 - d rate_c / d q_j.  Perforations with dd > 0 and wells without the switch take the expressions above
-  unchanged.  Left out: vaporised oil (rv = 0, d = 1, tmp_oil = cmix_o: as the producing branch, which adds rs q_o to the gas and nothing
-  to the oil), openCrossFlowAvoidSingularity (the guard for a well without a flowing completion stays).
+  unchanged.  The default is the dry-gas form (rv = 0, d = 1, tmp_oil = cmix_o: as the producing branch, which by default adds rs q_o to
+  the gas and nothing to the oil); StandardWells(vaporised_oil=True) takes the wet-gas form below.  Left out: openCrossFlowAvoidSingularity
+  (the guard for a well without a flowing completion stays).
   Injectors: refused (ValueError).  In the reference an injector re-injects what crosses into it, because its composition (WFrac, GFrac)
   is an unknown while getQs pins the other components to zero; this parametrisation fixes the injected composition, and a half-measure
   would let oil leave through an injector's wellhead.
+
+Vaporised oil in the connection rates (StandardWells(vaporised_oil=True) / DeviceStandardWells(vaporised_oil=True), per list, off by
+default; needs the 19-field record of a fluid with PVTG): the oil the produced gas carries counts as oil - computePerfRate's rs / rv terms
+(wells/StandardWellEval.cpp:999-1021, 1055-1073, 1092-1112).  surf[ph] = b_ph * (-tw * (mob_ph * dd)); rs, rv: the record's F_RS, F_RV with
+their three cell derivatives.
+    producing perforation (dd > 0, N = 5):  rate_o = surf_o + rv * surf_g;  rate_g = surf_g + rs * surf_o;  rate_w = surf_w
+        (both products from the surf values before either sum); for a producer perf_dis_gas = (rs * surf_o).value,
+        perf_vap_oil = (rv * surf_g).value
+    reversed perforation of a producer with the crossflow switch (N = 8):
+        d = 1 - rv * rs;  tmp_oil = (cmix_o - rv * cmix_g) / d;  tmp_gas = (cmix_g - rs * cmix_o) / d
+        volumeRatio = (cmix_w / b_w + tmp_oil / b_o) + tmp_gas / b_g;  cqt_is and rate_c as above
+        a perforation whose d is not > 0 stays closed for that evaluation, like one whose volumeRatio is not > 0 (the reference throws
+        a NumericalIssue where d == 0)
+        on values only (:1105-1111):  perf_vap_oil = rv * (q_g - rs * q_o) / d;  perf_dis_gas = rs * (q_o - rv * q_g) / d   (q = rate_c)
+    injectors: unchanged - the injected composition is fixed, nothing of rv enters.
+  solution_rates(): per well the sums of perf_dis_gas and perf_vap_oil over a producer's perforations as the last assemble formed them,
+  in perforation order (StandardWell_impl.hpp:313-336, WellState.cpp:562-563), in this module's sign: rates into the reservoir, production
+  negative.  Zeros for injectors and - both - with the switch off: the default model keeps the code it had, which forms neither.
+  With the switch off a wet-gas record gives the dry-gas rates: no oil for the condensate, no sink for it in the perforated cells' oil rows.
+  UNVERIFIED in the usual sense: the reference tree holds no number for a well's rates.
 
 A tubing-head-pressure limit (Well(thp_limit=, vfp_table=, alq=), StandardWells(vfp=[tables])): a third control beside the rate target and
 the BHP limit, through the VFPPROD (producers) / VFPINJ (injectors) tables of vfp.py.
@@ -99,6 +120,7 @@ from . import vfp as vfp_mod
 OIL, WATER, GAS = 0, 1, 2          # equation / component order of the blocks (csrc/assemble.hip: EQ_OIL, EQ_WATER, EQ_GAS)
 PH_W, PH_O, PH_G = 0, 1, 2         # phase order of the intensive-quantity record (opmhip_get_iq)
 F_S, F_P, F_B, F_MOB, F_RHO, F_RS = 0, 3, 6, 9, 12, 15
+F_RV = 16                          # in the 19-field record only (a fluid with PVTG, ROCKTAB or pc_scaling)
 GRAVITY = 9.80665
 COMPONENT_OF_PHASE = (WATER, OIL, GAS)      # indexed by PH_W, PH_O, PH_G
 PHASE_BY_NAME = {"water": PH_W, "oil": PH_O, "gas": PH_G}
@@ -375,8 +397,9 @@ class StandardWells:
     arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
     bit; a singular D raises SingularWellEquations there."""
 
-    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None, volume=None):
-        """volume: the cells' volumes, for the reservoir averages of a RESV limit where the model has no reservoir_averages() of its own
+    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None, volume=None, vaporised_oil=False):
+        """vaporised_oil: the wet-gas rate model (the module's text); the records handed in must then have 19 fields (ValueError otherwise).
+        volume: the cells' volumes, for the reservoir averages of a RESV limit where the model has no reservoir_averages() of its own
         (a RESV limit also needs props).  head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
         pvt_region=) - capi.HipFluid(fluid), the device's, or the CPU oracle's in tests, as equil.py takes them - with the deck-level
         tables as props.fluid (the surface densities); pvtnum: PVT region per cell (None: region 0); vfp: the vfp.VFPTable list the wells' THP
@@ -388,6 +411,7 @@ class StandardWells:
         if head_model == "wellbore" and props is None:
             raise ValueError("head_model='wellbore' needs props (probe / probe_gas)")
         self.arithmetic = arithmetic
+        self.vaporised_oil = bool(vaporised_oil)
         self.head_model, self.props = head_model, props
         self.wells = list(wells)
         self.nw = len(self.wells)
@@ -409,6 +433,8 @@ class StandardWells:
         self.tw = np.concatenate([w.tw for w in self.wells])
         self._rate_dq = None                       # d rate_c / d q_j of the last _perf_rates, (nperf, 3, 3); None: no perforation crossflows
         self.rate_dq = np.zeros((len(self.cells), 3, 3))   # ... of the last _assemble_wells, zeros without crossflow
+        self._perf_solution = np.zeros((len(self.cells), 2))   # perf_dis_gas, perf_vap_oil of the last _perf_rates (vaporised_oil; zeros without)
+        self._solution_rates = np.zeros((self.nw, 2))          # their per-well sums of the last _assemble_wells
         self.well_of_perf = np.repeat(np.arange(self.nw), np.diff(self.vp))
         # the cells the model is asked about / told about: every perforated cell once
         self.ucells, self.perf_row = np.unique(self.cells, return_inverse=True)
@@ -681,6 +707,12 @@ class StandardWells:
         b = [ad(F_B + ph) for ph in range(3)]
         mob = [ad(F_MOB + ph) for ph in range(3)]
         rs = ad(F_RS)
+        rv = None
+        self._perf_solution = np.zeros((n, 2))
+        if self.vaporised_oil:
+            if q.shape[1] != 19:
+                raise ValueError("vaporised_oil=True needs the 19-field record of a fluid with PVTG: these records have %d fields" % q.shape[1])
+            rv = ad(F_RV)
         tw = self.tw[:, None]
         out = np.zeros((n, 3, 5))
         producer = np.array([w.producer for w in self.wells])[self.well_of_perf]
@@ -689,9 +721,17 @@ class StandardWells:
         flows = producer & (dd[:, 0] > 0.0)
         if flows.any():
             surf = [mul(b[ph], -tw * mul(mob[ph], dd)) for ph in range(3)]
-            out[flows, OIL] = surf[PH_O][flows]
-            out[flows, WATER] = surf[PH_W][flows]
-            out[flows, GAS] = (surf[PH_G] + mul(rs, surf[PH_O]))[flows]
+            if rv is None:
+                out[flows, OIL] = surf[PH_O][flows]
+                out[flows, WATER] = surf[PH_W][flows]
+                out[flows, GAS] = (surf[PH_G] + mul(rs, surf[PH_O]))[flows]
+            else:                                  # the oil the gas carries counts as oil
+                dis_gas, vap_oil = mul(rs, surf[PH_O]), mul(rv, surf[PH_G])
+                out[flows, OIL] = (surf[PH_O] + vap_oil)[flows]
+                out[flows, WATER] = surf[PH_W][flows]
+                out[flows, GAS] = (surf[PH_G] + dis_gas)[flows]
+                self._perf_solution[flows, 0] = dis_gas[flows, 0]
+                self._perf_solution[flows, 1] = vap_oil[flows, 0]
         # injecting perforations: total mobility, the injected phase's 1/B
         inj = ~producer & (dd[:, 0] < 0.0)
         if inj.any():
@@ -704,11 +744,12 @@ class StandardWells:
         # a perforation that would flow against the well's kind is closed, unless it is a producer's and the well allows crossflow
         cross = producer & self.allow_crossflow[self.well_of_perf] & ~(dd[:, 0] > 0.0)
         if cross.any():
-            self._crossflow_rates(np.flatnonzero(cross), dd, b, mob, rs, out)
+            self._crossflow_rates(np.flatnonzero(cross), dd, b, mob, rs, out, rv)
         return out
 
-    def _crossflow_rates(self, sel, dd, b, mob, rs, out):
-        """the perforations `sel` of producers with the switch: the module's formulas on A8 arrays, into out and self._rate_dq"""
+    def _crossflow_rates(self, sel, dd, b, mob, rs, out, rv=None):
+        """the perforations `sel` of producers with the switch: the module's formulas on A8 arrays, into out and self._rate_dq; rv: the
+        wet-gas form (vaporised_oil), which also leaves the split of the rates in self._perf_solution"""
         mix = np.zeros((self.nw, 3, 8))            # cmix_c of every well: value and d/dq
         flowing = np.zeros(self.nw, bool)
         for k in np.flatnonzero(self.allow_crossflow):
@@ -743,16 +784,33 @@ class StandardWells:
         d8, b8, mob8, rs8 = wide(dd), [wide(v) for v in b], [wide(v) for v in mob], wide(rs)
         cqt_i = -self.tw[sel, None] * mul((mob8[PH_W] + mob8[PH_O]) + mob8[PH_G], d8)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):      # rows that end closed below
-            ratio = (div(cmix[WATER], b8[PH_W]) + div(cmix[OIL], b8[PH_O])) + div(cmix[GAS] - mul(rs8, cmix[OIL]), b8[PH_G])
+            if rv is None:
+                ratio = (div(cmix[WATER], b8[PH_W]) + div(cmix[OIL], b8[PH_O])) + div(cmix[GAS] - mul(rs8, cmix[OIL]), b8[PH_G])
+                ok = ratio[:, 0] > 0.0             # a volume ratio that is not positive: closed for this evaluation
+            else:
+                rv8 = wide(rv)
+                one = np.zeros_like(rs8)
+                one[:, 0] = 1.0
+                d = one - mul(rv8, rs8)
+                tmp_oil = div(cmix[OIL] - mul(rv8, cmix[GAS]), d)
+                tmp_gas = div(cmix[GAS] - mul(rs8, cmix[OIL]), d)
+                ratio = (div(cmix[WATER], b8[PH_W]) + div(tmp_oil, b8[PH_O])) + div(tmp_gas, b8[PH_G])
+                ok = (d[:, 0] > 0.0) & (ratio[:, 0] > 0.0)     # ... and a d that is not positive (the reference throws where d == 0)
             cqt_is = div(cqt_i, ratio)
             rates = [mul(cmix[c], cqt_is) for c in range(3)]
-        ok = ratio[:, 0] > 0.0                     # a volume ratio that is not positive: closed for this evaluation
+            if rv is not None:                     # the split, on values only
+                rs0, rv0, d0 = rs8[:, 0], rv8[:, 0], d[:, 0]
+                vap_oil = rv0 * (rates[GAS][:, 0] - rs0 * rates[OIL][:, 0]) / d0
+                dis_gas = rs0 * (rates[OIL][:, 0] - rv0 * rates[GAS][:, 0]) / d0
         if not ok.any():
             return
         self._rate_dq = np.zeros((len(self.cells), 3, 3))
         for c in range(3):
             out[sel[ok], c] = rates[c][ok, :5]
             self._rate_dq[sel[ok], c] = rates[c][ok, 5:]
+        if rv is not None:
+            self._perf_solution[sel[ok], 0] = dis_gas[ok]
+            self._perf_solution[sel[ok], 1] = vap_oil[ok]
 
     def _control_rows(self):
         """(residual, d/d(q_o, q_w, q_g, bhp)) of every well's control equation"""
@@ -866,6 +924,11 @@ class StandardWells:
             flat = dq.reshape(nperf, 9)
             qsums = sequential_sums(flat, self.vp) if self.arithmetic == "stated" else np.add.reduceat(flat, seg, axis=0)
             D[:, :3, :3] = D[:, :3, :3] - qsums.reshape(self.nw, 3, 3)
+        if self.vaporised_oil:                   # the dissolved gas and the vaporised oil a producer's rates hold (injectors' perforations: zeros)
+            ps = self._perf_solution
+            self._solution_rates = sequential_sums(ps, self.vp) if self.arithmetic == "stated" else np.add.reduceat(ps, seg, axis=0)
+        else:
+            self._solution_rates = np.zeros((self.nw, 2))
         r[:, 3], D[:, 3, :] = self._control_rows()
         # a well none of whose completions flows (its bottom-hole pressure on the wrong side of every completion's pressure) has no rate that
         # answers to its bottom-hole pressure: under a rate target its equations would be singular.  It keeps its bottom-hole pressure for
@@ -927,6 +990,11 @@ class StandardWells:
             out["source"], out["dsource"] = np.ascontiguousarray(source.reshape(-1)), np.ascontiguousarray(dsource.reshape(-1))
         return out
 
+    def solution_rates(self):
+        """(dissolved_gas, vaporised_oil): per well, the sums over a producer's perforations that the last assemble formed - rates into the
+        reservoir, production negative; zeros for injectors and with vaporised_oil off (the module's text)"""
+        return self._solution_rates[:, 0].copy(), self._solution_rates[:, 1].copy()
+
     def update(self, xw, relax=1.0):
         """updateWellState: the well unknowns follow their Newton update (x_w = D^-1 (r_w - B x) from the device)"""
         self.x -= relax * np.asarray(xw, float).reshape(self.nw, 4)
@@ -967,11 +1035,12 @@ class DeviceStandardWells:
     """The same wells resident on the device (opmhip_set_std_wells): model is a capi.HipModel whose state is set.  The well unknowns, the
     controls, the heads and the blocks B, C, D^-1 live there; what this object holds of them (x, controls, res_well) is the last read-back
     (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow), further rate limits (Well(limits=)) sent
-    with opmhip_set_std_wells_limits.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
+    with opmhip_set_std_wells_limits, the wet-gas rate model switched on with opmhip_set_std_wells_vaporised_oil.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
-    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None):
-        """head_model="wellbore": the heads from the well-bore density (opmhip_set_std_wells_head_model), StandardWells(head_model="wellbore",
+    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None, vaporised_oil=False):
+        """vaporised_oil: the wet-gas rate model (opmhip_set_std_wells_vaporised_oil; ValueError on a context whose fluid has no PVTG);
+        head_model="wellbore": the heads from the well-bore density (opmhip_set_std_wells_head_model), StandardWells(head_model="wellbore",
         arithmetic="stated")'s with the device's own property functions; vfp: the vfp.VFPTable list the wells' THP limits name - sent to the
         context (opmhip_set_vfp_tables) with the limits (opmhip_set_std_wells_thp) when some well has one"""
         if head_model not in HEAD_MODELS:
@@ -1005,6 +1074,9 @@ class DeviceStandardWells:
             bhp_limit=[w.bhp_limit for w in self.wells], control=[int(w.control[0] == "bhp") for w in self.wells], x=None))
         if self.allow_crossflow.any():           # (a list without the switch makes the calls it made before)
             model.set_std_wells_crossflow(self.allow_crossflow.astype(np.int32))
+        self.vaporised_oil = bool(vaporised_oil)
+        if self.vaporised_oil:                   # (likewise)
+            model.set_std_wells_vaporised_oil(True)
         if head_model == "wellbore":
             self._wellbore = dict(perf_depth=depth[self.cells], ref_depth=[w.ref_depth for w in self.wells],
                                   preferred_phase=[phase[w.preferred_phase] if w.producer else PH_O for w in self.wells])
@@ -1057,6 +1129,10 @@ class DeviceStandardWells:
 
     def _send(self):
         self.m.set_std_wells_state(self.x, [CONTROL_CODE[w.control[0]] for w in self.wells], [w.rate_control[2] for w in self.wells])
+
+    def solution_rates(self):
+        """opmhip_get_std_wells_solution_rates: (dissolved_gas, vaporised_oil) per well - StandardWells.solution_rates()"""
+        return self.m.std_wells_solution_rates()
 
     def resv(self):
         """opmhip_get_std_wells_resv: dict(averages, coeff, resv_current) - StandardWells' resv_averages, resv_coeff, resv_current"""
