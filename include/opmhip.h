@@ -764,8 +764,8 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * computeBhpAtThpLimitProd; well potentials; THP for multisegment wells; the deck-level parsing and unit conversion of VFPPROD / VFPINJ
  * (opm-common's: it stays with the caller); crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
  * because its composition - WFrac, GFrac - is an unknown while getQs pins the other components to zero; this parametrisation fixes
- * the injected composition, and a half-measure would let oil leave through an injector's wellhead), decomposed contexts (refused),
- * the matrix-add form (opmhip_add_well_contributions stays with host lists).
+ * the injected composition, and a half-measure would let oil leave through an injector's wellhead), decomposed contexts (refused).
+ * The matrix-add form - the wells written into the Jacobian - is opmhip_set_std_wells_matrix_add, below.
  * Phases: 0 water, 1 oil, 2 gas (the intensive-quantity record's order); components: 0 oil, 1 water, 2 gas (the equations' order). */
 typedef struct opmhip_std_wells {
     int num_wells;
@@ -875,6 +875,34 @@ int opmhip_set_std_wells_vaporised_oil(opmhip_ctx* ctx, int on);
  * a list and with the switch off - dissolved_gas too: the default model runs the kernels it ran before, which form neither.  Waits for
  * the stream. */
 int opmhip_get_std_wells_solution_rates(opmhip_ctx* ctx, double* dissolved_gas, double* vaporised_oil);
+/* ---- the matrix-add form of the resident standard wells.  Additive to ABI 11 -------------------------------------------------
+ * replaces: StandardWell::addWellContributions (wells/StandardWell_impl.hpp:1688-1712) on the pattern ISTLSolverEbos builds with
+ * --matrix-add-well-contributions=true (flow/flow_blackoil_dunecpr.cpp:36), which holds a block (cell_a, cell_b) for every ordered pair of
+ * one well's perforated cells (its clique, the diagonal included): A -= C^T D^-1 B is written into the Jacobian, so that ILU0 factors the
+ * wells, the CPR pressure matrix carries them and the products run without an operator form.  Per list, off by default: a list that does
+ * not ask reaches the solver as the operator A - C^T D^-1 B and launches what it launched before.
+ * opmhip_set_std_wells_matrix_add, on = 1: every pair (a, b) of every well is looked up in the pattern given to opmhip_set_pattern and
+ * the schedule - per DISTINCT block its contributions (well, a, b), ordered by well and then by a * np + b - is built and uploaded once;
+ * the pattern and the perforated cells are fixed, nothing is rebuilt per iteration.  on = 0 frees it.  Call it after
+ * opmhip_set_std_wells; replacing or clearing the list clears it.  OPMHIP_NOT_READY without a list; OPMHIP_INVALID_ARGUMENT for a value
+ * other than 0 / 1 and for a block that is not in the pattern (the text names the well and the two natural cell ids).  A refused call
+ * leaves the switch as it was.  The switch adds no state to save or restore.
+ * opmhip_std_wells_add_to_matrix: once per Newton iteration, after opmhip_assemble (and, in the reference's order, after
+ * opmhip_std_wells_apply_residual).  Asynchronous: one launch on the context's stream, no read-back, no host array.  One lane per distinct
+ * block adds its contributions in list order, each blk[i][j] += -(sum_k C_a[k][i] * (sum_l D^-1[k][l] * B_b[l][j])), both sums ascending
+ * from 0.0 - the expressions and, block by block, the order of opmhip_add_well_contributions on the same B, C, D^-1: the same bits.  Two
+ * wells in one cell and a well that perforates a cell twice are ordinary entries of one list.  OPMHIP_NOT_READY without a list, without
+ * the switch, before an assemble, and when the last assemble's wells are in the matrix already (a second call would subtract them twice).
+ * Afterwards the factorisation is stale, and until the next opmhip_assemble (or an uploaded matrix) opmhip_solve_system installs no
+ * operator form for the list: the plain products run, scalar products riding in them.  It still copies and checks the zero-pivot flags: a
+ * flagged D^-1 is stored as zeros, so that the add is harmless and the error is reported where it is reported otherwise.
+ * opmhip_std_wells_apply_residual and opmhip_std_wells_update are unchanged: both need only the resident blocks.
+ * info: [0] the switch, [1] distinct target blocks, [2] contributions (pairs), [3] 1 while the last assemble's wells are in the matrix.
+ * NOT covered: building the clique pattern (the caller's: grid.with_well_cliques in the Python package; a row may hold at most 64 blocks,
+ * opmhip_set_static's limit); decomposed contexts (the list is refused there). */
+int opmhip_set_std_wells_matrix_add(opmhip_ctx* ctx, int on);
+int opmhip_std_wells_add_to_matrix(opmhip_ctx* ctx);
+int opmhip_get_std_wells_matrix_add(opmhip_ctx* ctx, int info[4]);
 /* ---- the heads from the well-bore density.  Additive to ABI 11 -------------------------------------------------------------
  * replaces: StandardWell::computeWellConnectionPressures (wells/StandardWell_impl.hpp:1195-1210), that is
  * computePropertiesForWellConnectionPressures (:899-1012), computeWellConnectionDensitesPressures (:1124-1189),

@@ -757,6 +757,9 @@ def _bind_assembly(L):
     L.opmhip_get_std_wells_thp.argtypes = [vp, vp, vp, vp]
     L.opmhip_set_std_wells_limits.argtypes = [vp, C.POINTER(StdWellsLimits)]
     L.opmhip_get_std_wells_resv.argtypes = [vp, vp, vp, vp]
+    L.opmhip_set_std_wells_matrix_add.argtypes = [vp, C.c_int]
+    L.opmhip_std_wells_add_to_matrix.argtypes = [vp]
+    L.opmhip_get_std_wells_matrix_add.argtypes = [vp, vp]
 
 
 class HipFluid(HipSolver):
@@ -1106,6 +1109,28 @@ class HipModel(HipSolver):
             if e.code == INVALID_ARGUMENT and "no PVTG" in str(e):
                 raise ValueError(str(e)) from e
             raise
+
+    def set_std_wells_matrix_add(self, on=True):
+        """opmhip_set_std_wells_matrix_add: the resident list goes into the Jacobian (opmhip_std_wells_add_to_matrix) instead of reaching the
+        solver as an operator.  The context's pattern must hold every pair of a well's perforated cells (grid.with_well_cliques): a missing
+        block is a ValueError with the library's text; a refused call leaves the switch as it was."""
+        try:
+            self._check(lib().opmhip_set_std_wells_matrix_add(self._h, int(on)))
+        except OpmHipError as e:
+            if e.code == INVALID_ARGUMENT and "not in the pattern" in str(e):
+                raise ValueError(str(e)) from e
+            raise
+
+    def std_wells_add_to_matrix(self):
+        """opmhip_std_wells_add_to_matrix: A -= C^T D^-1 B with the resident blocks of the last assemble, once per assemble (asynchronous)"""
+        self._check(lib().opmhip_std_wells_add_to_matrix(self._h))
+
+    def std_wells_matrix_add_info(self):
+        """opmhip_get_std_wells_matrix_add: dict(on, targets: distinct blocks written, pairs: contributions, in_matrix: the last assemble's
+        wells are in the matrix)"""
+        a = np.zeros(4, np.int32)
+        self._check(lib().opmhip_get_std_wells_matrix_add(self._h, _ptr(a)))
+        return dict(on=bool(a[0]), targets=int(a[1]), pairs=int(a[2]), in_matrix=bool(a[3]))
 
     def std_wells_solution_rates(self):
         """opmhip_get_std_wells_solution_rates: (dissolved_gas, vaporised_oil) per well of the last assemble - rates into the reservoir,

@@ -273,6 +273,7 @@ int upload_system(opmhip_ctx* c, const double* vals, const double* b) {
         OPMHIP_HIP(c, hipMemcpyAsync(c->d_stageA, vals, (size_t)P.nnzb * BB * sizeof(double), hipMemcpyHostToDevice, c->stream));
         launch_permute_blocks(c, c->d_stageA, c->d_A);
         c->factored = false;
+        c->wells.sw.in_matrix = false;   // the caller's matrix replaces the one the resident wells were written into
     }
     if (b) {
         OPMHIP_HIP(c, hipMemcpyAsync(c->d_stageV, b, (size_t)P.Nb * BS * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -465,7 +466,7 @@ int opmhip_solve_system(opmhip_ctx* c, int N, int nnz, int dim, double* vals, co
         std::optional<StdWellsOperatorForm> form;   // the resident standard wells: B, C, D^-1 as the last assemble formed them, in operator form
         if (c->wells.sw.num > 0) {
             if ((rc = std_wells_check(c, c->wells.sw.h_flag.data()))) return rc;
-            form.emplace(c->wells);
+            if (!c->wells.sw.in_matrix) form.emplace(c->wells);   // (opmhip_std_wells_add_to_matrix: they are in A already, the plain products run)
         }
         const double t1 = now();
         FactorRider rider;   // CPR: weights and level 0's values of the pressure hierarchy are formed while the rows are in LDS

@@ -1139,9 +1139,18 @@ void std_wells_limits_release(opmhip_ctx* c) {   // the stream is idle
     S.h_lim.clear(); S.h_lim_use.clear();
     S.limits = S.resv = false;
 }
+void std_wells_matrix_add_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_ma_target); dev_free(c, &S.d_ma_tptr); dev_free(c, &S.d_ma_contrib);
+    S.h_ma_target.clear(); S.h_ma_tptr.clear(); S.h_ma_contrib.clear();
+    S.ma_targets = S.ma_pairs = 0;
+    S.matrix_add = false;   // (in_matrix is a fact about the matrix: it stays until the next assemble, so that these wells are not applied a second time)
+}
 void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
     std_wells_limits_release(c);
+    std_wells_matrix_add_release(c);
+    S.h_vp.clear(); S.h_pos.clear();
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
     dev_free(c, &S.d_pack); dev_free(c, &S.d_saved); dev_free(c, &S.d_Dmat);
     dev_free(c, &S.d_cpos); dev_free(c, &S.d_cptr); dev_free(c, &S.d_cperf); dev_free(c, &S.d_save);
@@ -1260,6 +1269,8 @@ int opmhip_set_std_wells(opmhip_ctx* c, const opmhip_std_wells* sw) {
         if (rc) { std_wells_release(c); return rc; }
         S.num = nw; S.nperf = np; S.nd = (int)H.cpos.size();
         S.h_wi = std::move(H.wi); S.h_wd = std::move(H.wd);
+        S.h_vp.assign(sw->perf_pointers, sw->perf_pointers + nw + 1);
+        S.h_pos = std::move(H.pos);
         return OPMHIP_SUCCESS;
     });
 }
@@ -1316,6 +1327,65 @@ int opmhip_std_wells_update(opmhip_ctx* c, double relax) {
         }
         launch_std_wells_axpy(c, relax);
         OPMHIP_HIP(c, hipGetLastError());
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_matrix_add(opmhip_ctx* c, int on) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        const Pattern& P = c->pat;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_matrix_add: no resident list (opmhip_set_std_wells)");
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the switch as it was
+        if (int r = std_wells_matrix_add_check(on, msg)) return fail(c, r, "%s", msg.c_str());
+        StdWellsMatrixAdd H;
+        if (on)
+            if (int r = std_wells_matrix_add_schedule(S.num, S.h_vp.data(), S.h_pos.data(), P.fromOrder.data(), P.rowptr.data(), P.col.data(), H, msg))
+                return fail(c, r, "%s", msg.c_str());
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        int *d_target = nullptr, *d_tptr = nullptr, *d_contrib = nullptr;
+        if (on) {
+            int r;
+            if ((r = dev_upload(c, &d_target, H.target)) || (r = dev_upload(c, &d_tptr, H.tptr)) || (r = dev_upload(c, &d_contrib, H.contrib))) {
+                dev_free(c, &d_target); dev_free(c, &d_tptr); dev_free(c, &d_contrib);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        std_wells_matrix_add_release(c);
+        S.d_ma_target = d_target; S.d_ma_tptr = d_tptr; S.d_ma_contrib = d_contrib;
+        S.ma_targets = (int)H.target.size(); S.ma_pairs = H.pairs;
+        S.h_ma_target = std::move(H.target); S.h_ma_tptr = std::move(H.tptr); S.h_ma_contrib = std::move(H.contrib);
+        S.matrix_add = on != 0;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_std_wells_add_to_matrix(opmhip_ctx* c) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "std_wells_add_to_matrix: no resident list (opmhip_set_std_wells)");
+        if (!S.matrix_add) return fail(c, OPMHIP_NOT_READY, "std_wells_add_to_matrix: the list's matrix-add form is not switched on (opmhip_set_std_wells_matrix_add)");
+        if (!S.assembled || !c->asmb.assembled) return fail(c, OPMHIP_NOT_READY, "std_wells_add_to_matrix before opmhip_assemble: there are no B, C and D^-1");
+        if (S.in_matrix) return fail(c, OPMHIP_NOT_READY, "std_wells_add_to_matrix: the wells of the last opmhip_assemble are in the matrix already - a second call would subtract them twice");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        launch_std_wells_add_to_matrix(c);   // A -= C^T D^-1 B
+        OPMHIP_HIP(c, hipGetLastError());
+        c->factored = false;
+        S.in_matrix = true;
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_matrix_add(opmhip_ctx* c, int info[4]) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (!info) return fail(c, OPMHIP_INVALID_ARGUMENT, "get_std_wells_matrix_add: null array");
+        info[0] = S.matrix_add ? 1 : 0; info[1] = S.ma_targets; info[2] = S.ma_pairs; info[3] = S.in_matrix ? 1 : 0;
         return OPMHIP_SUCCESS;
     });
 }
@@ -1736,6 +1806,7 @@ int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double
         OPMHIP_HIP(c, hipSetDevice(c->device));
         c->asmb.last_dt = dt;
         c->asmb.last_iteration = iteration;
+        SW.in_matrix = false;   // a new Jacobian: the matrix-add form's wells are not in it yet
         if (SW.num > 0) { launch_std_wells_assemble(c); SW.assembled = true; }   // wellModel().assemble: rates first, then the aquifers (the host order)
         if (Q.nd > 0) launch_aquifer_apply(c);     // aquiferModel_.addToSource (ebos/eclproblem.hh:1843)
         launch_assemble(c, dt, iteration);

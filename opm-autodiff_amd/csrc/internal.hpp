@@ -228,6 +228,14 @@ struct StdWellsDev {
     std::vector<int> h_lim_use;
     double *d_lim = nullptr, *d_lim_out = nullptr;
     int* d_lim_use = nullptr;
+    // the matrix-add form (opmhip_set_std_wells_matrix_add): d_ma_target [ma_targets]: the distinct blocks of the device's block-CSR the
+    // pairs write; d_ma_tptr [ma_targets + 1] / d_ma_contrib [3 ma_pairs]: per block its contributions (well, a, b) in the order of the host
+    // path; h_ma_*: what they hold.  in_matrix: opmhip_std_wells_add_to_matrix has run since the last assemble - the solve then installs no
+    // operator form.  h_vp / h_pos: the list's ranges and the internal positions of its perforated cells (the schedule is built from them)
+    bool matrix_add = false, in_matrix = false;
+    int ma_targets = 0, ma_pairs = 0;
+    int *d_ma_target = nullptr, *d_ma_tptr = nullptr, *d_ma_contrib = nullptr;
+    std::vector<int> h_ma_target, h_ma_tptr, h_ma_contrib, h_vp, h_pos;
     double* x() const { return d_pack + (size_t)SW_X * num; }
     double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
     double* rw() const { return d_pack + (size_t)SW_RW * num; }
@@ -780,6 +788,7 @@ void launch_std_wells_resv(opmhip_ctx* c);                // the field's average
 void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
 void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)
 void launch_std_wells_axpy(opmhip_ctx* c, double relax);  // x -= relax * x_w
+void launch_std_wells_add_to_matrix(opmhip_ctx* c);       // solver.hip: A -= C^T D^-1 B by StdWellsDev's schedule (the matrix-add form), one launch
 void launch_last_rs_rv(opmhip_ctx* c);
 void launch_set_limits(opmhip_ctx* c, double dt);
 void launch_min_pressure(opmhip_ctx* c, bool init);

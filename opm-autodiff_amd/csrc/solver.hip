@@ -1842,9 +1842,27 @@ __global__ __launch_bounds__(MSW_APPLY_THREADS) void k_ms_wells_apply(const MsWe
     }
 }
 
+// blk += -C_c^T (D^-1 B_b) for one perforation pair: tmp = D^-1 B_b (4 x 3), then s = sum_k C_c[k][i] tmp[k][j], every sum ascending in k
+// from 0.0 (Detail::multMatrix and Detail::negativeMultMatrixTransposed, linalg/MatrixBlock.hpp:496-570).  The one copy of the
+// arithmetic of both matrix-add kernels below.
+__device__ __forceinline__ void wells_pair_add(const double* __restrict__ Cc, const double* __restrict__ Dw, const double* __restrict__ Bb, double* blk) {
+    double tmp[4][3];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k) s += Dw[i * 4 + k] * Bb[k * 3 + j];
+            tmp[i][j] = s;
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k) s += Cc[k * 3 + i] * tmp[k][j];
+            blk[i * 3 + j] += -s;
+        }
+}
+
 // A(Ccols[c], Bcols[b]) += -C_c^T (D^-1 B_b) for every perforation pair (c, b) of well w0 + blockIdx.x
-// (StandardWell::addWellContributions, wells/StandardWell_impl.hpp:1688-1712; sums in the order of Detail::multMatrix
-// and Detail::negativeMultMatrixTransposed, linalg/MatrixBlock.hpp:496-570).  entry[] holds, per pair, the position of
+// (StandardWell::addWellContributions, wells/StandardWell_impl.hpp:1688-1712).  entry[] holds, per pair, the position of
 // the block in the device's block-CSR (found on the host).
 // serial != 0: the well has two perforations in one cell, i.e. several of its pairs hit the same block - one lane then
 // adds all pairs in the perforation order of the CPU loop (no race, same bits).
@@ -1860,20 +1878,24 @@ __global__ __launch_bounds__(64) void k_wells_add_to_matrix(int w0, int serial, 
         const double* Bb = &B[(size_t)(pb + b) * 12];
         const double* Cc = &C[(size_t)(pb + c) * 12];
         const double* Dw = &D[(size_t)w * 16];
-        double tmp[4][3];
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-                for (int k = 0; k < 4; ++k) s += Dw[i * 4 + k] * Bb[k * 3 + j];
-                tmp[i][j] = s;
-            }
-        double* blk = &A[(size_t)entry[pair_ptr[w] + q] * BB];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-                for (int k = 0; k < 4; ++k) s += Cc[k * 3 + i] * tmp[k][j];
-                blk[i * 3 + j] += -s;
-            }
+        wells_pair_add(Cc, Dw, Bb, &A[(size_t)entry[pair_ptr[w] + q] * BB]);
+    }
+}
+
+// The same for the resident standard wells (opmhip_set_std_wells_matrix_add), by the schedule source_lists.cpp built once: one lane per
+// distinct block of the matrix; the lane adds that block's contributions (well, a, b) one after the other in list order - by well, then
+// by a * np + b, the order of the kernel above across its launches and inside its serial case.  Two wells in one cell and a well with
+// two perforations in one cell are then ordinary entries of one list: one launch, no atomics, no LDS.  B, C and D^-1 are a few KB (L2).
+__global__ __launch_bounds__(64) void k_std_wells_add_to_matrix(int nt, const int* __restrict__ target, const int* __restrict__ tptr,
+                                                                const int* __restrict__ contrib, const int* __restrict__ vp,
+                                                                const double* __restrict__ C, const double* __restrict__ D,
+                                                                const double* __restrict__ B, double* __restrict__ A) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= nt) return;
+    double* blk = &A[(size_t)target[t] * BB];
+    for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
+        const int w = contrib[3 * k], pb = vp[w];
+        wells_pair_add(&C[(size_t)(pb + contrib[3 * k + 1]) * 12], &D[(size_t)w * 16], &B[(size_t)(pb + contrib[3 * k + 2]) * 12], blk);
     }
 }
 
@@ -2342,6 +2364,14 @@ int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
 void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const int* d_pair_ptr, const int* d_entry) {
     const WellsDev& W = c->wells;
     hipLaunchKernelGGL(k_wells_add_to_matrix, dim3(nw), dim3(64), 0, c->stream, w0, serial, W.d_val_pointers, W.d_C, W.d_D, W.d_B, d_pair_ptr, d_entry, c->d_A);
+}
+void launch_std_wells_add_to_matrix(opmhip_ctx* c) {
+    const WellsDev& W = c->wells;
+    const StdWellsDev& S = W.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);   // (the well model's, as the standard wells' other launches: one scope)
+    hipLaunchKernelGGL(k_std_wells_add_to_matrix, dim3((S.ma_targets + 63) / 64), dim3(64), 0, c->stream, S.ma_targets, S.d_ma_target, S.d_ma_tptr, S.d_ma_contrib,
+                       W.d_val_pointers, W.d_C, W.d_D, W.d_B, c->d_A);
+    prof_end(c, ps);
 }
 void launch_wells_residual(opmhip_ctx* c, const double* d_resWell, double* r) {
     const WellsDev& W = c->wells;

@@ -189,6 +189,47 @@ int std_wells_check_perf_state(size_t np, const double* perf_pressure, const dou
     return OPMHIP_SUCCESS;
 }
 
+int std_wells_matrix_add_check(int on, std::string& msg) {
+    if (on != 0 && on != 1) return refuse(msg, "set_std_wells_matrix_add: on = %d (0 off, 1 on)", on);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_matrix_add_schedule(int nw, const int* perf_pointers, const int* pos, const int* fromOrder, const int* rowptr, const int* col,
+                                  StdWellsMatrixAdd& out, std::string& msg) {
+    struct Pair { int entry, well, a, b; };
+    std::vector<Pair> pairs;
+    for (int w = 0; w < nw; ++w) {
+        const int pb = perf_pointers[w], np = perf_pointers[w + 1] - pb;
+        for (int a = 0; a < np; ++a) {
+            const int row = pos[pb + a];
+            const int* lo = col + rowptr[row];
+            const int* hi = col + rowptr[row + 1];
+            for (int b = 0; b < np; ++b) {
+                const int* it = std::lower_bound(lo, hi, pos[pb + b]);
+                if (it == hi || *it != pos[pb + b])
+                    return refuse(msg, "set_std_wells_matrix_add: block (%d, %d) of well %d is not in the pattern given to set_pattern: the form needs every pair of a "
+                                       "well's perforated cells there (the clique pattern)", fromOrder[row], fromOrder[pos[pb + b]], w);
+                pairs.push_back({(int)(it - col), w, a, b});
+            }
+        }
+    }
+    // by block; the pairs of one block stay in the order they were listed in: by well, then by a * np + b
+    std::stable_sort(pairs.begin(), pairs.end(), [](const Pair& x, const Pair& y) { return x.entry < y.entry; });
+    StdWellsMatrixAdd H;
+    H.contrib.reserve(3 * pairs.size());
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        if (k == 0 || pairs[k].entry != pairs[k - 1].entry) {
+            H.target.push_back(pairs[k].entry);
+            H.tptr.push_back((int)k);
+        }
+        H.contrib.push_back(pairs[k].well); H.contrib.push_back(pairs[k].a); H.contrib.push_back(pairs[k].b);
+    }
+    H.tptr.push_back((int)pairs.size());
+    H.pairs = (int)pairs.size();
+    out = std::move(H);
+    return OPMHIP_SUCCESS;
+}
+
 // ---- analytic aquifers ----
 int aquifer_lists(const opmhip_aquifers* aq, int Nb, const int* toOrder, AquiferLists& out, std::string& msg) {
     const int na = aq->num_aquifers;

@@ -45,6 +45,20 @@ int std_wells_head_model(const opmhip_std_wells_wellbore* wb, size_t nw, size_t 
 // state_set: the perforation pressures exist already
 int std_wells_check_perf_state(size_t np, const double* perf_pressure, const double* perf_rates, bool state_set, std::string& msg);
 
+// opmhip_set_std_wells_matrix_add: the schedule of A -= C^T D^-1 B for the list (StandardWell::addWellContributions,
+// wells/StandardWell_impl.hpp:1688-1712, on ISTLSolverEbos' clique pattern).  perf_pointers / pos: the list's ranges and the internal
+// positions of its perforated cells; fromOrder: internal -> natural (for the text of a refusal); rowptr / col: the device's block-CSR,
+// columns ascending.  target[t]: the position of the t-th distinct block some pair (a, b) of one well writes, ascending; its
+// contributions are contrib[3 k .. 3 k + 3) = (well, a, b), k in [tptr[t], tptr[t + 1]), a and b counted inside the well, ordered by well
+// and then by a * np + b: the order in which opmhip_add_well_contributions adds them.  pairs = tptr.back().
+struct StdWellsMatrixAdd {
+    std::vector<int> target, tptr, contrib;
+    int pairs = 0;
+};
+int std_wells_matrix_add_check(int on, std::string& msg);
+int std_wells_matrix_add_schedule(int nw, const int* perf_pointers, const int* pos, const int* fromOrder, const int* rowptr, const int* col,
+                                  StdWellsMatrixAdd& out, std::string& msg);
+
 // ---- analytic aquifers ----
 struct AquiferLists {
     int nc = 0;                                // connections

@@ -73,6 +73,31 @@ def cartesian_case(nx, ny, nz, dx=20.0, dy=20.0, dz=5.0, top=2500.0, poro=0.25, 
                 perm=c["perm"], dx=dx, dy=dy, dz=dz)
 
 
+def with_well_cliques(case, wells):
+    """The case on the pattern that also holds a block for every pair of one well's perforated cells (grid.with_well_cliques): what the
+    matrix-add form of the resident wells writes into (wells.DeviceStandardWells(matrix_add=True)).  wells: wells.Well objects (or anything
+    with .cells), a wells.StandardWells, or plain lists of cells.
+    For the assembly a clique entry is a face with transmissibility zero: trans and thpres (where the case has it) are 0 there, so the flux
+    and all its derivatives vanish and the Jacobian's clique blocks are zero until the wells are added.  area is 1.0 there - the flux
+    divides by the face area, and an area of 0 would make 0 / 0 - and face_dir is grid.CLIQUE_FACE (no direction).  Every per-cell array
+    is shared with `case`.
+    A row may hold at most 64 blocks (the assembly tile; opmhip_set_static refuses longer rows): the row of a perforated cell holds its
+    stencil and the well's other cells that are not in the stencil already - see DESIGN.md section 5 for what that allows."""
+    lists = [np.asarray(getattr(w, "cells", w), np.int64) for w in getattr(wells, "wells", wells)]
+    pat, old_pos = _grid.with_well_cliques(dict(Nb=case["Nb"], rowptr=case["rowptr"], col=case["col"], face_dir=case.get("face_dir")), lists)
+    n = len(pat["col"])
+    out = dict(case)
+    out.update(rowptr=pat["rowptr"], col=pat["col"])
+    if case.get("face_dir") is not None:
+        out["face_dir"] = pat["face_dir"]
+    for key, fill in (("trans", 0.0), ("thpres", 0.0), ("area", 1.0)):
+        if case.get(key) is not None:
+            v = np.full(n, fill)
+            v[old_pos] = case[key]
+            out[key] = v
+    return out
+
+
 def spe1_case(props=None, state="equil"):
     """The SPE1CASE1 deck (python/test_data/SPE1CASE1/SPE1CASE1.DATA; FIELD units converted to SI in data/spe1_fluid.json): its grid
     (10 x 10 x 3, layered DZ / PERM, :64-108), its PROPS (:109-250) and, state = "equil", its SOLUTION section (:252-290) - EQUIL 8400 ft /

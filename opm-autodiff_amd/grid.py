@@ -35,6 +35,39 @@ def row_of_entries(rowptr):
     return np.repeat(np.arange(len(rowptr) - 1, dtype=np.int32), np.diff(rowptr))
 
 
+CLIQUE_FACE = 4  # face_dir of an entry that is no face of the grid: a pair of one well's perforated cells (with_well_cliques)
+
+
+def with_well_cliques(pat, cell_lists):
+    """-> (pattern, old_pos): the pattern enlarged by the block (a, b) for every ordered pair of cells of every list in cell_lists (one
+    list per well: its perforated cells; a cell may repeat), columns ascending - the pattern ISTLSolverEbos builds with
+    --matrix-add-well-contributions=true, which StandardWell::addWellContributions (wells/StandardWell_impl.hpp:1688-1712) writes into.
+    old_pos[k]: the position of pat's entry k in the new pattern.  face_dir (if pat has one) keeps its values on the old entries and is
+    CLIQUE_FACE on the new ones: they belong to no direction, so the geometry and transmissibility builders leave them at zero.  Every
+    other key of pat is carried over.  A list of one cell adds nothing (the diagonal is there)."""
+    Nb = int(pat["Nb"])
+    rowptr, col = np.asarray(pat["rowptr"], np.int64), np.asarray(pat["col"], np.int64)
+    old = row_of_entries(rowptr).astype(np.int64) * Nb + col
+    extra = [np.zeros(0, np.int64)]
+    for cells in cell_lists:
+        c = np.unique(np.asarray(cells, np.int64))
+        if c.size and (c[0] < 0 or c[-1] >= Nb):
+            raise ValueError("with_well_cliques: cell outside [0, %d)" % Nb)
+        extra.append((c[:, None] * Nb + c[None, :]).reshape(-1))
+    keys = np.union1d(old, np.concatenate(extra))       # sorted by (row, column)
+    assert len(keys) < 2 ** 31
+    old_pos = np.searchsorted(keys, old).astype(np.int64)
+    new_rowptr = np.zeros(Nb + 1, np.int64)
+    np.cumsum(np.bincount(keys // Nb, minlength=Nb), out=new_rowptr[1:])
+    out = dict(pat)
+    out.update(rowptr=new_rowptr.astype(np.int32), col=(keys % Nb).astype(np.int32))
+    if pat.get("face_dir") is not None:
+        fd = np.full(len(keys), CLIQUE_FACE, np.int8)
+        fd[old_pos] = pat["face_dir"]
+        out["face_dir"] = fd
+    return out, old_pos
+
+
 def cartesian_geometry(pat, dx, dy, dz, top=2500.0):
     """Cell volumes, centre depths and per-entry face areas for a box grid with uniform spacings (metres)."""
     nx, ny, nz, Nb = pat["nx"], pat["ny"], pat["nz"], pat["Nb"]

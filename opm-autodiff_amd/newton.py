@@ -179,7 +179,9 @@ class BlackoilModelHip:
                 res = self.m.solve_jacobian_system(wells=wa["wells"])           # the operator A - C^T D^-1 B (WellModelMatrixAdapter)
             elif dev_wells:
                 self.m.std_wells_apply_residual()
-                res = self.m.solve_jacobian_system()         # the resident B / C / D^-1 are its operator form
+                if self.wells.matrix_add:
+                    self.m.std_wells_add_to_matrix()         # addWellContributions: A -= C^T D^-1 B, the preconditioner sees the wells
+                res = self.m.solve_jacobian_system()         # the resident B / C / D^-1 are its operator form, unless they are in the matrix
             else:
                 res = self.m.solve_jacobian_system()         # solveJacobianSystem: ILU0 setup + BiCGStab
             rep.linear_solve_setup_time += res.t_factor

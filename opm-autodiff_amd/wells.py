@@ -1038,8 +1038,11 @@ class DeviceStandardWells:
     with opmhip_set_std_wells_limits, the wet-gas rate model switched on with opmhip_set_std_wells_vaporised_oil.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
-    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None, vaporised_oil=False):
-        """vaporised_oil: the wet-gas rate model (opmhip_set_std_wells_vaporised_oil; ValueError on a context whose fluid has no PVTG);
+    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None, vaporised_oil=False, matrix_add=False):
+        """matrix_add: the wells are written into the Jacobian every Newton iteration (opmhip_set_std_wells_matrix_add,
+        opmhip_std_wells_add_to_matrix) instead of reaching the solver as the operator A - C^T D^-1 B; the model's pattern must hold the wells'
+        cliques (decks.with_well_cliques) - ValueError with the library's text when a block is missing;
+        vaporised_oil: the wet-gas rate model (opmhip_set_std_wells_vaporised_oil; ValueError on a context whose fluid has no PVTG);
         head_model="wellbore": the heads from the well-bore density (opmhip_set_std_wells_head_model), StandardWells(head_model="wellbore",
         arithmetic="stated")'s with the device's own property functions; vfp: the vfp.VFPTable list the wells' THP limits name - sent to the
         context (opmhip_set_vfp_tables) with the limits (opmhip_set_std_wells_thp) when some well has one"""
@@ -1077,6 +1080,9 @@ class DeviceStandardWells:
         self.vaporised_oil = bool(vaporised_oil)
         if self.vaporised_oil:                   # (likewise)
             model.set_std_wells_vaporised_oil(True)
+        self.matrix_add = bool(matrix_add)
+        if self.matrix_add:                      # (likewise)
+            model.set_std_wells_matrix_add(True)
         if head_model == "wellbore":
             self._wellbore = dict(perf_depth=depth[self.cells], ref_depth=[w.ref_depth for w in self.wells],
                                   preferred_phase=[phase[w.preferred_phase] if w.producer else PH_O for w in self.wells])
