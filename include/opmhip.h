@@ -419,6 +419,14 @@ int opmhip_get_ilu_factors(opmhip_ctx* ctx, int* toOrder, int* lrowptr, int* lco
  * their U part plus its boundary tiles' whole rows); info[3] launch positions of that
  * product.  ABI 10 */
 int opmhip_get_product_form(opmhip_ctx* ctx, int info[4]);
+/* Split assembly, for tests and measurements: on the plain ILU0 context of the half-product form (no CPR, no fill, no ghost columns, no well
+ * list in its matrix-add form) opmhip_assemble writes the Jacobian straight into the two arrays the ILU0 solve reads - the matrix beside its
+ * U part and the U part - and the factorisation copies nothing; the matrix's own array is brought up to date only when something reads it.
+ * info[0] 1 if the next opmhip_assemble writes that way; info[1] 1 if the matrix in force lives in the two arrays only; info[2] assemblies
+ * written that way so far; info[3] times the matrix's own array was gathered from them.  rest (nullable, info[2] of opmhip_get_product_form
+ * x 9): the matrix beside its U part, internal order, as the product after M^-1 streams it (needs the half-product form).  matrix
+ * (nullable, nnzb x 9): the matrix in force, natural order (gathers first where needed).  No ABI change: a new symbol */
+int opmhip_get_split_assembly(opmhip_ctx* ctx, long long info[4], double* rest, double* matrix);
 /* Device-timed repetitions of one kernel on the uploaded system, for bench.py's roofline object:
  * which = 0 SpMV, 1 ILU0 apply, 2 ILU0 factor, 3 one BiCGStab iteration's vector kernels, 4 a plain streaming read of
  * the Jacobian's value array (72 * nnzb bytes; the on-box HBM ceiling the roofline fractions are put beside), 5 / 6 the SpMV

@@ -349,6 +349,7 @@ def lib():
         L.opmhip_get_ordering.argtypes = [vp, ip, ip, ip]
         L.opmhip_get_ordering_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_get_product_form.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.opmhip_get_split_assembly.argtypes = [vp, C.POINTER(C.c_longlong * 4), dp, dp]
         L.opmhip_set_ilu_fillin_level.argtypes = [vp, C.c_int]
         L.opmhip_get_ilu_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_set_ms_wells.argtypes = [vp, C.POINTER(MsWells)]
@@ -633,6 +634,20 @@ class HipSolver:
         info = (C.c_int * 4)()
         self._check(lib().opmhip_get_product_form(self._h, C.byref(info)))
         return {"half_product": bool(info[0]), "u_is_upper_a": bool(info[1]), "rest_blocks": int(info[2]), "rest_positions": int(info[3])}
+
+    def split_assembly(self, rest=False, matrix=False):
+        """opmhip_get_split_assembly: whether opmhip_assemble writes the Jacobian into the arrays the ILU0 solve reads, and how often it did;
+        rest / matrix: also the matrix beside its U part (internal order, blocks [nr, 3, 3]) / the matrix in force (natural order, nnzb * 9)"""
+        info = (C.c_longlong * 4)()
+        r = np.empty((self.product_form()["rest_blocks"], 3, 3)) if rest else None
+        m = np.empty(9 * self.nnzb) if matrix else None
+        self._check(lib().opmhip_get_split_assembly(self._h, C.byref(info), _ptr(r), _ptr(m)))
+        out = {"on": bool(info[0]), "stale": bool(info[1]), "assemblies": int(info[2]), "gathers": int(info[3])}
+        if rest:
+            out["rest"] = r
+        if matrix:
+            out["matrix"] = m
+        return out
 
     PROF = ["spmv", "ilu_apply", "ilu_factor", "vector", "assemble", "iq_update", "convergence", "cpr_amg", "spmv_boundary",
             "halo", "allreduce", "cpr_gather"]   # the last three: communication spans of decomposed runs (they overlap the kernel scopes)

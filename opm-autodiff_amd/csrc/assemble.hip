@@ -1014,12 +1014,16 @@ constexpr int ASM_PRE = 10;  // what a diagonal lane fetches ahead for its cell:
 //      drift (into the same registers, parked in LDS before the arithmetic starts)
 // The arithmetic then runs out of LDS / registers.  LDS: the own records are dead once every face is evaluated; the face
 // fluxes and the tile's blocks take their place (11 KiB per workgroup instead of 18).
-template <bool EXT>
+// SPLIT (opmhip_ctx::split_asm): the blocks leave as two runs, the tile's lower and diagonal entries into the rest stream (A = d_R, rows by
+// rrowptr) and its upper entries into the U stream (Uout = d_U, rows by urowptr) - the arrays the sweeps and the rest product read.  Every
+// lane's place comes with its entry word, the two row pointers of the tile's first row with round 2's loads: no further round.
+template <bool EXT, bool SPLIT>
 __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, const int4* __restrict__ sched, const int2* __restrict__ desc, int wet,
                                                           EntryStatic ES, CellStatic C, const double* __restrict__ iq,
                                                           double* __restrict__ storageOld, const double* __restrict__ source,
                                                           const double* __restrict__ dsource, const double* __restrict__ drift, double maxCompensation,
-                                                          double dt, int iteration, double* __restrict__ A, double* __restrict__ resid) {
+                                                          double dt, int iteration, double* __restrict__ A, double* __restrict__ resid,
+                                                          double* __restrict__ Uout, const int* __restrict__ rrowptr, const int* __restrict__ urowptr) {
     constexpr int IQS = Lay<EXT>::IQS, RQ_F0 = Lay<EXT>::RQ_F0, RQ_NF = Lay<EXT>::RQ_NF, F_PORO = Lay<EXT>::F_PORO;
     constexpr int N_OWN = ASM_MAX_ROWS * IQS, N_FLUX = ASM_THREADS * 12, N_OUT = N_FLUX + (ASM_THREADS + 2) * BB;
     __shared__ __attribute__((aligned(16))) double sU[N_OWN > N_OUT ? N_OWN : N_OUT];
@@ -1055,6 +1059,14 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
     }
     if (tid < nrows) { sgeo[tid] = C.depth[r0 + tid]; sgeo[ASM_MAX_ROWS + tid] = C.volume[r0 + tid]; }
     const double trans = ES.trans[k], area = ES.area[k], thp = ES.thpres ? ES.thpres[k] : 0.0;
+    // SPLIT: the tile's runs of the two streams, [rb0, rb1) and [ub0, ub1), and where they stand in sblk - each with the parity of its
+    // first double in memory, so that 16-byte pieces of LDS are 16-byte pieces of the stream
+    int rb0 = 0, ub0 = 0, nR = 0, nU = 0;
+    if (SPLIT) { rb0 = rrowptr[r0]; ub0 = urowptr[r0]; nR = rrowptr[r0 + nrows] - rb0; nU = urowptr[r0 + nrows] - ub0; }
+    const int ldsR = (rb0 & 1) * BB;
+    const int ldsU = SPLIT ? ldsR + nR * BB + (((ldsR + nR * BB) ^ (ub0 * BB)) & 1) : 0;
+    // the lane's block in sblk (doubles): by its entry in the matrix, or by its place in its stream
+    const int bofs = SPLIT ? (((m >> 16) & 1u) ? ldsU : ldsR) + (int)((m >> 17) & 127u) * BB : (k - k0e) * BB;
     const int lrow = m & 63;
     const bool lowI = ((m >> 6) & 1u) != 0;
     const int I = r0 + lrow;
@@ -1117,7 +1129,7 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
     if (isOff) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) store_ad(&sflux[tid * 12 + e * 4], f[e]);
-        double* b = &sblk[(k - k0e) * BB];
+        double* b = &sblk[bofs];
 #pragma unroll
         for (int q = 0; q < BB; ++q) b[q] = blk[q];
     }
@@ -1172,20 +1184,18 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
             s = s * V;
             R[e] = R[e] - s;
         }
-        double* b = &sblk[(k - k0e) * BB];
+        double* b = &sblk[bofs];
         for (int e = 0; e < 3; ++e) {
             resid[(size_t)I * 3 + e] = R[e].v;
             b[e * 3 + 0] = R[e].d0; b[e * 3 + 1] = R[e].d1; b[e * 3 + 2] = R[e].d2;
         }
     }
     __syncthreads();
-    // stream the tile's blocks out: contiguous range [k0, k1) x 72 B
-    {
-        const int head = (k0 - k0e) * BB;      // doubles to skip at the front (0 or 9)
-        const int n = nent * BB;
-        double* dst = A + (size_t)k0e * BB;
-        int b = head, e = head + n;
+    // stream the tile's blocks out: contiguous range [k0, k1) x 72 B; SPLIT: one such range in either stream
+    // (sblk[i] goes to dst[i]: dst is the stream's address moved back by the run's offset in sblk, an even number of doubles)
+    auto stream_out = [&](double* dst, int b, int e) {
         // unaligned head / tail doubles go out one by one, the body as double2
+        if (e <= b) return;   // (an empty run: the last rows own no upper entry)
         if ((b & 1) && tid == 0) dst[b] = sblk[b];
         if ((e & 1) && tid == 0) dst[e - 1] = sblk[e - 1];
         b = (b + 1) & ~1;
@@ -1200,6 +1210,13 @@ __global__ __launch_bounds__(ASM_THREADS) ASM_OCC void k_assemble(int nsched, co
             v2d_a v; v.x = t.x; v.y = t.y;
             __builtin_nontemporal_store(v, reinterpret_cast<v2d_a*>(&d2[i]));
         }
+    };
+    if (SPLIT) {
+        stream_out(A + ((ptrdiff_t)rb0 * BB - ldsR), ldsR, ldsR + nR * BB);
+        stream_out(Uout + ((ptrdiff_t)ub0 * BB - ldsU), ldsU, ldsU + nU * BB);
+    } else {
+        const int head = (k0 - k0e) * BB;      // doubles to skip at the front (0 or 9)
+        stream_out(A + (size_t)k0e * BB, head, head + nent * BB);
     }
 }
 
@@ -2671,11 +2688,18 @@ void launch_assemble(opmhip_ctx* c, double dt, int iteration) {
     const double* drift = c->asmb.drift_enabled ? c->asmb.d_drift : (const double*)nullptr;
     const int grid = c->asmb.nsched;
     if (iteration == 0 && c->asmb.storage_frozen) iteration = 1;   // the old time level's storage was formed by opmhip_begin_time_step
-    OPMHIP_LAYOUT(c,
-        hipLaunchKernelGGL(k_assemble<false>, dim3(grid), dim3(ASM_THREADS), 0, c->stream, c->asmb.nsched, reinterpret_cast<const int4*>(c->asmb.d_asm_sched), reinterpret_cast<const int2*>(c->asmb.d_asm_desc), 0, ES,
-                           cells_of(c), c->asmb.d_iq, c->asmb.d_storageOld, c->asmb.d_source, c->asmb.d_dsource, drift, c->asmb.max_compensation, dt, iteration, c->d_A, c->d_b),
-        hipLaunchKernelGGL(k_assemble<true>, dim3(grid), dim3(ASM_THREADS), 0, c->stream, c->asmb.nsched, reinterpret_cast<const int4*>(c->asmb.d_asm_sched), reinterpret_cast<const int2*>(c->asmb.d_asm_desc), c->asmb.wet_gas ? 1 : 0, ES,
-                           cells_of(c), c->asmb.d_iq, c->asmb.d_storageOld, c->asmb.d_source, c->asmb.d_dsource, drift, c->asmb.max_compensation, dt, iteration, c->d_A, c->d_b));
+    // split assembly: the Jacobian goes where the ILU0 solve reads it (d_R, d_U) and d_A is left alone - unless a well list is to be
+    // added to the matrix afterwards, which works on d_A
+    const bool split = c->split_asm && c->asmb.split_ok && !c->wells.sw.matrix_add;
+#define OPMHIP_ASM_LAUNCH(EXT, SPL, WET)                                                                                                                                   \
+    hipLaunchKernelGGL((k_assemble<EXT, SPL>), dim3(grid), dim3(ASM_THREADS), 0, c->stream, c->asmb.nsched, reinterpret_cast<const int4*>(c->asmb.d_asm_sched),                \
+                       reinterpret_cast<const int2*>(c->asmb.d_asm_desc), WET, ES, cells_of(c), c->asmb.d_iq, c->asmb.d_storageOld, c->asmb.d_source, c->asmb.d_dsource, drift, \
+                       c->asmb.max_compensation, dt, iteration, SPL ? c->d_R : c->d_A, c->d_b, c->d_U, c->pat.d_rrowptr, c->pat.d_urowptr)
+    if (split) { OPMHIP_LAYOUT(c, OPMHIP_ASM_LAUNCH(false, true, 0), OPMHIP_ASM_LAUNCH(true, true, c->asmb.wet_gas ? 1 : 0)); }
+    else { OPMHIP_LAYOUT(c, OPMHIP_ASM_LAUNCH(false, false, 0), OPMHIP_ASM_LAUNCH(true, false, c->asmb.wet_gas ? 1 : 0)); }
+#undef OPMHIP_ASM_LAUNCH
+    c->A_stale = split;
+    if (split) c->split_assemblies++;
     prof_end(c, ps);
 }
 void launch_last_rs_rv(opmhip_ctx* c) {

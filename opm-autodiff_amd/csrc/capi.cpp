@@ -43,6 +43,8 @@ int alloc_system(opmhip_ctx* c) {
         if ((rc = dev_alloc(c, &c->d_usum, n))) return rc;
         OPMHIP_HIP(c, hipMemsetAsync(c->d_usum, 0, n * sizeof(double), c->stream));
     }
+    c->split_asm = split_asm_wanted(c);   // the assembly may write d_R and d_U itself (k_assemble<., true>); a new pattern starts with the matrix in d_A
+    c->A_stale = false;
     double** vecs[] = {&c->d_b, &c->d_x, &c->d_r, &c->d_rw, &c->d_p, &c->d_v, &c->d_s, &c->d_t, &c->d_pw, &c->d_vu, &c->d_stageV};
     for (double** v : vecs) {
         if ((rc = dev_alloc(c, v, n))) return rc;
@@ -272,6 +274,7 @@ int upload_system(opmhip_ctx* c, const double* vals, const double* b) {
     if (vals) {
         OPMHIP_HIP(c, hipMemcpyAsync(c->d_stageA, vals, (size_t)P.nnzb * BB * sizeof(double), hipMemcpyHostToDevice, c->stream));
         launch_permute_blocks(c, c->d_stageA, c->d_A);
+        c->A_stale = false;   // the caller's matrix is the one in force: the factorisation reads d_A and writes the two streams from it
         c->factored = false;
         c->wells.sw.in_matrix = false;   // the caller's matrix replaces the one the resident wells were written into
     }
@@ -981,6 +984,32 @@ int opmhip_get_product_form(opmhip_ctx* c, int info[4]) {
     }
     info[3] = P.rest.on ? P.rest.nsched : 0;
     return OPMHIP_SUCCESS;
+}
+
+int opmhip_get_split_assembly(opmhip_ctx* c, long long info[4], double* rest, double* matrix) {
+    if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_split_assembly before set_pattern");
+        info[0] = (c->split_asm && c->asmb.split_ok && !c->wells.sw.matrix_add) ? 1 : 0;
+        info[1] = c->A_stale ? 1 : 0;
+        info[2] = c->split_assemblies;
+        info[3] = c->split_gathers;
+        if (rest) {
+            if (!c->half_product) return fail(c, OPMHIP_NOT_READY, "get_split_assembly: the half-product form is not in force, there is no rest stream");
+            OPMHIP_HIP(c, hipSetDevice(c->device));
+            OPMHIP_HIP(c, hipMemcpyAsync(rest, c->d_R, (size_t)c->pat.nr * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        if (matrix) {   // the matrix in force, natural order: from d_A, gathered first where the assembly left it in the two streams
+            if (!c->system_loaded) return fail(c, OPMHIP_NOT_READY, "get_split_assembly: no matrix on the device");
+            OPMHIP_HIP(c, hipSetDevice(c->device));
+            ensure_A(c);
+            launch_unpermute_blocks(c, c->d_A, c->d_stageA);
+            OPMHIP_HIP(c, hipMemcpyAsync(matrix, c->d_stageA, (size_t)c->pat.nnzb * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        }
+        return OPMHIP_SUCCESS;
+    });
 }
 
 int opmhip_profile_enable(opmhip_ctx* c, int on) {

@@ -235,10 +235,15 @@ int opmhip_set_static(opmhip_ctx* c, const double* trans, const double* area, co
             //   bits 8-15 the row's entries in ascending natural-column order (ascending GLOBAL neighbour id in decomposed
             //             runs): in-row position of the entry that comes i-th, stored with the row's i-th entry - the order
             //             in which the natural-order CPU path sums the face fluxes of a cell
+            //   bit  16, bits 17-23 (split assembly, ILU0 patterns without ghost columns): the block belongs to the U stream (1) or to the
+            //             rest stream (0), and its place there counted from the first block of the tile's rows in that stream - a tile is a
+            //             run of whole rows, so it owns one contiguous run of either stream
             {
                 const int T = asm_threads();
                 std::vector<int> desc((size_t)2 * T * A.nsched, 0);
                 std::vector<int> byNat;
+                const bool places = P.fillLevel == 0 && P.Nghost == 0 && (int)P.rdest.size() == P.nnzb && (int)P.fdest.size() == P.nnzb;
+                A.split_ok = places;
                 for (int b = 0; b < A.nsched; ++b) {
                     const int tr0 = sched[(size_t)4 * b], tr1 = sched[(size_t)4 * b + 1], tk0 = sched[(size_t)4 * b + 2];
                     for (int p = tr0; p < tr1; ++p) {
@@ -258,6 +263,12 @@ int opmhip_set_static(opmhip_ctx* c, const double* trans, const double* area, co
                             const size_t o = (size_t)2 * ((size_t)b * T + (k - tk0));
                             desc[o] = P.col[k];
                             desc[o + 1] = (p - tr0) | (gi < gj ? 64 : 0) | ((byNat[k - kb] - kb) << 8);
+                            if (places) {
+                                const bool upper = P.rdest[k] < 0;
+                                const int rel = upper ? (-2 - P.fdest[k]) - P.urowptr[tr0] : P.rdest[k] - P.rrowptr[tr0];
+                                if (rel < 0 || rel >= T || (upper && P.fdest[k] > -2)) A.split_ok = false;   // (cannot happen on such a pattern: the assembly then keeps writing the matrix itself)
+                                else desc[o + 1] |= (upper ? 1 << 16 : 0) | (rel << 17);
+                            }
                         }
                     }
                 }
@@ -1817,6 +1828,7 @@ int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double
         c->factored = false;
         c->asmb.assembled = true;
         if (jac) {
+            ensure_A(c);
             launch_unpermute_blocks(c, c->d_A, c->d_stageA);
             OPMHIP_HIP(c, hipMemcpyAsync(jac, c->d_stageA, (size_t)c->pat.nnzb * BB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }

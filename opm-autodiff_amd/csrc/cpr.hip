@@ -940,6 +940,7 @@ static int cpr_weights(opmhip_ctx* c) {
         else hipLaunchKernelGGL(k_cpr_true_weights<false>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, P.Nloc, 0, A.d_iq, A.d_volume, A.last_dt, R.d_w);
         return OPMHIP_SUCCESS;
     }
+    ensure_A(c);
     hipLaunchKernelGGL(k_cpr_weights, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, P.d_diag, c->d_A, R.d_w);
     return OPMHIP_SUCCESS;
 }
@@ -1235,6 +1236,7 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
     note(dev_upload(c, &G.d_qentry, qentry));
     note(dev_alloc(c, &G.d_apg, (size_t)std::max(G.nq, 1)));
     if (G.nq > 0 && !lerr) {
+        ensure_A(c);
         hipLaunchKernelGGL(k_cpr_ghost_pvals, g256(G.nq), dim3(256), 0, c->stream, G.nq, G.d_qrow, G.d_qentry, c->d_A, R.d_w, G.d_apg);
         hipnote(hipMemcpyAsync(apg.data(), G.d_apg, (size_t)G.nq * sizeof(double), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
         hipnote(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
@@ -1340,7 +1342,7 @@ static int cpr_gather_values(opmhip_ctx* c) {
     CprDev& R = c->cpr;
     CprGatherDev& G = R.gather;
     int rc;
-    if (G.nq > 0) hipLaunchKernelGGL(k_cpr_ghost_pvals, g256(G.nq), dim3(256), 0, c->stream, G.nq, G.d_qrow, G.d_qentry, c->d_A, R.d_w, G.d_apg);
+    if (G.nq > 0) { ensure_A(c); hipLaunchKernelGGL(k_cpr_ghost_pvals, g256(G.nq), dim3(256), 0, c->stream, G.nq, G.d_qrow, G.d_qentry, c->d_A, R.d_w, G.d_apg); }
     if (G.nnzloc > 0) hipLaunchKernelGGL(k_cpr_gather_vals, g256(G.nnzloc), dim3(256), 0, c->stream, G.nnzloc, G.d_src, G.d_xptr, G.d_xidx, G.d_apg, R.lv.back().d_val, G.d_vsend);
     if ((rc = comm_allgather(c, G.d_vsend, G.d_vrecv, (size_t)G.maxnnz))) return rc;
     hipLaunchKernelGGL(k_cpr_scatter_vals, g256(G.nnzG), dim3(256), 0, c->stream, G.nnzG, G.d_vunpad, G.d_vpos, G.d_vrecv, G.glob->lv[0].d_val);
@@ -1470,6 +1472,7 @@ int cpr_update(opmhip_ctx* c, bool solveBoundary) {
     if (R.pvals_fresh) R.pvals_fresh = false;   // this solve's factorisation formed the weights and level 0's values as it staged the rows (FactorRider)
     else {
         if ((rc = cpr_weights(c))) { prof_end(c, ps); return rc; }
+        ensure_A(c);
         hipLaunchKernelGGL(k_cpr_pvals, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, P.d_rowptr, (P.Nghost > 0 && !cpr_gathering(c)) ? P.d_col : (const int*)nullptr, c->d_A, R.d_w, R.lv[0].d_val, R.d_pcol);
     }
     if (!R.structured) {   // first solve, or a synchronous rebuild: from the pressure matrix just formed

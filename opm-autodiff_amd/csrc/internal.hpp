@@ -370,7 +370,8 @@ struct AsmDev {
     bool prev_set = false;
     int* d_nswitched = nullptr;
     int* d_asm_sched = nullptr;            // per workgroup of k_assemble: first row, end row, first entry, end entry of its tile
-    int* d_asm_desc = nullptr;             // per workgroup and lane: column and entry word (row inside the tile, upwind tie-break flag, natural summation order)
+    int* d_asm_desc = nullptr;             // per workgroup and lane: column and entry word (row inside the tile, upwind tie-break flag, natural summation order, place in the rest / U stream)
+    bool split_ok = false;                 // every entry word carries its block's place in the tile's run of the rest or the U stream (ILU0 patterns without ghost columns)
     int ntiles = 0, nsched = 0;
     double *d_conv_part = nullptr, *d_conv_out = nullptr;
     double* d_stage_cell = nullptr;   // staging for per-cell doubles (natural order), Nb * max(9, IQS)
@@ -534,6 +535,12 @@ struct opmhip_ctx {
     double *d_A = nullptr, *d_L = nullptr, *d_U = nullptr, *d_invD = nullptr;
     double *d_R = nullptr, *d_usum = nullptr;   // Pattern::ualias: the rest of the matrix beside U (values), the backward sweeps' row sums (3 per row)
     bool half_product = false;                  // BiCGStab forms the product after an ILU0 application from d_R and d_usum (opmhip_config.half_product)
+    // Split assembly: k_assemble writes the Jacobian straight into d_R (lower entries, diagonal) and d_U (upper entries), the
+    // streams the sweeps and the rest product read, and k_ilu_factor forms L and D^-1 from d_R without copying anything.  d_A is then NOT
+    // written: A_stale says so, and whoever reads d_A calls ensure_A first (one gather, counted in split_gathers).
+    bool split_asm = false;                     // the context can assemble that way (split_asm_wanted, resolved with half_product)
+    bool A_stale = false;                       // the matrix in force lives in d_R / d_U; d_A holds an older one
+    long long split_gathers = 0, split_assemblies = 0;
     // vectors, internal order, 3*Nb each
     double *d_b = nullptr, *d_x = nullptr, *d_r = nullptr, *d_rw = nullptr, *d_p = nullptr, *d_v = nullptr,
            *d_s = nullptr, *d_t = nullptr, *d_pw = nullptr, *d_vu = nullptr;
@@ -738,6 +745,8 @@ void launch_zero_diag_fix(opmhip_ctx* c);
 // y = A x (+ wells) with the partial sums of ndot scalar products.  exchange: x's ghost entries are brought up to date first
 // (copyOwnerToAll) - on the halo stream, beside the product of the interior tiles; x is then written (its ghost part)
 int launch_spmv(opmhip_ctx* c, double* x, double* y, int ndot, const double* w0, double xs = 1.0, bool exchange = false, const double* uadd = nullptr, const double* w1 = nullptr);
+bool split_asm_wanted(const opmhip_ctx* c);      // solver.hip: half_product in force, ILU0 without CPR, no ghost columns, the assembly's entry records carry the places; OPMHIP_SPLIT_ASM=0 (tuning) forces it off
+void ensure_A(opmhip_ctx* c);                    // solver.hip: A_stale -> d_A gathered from d_R / d_U on the context's stream; in front of every reader of d_A
 bool half_product_wanted(const opmhip_ctx* c);   // solver.hip: opmhip_config.half_product resolved for the pattern in hand (asked once, when the system's buffers are allocated)
 void launch_wells_residual(opmhip_ctx* c, const double* d_resWell, double* r);
 void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const int* d_pair_ptr, const int* d_entry);

@@ -1288,7 +1288,11 @@ __global__ __launch_bounds__(64) void k_ilu_sweep_chain_LU(const int* __restrict
 // RIDER (CPR, FactorRider): the staged, fixed-up row also leaves its pressure-column image and its entries of the pressure matrix behind
 // - and with RIDER == 2 its quasi-IMPES weights - before the elimination touches it: the pass k_cpr_pvals / k_cpr_weights made over the
 // whole Jacobian right after this kernel (1 142 MB of traffic, 0.20 ms per solve) rides here on values that are in LDS anyway.
-template <int RIDER>
+// SPLIT (opmhip_ctx::A_stale: the assembly wrote the rest stream Rv and the U stream itself, A is not read): the tile's rows are staged from
+// Rv - lower entries and diagonal, all the elimination of a Pattern::ualias row ever touches (its targets lie on or left of the diagonal) - and
+// only L and D^-1 are written; a row's blocks stand in LDS in the same order as before, so the steps and their operands are the same ones.
+// The zero-diagonal fix (Afix == Rv) goes into the rest stream's diagonal block.
+template <int RIDER, bool SPLIT = false>
 __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched, const int* __restrict__ ct_first, const int* __restrict__ tile_row0,
                                                    const int* __restrict__ rowptr, const int* __restrict__ col,
                                                    const int* __restrict__ diag, const double* __restrict__ A,
@@ -1307,27 +1311,50 @@ __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched
     __shared__ int scol[TILE_CAP_BLOCKS + 2], sdest[TILE_CAP_BLOCKS + 2], slm[TILE_CAP_BLOCKS + 2];
     __shared__ short ssrc[TILE_CAP_BLOCKS + 2];   // Rv != NULL: per block of the tile's stretch of the rest stream, its place in the staged tile
     for (int t = q0; t < q1; ++t) {  // steps of a chain-tile in order (a single step unless the ordering is line-coloured)
-        const TileCtx T = tile_stage_values(t, tile_row0, rowptr, A, sval, lane);
+        TileCtx T;
+        int rb0e = 0, nbR = 0;   // SPLIT: the 16-byte aligned start of the tile's run of the rest stream and its length in blocks
+        if (SPLIT) {
+            T.r0 = tile_row0[t]; T.r1 = tile_row0[t + 1];
+            const int k0 = rowptr[T.r0], k1 = rowptr[T.r1], rb0 = rrowptr[T.r0];
+            T.k0e = k0 & ~1; T.nb = k1 - T.k0e;
+            T.staged = (T.nb <= TILE_CAP_BLOCKS + 1);   // (by the matrix's tile, as unsplit: the column lists below are the matrix's)
+            rb0e = rb0 & ~1; nbR = rrowptr[T.r1] - rb0e;
+            if (T.staged && nbR > 0) stage_doubles(Rv + (size_t)rb0e * BB, sval, nbR * BB, lane);
+            wave_sync();
+        } else T = tile_stage_values(t, tile_row0, rowptr, A, sval, lane);
         // the tile's column indices next to its values: the elimination searches them many times
         if (T.staged) {
             const int kk0 = rowptr[T.r0], kk1 = rowptr[T.r1];
-            const int rb0 = Rv ? rrowptr[T.r0] : 0;
+            const int rb0 = (Rv && !SPLIT) ? rrowptr[T.r0] : 0;
             for (int q = kk0 + lane; q < kk1; q += 64) {
-                scol[q - T.k0e] = col[q]; sdest[q - T.k0e] = fdest[q]; slm[q - T.k0e] = lmatch[q];
-                if (Rv) { const int rd = rdest[q]; if (rd >= 0) ssrc[rd - rb0] = (short)(q - T.k0e); }
+                scol[q - T.k0e] = col[q]; slm[q - T.k0e] = lmatch[q];
+                if (SPLIT) { const int rd = rdest[q]; if (rd >= 0) sdest[rd - rb0e] = fdest[q]; }   // per block of the staged run: its place in L (the diagonal: -1)
+                else {
+                    sdest[q - T.k0e] = fdest[q];
+                    if (Rv) { const int rd = rdest[q]; if (rd >= 0) ssrc[rd - rb0] = (short)(q - T.k0e); }
+                }
             }
-            if (kk0 > T.k0e && lane == 0) sdest[0] = -1;   // the alignment block in front of the tile belongs to the previous row
+            if (SPLIT) { if (nbR > 0 && (rrowptr[T.r0] & 1) && lane == 0) sdest[0] = -1; }
+            else if (kk0 > T.k0e && lane == 0) sdest[0] = -1;   // the alignment block in front of the tile belongs to the previous row
         }
         wave_sync();
         const int i = T.r0 + lane;
-        if (Afix && i < T.r1) {   // the zero-diagonal fix of the device-assembled Jacobian (k_zero_diag_fix's statement), on the staged row and - rarely - in the matrix itself, which the operator reads later
+        const int rbi = (SPLIT && i < T.r1) ? rrowptr[i] : 0;   // SPLIT: the row's first block in the rest stream
+        if (SPLIT && Afix && i < T.r1) {   // the same fix, on the staged row and in the rest stream, which the product reads later
+            const int nd = diag[i] - rowptr[i];
+            double* dblk = &sval[(rbi + nd - rb0e) * BB];
+#pragma unroll
+            for (int dgn = 0; dgn < BS; ++dgn)
+                if (dblk[dgn * 4] == 0.0) { dblk[dgn * 4] = 1e-15; Rv[(size_t)(rbi + nd) * BB + dgn * 4] = 1e-15; }
+        }
+        if (!SPLIT && Afix && i < T.r1) {   // the zero-diagonal fix of the device-assembled Jacobian (k_zero_diag_fix's statement), on the staged row and - rarely - in the matrix itself, which the operator reads later
             const int kd = diag[i];
             double* dblk = &sval[(kd - T.k0e) * BB];
 #pragma unroll
             for (int dgn = 0; dgn < BS; ++dgn)
                 if (dblk[dgn * 4] == 0.0) { dblk[dgn * 4] = 1e-15; Afix[(size_t)kd * BB + dgn * 4] = 1e-15; }
         }
-        if (Rv && T.staged) {
+        if (!SPLIT && Rv && T.staged) {
             // Pattern::ualias: the matrix's own entries beside the U part - lower entries, diagonal, ghost columns - leave LDS BEFORE the
             // elimination touches them, as one stream the product after an M^-1 application reads in place of the whole matrix
             // (rows are stored one after the other in the rest stream as in the matrix: the tile's stretch of it is ONE range, written
@@ -1351,7 +1378,7 @@ __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched
         if (i < T.r1) {
             const int kb = rowptr[i], ke = rowptr[i + 1], kd = diag[i];
             // an over-long row (not staged) cannot be eliminated in LDS: such rows are rejected at set_pattern time
-            double* row = &sval[(kb - T.k0e) * BB];
+            double* row = &sval[(SPLIT ? rbi - rb0e : kb - T.k0e) * BB];
             const int* rcol = &scol[kb - T.k0e];
             const int* rlm = &slm[kb - T.k0e];
             const int n = ke - kb, nd = kd - kb;
@@ -1507,11 +1534,11 @@ __global__ __launch_bounds__(64) void k_ilu_factor(const int* __restrict__ sched
         // write neighbouring doubles.  (One lane per row storing its own 6 + 6 blocks cost a third of the kernel: 63 store
         // instructions per lane, each scattering 8 bytes into 32 different rows.)
         if (T.staged) {
-            const int n9 = T.nb * BB;
+            const int n9 = (SPLIT ? nbR : T.nb) * BB;
             for (int e = lane; e < n9; e += 64) {
                 const int blk = e / BB, dst = sdest[blk];
                 if (dst >= 0) L[(size_t)dst * BB + (e - blk * BB)] = sval[e];
-                else if (dst <= -2) U[(size_t)(-2 - dst) * BB + (e - blk * BB)] = sval[e];
+                else if (!SPLIT && dst <= -2) U[(size_t)(-2 - dst) * BB + (e - blk * BB)] = sval[e];
             }
         }
         __syncthreads();  // drains vmcnt: this step's factors (global stores) are complete before the next step reads them (measured: without it, wrong factors and 0.333 against 0.325 ms - the drain costs nothing)
@@ -2301,6 +2328,7 @@ __global__ __launch_bounds__(256) void k_stream_read(size_t n2, const double2* _
 }
 void launch_stream_read(opmhip_ctx* c) {
     const size_t n2 = (size_t)c->pat.nnzb * BB / 2;
+    ensure_A(c);
     hipLaunchKernelGGL(k_stream_read, dim3(256 * 8), dim3(256), 0, c->stream, n2, reinterpret_cast<const double2*>(c->d_A), c->d_part2);
 }
 
@@ -2322,6 +2350,7 @@ void launch_vec_to_natural(opmhip_ctx* c, const double* internal, double* nat, i
     hipLaunchKernelGGL(k_vec_to_natural, dim3(cdiv((size_t)n * BS, 256)), dim3(256), 0, c->stream, n, c->pat.d_toOrder, internal, nat);
 }
 void launch_zero_diag_fix(opmhip_ctx* c) {
+    ensure_A(c);
     hipLaunchKernelGGL(k_zero_diag_fix, dim3(cdiv((size_t)c->pat.Nb * BS, 256)), dim3(256), 0, c->stream, c->pat.Nb, c->pat.d_diag, c->d_A);
 }
 void launch_lu_to_natural(opmhip_ctx* c, double* d_out) {
@@ -2363,11 +2392,13 @@ int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
 }
 void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const int* d_pair_ptr, const int* d_entry) {
     const WellsDev& W = c->wells;
+    ensure_A(c);   // the wells are added to the matrix itself; the factorisation that follows reads it and rewrites the two streams
     hipLaunchKernelGGL(k_wells_add_to_matrix, dim3(nw), dim3(64), 0, c->stream, w0, serial, W.d_val_pointers, W.d_C, W.d_D, W.d_B, d_pair_ptr, d_entry, c->d_A);
 }
 void launch_std_wells_add_to_matrix(opmhip_ctx* c) {
     const WellsDev& W = c->wells;
     const StdWellsDev& S = W.sw;
+    ensure_A(c);
     const int ps = prof_begin(c, PROF_ASSEMBLE);   // (the well model's, as the standard wells' other launches: one scope)
     hipLaunchKernelGGL(k_std_wells_add_to_matrix, dim3((S.ma_targets + 63) / 64), dim3(64), 0, c->stream, S.ma_targets, S.d_ma_target, S.d_ma_tptr, S.d_ma_contrib,
                        W.d_val_pointers, W.d_C, W.d_D, W.d_B, c->d_A);
@@ -2412,6 +2443,32 @@ bool half_product_wanted(const opmhip_ctx* c) {
     if (c->cfg.half_product > 0) return true;
     return spmv_pipelined(c);
 }
+// Split assembly resolved (beside half_product, when the system's buffers are allocated): the plain ILU0 context of the half-product form -
+// no CPR, no fill, no ghost columns - whose d_R and d_U then hold every block of the matrix between them.  Whether an assembly really
+// writes that way is decided per call (launch_assemble: the entry records carry the places, no well list is to be added to the matrix).
+// OPMHIP_SPLIT_ASM=0 (tuning / A-B measurements, the tests): never.
+bool split_asm_wanted(const opmhip_ctx* c) {
+    static const int env = [] { const char* e = tuning_env("OPMHIP_SPLIT_ASM"); return e ? std::atoi(e) : 1; }();
+    const Pattern& P = c->pat;
+    return env != 0 && c->half_product && !use_cpr(c) && P.fillLevel == 0 && P.chained && P.ualias && P.Nghost == 0 && P.d_rdest && P.d_rrowptr;
+}
+// d_A from the two streams, by the maps the factorisation scatters with (Pattern::rdest, Pattern::fdest): one thread per double
+__global__ __launch_bounds__(256) void k_gather_A(size_t n, const int* __restrict__ rdest, const int* __restrict__ fdest, const double* __restrict__ Rv,
+                                                  const double* __restrict__ Uv, double* __restrict__ A) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const size_t blk = e / BB;
+    const int q = (int)(e - blk * BB), rd = rdest[blk];
+    A[e] = rd >= 0 ? Rv[(size_t)rd * BB + q] : Uv[(size_t)(-2 - fdest[blk]) * BB + q];
+}
+void ensure_A(opmhip_ctx* c) {
+    if (!c->A_stale) return;
+    const Pattern& P = c->pat;
+    const size_t n = (size_t)P.nnzb * BB;
+    hipLaunchKernelGGL(k_gather_A, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, P.d_rdest, P.d_fdest, c->d_R, c->d_U, c->d_A);
+    c->A_stale = false;
+    c->split_gathers++;
+}
 // the scalar products ride in the product's kernel unless wells modify y after it (then k_dots forms them afterwards)
 static bool spmv_dots_env() {   // OPMHIP_DOTS_SEPARATE=1 (tuning / A-B measurements): k_dots behind every product, as with wells
     static const bool v = [] { const char* e = tuning_env("OPMHIP_DOTS_SEPARATE"); return e && std::atoi(e) != 0; }();
@@ -2424,6 +2481,7 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
                             const double* uadd = nullptr, const double* w1 = nullptr) {
     const Pattern& P = c->pat;
     if (np <= 0) return 0;
+    if (!uadd) ensure_A(c);   // the whole product streams d_A
     double* part = c->d_part + pofs;
     // timed by its own dispatch (kernel begin to kernel end), which is what bench.py's roofline quotes
     int es = -1, ee = -1;
@@ -2570,6 +2628,7 @@ void launch_ilu_factor(opmhip_ctx* c, bool fix_zero_diagonal, const FactorRider*
     const Pattern& P = c->pat;
     const int ps = prof_begin(c, PROF_ILU_FACTOR);
     if (P.fillLevel > 0) {   // ILU(n): no rider (a CPR context factors ILU0)
+        ensure_A(c);
         hipLaunchKernelGGL(k_ilun_scatter, dim3((P.Nb + 255) / 256), dim3(256), 0, c->stream, P.Nb, P.d_rowptr, P.d_col, c->d_A, P.d_fdest,
                            P.d_lrowptr, P.d_urowptr, c->d_L, c->d_U, c->d_invD, fix_zero_diagonal ? 1 : 0);
         for (int col = 0; col < P.numColors; ++col) {
@@ -2583,9 +2642,17 @@ void launch_ilu_factor(opmhip_ctx* c, bool fix_zero_diagonal, const FactorRider*
     }
     const FactorRider none;
     const FactorRider& R = rider ? *rider : none;
+    if (c->A_stale && R.mode != 0) ensure_A(c);   // (a rider reads whole rows; a split context has no CPR, so this never runs)
+    const bool split = c->A_stale;                // the assembly wrote d_R and d_U: L and D^-1 from d_R, nothing copied
     for (int col = 0; col < P.numColors; ++col) {
         const int off = P.tiles.ctSchedOff[col], npos = P.tiles.ctSchedOff[col + 1] - off;
         if (npos <= 0) continue;
+        if (split) {
+            hipLaunchKernelGGL((k_ilu_factor<0, true>), dim3(npos), dim3(64), 0, c->stream, P.tiles.d_ctSched + off, P.tiles.d_ctFirst, P.tiles.d_row0, P.d_rowptr, P.d_col,
+                               P.d_diag, (const double*)nullptr, P.d_fdest, P.d_lmatch, P.d_urowptr, P.d_ucol, c->d_L, c->d_U, c->d_invD, fix_zero_diagonal ? c->d_R : (double*)nullptr,
+                               P.Nb, R.W, R.ghostFrom, R.w, R.ap, R.pcol, P.d_rdest, P.d_rrowptr, c->d_R);
+            continue;
+        }
 #define OPMHIP_FACTOR_LAUNCH(RID)                                                                                                                          \
     hipLaunchKernelGGL(k_ilu_factor<RID>, dim3(npos), dim3(64), 0, c->stream, P.tiles.d_ctSched + off, P.tiles.d_ctFirst, P.tiles.d_row0, P.d_rowptr, P.d_col, \
                        P.d_diag, c->d_A, P.d_fdest, P.d_lmatch, P.d_urowptr, P.d_ucol, c->d_L, c->d_U, c->d_invD, fix_zero_diagonal ? c->d_A : (double*)nullptr, \
