@@ -768,7 +768,9 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * (opmhip_set_std_wells_head_model, below).
  * A tubing-head-pressure limit through VFPPROD / VFPINJ tables is a third control (opmhip_set_vfp_tables, opmhip_set_std_wells_thp, below).
  * Further rate limits - ORAT, WRAT, GRAT, LRAT, RESV beside the list's own target - are controls 3 .. 7 (opmhip_set_std_wells_limits, below).
- * NOT covered: groups and GRUP control; CRAT; history-mode RESV; gas lift (ALQ is a constant per well); bhpwithflo and the robust BHP-THP intersection of
+ * Group production control - GCONPROD targets shared by guide rate, control 8 (GRUP) - is opmhip_set_std_wells_groups, below.
+ * NOT covered: nested groups, a control on FIELD, group guide rates, efficiency factors, GCONINJE, GCONSALE / GCONSUMP and exceed actions other
+ * than RATE (the groups' section below); CRAT; history-mode RESV; gas lift (ALQ is a constant per well); bhpwithflo and the robust BHP-THP intersection of
  * computeBhpAtThpLimitProd; well potentials; THP for multisegment wells; the deck-level parsing and unit conversion of VFPPROD / VFPINJ
  * (opm-common's: it stays with the caller); crossflow in injectors (refused: in the reference an injector re-injects what crosses into it,
  * because its composition - WFrac, GFrac - is an unknown while getQs pins the other components to zero; this parametrisation fixes
@@ -1088,14 +1090,91 @@ typedef struct opmhip_std_wells_limits {
  * changing the well state (:140-166); here the well switches.
  * A list without limits launches the instantiations it launched before; with limits another instantiation runs in their place: the
  * number of launches of a Newton iteration does not change, and a time step gains the averages and coefficients only with a RESV limit.
- * Left out: groups / GRUP, CRAT, history-mode RESV (form WCONHIST's target from the averages and hand it in as resv_rate), FIP regions
+ * Left out: CRAT, history-mode RESV (form WCONHIST's target from the averages and hand it in as resv_rate), FIP regions
  * other than the whole field, salt and temperature in the converter, decomposed contexts. */
 int opmhip_set_std_wells_limits(opmhip_ctx* ctx, const opmhip_std_wells_limits* limits);
 /* averages[5] as opmhip_reservoir_averages gives them, of the last opmhip_std_wells_begin_iteration(0) that formed them; coeff[num_wells * 3]
  * (oil, water, gas): the control equation's coefficients of every well with a RESV limit (calcCoeff for a producer, calcInjCoeff for an
  * injector), zeros otherwise; resv_current[num_wells]: the voidage rate the last controls pass formed.  Any pointer may be NULL; waits for
- * the stream.  Zeros without limits. */
+ * the stream.  Zeros without limits and without groups (a producer of a group with a RESV target has its calcCoeff here too). */
 int opmhip_get_std_wells_resv(opmhip_ctx* ctx, double* averages, double* coeff, double* resv_current);
+
+/* ---- group production control of the resident wells: GCONPROD / GRUP.  Additive to ABI 11 ------------------------------------------
+ * A flat list of production groups, each a direct child of FIELD; every well is in at most one (well_group -1: directly under FIELD, no
+ * group control).  Per group five targets - oil, water, gas, liquid surface rates and a reservoir voidage rate [m^3/s], positive,
+ * +infinity: none, a NULL array: none of that kind - with the exceed action RATE, and a production control mode: 0 NONE, 1 ORAT, 2 WRAT,
+ * 3 GRAT, 4 LRAT, 5 RESV.  Per well one guide rate per target mode, in that order (>= 0, finite: GuideRate::get and its phase conversion
+ * are opm-common's, the converted values stay with the caller), and `available` (WGRUPCON item 2; NULL: all 1).  nupcol: the deck's NUPCOL.
+ * The arithmetic is wells.py StandardWells(groups=, arithmetic="stated")'s, operation by operation; like every well rate here it is
+ * UNVERIFIED against Flow's numbers (the reference tree holds no output of a deck with groups).  With groups in force:
+ *   control value 8 (GRUP) exists in opmhip_set_std_wells_state - for an available producer in a group - and opmhip_get_std_wells;
+ *   opmhip_std_wells_begin_iteration(iteration), iteration being the reference's iterationIdx, runs BlackoilWellModel::updateWellControls
+ *     (wells/BlackoilWellModel_impl.hpp:1239-1287): group data, the groups' check, group data, every well's group check, group data, the
+ *     individual check of the wells that did not just switch, group data (the first group data is elided: the groups' check reads the present
+ *     rates only, and the NUPCOL copy and the record that pass would leave are overwritten by the second, under the same condition);
+ *   group data (BlackoilWellModelGeneric.cpp:1494-1539, WellGroupHelpers.cpp:300-427): while iteration < nupcol the rates of the groups'
+ *     producers are copied to the NUPCOL rates; per group and component reduction = 0 - the NUPCOL rates of its producers not under GRUP,
+ *     guide_sum = the mode's guide rates of its producers under GRUP, rates = 0 - the present rates of its producers, voidage = the sum of
+ *     their voidage rates (calcReservoirVoidageRates; groups with a RESV target), every sum over the group's wells in list order starting
+ *     from 0.  This record stays as it is until the next group data: the wells' checks and the control rows read it frozen;
+ *   the group's check (BlackoilWellModelGeneric.cpp:537-650, 888-943) runs only while iteration <= nupcol (the asymmetry with the copy's <
+ *     is the reference's): ORAT, WRAT, GRAT, LRAT, RESV in that order, the first target that is < current and is not the mode in force
+ *     wins; current from the present rates (LRAT: the oil sum + the water sum; RESV: the voidage sum); on a switch the rates of the group's
+ *     wells under GRUP are multiplied by target / current when current > 1e-12 (updateWellRatesFromGroupTargetScale, WellGroupHelpers.cpp:429-);
+ *   a well's group check (WellInterfaceFluidSystem.cpp:363-432, WellGroupHelpers.cpp:1055-1180) - a producer not under GRUP, available, in a
+ *     group whose mode is not NONE: mode(v) = v[c] (ORAT, WRAT, GRAT), v_o + v_w (LRAT), (c_w v_w + c_o v_o) + c_g v_g with the well's calcCoeff
+ *     (RESV; TargetCalculator::calcModeRateFromRates, TargetCalculator.cpp:53-90); current = -mode(x); fraction = g_w / (guide_sum + g_w), 0
+ *     where that sum is <= 1e-12; target_rate = max(1e-12, ((target - mode(reduction)) + current) * fraction); where current > target_rate
+ *     the control becomes 8 and the three rates are multiplied by target_rate / current;
+ *   the control row under 8 (WellInterfaceEval.cpp:178-266): target_rate = max(0, (target - mode(reduction)) * (g_w / guide_sum)), the
+ *     fraction 0 where guide_sum <= 1e-12; r_w[3] = mode(x) + target_rate with D[3] the mode's derivatives (the rows of controls 3 .. 7 with
+ *     target_rate in the limit's place); a group of mode NONE gives the BHP row bhp - bhp_limit (:189-221);
+ *   a well leaves control 8 only through its individual limits, by the rule it had;
+ *   opmhip_std_wells_begin_iteration(0) forms the averages and calcCoeff for every producer of a group with a RESV target, and the group
+ *     data before the wells alone are solved; during that solve the record is frozen, as the reference's group state is;
+ *   opmhip_advance_time_level / opmhip_update_failed save and restore the groups' modes and the NUPCOL rates with the controls.
+ * A list without groups launches exactly the kernels it launched before.  With groups a begin_iteration launches the group kernel in front of
+ * and behind the controls (and, at iteration 0, in front of the wells-alone solve): a number that depends neither on the wells nor on the groups.
+ * KNOWN DIFFERENCE FROM FLOW: updateWellStateWithTarget's second rescaling on a switch to GRUP (wells/WellInterface_impl.hpp:902-921) is left
+ * out, as the rescaling is for every other mode here.
+ * The averages and calcCoeff are formed at opmhip_std_wells_begin_iteration(0) only.  A group's first RESV target handed in by
+ * opmhip_set_std_wells_group_targets, and opmhip_set_std_wells_limits called with groups in force (the coefficients then move to the limits'
+ * array, which starts from zeros), therefore take effect at the next time step's first iteration: until then the voidage rates and RESV rows
+ * are evaluated at zero averages and coefficients.  Both calls are events of a report or time step, in front of begin_iteration(0).
+ * The NUPCOL rates are the library's own: opmhip_get_std_wells_groups reads them, no entry point sets them.
+ * NOT covered: nested groups and a control on FIELD (updateGroupHigherControls); group guide rates; group and well efficiency factors (all 1);
+ * GCONINJE (RATE / RESV / REIN / VREP); GCONSALE / GCONSUMP; exceed actions other than RATE; CRAT / PRBL; injectors in a group's arithmetic
+ * (an injector may name a group and is ignored by it); well potentials; decomposed contexts (refused as the list itself is). */
+typedef struct opmhip_std_wells_groups {
+    int num_groups;
+    const int* well_group;         /* [num_wells] the well's group, -1: directly under FIELD */
+    const double* oil_target;      /* [num_groups] each; +infinity: no such target; NULL: none of that kind */
+    const double* water_target;
+    const double* gas_target;
+    const double* liquid_target;
+    const double* resv_target;
+    const int* mode;               /* [num_groups] 0 NONE, 1 ORAT, 2 WRAT, 3 GRAT, 4 LRAT, 5 RESV; NULL: all NONE */
+    const double* guide_rate;      /* [num_wells * 5] per well ORAT, WRAT, GRAT, LRAT, RESV */
+    const int* available;          /* [num_wells] 0 / 1; NULL: all 1 */
+    int nupcol;
+} opmhip_std_wells_groups;
+/* Call it after opmhip_set_std_wells; NULL (or num_groups == 0) clears; replacing or clearing the list clears.  OPMHIP_NOT_READY without
+ * a list; OPMHIP_INVALID_ARGUMENT, the text naming the reason, for: a decomposed context (checked first); num_groups < 0; a NULL well_group or guide_rate; a group index outside
+ * [-1, num_groups); a target that is NaN, -infinity or not > 0; a mode outside 0 .. 5 or one whose target the group lacks; a guide rate that
+ * is negative or not finite; an available other than 0 / 1; nupcol < 0; a well under control 8 that is an injector, has no group or is not
+ * available; removing the groups while a well is under control 8.  A refused call leaves the previous values in force.  The NUPCOL rates
+ * start from zero. */
+int opmhip_set_std_wells_groups(opmhip_ctx* ctx, const opmhip_std_wells_groups* groups);
+/* Events at a report or time step, with groups in force (OPMHIP_NOT_READY otherwise): new guide rates [num_wells * 5]; new targets
+ * (a NULL array: that kind stays) and modes (NULL: stay).  Checked as above; a refused call leaves the previous values in force.  Both wait
+ * for the stream and mark the last assembly stale, as opmhip_set_std_wells_state does. */
+int opmhip_set_std_wells_guide_rates(opmhip_ctx* ctx, const double* guide_rate);
+int opmhip_set_std_wells_group_targets(opmhip_ctx* ctx, const double* oil_target, const double* water_target, const double* gas_target,
+                                       const double* liquid_target, const double* resv_target, const int* mode);
+/* Per group, as the last group data left them (any pointer may be NULL; waits for the stream): mode [num_groups], rates [num_groups * 3]
+ * (oil, water, gas produced), voidage [num_groups], reduction [num_groups * 3], guide_sum [num_groups]; per well nupcol_rates
+ * [num_wells * 3].  Nothing is written without groups. */
+int opmhip_get_std_wells_groups(opmhip_ctx* ctx, int* mode, double* rates, double* voidage, double* reduction, double* guide_sum, double* nupcol_rates);
 
 /* With a list set:
  * opmhip_assemble forms, in front of the assembly kernel and of the aquifers' influx (the host order: wells' rates first), the

@@ -137,6 +137,36 @@ def make_std_wells_limits(t, num_wells):
     return s, arr
 
 
+class StdWellsGroups(C.Structure):
+    """opmhip_std_wells_groups: group production control of the resident standard wells (opmhip_set_std_wells_groups)"""
+    _fields_ = [("num_groups", C.c_int), ("well_group", C.c_void_p), ("oil_target", C.c_void_p), ("water_target", C.c_void_p), ("gas_target", C.c_void_p),
+                ("liquid_target", C.c_void_p), ("resv_target", C.c_void_p), ("mode", C.c_void_p), ("guide_rate", C.c_void_p), ("available", C.c_void_p),
+                ("nupcol", C.c_int)]
+
+
+def make_std_wells_groups(t, num_wells):
+    """dict(num_groups, well_group per well, any of oil_target, water_target, gas_target, liquid_target, resv_target per group, mode per
+    group, guide_rate (wells, 5), available per well, nupcol) -> (StdWellsGroups struct, keep-alive dict); None -> (None, {}).  An absent
+    or None entry is a NULL array."""
+    if t is None:
+        return None, {}
+    ng = int(t["num_groups"])
+    arr = {}
+    for name, _ in StdWellsGroups._fields_:
+        v = t.get(name)
+        if name in ("num_groups", "nupcol") or v is None:
+            continue
+        arr[name] = _i32(np.asarray(v).reshape(-1)) if name in ("well_group", "mode", "available") else _f64(np.asarray(v, float).reshape(-1))
+        want = 5 * num_wells if name == "guide_rate" else (num_wells if name in ("well_group", "available") else ng)
+        if len(arr[name]) != want:
+            raise ValueError("make_std_wells_groups: %s has %d entries, %d expected" % (name, len(arr[name]), want))
+    s = StdWellsGroups()
+    s.num_groups, s.nupcol = ng, int(t.get("nupcol", 0))
+    for name, a in arr.items():
+        setattr(s, name, a.ctypes.data)
+    return s, arr
+
+
 def make_vfp_tables(tables):
     """list of vfp.VFPTable (or objects with its attributes: kind, table_num, flo_type, wfr_type, gfr_type, datum_depth, axes in the order flo,
     thp[, wfr, gfr, alq], values with flo fastest) -> (VfpTables struct, keep-alive dict); empty / None -> (None, {})"""
@@ -772,6 +802,10 @@ def _bind_assembly(L):
     L.opmhip_get_std_wells_thp.argtypes = [vp, vp, vp, vp]
     L.opmhip_set_std_wells_limits.argtypes = [vp, C.POINTER(StdWellsLimits)]
     L.opmhip_get_std_wells_resv.argtypes = [vp, vp, vp, vp]
+    L.opmhip_set_std_wells_groups.argtypes = [vp, C.POINTER(StdWellsGroups)]
+    L.opmhip_set_std_wells_guide_rates.argtypes = [vp, vp]
+    L.opmhip_set_std_wells_group_targets.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.opmhip_get_std_wells_groups.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.opmhip_set_std_wells_matrix_add.argtypes = [vp, C.c_int]
     L.opmhip_std_wells_add_to_matrix.argtypes = [vp]
     L.opmhip_get_std_wells_matrix_add.argtypes = [vp, vp]
@@ -1063,6 +1097,7 @@ class HipModel(HipSolver):
         """opmhip_set_std_wells: the standard wells (dict, see make_std_wells) on the device; None clears them"""
         sw, keep = make_std_wells(wells)
         self._nsw = self._nswperf = 0      # a refused call leaves no list set
+        self._nswgroups = 0                # replacing the list clears its groups
         self._check(lib().opmhip_set_std_wells(self._h, C.byref(sw) if sw else None))
         if sw:
             self._nsw, self._nswperf = sw.num_wells, len(keep["cell"])
@@ -1113,6 +1148,37 @@ class HipModel(HipSolver):
         n = getattr(self, "_nsw", 0)
         out = dict(averages=np.zeros(5), coeff=np.zeros((n, 3)), resv_current=np.zeros(n))
         self._check(lib().opmhip_get_std_wells_resv(self._h, _ptr(out["averages"]), _ptr(out["coeff"]), _ptr(out["resv_current"])))
+        return out
+
+    def set_std_wells_groups(self, groups):
+        """opmhip_set_std_wells_groups: group production control (dict, see make_std_wells_groups); None clears.  A refused call leaves the
+        previous values in force."""
+        t, keep = make_std_wells_groups(groups, getattr(self, "_nsw", 0))
+        self._check(lib().opmhip_set_std_wells_groups(self._h, C.byref(t) if t else None))
+        self._nswgroups = 0 if t is None else int(t.num_groups)
+
+    def set_std_wells_guide_rates(self, guide_rate):
+        """opmhip_set_std_wells_guide_rates: (wells, 5) - ORAT, WRAT, GRAT, LRAT, RESV per well"""
+        g = _f64(np.asarray(guide_rate, float).reshape(-1))
+        if g.size != 5 * getattr(self, "_nsw", 0):
+            raise ValueError("set_std_wells_guide_rates: %d entries for the %d wells set" % (g.size, getattr(self, "_nsw", 0)))
+        self._check(lib().opmhip_set_std_wells_guide_rates(self._h, _ptr(g)))
+
+    def set_std_wells_group_targets(self, oil=None, water=None, gas=None, liquid=None, resv=None, mode=None):
+        """opmhip_set_std_wells_group_targets: per group; None = that kind (the modes) stays"""
+        ng = getattr(self, "_nswgroups", 0)
+        a = [_f64(v) for v in (oil, water, gas, liquid, resv)] + [_i32(mode)]
+        if any(v is not None and v.size != ng for v in a):
+            raise ValueError("set_std_wells_group_targets: array lengths do not fit the %d groups set" % ng)
+        self._check(lib().opmhip_set_std_wells_group_targets(self._h, *[_ptr(v) for v in a]))
+
+    def std_wells_groups(self):
+        """opmhip_get_std_wells_groups: dict(mode, rates (groups, 3), voidage, reduction (groups, 3), guide_sum per group as the last group
+        data left them, nupcol_rates (wells, 3))"""
+        ng, n = getattr(self, "_nswgroups", 0), getattr(self, "_nsw", 0)
+        out = dict(mode=np.zeros(ng, np.int32), rates=np.zeros((ng, 3)), voidage=np.zeros(ng), reduction=np.zeros((ng, 3)), guide_sum=np.zeros(ng),
+                   nupcol_rates=np.zeros((n, 3)))
+        self._check(lib().opmhip_get_std_wells_groups(self._h, *[_ptr(out[k]) for k in ("mode", "rates", "voidage", "reduction", "guide_sum", "nupcol_rates")]))
         return out
 
     def set_std_wells_vaporised_oil(self, on=True):
@@ -1195,8 +1261,8 @@ class HipModel(HipSolver):
         self._check(lib().opmhip_std_wells_update(self._h, float(relax)))
 
     def get_std_wells(self):
-        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp / 2 thp / 3 - 7 orat, wrat, grat, lrat, resv,
-        r_w (wells, 4))"""
+        """the one read-back of a Newton iteration: (x (wells, 4), control (wells) 0 rate / 1 bhp / 2 thp / 3 - 7 orat, wrat, grat, lrat, resv /
+        8 grup, r_w (wells, 4))"""
         n = getattr(self, "_nsw", 0)
         x, ctl, rw = np.zeros((n, 4)), np.zeros(n, np.int32), np.zeros((n, 4))
         self._check(lib().opmhip_get_std_wells(self._h, _ptr(x), _ptr(ctl), _ptr(rw)))

@@ -2046,6 +2046,24 @@ struct SwLim {
     const int* use;
     double* out;
 };
+// Group production control (opmhip_set_std_wells_groups; read by the GRP instantiations only).  ptr / idx: per group its producers, wells
+// ascending; of / avail: per well its group (-1: none), available for group control; guide: per well ORAT, WRAT, GRAT, LRAT, RESV; target:
+// per group the same five (+infinity: none); mode: per group 0.0 NONE, 1.0 .. 5.0; nupcol: per well the three NUPCOL rates; rec: per group
+// rates [3] | voidage | reduction [3] | guide_sum of the last group data (k_std_wells_groups), read frozen by everything else
+struct SwGrp {
+    int ng, nupcol_n;
+    const int *ptr, *idx, *of, *avail;
+    const double *guide, *target;
+    double *mode, *nupcol, *rec;
+};
+constexpr int GRP_REC = 8, GRP_VOID = 3, GRP_RED = 4, GRP_GSUM = 7;
+// TargetCalculator::calcModeRateFromRates (wells/TargetCalculator.cpp:53-90) for group mode 1 .. 5 on three values v (oil, water, gas); cf: the
+// well's calcCoeff
+__device__ __forceinline__ double grp_mode_rate(int mode, const double* v, const double* cf) {
+    if (mode <= 3) return v[mode - 1];
+    if (mode == 4) return v[EQ_OIL] + v[EQ_WATER];
+    return (cf[EQ_WATER] * v[EQ_WATER] + cf[EQ_OIL] * v[EQ_OIL]) + cf[EQ_GAS] * v[EQ_GAS];
+}
 // RateConverter::calcCoeff / calcInjCoeff / calcReservoirVoidageRates (wells/RateConverter.hpp:592-777) in the statement order of wells.py
 // calc_coeff / calc_inj_coeff / calc_reservoir_voidage_rates; components oil, water, gas; avg: pressure, rs, rv
 __device__ __forceinline__ void rc_calc_coeff(const Tables& T, int pr, const double* avg, double* coeff) {
@@ -2101,15 +2119,17 @@ __device__ __forceinline__ double rc_resv_current(const Tables& T, int pr, const
 }
 // At opmhip_std_wells_begin_iteration(0), behind k_resv_avg_final, one lane per well: this time step's averages are kept beside the
 // coefficients (a later opmhip_reservoir_averages does not change them); the coefficients of every well with a RESV limit, at the PVT
-// region of its first perforated cell
+// region of its first perforated cell.  grp_resv (NULL without groups): per well, a producer of a group with a RESV target - it gets its
+// coefficients too; M.lim is NULL for a list with groups and without further limits
 __global__ __launch_bounds__(64) void k_std_wells_resv_coeff(int num, const int* __restrict__ wi, const int* __restrict__ vp, const int* __restrict__ cell,
-                                                             const int* __restrict__ pvtnum, Tables T, SwLim M, const double* __restrict__ avg) {
+                                                             const int* __restrict__ pvtnum, Tables T, SwLim M, const double* __restrict__ avg,
+                                                             const int* __restrict__ grp_resv) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= num) return;
     if (w == 0)
         for (int i = 0; i < 5; ++i) M.out[(size_t)4 * num + i] = avg[i];
     double coeff[3] = {0.0, 0.0, 0.0};
-    if (M.lim[5 * w + 4] < INFINITY && avg[5] > 0.0) {   // (a field without pore volume: zeros, nothing is divided)
+    if (((M.lim && M.lim[5 * w + 4] < INFINITY) || (grp_resv && grp_resv[w] != 0)) && avg[5] > 0.0) {   // (a field without pore volume: zeros, nothing is divided)
         const int pr = pvtnum ? pvtnum[cell[vp[w]]] : 0;
         if (wi[3 * w] != 0) rc_calc_coeff(T, pr, avg, coeff);
         else rc_calc_inj_coeff(T, pr, avg, coeff);
@@ -2131,8 +2151,11 @@ __global__ __launch_bounds__(64) void k_std_wells_resv_coeff(int num, const int*
 // row is that limit's (include/opmhip.h, opmhip_set_std_wells_limits); every other control gets today's bits.
 // VO: the list has the vaporised-oil switch (launched in place of the other instantiation): the wet-gas rate model of sw_perf_rates, two
 // more sums per lane - a perforation's dissolved gas and vaporised oil -, which the assembling form leaves per well in W.sol.
-template <bool SOLVE, bool CF, bool THP, bool LIM, bool VO>
-__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim M, int ncell, const double* __restrict__ iq, int first) {
+// GRP: the list has groups (launched in place of the other instantiation, for all its wells): under control 8 the control row is the
+// group mode's with target_rate = max(0, (target - mode(reduction)) (g_w / guide_sum)) in the limit's place, the BHP row for a group of mode
+// NONE (WellInterfaceEval.cpp:178-266); the group record is read as the last k_std_wells_groups left it.  Every other control gets today's bits.
+template <bool SOLVE, bool CF, bool THP, bool LIM, bool VO, bool GRP>
+__global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim M, SwGrp G, int ncell, const double* __restrict__ iq, int first) {
     constexpr int NS = (CF ? 15 : 6) + (VO ? 2 : 0), SOL = CF ? 15 : 6;   // SOL: where the two split values sit
     __shared__ double sums[64 * NS];
     __shared__ double xs[4];
@@ -2231,6 +2254,23 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim 
                 r[3] = xs[3] - fromThp;
                 D[12 + EQ_OIL] = 0.0 - V[7]; D[12 + EQ_WATER] = 0.0 - V[6]; D[12 + EQ_GAS] = 0.0 - V[8];
                 D[15] = 1.0;
+            }
+            else if (GRP && W.control[w] == 8.0) {
+                const int g = G.of[w], mode = (int)G.mode[g];
+                if (mode == 0) { r[3] = xs[3] - W.wd[2 * w + 1]; D[15] = 1.0; }
+                else {
+                    const double* rec = G.rec + (size_t)GRP_REC * g;
+                    const double* cf = M.out + (size_t)3 * w;
+                    const double gsum = rec[GRP_GSUM];
+                    const double frac = gsum > 1e-12 ? G.guide[5 * w + mode - 1] / gsum : 0.0;
+                    const double t = (G.target[5 * g + mode - 1] - grp_mode_rate(mode, rec + GRP_RED, cf)) * frac;
+                    const double targetRate = t > 0.0 ? t : 0.0;
+                    r[3] = grp_mode_rate(mode, xs, cf) + targetRate;
+                    if (mode <= 3) D[12 + mode - 1] = 1.0;
+                    else if (mode == 4) { D[12 + EQ_OIL] = 1.0; D[12 + EQ_WATER] = 1.0; }
+                    else
+                        for (int j = 0; j < 3; ++j) D[12 + j] = cf[j];
+                }
             }
             else if (LIM && W.control[w] >= 3.0) {
                 const int k = (int)W.control[w] - 3;
@@ -2420,10 +2460,14 @@ __global__ __launch_bounds__(64) void k_std_wells_wellbore(SwArrays W, WbArrays 
 // (updateWellStateWithTarget's THP case, WellInterface_impl.hpp:659-667, 882-890).  A well without a limit takes today's two branches.
 // LIM (the list has further rate limits): producers BHP, ORAT, WRAT, GRAT, LRAT, RESV, THP; injectors BHP, RATE, RESV, THP; the list's own
 // target at its component's place; RESV's current rate from rc_resv_current at the rates at hand.  A switch to a rate-type mode leaves x.
-template <bool THP, bool LIM>
+// GRP (the list has groups): the well's group check comes first (WellInterfaceFluidSystem.cpp:363-432, WellGroupHelpers.cpp:1055-1180) - a
+// producer not under GRUP, available, in a group whose mode is not NONE, whose current = -mode(x) exceeds target_rate = max(1e-12, ((target -
+// mode(reduction)) + current) g_w / (guide_sum + g_w)) goes under control 8 with its rates scaled by target_rate / current, and is not looked at
+// individually.  It reads the group record frozen (k_std_wells_groups ran in front), so the lanes are independent, as the reference's loop is.
+template <bool THP, bool LIM, bool GRP>
 __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* __restrict__ wi, const double* __restrict__ wd, double* __restrict__ xs,
                                                            double* __restrict__ controls, SwThp H, SwLim M, Tables T, const int* __restrict__ vp,
-                                                           const int* __restrict__ cell, const int* __restrict__ pvtnum) {
+                                                           const int* __restrict__ cell, const int* __restrict__ pvtnum, SwGrp G) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= num) return;
     const bool producer = wi[3 * w] != 0;
@@ -2431,6 +2475,28 @@ __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* _
     const double target = wd[2 * w], limit = wd[2 * w + 1];
     double* x = xs + (size_t)4 * w;
     double* control = controls + w;
+    if (GRP) {
+        const int g = G.of[w];
+        if (producer && *control != 8.0 && G.avail[w] != 0 && g >= 0 && G.mode[g] != 0.0) {
+            const int mode = (int)G.mode[g];
+            const double* rec = G.rec + (size_t)GRP_REC * g;
+            const double* cf = M.out + (size_t)3 * w;
+            const double cur = -grp_mode_rate(mode, x, cf);
+            const double gw = G.guide[5 * w + mode - 1];
+            const double gsum = rec[GRP_GSUM] + gw;
+            const double frac = gsum > 1e-12 ? gw / gsum : 0.0;
+            double t = G.target[5 * g + mode - 1] - grp_mode_rate(mode, rec + GRP_RED, cf);
+            t = t + cur;
+            t = t * frac;
+            const double targetRate = t > 1e-12 ? t : 1e-12;
+            if (cur > targetRate) {
+                *control = 8.0;
+                const double scale = cur > 1e-12 ? targetRate / cur : 1.0;
+                for (int i = 0; i < 3; ++i) x[i] = x[i] * scale;
+                return;
+            }
+        }
+    }
     const bool limited = THP && H.table[w] >= 0;
     double current = 0.0;
     if (THP) {
@@ -2481,6 +2547,69 @@ __global__ __launch_bounds__(64) void k_std_wells_controls(int num, const int* _
         x[3] = V[0] - H.out[(size_t)num + w];
     }
 }
+// Group data and the groups' check, one lane per group, walking the group's producers in list order: every sum is sequential from 0, so it
+// equals wells.py StandardWells._group_sums / _group_data / _group_check to the bit (no atomics).  CHECK (in front of the controls kernel,
+// while iteration <= nupcol; BlackoilWellModelGeneric.cpp:537-650, 888-943): ORAT, WRAT, GRAT, LRAT, RESV, the first target that is < current
+// and is not the mode in force wins; on a switch the rates of the group's wells under GRUP are multiplied by target / current when current >
+// 1e-12 (WellGroupHelpers.cpp:429-).  Then, always, the data (BlackoilWellModelGeneric.cpp:1494-1539, WellGroupHelpers.cpp:300-427): the
+// NUPCOL copy while iteration < nupcol, the reduction from the NUPCOL rates of the producers not under GRUP, the mode's guide-rate sum of those
+// under GRUP, the present rates' sums and - groups with a RESV target - the voidage sum, into the group's record.
+template <bool CHECK>
+__global__ __launch_bounds__(64) void k_std_wells_groups(SwGrp G, int num, int iteration, double* __restrict__ xs, const double* __restrict__ controls, SwLim M,
+                                                         Tables T, const int* __restrict__ vp, const int* __restrict__ cell, const int* __restrict__ pvtnum) {
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= G.ng) return;
+    const int kb = G.ptr[g], ke = G.ptr[g + 1];
+    const double* target = G.target + (size_t)5 * g;
+    const bool hasResv = target[4] < INFINITY;
+    const double* avg = M.out + (size_t)4 * num;
+    if (CHECK && iteration <= G.nupcol_n) {
+        double s[3] = {0.0, 0.0, 0.0}, voidage = 0.0;
+        for (int k = kb; k < ke; ++k) {
+            const int w = G.idx[k];
+            const double* x = xs + (size_t)4 * w;
+            for (int c = 0; c < 3; ++c) s[c] -= x[c];
+            if (hasResv) voidage += rc_resv_current(T, pvtnum ? pvtnum[cell[vp[w]]] : 0, avg, x, true);
+        }
+        const int inForce = (int)G.mode[g];
+        for (int mode = 1; mode <= 5; ++mode) {
+            const double tg = target[mode - 1];
+            if (!(tg < INFINITY) || inForce == mode) continue;
+            const double cur = mode <= 3 ? s[mode - 1] : (mode == 4 ? s[EQ_OIL] + s[EQ_WATER] : voidage);
+            if (tg < cur) {
+                G.mode[g] = (double)mode;
+                if (cur > 1e-12) {
+                    const double scale = tg / cur;
+                    for (int k = kb; k < ke; ++k) {
+                        const int w = G.idx[k];
+                        if (controls[w] == 8.0)
+                            for (int c = 0; c < 3; ++c) xs[(size_t)4 * w + c] = xs[(size_t)4 * w + c] * scale;
+                    }
+                }
+                break;
+            }
+        }
+    }
+    const int mode = (int)G.mode[g];
+    double s[3] = {0.0, 0.0, 0.0}, red[3] = {0.0, 0.0, 0.0}, voidage = 0.0, gsum = 0.0;
+    for (int k = kb; k < ke; ++k) {
+        const int w = G.idx[k];
+        const double* x = xs + (size_t)4 * w;
+        double* nup = G.nupcol + (size_t)3 * w;
+        if (iteration < G.nupcol_n)
+            for (int c = 0; c < 3; ++c) nup[c] = x[c];
+        if (controls[w] == 8.0) {
+            if (mode != 0) gsum += G.guide[5 * w + mode - 1];
+        } else
+            for (int c = 0; c < 3; ++c) red[c] -= nup[c];
+        for (int c = 0; c < 3; ++c) s[c] -= x[c];
+        if (hasResv) voidage += rc_resv_current(T, pvtnum ? pvtnum[cell[vp[w]]] : 0, avg, x, true);
+    }
+    double* rec = G.rec + (size_t)GRP_REC * g;
+    for (int c = 0; c < 3; ++c) { rec[c] = s[c]; rec[GRP_RED + c] = red[c]; }
+    rec[GRP_VOID] = voidage;
+    rec[GRP_GSUM] = gsum;
+}
 // In front of k_assemble (and of k_aquifer_apply), one lane per DISTINCT perforated cell: the caller's source and dsource rows are kept in
 // `save`, the rates of the cell's perforations are added in perforation order (computeTotalRatesForDof)
 __global__ __launch_bounds__(64) void k_std_wells_source(int nd, const int* __restrict__ cpos, const int* __restrict__ cptr, const int* __restrict__ cperf,
@@ -2524,21 +2653,27 @@ static SwThp std_wells_thp(opmhip_ctx* c) {
 }
 static SwLim std_wells_lim(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
-    return SwLim{S.d_lim, S.d_lim_use, S.d_lim_out};
+    return SwLim{S.d_lim, S.d_lim_use, S.limits ? S.d_lim_out : S.d_grp_out};   // (a list with groups and without limits keeps the coefficients and the averages in its own array)
+}
+static SwGrp std_wells_grp(opmhip_ctx* c) {
+    const StdWellsDev& S = c->wells.sw;
+    return SwGrp{S.grp_num, S.grp_nupcol, S.d_grp_ptr, S.d_grp_idx, S.d_grp_of, S.d_grp_avail, S.d_grp_guide, S.d_grp_target,
+                 S.d_grp_state, S.d_grp_state ? S.d_grp_state + S.grp_num : nullptr, S.d_grp_rec};
 }
 // the instantiation of k_std_wells_eq a list runs: one per combination of crossflow, THP limits, further rate limits and the vaporised-oil
 // switch (a list without the feature runs the code it ran before; the number of launches is the same)
-template <bool SOLVE, bool VO>
-static auto std_wells_eq_kernel_of(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, VO>) {
+template <bool SOLVE, bool VO, bool GRP>
+static auto std_wells_eq_kernel_of(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, VO, GRP>) {
     if (S.limits)
-        return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, true, VO> : k_std_wells_eq<SOLVE, false, true, true, VO>)
-                     : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, true, VO> : k_std_wells_eq<SOLVE, false, false, true, VO>);
-    return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, false, VO> : k_std_wells_eq<SOLVE, false, true, false, VO>)
-                 : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, false, VO> : k_std_wells_eq<SOLVE, false, false, false, VO>);
+        return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, true, VO, GRP> : k_std_wells_eq<SOLVE, false, true, true, VO, GRP>)
+                     : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, true, VO, GRP> : k_std_wells_eq<SOLVE, false, false, true, VO, GRP>);
+    return S.thp ? (S.crossflow ? k_std_wells_eq<SOLVE, true, true, false, VO, GRP> : k_std_wells_eq<SOLVE, false, true, false, VO, GRP>)
+                 : (S.crossflow ? k_std_wells_eq<SOLVE, true, false, false, VO, GRP> : k_std_wells_eq<SOLVE, false, false, false, VO, GRP>);
 }
 template <bool SOLVE>
-static auto std_wells_eq_kernel(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, false>) {
-    return S.vaporised_oil ? std_wells_eq_kernel_of<SOLVE, true>(S) : std_wells_eq_kernel_of<SOLVE, false>(S);
+static auto std_wells_eq_kernel(const StdWellsDev& S) -> decltype(&k_std_wells_eq<SOLVE, false, false, false, false, false>) {
+    if (S.groups) return S.vaporised_oil ? std_wells_eq_kernel_of<SOLVE, true, true>(S) : std_wells_eq_kernel_of<SOLVE, false, true>(S);
+    return S.vaporised_oil ? std_wells_eq_kernel_of<SOLVE, true, false>(S) : std_wells_eq_kernel_of<SOLVE, false, false>(S);
 }
 static SwArrays std_wells_arrays(const WellsDev& W) {
     const StdWellsDev& S = W.sw;
@@ -2551,7 +2686,7 @@ void launch_std_wells_solve(opmhip_ctx* c, bool first) {
     // (a list with a crossflow well runs the CF instantiation in place of the other: the number of launches is the same)
     // (... and one with a THP limit the THP instantiation)
     const StdWellsDev& S = c->wells.sw;
-    hipLaunchKernelGGL(std_wells_eq_kernel<true>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), c->pat.Nloc,
+    hipLaunchKernelGGL(std_wells_eq_kernel<true>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), std_wells_grp(c), c->pat.Nloc,
                        c->asmb.d_iq, first ? 1 : 0);
     prof_end(c, ps);
 }
@@ -2566,16 +2701,25 @@ void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init) {
 void launch_std_wells_controls(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    const auto kernel = S.limits ? (S.thp ? k_std_wells_controls<true, true> : k_std_wells_controls<false, true>)
-                                 : (S.thp ? k_std_wells_controls<true, false> : k_std_wells_controls<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control(), std_wells_thp(c), std_wells_lim(c),
-                       tables_of(c), c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum);
+    const auto plain = S.limits ? (S.thp ? k_std_wells_controls<true, true, false> : k_std_wells_controls<false, true, false>)
+                                : (S.thp ? k_std_wells_controls<true, false, false> : k_std_wells_controls<false, false, false>);
+    const auto grouped = S.limits ? (S.thp ? k_std_wells_controls<true, true, true> : k_std_wells_controls<false, true, true>)
+                                  : (S.thp ? k_std_wells_controls<true, false, true> : k_std_wells_controls<false, false, true>);
+    hipLaunchKernelGGL(S.groups ? grouped : plain, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, S.d_wd, S.x(), S.control(), std_wells_thp(c),
+                       std_wells_lim(c), tables_of(c), c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum, std_wells_grp(c));
+    prof_end(c, ps);
+}
+void launch_std_wells_groups(opmhip_ctx* c, int iteration, bool check) {
+    const StdWellsDev& S = c->wells.sw;
+    const int ps = prof_begin(c, PROF_ASSEMBLE);
+    hipLaunchKernelGGL(check ? k_std_wells_groups<true> : k_std_wells_groups<false>, dim3((S.grp_num + 63) / 64), dim3(64), 0, c->stream, std_wells_grp(c), S.num,
+                       iteration, S.x(), S.control(), std_wells_lim(c), tables_of(c), c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum);
     prof_end(c, ps);
 }
 void launch_std_wells_assemble(opmhip_ctx* c) {
     const StdWellsDev& S = c->wells.sw;
     const int ps = prof_begin(c, PROF_ASSEMBLE);
-    hipLaunchKernelGGL(std_wells_eq_kernel<false>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), c->pat.Nloc,
+    hipLaunchKernelGGL(std_wells_eq_kernel<false>(S), dim3(S.num), dim3(64), 0, c->stream, std_wells_arrays(c->wells), std_wells_thp(c), std_wells_lim(c), std_wells_grp(c), c->pat.Nloc,
                        c->asmb.d_iq, 0);
     hipLaunchKernelGGL(k_std_wells_source, dim3((S.nd + 63) / 64), dim3(64), 0, c->stream, S.nd, S.d_cpos, S.d_cptr, S.d_cperf, S.d_pr, c->asmb.d_source,
                        c->asmb.d_dsource, S.d_save);
@@ -2834,7 +2978,7 @@ void launch_std_wells_resv(opmhip_ctx* c) {
     const int ps = prof_begin(c, PROF_ASSEMBLE);
     const double* avg = resv_avg_kernels(c);
     hipLaunchKernelGGL(k_std_wells_resv_coeff, dim3((S.num + 63) / 64), dim3(64), 0, c->stream, S.num, S.d_wi, c->wells.d_val_pointers, c->wells.d_Ccols, c->asmb.d_pvtnum,
-                       tables_of(c), std_wells_lim(c), avg);
+                       tables_of(c), std_wells_lim(c), avg, S.grp_resv ? S.d_grp_resv : nullptr);
     prof_end(c, ps);
 }
 void launch_reservoir_averages(opmhip_ctx* c) {

@@ -1150,6 +1150,15 @@ void std_wells_limits_release(opmhip_ctx* c) {   // the stream is idle
     S.h_lim.clear(); S.h_lim_use.clear();
     S.limits = S.resv = false;
 }
+void std_wells_groups_release(opmhip_ctx* c) {   // the stream is idle
+    StdWellsDev& S = c->wells.sw;
+    dev_free(c, &S.d_grp_ptr); dev_free(c, &S.d_grp_idx); dev_free(c, &S.d_grp_of); dev_free(c, &S.d_grp_avail); dev_free(c, &S.d_grp_resv);
+    dev_free(c, &S.d_grp_guide); dev_free(c, &S.d_grp_target); dev_free(c, &S.d_grp_state); dev_free(c, &S.d_grp_saved); dev_free(c, &S.d_grp_rec);
+    dev_free(c, &S.d_grp_out);
+    S.grp_h = StdWellsGroupsLists();
+    S.groups = S.grp_resv = false;
+    S.grp_num = S.grp_nupcol = 0;
+}
 void std_wells_matrix_add_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
     dev_free(c, &S.d_ma_target); dev_free(c, &S.d_ma_tptr); dev_free(c, &S.d_ma_contrib);
@@ -1160,6 +1169,7 @@ void std_wells_matrix_add_release(opmhip_ctx* c) {   // the stream is idle
 void std_wells_release(opmhip_ctx* c) {   // the stream is idle
     StdWellsDev& S = c->wells.sw;
     std_wells_limits_release(c);
+    std_wells_groups_release(c);
     std_wells_matrix_add_release(c);
     S.h_vp.clear(); S.h_pos.clear();
     dev_free(c, &S.d_wi); dev_free(c, &S.d_wd); dev_free(c, &S.d_tw); dev_free(c, &S.d_dz); dev_free(c, &S.d_head); dev_free(c, &S.d_pr);
@@ -1181,6 +1191,8 @@ void std_wells_release(opmhip_ctx* c) {   // the stream is idle
 int std_wells_save_state(opmhip_ctx* c) {
     StdWellsDev& S = c->wells.sw;
     if (S.num > 0) OPMHIP_HIP(c, hipMemcpyAsync(S.d_saved, S.d_pack, (size_t)SW_SAVED * S.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (S.groups)   // the groups' modes and the NUPCOL rates go with the controls
+        OPMHIP_HIP(c, hipMemcpyAsync(S.d_grp_saved, S.d_grp_state, ((size_t)S.grp_num + 3 * (size_t)S.num) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     if (S.wellbore) {
         OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbsaved, S.d_wbstate, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         S.wb_state_saved = S.wb_state_set;
@@ -1194,6 +1206,8 @@ int std_wells_restore_state(opmhip_ctx* c) {
         OPMHIP_HIP(c, hipMemcpyAsync(S.d_pack, S.d_saved, (size_t)SW_SAVED * S.num * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         S.assembled = false;
     }
+    if (S.groups)
+        OPMHIP_HIP(c, hipMemcpyAsync(S.d_grp_state, S.d_grp_saved, ((size_t)S.grp_num + 3 * (size_t)S.num) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     if (S.wellbore) {
         OPMHIP_HIP(c, hipMemcpyAsync(S.d_wbstate, S.d_wbsaved, (size_t)4 * S.nperf * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         S.wb_state_set = S.wb_state_saved;
@@ -1298,11 +1312,16 @@ int opmhip_std_wells_begin_iteration(opmhip_ctx* c, int iteration) {
                 launch_std_wells_wellbore(c, !S.initialised, !S.wb_state_set);
                 S.wb_state_set = true;
             }
-            if (S.resv) launch_std_wells_resv(c);   // RateConverter::defineState and the coefficients, from the state the time step starts with
+            if (S.resv || S.grp_resv) launch_std_wells_resv(c);   // RateConverter::defineState and the coefficients, from the state the time step starts with
+            if (S.groups) launch_std_wells_groups(c, 0, false);   // the group record the wells alone read, frozen through their solve
             launch_std_wells_solve(c, !S.initialised);
             S.initialised = true;
         }
-        launch_std_wells_controls(c);   // updateWellControls
+        // the groups' check, then group data in one launch.  The reference's group data in FRONT of the check is elided: the check reads the present
+        // rates only, and all that pass would leave - the NUPCOL copy under the same condition and the record - the data behind the check overwrites
+        if (S.groups) launch_std_wells_groups(c, iteration, true);
+        launch_std_wells_controls(c);   // updateWellControls: [every well's group check,] the individual checks
+        if (S.groups) launch_std_wells_groups(c, iteration, false);   // group data: what the assembly reads
         OPMHIP_HIP(c, hipGetLastError());
         S.assembled = false;
         return OPMHIP_SUCCESS;
@@ -1415,7 +1434,7 @@ int opmhip_get_std_wells(opmhip_ctx* c, double* x, int* control, double* res_wel
         if (rc) return rc;
         if (x) std::memcpy(x, &h[SW_X * nw], 4 * nw * sizeof(double));
         if (control)
-            for (size_t w = 0; w < nw; ++w) control[w] = (int)h[SW_CONTROL * nw + w];   // 0 rate, 1 bhp, 2 thp, 3 .. 7 orat, wrat, grat, lrat, resv
+            for (size_t w = 0; w < nw; ++w) control[w] = (int)h[SW_CONTROL * nw + w];   // 0 rate, 1 bhp, 2 thp, 3 .. 7 orat, wrat, grat, lrat, resv, 8 grup
         if (res_well) std::memcpy(res_well, &h[SW_RW * nw], 4 * nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
@@ -1428,6 +1447,19 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
         if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_state: no resident list (opmhip_set_std_wells)");
         const size_t nw = S.num;
         std::string msg;
+        // control 8 (grup) exists with groups in force, for an available producer in a group; the other checks then see that well under 1
+        std::vector<int> others;
+        const int* const handed_in = control;
+        if (control) {
+            if (int r = std_wells_groups_check_controls(nw, control, S.h_wi.data(), S.groups ? S.grp_h.of.data() : nullptr, S.groups ? S.grp_h.available.data() : nullptr, msg))
+                return fail(c, r, "%s", msg.c_str());
+            if (S.groups) {
+                others.assign(control, control + nw);
+                for (size_t w = 0; w < nw; ++w)
+                    if (others[w] == 8) others[w] = 1;
+                control = others.data();
+            }
+        }
         if (S.limits) {   // controls 3 .. 7 exist, for the wells that have that limit
             if (int r = std_wells_limits_check_controls(nw, control, S.thp ? S.h_thp_table.data() : nullptr, S.h_lim.data(), S.h_lim_use.data(), msg)) return fail(c, r, "%s", msg.c_str());
             if (int r = std_wells_check_state(nw, x, nullptr, rate_target, msg)) return fail(c, r, "%s", msg.c_str());
@@ -1441,7 +1473,7 @@ int opmhip_set_std_wells_state(opmhip_ctx* c, const double* x, const int* contro
         if (x) OPMHIP_HIP(c, hipMemcpy(S.x(), x, 4 * nw * sizeof(double), hipMemcpyHostToDevice));
         if (control) {
             std::vector<double> h(nw);
-            for (size_t w = 0; w < nw; ++w) h[w] = control[w];
+            for (size_t w = 0; w < nw; ++w) h[w] = handed_in[w];
             OPMHIP_HIP(c, hipMemcpy(S.control(), h.data(), nw * sizeof(double), hipMemcpyHostToDevice));
         }
         if (rate_target) {
@@ -1793,14 +1825,152 @@ int opmhip_get_std_wells_resv(opmhip_ctx* c, double* averages, double* coeff, do
         if (S.num == 0) return OPMHIP_SUCCESS;
         const size_t nw = S.num;
         std::vector<double> h(4 * nw + 5, 0.0);
-        if (S.limits) {
+        if (S.limits || S.groups) {   // (a list with groups and without limits keeps them in its own array)
             OPMHIP_HIP(c, hipSetDevice(c->device));
             OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-            OPMHIP_HIP(c, hipMemcpy(h.data(), S.d_lim_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+            OPMHIP_HIP(c, hipMemcpy(h.data(), S.limits ? S.d_lim_out : S.d_grp_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
         }
         if (averages) std::memcpy(averages, &h[4 * nw], 5 * sizeof(double));
         if (coeff) std::memcpy(coeff, &h[0], 3 * nw * sizeof(double));
         if (resv_current) std::memcpy(resv_current, &h[3 * nw], nw * sizeof(double));
+        return OPMHIP_SUCCESS;
+    });
+}
+
+// ---- group production control (include/opmhip.h: opmhip_set_std_wells_groups) ----
+}  // extern "C"
+namespace {
+// the controls in force, read back (the stream is idle)
+int std_wells_controls_now(opmhip_ctx* c, std::vector<int>& control) {
+    const StdWellsDev& S = c->wells.sw;
+    std::vector<double> hc(S.num);
+    OPMHIP_HIP(c, hipMemcpy(hc.data(), S.control(), hc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    control.resize(S.num);
+    for (int w = 0; w < S.num; ++w) control[w] = (int)hc[w];
+    return OPMHIP_SUCCESS;
+}
+// the targets, the modes and the RESV flags of H to the device arrays in force (the stream is idle)
+int std_wells_group_targets_upload(opmhip_ctx* c, const StdWellsGroupsLists& H) {
+    StdWellsDev& S = c->wells.sw;
+    if (H.any_resv && !c->asmb.d_resv)
+        if (int r = dev_alloc(c, &c->asmb.d_resv, (size_t)RESV_MAX_PARTS * 8 + RESV_OUT)) return r;
+    std::vector<double> mode(H.mode.begin(), H.mode.end());
+    OPMHIP_HIP(c, hipMemcpy(S.d_grp_target, H.target.data(), H.target.size() * sizeof(double), hipMemcpyHostToDevice));
+    OPMHIP_HIP(c, hipMemcpy(S.d_grp_state, mode.data(), mode.size() * sizeof(double), hipMemcpyHostToDevice));
+    OPMHIP_HIP(c, hipMemcpy(S.d_grp_resv, H.resv.data(), H.resv.size() * sizeof(int), hipMemcpyHostToDevice));
+    OPMHIP_HIP(c, hipDeviceSynchronize());
+    return OPMHIP_SUCCESS;
+}
+}  // namespace
+extern "C" {
+
+int opmhip_set_std_wells_groups(opmhip_ctx* c, const opmhip_std_wells_groups* groups) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        // (in front of the no-list check: a decomposed context can never hold a list, and the caller is told why)
+        if (c->comm.nranks > 1)
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_std_wells_groups: decomposed context (%d ranks) - refused as the resident list itself is (opmhip_set_std_wells)", c->comm.nranks);
+        if (S.num == 0) return fail(c, OPMHIP_NOT_READY, "set_std_wells_groups: no resident list (opmhip_set_std_wells)");
+        const size_t nw = S.num;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        std::vector<int> control;
+        if (int r = std_wells_controls_now(c, control)) return r;
+        StdWellsGroupsLists H;
+        std::string msg;   // everything is looked at before anything changes: a refused call leaves the previous values in force
+        if (int r = std_wells_groups(groups, nw, S.h_wi.data(), control.data(), H, msg)) return fail(c, r, "%s", msg.c_str());
+        StdWellsDev N;     // the new arrays, held apart until all of them exist
+        if (H.any) {
+            const size_t ng = H.num_groups;
+            std::vector<double> state(ng + 3 * nw, 0.0);
+            for (size_t g = 0; g < ng; ++g) state[g] = H.mode[g];
+            int r;
+            if ((r = dev_upload(c, &N.d_grp_ptr, H.ptr)) || (r = dev_upload(c, &N.d_grp_idx, H.idx)) || (r = dev_upload(c, &N.d_grp_of, H.of)) ||
+                (r = dev_upload(c, &N.d_grp_avail, H.available)) || (r = dev_upload(c, &N.d_grp_resv, H.resv)) || (r = dev_upload(c, &N.d_grp_guide, H.guide)) ||
+                (r = dev_upload(c, &N.d_grp_target, H.target)) || (r = dev_upload(c, &N.d_grp_state, state)) || (r = dev_upload(c, &N.d_grp_saved, state)) ||
+                (r = dev_upload(c, &N.d_grp_rec, std::vector<double>(8 * ng, 0.0))) || (r = dev_upload(c, &N.d_grp_out, std::vector<double>(4 * nw + 5, 0.0))) ||
+                (H.any_resv && !c->asmb.d_resv && (r = dev_alloc(c, &c->asmb.d_resv, (size_t)RESV_MAX_PARTS * 8 + RESV_OUT)))) {
+                dev_free(c, &N.d_grp_ptr); dev_free(c, &N.d_grp_idx); dev_free(c, &N.d_grp_of); dev_free(c, &N.d_grp_avail); dev_free(c, &N.d_grp_resv);
+                dev_free(c, &N.d_grp_guide); dev_free(c, &N.d_grp_target); dev_free(c, &N.d_grp_state); dev_free(c, &N.d_grp_saved); dev_free(c, &N.d_grp_rec);
+                dev_free(c, &N.d_grp_out);
+                return r;
+            }
+            OPMHIP_HIP(c, hipDeviceSynchronize());
+        }
+        std_wells_groups_release(c);
+        S.d_grp_ptr = N.d_grp_ptr; S.d_grp_idx = N.d_grp_idx; S.d_grp_of = N.d_grp_of; S.d_grp_avail = N.d_grp_avail; S.d_grp_resv = N.d_grp_resv;
+        S.d_grp_guide = N.d_grp_guide; S.d_grp_target = N.d_grp_target; S.d_grp_state = N.d_grp_state; S.d_grp_saved = N.d_grp_saved; S.d_grp_rec = N.d_grp_rec;
+        S.d_grp_out = N.d_grp_out;
+        S.groups = H.any; S.grp_resv = H.any_resv; S.grp_num = H.num_groups; S.grp_nupcol = H.nupcol;
+        S.grp_h = std::move(H);
+        S.assembled = false;   // the blocks of the last assembly are no longer the model's
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_guide_rates(opmhip_ctx* c, const double* guide_rate) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0 || !S.groups) return fail(c, OPMHIP_NOT_READY, "set_std_wells_guide_rates: no groups in force (opmhip_set_std_wells_groups)");
+        std::string msg;
+        if (int r = std_wells_groups_check_guide_rates(S.num, guide_rate, msg)) return fail(c, r, "%s", msg.c_str());
+        S.assembled = false;
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        S.grp_h.guide.assign(guide_rate, guide_rate + 5 * (size_t)S.num);
+        OPMHIP_HIP(c, hipMemcpy(S.d_grp_guide, guide_rate, 5 * (size_t)S.num * sizeof(double), hipMemcpyHostToDevice));
+        OPMHIP_HIP(c, hipDeviceSynchronize());
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_set_std_wells_group_targets(opmhip_ctx* c, const double* oil_target, const double* water_target, const double* gas_target, const double* liquid_target,
+                                       const double* resv_target, const int* mode) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        StdWellsDev& S = c->wells.sw;
+        if (S.num == 0 || !S.groups) return fail(c, OPMHIP_NOT_READY, "set_std_wells_group_targets: no groups in force (opmhip_set_std_wells_groups)");
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        // the modes in force are the device's: a group may have switched since they were handed in
+        std::vector<double> now(S.grp_num);
+        OPMHIP_HIP(c, hipMemcpy(now.data(), S.d_grp_state, now.size() * sizeof(double), hipMemcpyDeviceToHost));
+        StdWellsGroupsLists cur = S.grp_h, H;
+        for (int g = 0; g < S.grp_num; ++g) cur.mode[g] = (int)now[g];
+        const double* arr[5] = {oil_target, water_target, gas_target, liquid_target, resv_target};
+        std::string msg;
+        if (int r = std_wells_group_targets(cur, S.num, arr, mode, H, msg)) return fail(c, r, "%s", msg.c_str());
+        S.assembled = false;
+        if (int r = std_wells_group_targets_upload(c, H)) return r;
+        S.grp_resv = H.any_resv;
+        S.grp_h = std::move(H);
+        return OPMHIP_SUCCESS;
+    });
+}
+
+int opmhip_get_std_wells_groups(opmhip_ctx* c, int* mode, double* rates, double* voidage, double* reduction, double* guide_sum, double* nupcol_rates) {
+    if (!c) return OPMHIP_INVALID_ARGUMENT;
+    return guarded(c, [&]() -> int {
+        const StdWellsDev& S = c->wells.sw;
+        if (S.num == 0 || !S.groups) return OPMHIP_SUCCESS;
+        const size_t ng = S.grp_num, nw = S.num;
+        std::vector<double> st(ng + 3 * nw), rec(8 * ng);
+        OPMHIP_HIP(c, hipSetDevice(c->device));
+        OPMHIP_HIP(c, hipMemcpyAsync(st.data(), S.d_grp_state, st.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipMemcpyAsync(rec.data(), S.d_grp_rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+        for (size_t g = 0; g < ng; ++g) {
+            if (mode) mode[g] = (int)st[g];
+            if (voidage) voidage[g] = rec[8 * g + 3];
+            if (guide_sum) guide_sum[g] = rec[8 * g + 7];
+            for (int k = 0; k < 3; ++k) {
+                if (rates) rates[3 * g + k] = rec[8 * g + k];
+                if (reduction) reduction[3 * g + k] = rec[8 * g + 4 + k];
+            }
+        }
+        if (nupcol_rates) std::memcpy(nupcol_rates, &st[ng], 3 * nw * sizeof(double));
         return OPMHIP_SUCCESS;
     });
 }

@@ -15,6 +15,7 @@
 #include "../../include/opmhip.h"
 #include "cpr_setup.hpp"
 #include "vfp_tables.hpp"
+#include "source_lists.hpp"
 
 namespace opmhip {
 
@@ -236,6 +237,16 @@ struct StdWellsDev {
     int ma_targets = 0, ma_pairs = 0;
     int *d_ma_target = nullptr, *d_ma_tptr = nullptr, *d_ma_contrib = nullptr;
     std::vector<int> h_ma_target, h_ma_tptr, h_ma_contrib, h_vp, h_pos;
+    // group production control (opmhip_set_std_wells_groups): set only while groups are in force.  d_grp_ptr [ng + 1] / d_grp_idx: per group
+    // its producers, wells ascending; d_grp_of / d_grp_avail / d_grp_resv: per well its group (-1: none), available, a producer in a group
+    // with a RESV target; d_grp_guide: 5 per well; d_grp_target: 5 per group; d_grp_state: mode [ng] | NUPCOL rates [3 num], d_grp_saved its
+    // copy of the last opmhip_advance_time_level; d_grp_rec: per group rates [3], voidage, reduction [3], guide_sum of the last group data;
+    // d_grp_out: what d_lim_out holds (coeff | resv_current | averages), for a list without further limits; grp_h: the host's copy
+    bool groups = false, grp_resv = false;
+    int grp_num = 0, grp_nupcol = 0;
+    int *d_grp_ptr = nullptr, *d_grp_idx = nullptr, *d_grp_of = nullptr, *d_grp_avail = nullptr, *d_grp_resv = nullptr;
+    double *d_grp_guide = nullptr, *d_grp_target = nullptr, *d_grp_state = nullptr, *d_grp_saved = nullptr, *d_grp_rec = nullptr, *d_grp_out = nullptr;
+    StdWellsGroupsLists grp_h;
     double* x() const { return d_pack + (size_t)SW_X * num; }
     double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
     double* rw() const { return d_pack + (size_t)SW_RW * num; }
@@ -793,6 +804,7 @@ int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_asm.cpp: the 
 void launch_std_wells_solve(opmhip_ctx* c, bool first);   // heads, then the wells alone against the frozen reservoir (iteration 0)
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init);   // the heads from the well-bore density, in front of launch_std_wells_solve
 void launch_std_wells_controls(opmhip_ctx* c);            // updateWellControls
+void launch_std_wells_groups(opmhip_ctx* c, int iteration, bool check);   // lists with groups: [the groups' check,] the NUPCOL copy and the group data
 void launch_std_wells_resv(opmhip_ctx* c);                // the field's averages and the RESV wells' coefficients (iteration 0, lists with a RESV limit)
 void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
 void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)

@@ -141,6 +141,112 @@ int std_wells_limits_check_controls(size_t nw, const int* control, const int* th
     return OPMHIP_SUCCESS;
 }
 
+// ---- group production control ----
+namespace {
+const char* const group_target_name[5] = {"oil_target", "water_target", "gas_target", "liquid_target", "resv_target"};
+// the targets' and the modes' part of a groups record, into H (whose `of` and `ptr` / `idx` stand): what both setters look at
+int group_targets_into(const char* who, const double* const arr[5], const int* mode, size_t nw, StdWellsGroupsLists& H, std::string& msg) {
+    const double inf = std::numeric_limits<double>::infinity();
+    const int ng = H.num_groups;
+    for (int g = 0; g < ng; ++g)
+        for (int k = 0; k < 5; ++k) {
+            if (!arr[k]) continue;
+            const double v = arr[k][g];
+            if (!(v > 0.0)) return refuse(msg, "%s: %s[%d] = %g is not > 0 (+infinity: no such target)", who, group_target_name[k], g, v);
+            H.target[5 * (size_t)g + k] = v;
+        }
+    if (mode)
+        for (int g = 0; g < ng; ++g) {
+            if (mode[g] < 0 || mode[g] > 5) return refuse(msg, "%s: mode[%d] = %d (0 none, 1 orat, 2 wrat, 3 grat, 4 lrat, 5 resv)", who, g, mode[g]);
+            H.mode[g] = mode[g];
+        }
+    for (int g = 0; g < ng; ++g)
+        if (H.mode[g] != 0 && !(H.target[5 * (size_t)g + H.mode[g] - 1] < inf))
+            return refuse(msg, "%s: group %d is under mode %d (%s) and has no such target", who, g, H.mode[g], group_target_name[H.mode[g] - 1]);
+    H.resv.assign(nw, 0);
+    H.any_resv = false;
+    for (int g = 0; g < ng; ++g)
+        if (H.target[5 * (size_t)g + 4] < inf) {
+            H.any_resv = true;
+            for (int k = H.ptr[g]; k < H.ptr[g + 1]; ++k) H.resv[H.idx[k]] = 1;
+        }
+    return OPMHIP_SUCCESS;
+}
+}  // namespace
+
+int std_wells_groups_check_guide_rates(size_t nw, const double* guide_rate, std::string& msg) {
+    if (!guide_rate) return refuse(msg, "set_std_wells_guide_rates: null array");
+    for (size_t i = 0; i < 5 * nw; ++i)
+        if (!std::isfinite(guide_rate[i]) || guide_rate[i] < 0.0)
+            return refuse(msg, "set_std_wells_guide_rates: guide_rate[%zu] = %g (well %zu) is negative or not finite", i, guide_rate[i], i / 5);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_groups_check_controls(size_t nw, const int* control, const int* wi, const int* of, const int* available, std::string& msg) {
+    if (!control) return OPMHIP_SUCCESS;
+    for (size_t w = 0; w < nw; ++w) {
+        if (control[w] != 8) continue;
+        if (!of) return refuse(msg, "set_std_wells_state: control[%zu] = 8 (grup) without groups in force (opmhip_set_std_wells_groups)", w);
+        if (!wi[3 * w]) return refuse(msg, "set_std_wells_state: control[%zu] = 8 (grup) for an injector", w);
+        if (of[w] < 0) return refuse(msg, "set_std_wells_state: control[%zu] = 8 (grup) for a well without a group", w);
+        if (!available[w]) return refuse(msg, "set_std_wells_state: control[%zu] = 8 (grup) for a well that is not available for group control", w);
+    }
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_groups(const opmhip_std_wells_groups* G, size_t nw, const int* wi, const int* control, StdWellsGroupsLists& out, std::string& msg) {
+    StdWellsGroupsLists H;
+    if (G && G->num_groups < 0) return refuse(msg, "set_std_wells_groups: num_groups = %d", G->num_groups);
+    if (G && G->num_groups > 0) {
+        const int ng = G->num_groups;
+        if (!G->well_group || !G->guide_rate) return refuse(msg, "set_std_wells_groups: null array (well_group and guide_rate are needed)");
+        if (G->nupcol < 0) return refuse(msg, "set_std_wells_groups: nupcol = %d is not >= 0", G->nupcol);
+        H.num_groups = ng; H.nupcol = G->nupcol; H.any = true;
+        H.of.assign(G->well_group, G->well_group + nw);
+        H.available.assign(nw, 1);
+        for (size_t w = 0; w < nw; ++w) {
+            if (H.of[w] < -1 || H.of[w] >= ng) return refuse(msg, "set_std_wells_groups: well_group[%zu] = %d is outside [-1, %d)", w, H.of[w], ng);
+            if (G->available) {
+                if (G->available[w] != 0 && G->available[w] != 1) return refuse(msg, "set_std_wells_groups: available[%zu] = %d (0 / 1)", w, G->available[w]);
+                H.available[w] = G->available[w];
+            }
+        }
+        if (std_wells_groups_check_guide_rates(nw, G->guide_rate, msg)) {
+            msg.replace(0, msg.find(':'), "set_std_wells_groups");
+            return OPMHIP_INVALID_ARGUMENT;
+        }
+        H.guide.assign(G->guide_rate, G->guide_rate + 5 * nw);
+        // per group its producers, wells ascending
+        H.ptr.assign((size_t)ng + 1, 0);
+        for (size_t w = 0; w < nw; ++w)
+            if (H.of[w] >= 0 && wi[3 * w]) H.ptr[H.of[w] + 1]++;
+        for (int g = 0; g < ng; ++g) H.ptr[g + 1] += H.ptr[g];
+        H.idx.assign(H.ptr[ng], 0);
+        std::vector<int> fill(H.ptr.begin(), H.ptr.end() - 1);
+        for (size_t w = 0; w < nw; ++w)
+            if (H.of[w] >= 0 && wi[3 * w]) H.idx[fill[H.of[w]]++] = (int)w;
+        H.target.assign((size_t)5 * ng, std::numeric_limits<double>::infinity());
+        H.mode.assign(ng, 0);
+        const double* arr[5] = {G->oil_target, G->water_target, G->gas_target, G->liquid_target, G->resv_target};
+        if (int r = group_targets_into("set_std_wells_groups", arr, G->mode, nw, H, msg)) return r;
+        for (size_t w = 0; w < nw; ++w)
+            if (control[w] == 8 && (!wi[3 * w] || H.of[w] < 0 || !H.available[w]))
+                return refuse(msg, "set_std_wells_groups: well %zu is under control 8 (grup): it must stay an available producer in a group", w);
+    } else {
+        for (size_t w = 0; w < nw; ++w)
+            if (control[w] == 8) return refuse(msg, "set_std_wells_groups: well %zu is under control 8 (grup): the groups cannot be removed", w);
+    }
+    out = std::move(H);
+    return OPMHIP_SUCCESS;
+}
+
+int std_wells_group_targets(const StdWellsGroupsLists& cur, size_t nw, const double* const arr[5], const int* mode, StdWellsGroupsLists& out, std::string& msg) {
+    StdWellsGroupsLists H = cur;
+    if (int r = group_targets_into("set_std_wells_group_targets", arr, mode, nw, H, msg)) return r;
+    out = std::move(H);
+    return OPMHIP_SUCCESS;
+}
+
 int std_wells_check_crossflow(size_t nw, const int* allow, const int* wi, bool& any, std::string& msg) {
     bool some = false;
     if (allow)

@@ -40,6 +40,25 @@ int std_wells_limits(const opmhip_std_wells_limits* L, size_t nw, const int* wi,
 // the controls opmhip_set_std_wells_state hands in, with limits in force: 0 .. 7, 2 only with a THP limit (thp_table NULL: none has one), 3 .. 7
 // only with that limit, 0 only with use_list_target
 int std_wells_limits_check_controls(size_t nw, const int* control, const int* thp_table, const double* lim, const int* use, std::string& msg);
+// opmhip_set_std_wells_groups.  wi: the list's; control: the controls in force (nw).  ptr / idx: per group its PRODUCERS, wells ascending
+// (an injector may name a group and is ignored by it); of / available: per well; guide: 5 per well; target: 5 per group (+infinity: none);
+// mode: per group 0 .. 5; resv: per well, a producer in a group with a RESV target; any: groups are in force; any_resv: some group has a
+// RESV target
+struct StdWellsGroupsLists {
+    int num_groups = 0, nupcol = 0;
+    std::vector<int> ptr, idx, of, available, mode, resv;
+    std::vector<double> guide, target;
+    bool any = false, any_resv = false;
+};
+int std_wells_groups(const opmhip_std_wells_groups* G, size_t nw, const int* wi, const int* control, StdWellsGroupsLists& out, std::string& msg);
+// opmhip_set_std_wells_guide_rates: 5 per well, >= 0 and finite
+int std_wells_groups_check_guide_rates(size_t nw, const double* guide_rate, std::string& msg);
+// opmhip_set_std_wells_group_targets on the values in force (cur): a NULL array leaves that kind, a NULL mode the modes; out: the new
+// target [5 per group], mode, resv and any_resv (the other fields as cur's)
+int std_wells_group_targets(const StdWellsGroupsLists& cur, size_t nw, const double* const arr[5], const int* mode, StdWellsGroupsLists& out, std::string& msg);
+// the control values 8 opmhip_set_std_wells_state hands in (every other value is the other checks'): an available producer in a group;
+// of NULL: no groups in force
+int std_wells_groups_check_controls(size_t nw, const int* control, const int* wi, const int* of, const int* available, std::string& msg);
 // pref: per well the preferred phase the kernel reads (an injector's is never looked at: oil)
 int std_wells_head_model(const opmhip_std_wells_wellbore* wb, size_t nw, size_t np, const int* wi, std::vector<int>& pref, std::string& msg);
 // state_set: the perforation pressures exist already

@@ -199,7 +199,7 @@ SPE9_PRODUCERS_IJ = [(5, 1), (8, 2), (11, 3), (10, 4), (12, 5), (4, 6), (8, 7), 
 
 
 def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, producer_bhp_limit=1000.0 * PSIA, injector_bhp_limit=400e5,
-                      diameter=0.1524, liquid_rate_stb_day=None, resv_rate=None):
+                      diameter=0.1524, liquid_rate_stb_day=None, resv_rate=None, groups=None):
     """BASELINE.json configs[2] with wells that are wells (wells.StandardWells) on a 24 x 25 x 15 cartesian_case: SPE9's water injector at
     (24, 25), completed in layers 11-15, on a surface-rate target with an upper BHP limit, and its 25 oil producers, completed in layers
     2-4, on an oil-rate target (1500 stb/day; the SPE9 schedule cuts it to 100 stb/day for a while) with a lower BHP limit of 1000 psia;
@@ -207,7 +207,10 @@ def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, 
     so that on the log-normal field some producers cannot hold their target and fall to the BHP limit.  A stand-in like the grid itself:
     the SPE9 deck is not in the reference tree, its fluid and its dipping layers are not reproduced.
     liquid_rate_stb_day / resv_rate (reservoir m^3/s): every producer also gets an LRAT / a RESV limit (wells.Well(limits=)); a RESV limit
-    needs the fluid's property functions: build wells.StandardWells(.wells, depth, props=, volume=) from the list returned."""
+    needs the fluid's property functions: build wells.StandardWells(.wells, depth, props=, volume=) from the list returned.
+    groups (default None: the list as it was): dict(count=, kind="lrat" | "orat", target_stb_day=[, guide_rate=1.0, nupcol=]) - the 25
+    producers go into `count` production groups, producer n into group n % count (a group's wells are interleaved in list order), every
+    group with that one target (per group where target_stb_day is a sequence) and mode "none"; the injector stays under FIELD."""
     from . import wells as _wells
     nx, ny, nz = case["nx"], case["ny"], case["nz"]
     if (nx, ny) != (24, 25) or nz < 15:
@@ -228,6 +231,15 @@ def spe9_shaped_wells(case, oil_rate_stb_day=1500.0, water_rate_stb_day=5000.0, 
             limits["resv"] = resv_rate
         out.append(_wells.Well("PRODU%d" % (n + 2), cells, tw, case["depth"][cells[0]], True, ("rate", _wells.OIL, oil_rate_stb_day * STB_PER_DAY), producer_bhp_limit,
                                **({"limits": limits} if limits else {})))
+    if groups is not None:
+        count, kind = int(groups["count"]), groups.get("kind", "lrat")
+        if count < 1 or kind not in ("lrat", "orat"):
+            raise ValueError("spe9_shaped_wells: groups needs count >= 1 and kind 'lrat' or 'orat'")
+        targets = np.broadcast_to(np.asarray(groups["target_stb_day"], float), (count,))
+        for n, w in enumerate(out[1:]):
+            w.group, w.guide_rate = n % count, np.full(5, float(groups.get("guide_rate", 1.0)))
+        glist = [_wells.Group("G%d" % (g + 1), {kind: targets[g] * STB_PER_DAY}) for g in range(count)]
+        return _wells.StandardWells(out, case["depth"], groups=glist, nupcol=groups.get("nupcol", _wells.NUPCOL_DEFAULT))
     return _wells.StandardWells(out, case["depth"])
 
 

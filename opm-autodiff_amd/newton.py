@@ -138,7 +138,10 @@ class BlackoilModelHip:
             if iteration == 0:
                 self.wells.calculate_explicit_quantities(iq)  # the completions' pressure differences, constant through the time step (:824-827)
                 self.wells.solve_well_equations(iq)          # prepareTimeStep: the wells alone against the frozen reservoir
-            self.wells.update_well_controls()
+            if getattr(self.wells, "groups", None):          # group control: the reference's iterationIdx decides the NUPCOL copy and the groups' check
+                self.wells.update_well_controls(iteration)
+            else:
+                self.wells.update_well_controls()
             host_aq = self.aquifers is not None and not self.aquifers.on_device    # then the influx joins the wells' rates below
             if hasattr(self.m, "set_source_cells"):
                 wa = self.wells.assemble(iq)
@@ -161,7 +164,7 @@ class BlackoilModelHip:
         if wa is not None:
             conv = conv and self.wells.converged(wa["res_well"])   # getWellConvergence (flow/BlackoilModelEbos.hpp:906-912)
         if dev_wells:
-            self.wells.fetch()                                     # the one read-back: x, controls, r_w (the stream has just been drained)
+            self.wells.fetch()                                     # the one read-back: x, controls, r_w (the stream has just been drained); with groups a second, small one: their modes
             conv = conv and self.wells.converged()
         t1 = time.perf_counter()
         # The reference books assembly under assemble_time and the convergence check under update_time

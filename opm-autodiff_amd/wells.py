@@ -84,7 +84,7 @@ the BHP limit, through the VFPPROD (producers) / VFPINJ (injectors) tables of vf
       bhp + dp, alq) (wells/StandardWellGeneric.cpp:116-156, wells/StandardWellEval.cpp:546-583); a producer switches when its limit >
       current, an injector when its limit < current, and its bhp becomes V - dp at the rates at hand (updateWellStateWithTarget's THP case,
       wells/WellInterface_impl.hpp:659-667, 882-890).
-  Left out: groups, gas lift (alq is a constant), bhpwithflo and the robust BHP-THP intersection (computeBhpAtThpLimitProd), well potentials.
+  Left out: gas lift (alq is a constant), bhpwithflo and the robust BHP-THP intersection (computeBhpAtThpLimitProd), well potentials.
 
 Several rate limits per well (Well(limits={"orat": , "wrat": , "grat": , "lrat": , "resv": }); WCONPROD's ORAT, WRAT, GRAT, LRAT, RESV and
 WCONINJE's RESV): positive surface volume rates, "resv" a reservoir volume rate; a limit that is absent does not exist.  They stand beside
@@ -110,8 +110,38 @@ component.  The control tuples ("orat", v) ... ("resv", v) name the limit in for
       left out, as under control 0).  The reference's injector RESV and THP branches assign a local copy of the control and return true
       without changing the well state (:140-166); here the well switches.  props.probe takes the saturated curve where Rs >= RsSat(p)
       (probe_gas where Rv >= RvSat); the reference's converter evaluates the undersaturated function at the averages as they are.
-  Left out: groups / GRUP, CRAT, history-mode RESV (prediction_mode == false; a caller forms WCONHIST's target from the averages and hands it
+  Left out: CRAT, history-mode RESV (prediction_mode == false; a caller forms WCONHIST's target from the averages and hands it
       in as "resv"), FIP regions other than the whole field, salt and temperature in the converter.
+
+Group production control (StandardWells(groups=[Group(...)], nupcol=), Well(group=, guide_rate=, available_for_group_control=); GCONPROD
+with the exceed action RATE, WGRUPCON): a flat list of production groups, each a direct child of FIELD, every well in at most one.  A group
+has targets "orat", "wrat", "grat", "lrat" (surface m^3/s), "resv" (reservoir m^3/s) and a mode, "none" or one of them; a well has one guide
+rate per target mode (the converted values of opm-common's GuideRate::get stay with the caller).  A well that can hold its share is under
+the control ("grup",), code GRUP_CODE = 8.  UNVERIFIED against Flow's numbers: the reference tree holds no output of a deck with groups.
+  update_well_controls(iteration) runs BlackoilWellModel::updateWellControls (wells/BlackoilWellModel_impl.hpp:1239-1287): group data, the
+      groups' check, group data, every well's group check, group data, the individual check of the wells that did not just switch, group data.
+  group data (BlackoilWellModelGeneric.cpp:1494-1539, WellGroupHelpers.cpp:300-427): while iteration < nupcol the rates of the groups' producers
+      are copied to the NUPCOL rates; per group and component reduction = 0 - the NUPCOL rates of its producers not under GRUP, guide_sum = the
+      mode's guide rates of its producers under GRUP, rates = 0 - the present rates of its producers, voidage = their _resv_current (groups
+      with a RESV target); every sum in list order starting from 0.  The record stays as it is until the next group data.
+  the group's check (BlackoilWellModelGeneric.cpp:537-650, 888-943), only while iteration <= nupcol (the asymmetry with the copy's < is the
+      reference's): ORAT, WRAT, GRAT, LRAT, RESV in that order, the first target that is < current and is not the mode in force wins;
+      current from the present rates (LRAT: oil sum + water sum; RESV: the voidage sum); on a switch the rates of the group's wells under
+      GRUP are multiplied by target / current when current > 1e-12 (updateWellRatesFromGroupTargetScale, WellGroupHelpers.cpp:429-).
+  a well's group check (WellInterfaceFluidSystem.cpp:363-432, WellGroupHelpers.cpp:1055-1180) - a producer not under GRUP, available, in a group
+      whose mode is not "none": mode(v) is v[c] for ORAT / WRAT / GRAT, v_o + v_w for LRAT, (c_w v_w + c_o v_o) + c_g v_g with the well's
+      calc_coeff for RESV (TargetCalculator::calcModeRateFromRates, TargetCalculator.cpp:53-90); current = -mode(x);
+      fraction = g_w / (guide_sum + g_w), 0 where that sum is <= 1e-12; target_rate = max(1e-12, ((target - mode(reduction)) + current) fraction);
+      where current > target_rate the control becomes GRUP and the three rates are multiplied by target_rate / current (current > 1e-12).
+  the control row under GRUP (WellInterfaceEval.cpp:178-266): target_rate = max(0, (target - mode(reduction)) (g_w / guide_sum)), the fraction 0
+      where guide_sum <= 1e-12; the row is mode(x) + target_rate with the mode's derivatives - the rows of "orat" .. "resv" with target_rate in
+      the limit's place; a group of mode "none" gives the BHP row bhp - bhp_limit (:189-221).
+  A well leaves GRUP only through its individual limits: the existing rule.  Without groups every statement is the one it was.
+  KNOWN DIFFERENCE FROM FLOW: updateWellStateWithTarget's second rescaling on a switch to GRUP (wells/WellInterface_impl.hpp:902-921) is left out,
+      as it is for every other mode here.
+  Left out: nested groups and a control on FIELD (updateGroupHigherControls), group guide rates, group and well efficiency factors (all 1),
+      GCONINJE, GCONSALE / GCONSUMP, exceed actions other than RATE, CRAT / PRBL, injectors in a group's arithmetic (an injector may name a
+      group and is ignored by it), well potentials.
 """
 import numpy as np
 
@@ -200,10 +230,14 @@ class Well:
     limit - lower (producer) / upper (injector); control may then also be ("thp", thp_limit);
     limits: dict of further rate limits, any of "orat", "wrat", "grat", "lrat" (surface m^3/s) and "resv" (reservoir m^3/s), all > 0 - an
     injector's only "resv" - and control may be (kind, that limit); use_list_target=False: the rate target of `rate_control` is not a limit
-    of this well (the control must then be another one); rate_control: the well's own rate target where control is not the "rate" tuple"""
+    of this well (the control must then be another one); rate_control: the well's own rate target where control is not the "rate" tuple;
+    group: the index of the well's group in StandardWells(groups=) (None: directly under FIELD, no group control); guide_rate: one value for
+    all five target modes or five (ORAT, WRAT, GRAT, LRAT, RESV), >= 0 and finite; available_for_group_control: WGRUPCON item 2; control may be
+    ("grup",) for an available producer in a group (rate_control then names the well's own target)"""
 
     def __init__(self, name, cells, tw, ref_depth, producer, control, bhp_limit, inj_phase=None, preferred_phase="oil", allow_crossflow=False,
-                 thp_limit=None, vfp_table=None, alq=0.0, limits=None, use_list_target=True, rate_control=None):
+                 thp_limit=None, vfp_table=None, alq=0.0, limits=None, use_list_target=True, rate_control=None, group=None, guide_rate=0.0,
+                 available_for_group_control=True):
         self.name, self.cells, self.tw = name, np.asarray(cells, np.int32), np.asarray(tw, float)
         self.ref_depth, self.producer, self.inj_phase = float(ref_depth), bool(producer), inj_phase
         self.preferred_phase = preferred_phase     # a producer's (WELSPECS item 6): the well bore's content where nothing flows (head_model="wellbore")
@@ -219,6 +253,42 @@ class Well:
         self.vfp_table, self.alq = None if vfp_table is None else int(vfp_table), float(alq)
         if control[0] == "thp" and (self.thp_limit is None or float(control[1]) != self.thp_limit):
             raise ValueError("well %s: THP control needs thp_limit, and the limit as its target" % name)
+        self.group = None if group is None else int(group)
+        self.guide_rate = _check_guide_rate(name, guide_rate)
+        self.available_for_group_control = bool(available_for_group_control)
+        if control[0] == "grup" and (not self.producer or self.group is None or not self.available_for_group_control):
+            raise ValueError("well %s: GRUP control is for an available producer in a group" % name)
+
+
+class Group:
+    """a production group directly under FIELD (GCONPROD, exceed action RATE): name; targets: dict of any of "orat", "wrat", "grat", "lrat"
+    (surface m^3/s) and "resv" (reservoir m^3/s), all > 0, None / +infinity: none; mode: the production control mode the group starts
+    under, "none" or one of its targets"""
+
+    def __init__(self, name, targets=None, mode="none"):
+        self.name = name
+        self.targets = {}
+        for kind, v in (targets or {}).items():
+            if kind not in LIMIT_KINDS:
+                raise ValueError("group %s: unknown target %r (one of %s)" % (name, kind, ", ".join(LIMIT_KINDS)))
+            if v is None or v == np.inf:
+                continue
+            v = float(v)
+            if not v > 0.0:
+                raise ValueError("group %s: the %s target %r is not > 0" % (name, kind, v))
+            self.targets[kind] = v
+        if mode not in GROUP_MODES or (mode != "none" and mode not in self.targets):
+            raise ValueError("group %s: mode %r is not 'none' or one of the group's targets" % (name, mode))
+        self.mode = mode
+
+
+def _check_guide_rate(name, guide_rate):
+    g = np.asarray(guide_rate, float).reshape(-1)
+    if g.size == 1:
+        g = np.repeat(g, 5)
+    if g.size != 5 or not np.all(np.isfinite(g)) or np.any(g < 0.0):
+        raise ValueError("well %s: guide_rate is one value or five (ORAT, WRAT, GRAT, LRAT, RESV), >= 0 and finite: %r" % (name, guide_rate))
+    return g.copy()
 
 
 class CellRecords:
@@ -248,6 +318,14 @@ CONTROL_CODE = {"rate": 0, "bhp": 1, "thp": 2, "orat": 3, "wrat": 4, "grat": 5, 
 LIMIT_KINDS = ("orat", "wrat", "grat", "lrat", "resv")       # in the order update_well_controls looks at them
 LIMIT_OF_COMPONENT = {OIL: "orat", WATER: "wrat", GAS: "grat"}
 COMPONENT_OF_LIMIT = {"orat": OIL, "wrat": WATER, "grat": GAS}
+GRUP_CODE = 8                                                # the control ("grup",): exists only with groups in force, so it is not in CONTROL_CODE
+GROUP_MODES = ("none",) + LIMIT_KINDS                        # a group's production control mode, codes 0 .. 5 (opmhip_std_wells_groups.mode)
+NUPCOL_DEFAULT = 3                                           # the deck keyword's default
+
+
+def control_code(control):
+    """the code of a control tuple: CONTROL_CODE's, GRUP_CODE for ("grup",)"""
+    return GRUP_CODE if control[0] == "grup" else CONTROL_CODE[control[0]]
 
 
 def reservoir_averages(iq, volume):
@@ -387,6 +465,40 @@ def _thp_tables(wells, tables):
     return out
 
 
+def _group_lists(obj, groups, nupcol):
+    """onto obj (StandardWells / DeviceStandardWells, with .wells): groups, nupcol, group_of_well (-1: under FIELD), guide (wells, 5),
+    available, group_wells (per group its PRODUCERS, ascending: an injector may name a group and is ignored by it), group_target (groups, 5;
+    +infinity: none), group_mode (codes of GROUP_MODES), group_resv (per well: a producer in a group with a RESV target), nupcol_rates and
+    the group record of the last group data; ValueError for what opmhip_set_std_wells_groups refuses"""
+    obj.groups = list(groups or [])
+    ng, nw = len(obj.groups), len(obj.wells)
+    obj.nupcol = int(nupcol)
+    if obj.nupcol < 0:
+        raise ValueError("nupcol = %d is not >= 0" % obj.nupcol)
+    obj.group_of_well = np.full(nw, -1, np.int32)
+    obj.guide = np.zeros((nw, 5))
+    obj.available = np.ones(nw, np.int32)
+    for k, w in enumerate(obj.wells):
+        g = getattr(w, "group", None)
+        if g is not None:
+            if not 0 <= g < ng:
+                raise ValueError("well %s: group %d is outside [0, %d)" % (w.name, g, ng))
+            obj.group_of_well[k] = g
+        obj.guide[k] = _check_guide_rate(w.name, getattr(w, "guide_rate", 0.0))
+        obj.available[k] = int(bool(getattr(w, "available_for_group_control", True)))
+        if w.control[0] == "grup" and (not w.producer or g is None or not obj.available[k]):
+            raise ValueError("well %s: GRUP control is for an available producer in a group" % w.name)
+    obj.group_wells = [[k for k in range(nw) if obj.group_of_well[k] == g and obj.wells[k].producer] for g in range(ng)]
+    obj.group_target = np.array([[G.targets.get(kind, np.inf) for kind in LIMIT_KINDS] for G in obj.groups], float).reshape(ng, 5)
+    obj.group_mode = [GROUP_MODES.index(G.mode) for G in obj.groups]
+    obj.group_resv = np.zeros(nw, bool)
+    for g in range(ng):
+        if obj.group_target[g, 4] < np.inf:
+            obj.group_resv[obj.group_wells[g]] = True
+    obj.nupcol_rates = np.zeros((nw, 3))
+    obj.group_record = dict(rates=np.zeros((ng, 3)), voidage=np.zeros(ng), reduction=np.zeros((ng, 3)), guide_sum=np.zeros(ng))
+
+
 class StandardWells:
     """All wells at once: every step below is one pass of array arithmetic over the perforations (nperf x 5: value, d/dSw, d/dp, d/dX of the
     perforated cell, d/dbhp), per-well sums in the order of the perforations.
@@ -397,8 +509,11 @@ class StandardWells:
     arithmetic in both.  The stated form is what the device-resident wells (opmhip_set_std_wells, DeviceStandardWells) compute, bit for
     bit; a singular D raises SingularWellEquations there."""
 
-    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None, volume=None, vaporised_oil=False):
-        """vaporised_oil: the wet-gas rate model (the module's text); the records handed in must then have 19 fields (ValueError otherwise).
+    def __init__(self, wells, cell_depth, arithmetic="numpy", head_model="cell_oil", props=None, pvtnum=None, vfp=None, volume=None, vaporised_oil=False,
+                 groups=None, nupcol=NUPCOL_DEFAULT):
+        """groups: the list of Group objects the wells' `group` indices name (the module's text; None or empty: no group control, every
+        statement as it was); nupcol: the deck's NUPCOL, >= 0.
+        vaporised_oil: the wet-gas rate model (the module's text); the records handed in must then have 19 fields (ValueError otherwise).
         volume: the cells' volumes, for the reservoir averages of a RESV limit where the model has no reservoir_averages() of its own
         (a RESV limit also needs props).  head_model="wellbore" needs props: the fluid's property functions behind probe(p, rs, pvt_region=) and probe_gas(p, rv,
         pvt_region=) - capi.HipFluid(fluid), the device's, or the CPU oracle's in tests, as equil.py takes them - with the deck-level
@@ -422,6 +537,8 @@ class StandardWells:
         self.bhp_from_thp = np.zeros(self.nw)      # ... V - dp of the last assemble()
         self._from_thp = np.zeros(self.nw)
         self.has_resv = any("resv" in getattr(w, "limits", {}) for w in self.wells)
+        _group_lists(self, groups, nupcol)
+        self.has_resv = self.has_resv or bool(self.group_resv.any())     # a group's RESV target needs the averages and the coefficients too
         self.volume = None if volume is None else np.asarray(volume, float)
         self.pvt_of_well = np.array([0 if pvtnum is None else int(np.asarray(pvtnum)[w.cells[0]]) for w in self.wells], int)
         self._model_averages = None                # what records() / set_reservoir_averages last took
@@ -497,8 +614,10 @@ class StandardWells:
                 raise ValueError("a RESV limit needs props (probe / probe_gas) and the reservoir averages: records(model) or set_reservoir_averages")
             self.resv_averages = self._model_averages.copy()
             for k, w in enumerate(self.wells):
-                if "resv" in w.limits:
+                if "resv" in w.limits or self.group_resv[k]:
                     self.resv_coeff[k] = (calc_coeff if w.producer else calc_inj_coeff)(self.props, self.resv_averages, self.pvt_of_well[k])
+        if self.groups:                              # the group record the wells-alone solve reads: frozen through it, as the reference's group state is
+            self._group_data(0)
 
     def _resv_current(self, k):
         """the voidage rate of well k at its present rates: the sum of calc_reservoir_voidage_rates, positive for what a producer takes out /
@@ -824,6 +943,24 @@ class StandardWells:
                 g[k, OIL], g[k, WATER], g[k, GAS], g[k, 3] = 0.0 - V[7], 0.0 - V[6], 0.0 - V[8], 1.0
             elif w.control[0] == "bhp":
                 r[k], g[k, 3] = x[3] - w.control[1], 1.0
+            elif w.control[0] == "grup":
+                gi = self.group_of_well[k]
+                mode = self.group_mode[gi]
+                if mode == 0:                      # the group has no target in force: the BHP row
+                    r[k], g[k, 3] = x[3] - w.bhp_limit, 1.0
+                else:
+                    rec = self.group_record
+                    gsum = float(rec["guide_sum"][gi])
+                    frac = float(self.guide[k, mode - 1]) / gsum if gsum > 1e-12 else 0.0
+                    t = (float(self.group_target[gi, mode - 1]) - self._mode_rate(k, mode, rec["reduction"][gi])) * frac
+                    target_rate = t if t > 0.0 else 0.0
+                    r[k] = self._mode_rate(k, mode, x) + target_rate
+                    if mode <= 3:
+                        g[k, mode - 1] = 1.0
+                    elif mode == 4:
+                        g[k, OIL], g[k, WATER] = 1.0, 1.0
+                    else:
+                        g[k, :3] = self.resv_coeff[k]
             elif w.control[0] in COMPONENT_OF_LIMIT:
                 comp = COMPONENT_OF_LIMIT[w.control[0]]
                 r[k], g[k, comp] = x[comp] + w.control[1], 1.0
@@ -842,13 +979,24 @@ class StandardWells:
                 r[k], g[k, comp] = x[comp] - (-1.0 if w.producer else 1.0) * target, 1.0
         return r, g
 
-    def update_well_controls(self):
+    def update_well_controls(self, iteration=0):
         """BlackoilWellModel::updateWellControls: the limits in the reference's order, the first that is violated and is not the control in
         force wins.  A well leaves its rate target (or its THP limit) for BHP control when its BHP leaves the limit; it returns to the rate
         target once the rate exceeds it; with a THP limit it goes under THP control when the tubing-head pressure its state implies is
         beyond the limit; the further rate limits (Well(limits=)) stand between BHP and THP in the order ORAT, WRAT, GRAT, LRAT, RESV, the
-        well's own target at its component's place (the module's text).  On a switch to a rate-type mode the state stays as it is."""
+        well's own target at its component's place (the module's text).  On a switch to a rate-type mode the state stays as it is.
+        With groups (iteration: the reference's iterationIdx): the groups' check and every well's group check come first; a well that has
+        just gone under GRUP is not looked at individually; group data in between and at the end (the module's text)."""
+        just_switched = ()
+        if self.groups:
+            self._group_data(iteration)
+            self._group_check(iteration)
+            self._group_data(iteration)
+            just_switched = [k for k in range(self.nw) if self._well_group_check(k)]
+            self._group_data(iteration)
         for k, (w, x) in enumerate(zip(self.wells, self.x)):
+            if k in just_switched:
+                continue
             sign = -1.0 if w.producer else 1.0
             t = self.thp_tables[k]
             if t is not None:
@@ -888,6 +1036,94 @@ class StandardWells:
             if t is not None and w.control[0] != "thp" and (w.thp_limit > self.thp_current[k] if w.producer else w.thp_limit < self.thp_current[k]):
                 w.control = ("thp", w.thp_limit)
                 x[3] = self._bhp_at_thp_limit(k)[0] - self.thp_dp[k]
+        if self.groups:
+            self._group_data(iteration)
+
+    # ---- group production control (the module's text) ------------------------------------------------------------------------------------
+    def _mode_rate(self, k, mode, v):
+        """calcModeRateFromRates for well k: the group mode's combination (code 1 .. 5) of the three values v (oil, water, gas)"""
+        if mode <= 3:
+            return float(v[mode - 1])
+        if mode == 4:
+            return float(v[OIL]) + float(v[WATER])
+        c = self.resv_coeff[k]
+        return (float(c[WATER]) * float(v[WATER]) + float(c[OIL]) * float(v[OIL])) + float(c[GAS]) * float(v[GAS])
+
+    def _group_sums(self, g):
+        """(rates (3), voidage) of group g's producers at their present rates, every sum in list order starting from 0"""
+        s, void = [0.0, 0.0, 0.0], 0.0
+        for k in self.group_wells[g]:
+            for c in range(3):
+                s[c] -= float(self.x[k, c])
+            if self.group_target[g, 4] < np.inf:
+                void += self._resv_current(k)
+        return s, void
+
+    def _group_data(self, iteration):
+        rec = self.group_record
+        for g, members in enumerate(self.group_wells):
+            mode = self.group_mode[g]
+            red, gsum = [0.0, 0.0, 0.0], 0.0
+            for k in members:
+                if iteration < self.nupcol:
+                    self.nupcol_rates[k] = self.x[k, :3]
+                if self.wells[k].control[0] == "grup":
+                    if mode != 0:
+                        gsum += float(self.guide[k, mode - 1])
+                else:
+                    for c in range(3):
+                        red[c] -= float(self.nupcol_rates[k, c])
+            s, void = self._group_sums(g)
+            rec["rates"][g], rec["voidage"][g], rec["reduction"][g], rec["guide_sum"][g] = s, void, red, gsum
+
+    def _group_check(self, iteration):
+        if iteration > self.nupcol:
+            return
+        for g, members in enumerate(self.group_wells):
+            s, void = self._group_sums(g)
+            for mode in range(1, 6):
+                target = float(self.group_target[g, mode - 1])
+                if not target < np.inf or self.group_mode[g] == mode:
+                    continue
+                current = s[mode - 1] if mode <= 3 else (s[OIL] + s[WATER] if mode == 4 else void)
+                if target < current:
+                    self.group_mode[g] = mode
+                    if current > 1e-12:
+                        scale = target / current
+                        for k in members:
+                            if self.wells[k].control[0] == "grup":
+                                for c in range(3):
+                                    self.x[k, c] = self.x[k, c] * scale
+                    break
+
+    def _well_group_check(self, k):
+        """-> whether well k has just gone under GRUP"""
+        w, g = self.wells[k], int(self.group_of_well[k])
+        if not w.producer or w.control[0] == "grup" or not self.available[k] or g < 0 or self.group_mode[g] == 0:
+            return False
+        mode, rec = self.group_mode[g], self.group_record
+        current = -self._mode_rate(k, mode, self.x[k])
+        gw = float(self.guide[k, mode - 1])
+        gsum = float(rec["guide_sum"][g]) + gw
+        frac = gw / gsum if gsum > 1e-12 else 0.0
+        t = float(self.group_target[g, mode - 1]) - self._mode_rate(k, mode, rec["reduction"][g])
+        t = t + current
+        t = t * frac
+        target_rate = t if t > 1e-12 else 1e-12
+        if not current > target_rate:
+            return False
+        w.control = ("grup",)
+        scale = target_rate / current if current > 1e-12 else 1.0
+        for c in range(3):
+            self.x[k, c] = self.x[k, c] * scale
+        return True
+
+    def group_rates(self):
+        """per group, as the last group data left them: dict(mode (codes of GROUP_MODES), rates (groups, 3: oil, water, gas produced),
+        voidage (groups with a RESV target; 0 otherwise), reduction (groups, 3), guide_sum)"""
+        out = {k: v.copy() for k, v in self.group_record.items()}
+        out["mode"] = np.array(self.group_mode, np.int32)
+        return out
 
     def set_rate_target(self, k, target):
         """a WCONPROD / WCONINJE record at a report step (ScheduleEvents::PRODUCTION_UPDATE / INJECTION_UPDATE, wells/WellState.hpp:57): the
@@ -1007,7 +1243,8 @@ class StandardWells:
             if np.abs(rw[k, :3]).max() > tol_rate * scale:
                 return False
             ctl = abs(rw[k, 3])
-            if ctl > (tol_bhp if w.control[0] in ("bhp", "thp") else tol_rate * scale):
+            in_pressure = w.control[0] in ("bhp", "thp") or (w.control[0] == "grup" and self.group_mode[self.group_of_well[k]] == 0)
+            if ctl > (tol_bhp if in_pressure else tol_rate * scale):
                 return False
         return True
 
@@ -1018,12 +1255,17 @@ class StandardWells:
         st = self.x.copy(), [w.control for w in self.wells]
         if self.head_model == "wellbore":
             st += ((None if self.perf_pressure is None else self.perf_pressure.copy(), self.perf_rates.copy(), self.initialised),)
+        if self.groups:                          # last entry, a dict: the groups' modes and the NUPCOL rates
+            st += (dict(group_mode=list(self.group_mode), nupcol_rates=self.nupcol_rates.copy()),)
         return st
 
     def set_state(self, st):
         self.x = st[0].copy()
         for w, c in zip(self.wells, st[1]):
             w.control = c
+        if self.groups and isinstance(st[-1], dict):
+            self.group_mode = list(st[-1]["group_mode"])
+            self.nupcol_rates = st[-1]["nupcol_rates"].copy()
         if self.head_model == "wellbore" and len(st) > 2:
             self.perf_pressure = None if st[2][0] is None else st[2][0].copy()
             self.perf_rates = st[2][1].copy()
@@ -1035,11 +1277,14 @@ class DeviceStandardWells:
     """The same wells resident on the device (opmhip_set_std_wells): model is a capi.HipModel whose state is set.  The well unknowns, the
     controls, the heads and the blocks B, C, D^-1 live there; what this object holds of them (x, controls, res_well) is the last read-back
     (fetch).  Wells with allow_crossflow are named to the library (opmhip_set_std_wells_crossflow), further rate limits (Well(limits=)) sent
-    with opmhip_set_std_wells_limits, the wet-gas rate model switched on with opmhip_set_std_wells_vaporised_oil.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
+    with opmhip_set_std_wells_limits, the wet-gas rate model switched on with opmhip_set_std_wells_vaporised_oil, group production control
+    (groups=, nupcol=; Well(group=, guide_rate=)) sent with opmhip_set_std_wells_groups.  The arithmetic is StandardWells(arithmetic="stated")'s, bit for bit; newton.BlackoilModelHip takes the branch on_device."""
     on_device = True
 
-    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None, vaporised_oil=False, matrix_add=False):
-        """matrix_add: the wells are written into the Jacobian every Newton iteration (opmhip_set_std_wells_matrix_add,
+    def __init__(self, wells, cell_depth, model, head_model="cell_oil", vfp=None, vaporised_oil=False, matrix_add=False, groups=None, nupcol=NUPCOL_DEFAULT):
+        """groups / nupcol: group production control as StandardWells(groups=, nupcol=) - sent (opmhip_set_std_wells_groups) when some
+        well names a group, a list without makes the calls it made before;
+        matrix_add: the wells are written into the Jacobian every Newton iteration (opmhip_set_std_wells_matrix_add,
         opmhip_std_wells_add_to_matrix) instead of reaching the solver as the operator A - C^T D^-1 B; the model's pattern must hold the wells'
         cliques (decks.with_well_cliques) - ValueError with the library's text when a block is missing;
         vaporised_oil: the wet-gas rate model (opmhip_set_std_wells_vaporised_oil; ValueError on a context whose fluid has no PVTG);
@@ -1067,6 +1312,8 @@ class DeviceStandardWells:
             if head_model == "wellbore" and w.producer and w.preferred_phase not in phase:
                 raise ValueError("DeviceStandardWells: producer %s with unknown preferred phase %r" % (w.name, w.preferred_phase))
         self.thp_tables = _thp_tables(self.wells, vfp)
+        _group_lists(self, groups, nupcol)
+        self.has_groups = bool(self.groups) and bool((self.group_of_well >= 0).any())
         self.vp = np.concatenate([[0], np.cumsum([len(w.cells) for w in self.wells])]).astype(np.int32)
         self.cells = np.concatenate([w.cells for w in self.wells]).astype(np.int32)
         model.set_std_wells(dict(
@@ -1100,12 +1347,17 @@ class DeviceStandardWells:
             # a well that starts under one of the new modes is under BHP control until the state call below: its own target may not be a limit
             lim = {field: [w.limits.get(kind, inf) for w in self.wells] for field, kind in kinds.items()}
             lim["use_list_target"] = [int(w.use_list_target) for w in self.wells]
-            start = [1 if (w.control[0] in LIMIT_KINDS or w.control[0] == "thp") else CONTROL_CODE[w.control[0]] for w in self.wells]
+            start = [1 if (w.control[0] in LIMIT_KINDS or w.control[0] in ("thp", "grup")) else CONTROL_CODE[w.control[0]] for w in self.wells]
             if any(s != int(w.control[0] == "bhp") for s, w in zip(start, self.wells)):
                 model.set_std_wells_state(None, start, None)
             model.set_std_wells_limits(lim)
+        if self.has_groups:                                  # (a list without groups makes the calls it made before)
+            T = self.group_target
+            model.set_std_wells_groups(dict(num_groups=len(self.groups), well_group=self.group_of_well, oil_target=T[:, 0], water_target=T[:, 1], gas_target=T[:, 2],
+                                            liquid_target=T[:, 3], resv_target=T[:, 4], mode=self.group_mode, guide_rate=self.guide, available=self.available,
+                                            nupcol=self.nupcol))
         if any(w.control[0] not in ("rate", "bhp") for w in self.wells):   # the list itself starts under the deck's modes: the others through the state call
-            model.set_std_wells_state(None, [CONTROL_CODE[w.control[0]] for w in self.wells], None)
+            model.set_std_wells_state(None, [control_code(w.control) for w in self.wells], None)
         self.x = np.zeros((self.nw, 4))
         self.res_well = np.zeros((self.nw, 4))
 
@@ -1113,11 +1365,17 @@ class DeviceStandardWells:
         self.m.std_wells_begin_iteration(iteration)
 
     def fetch(self):
-        """opmhip_get_std_wells: x, the controls in force (onto the Well objects) and r_w of the last assemble"""
+        """opmhip_get_std_wells: x, the controls in force (onto the Well objects) and r_w of the last assemble; with groups also their
+        modes in force (opmhip_get_std_wells_groups): converged() reads them to tell a GRUP well's rate row from its BHP row"""
         self.x, ctl, self.res_well = self.m.get_std_wells()
+        if self.has_groups:
+            self.group_rates()
         for w, k in zip(self.wells, ctl):
             k = int(k)
-            w.control = (w.rate_control, ("bhp", w.bhp_limit), ("thp", w.thp_limit))[k] if k < 3 else (LIMIT_KINDS[k - 3], w.limits[LIMIT_KINDS[k - 3]])
+            if k == GRUP_CODE:
+                w.control = ("grup",)
+            else:
+                w.control = (w.rate_control, ("bhp", w.bhp_limit), ("thp", w.thp_limit))[k] if k < 3 else (LIMIT_KINDS[k - 3], w.limits[LIMIT_KINDS[k - 3]])
         return self.x
 
     def update(self, relax=1.0):
@@ -1134,11 +1392,18 @@ class DeviceStandardWells:
         self._send()
 
     def _send(self):
-        self.m.set_std_wells_state(self.x, [CONTROL_CODE[w.control[0]] for w in self.wells], [w.rate_control[2] for w in self.wells])
+        self.m.set_std_wells_state(self.x, [control_code(w.control) for w in self.wells], [w.rate_control[2] for w in self.wells])
 
     def solution_rates(self):
         """opmhip_get_std_wells_solution_rates: (dissolved_gas, vaporised_oil) per well - StandardWells.solution_rates()"""
         return self.m.std_wells_solution_rates()
+
+    def group_rates(self):
+        """opmhip_get_std_wells_groups: StandardWells.group_rates() - dict(mode, rates, voidage, reduction, guide_sum) per group - and
+        nupcol_rates (wells, 3); the groups' modes in force are kept on this object too"""
+        out = self.m.std_wells_groups()
+        self.group_mode = [int(v) for v in out["mode"]]
+        return out
 
     def resv(self):
         """opmhip_get_std_wells_resv: dict(averages, coeff, resv_current) - StandardWells' resv_averages, resv_coeff, resv_current"""
@@ -1156,15 +1421,24 @@ class DeviceStandardWells:
         if self.head_model == "wellbore":
             wb = self.m.std_wells_wellbore()
             st += ((wb["perf_pressure"] if wb["perf_state_set"] else None, wb["perf_rates"]),)
+        if self.has_groups:
+            g = self.group_rates()
+            st += (dict(group_mode=[int(v) for v in g["mode"]], nupcol_rates=g["nupcol_rates"]),)
         return st
 
     def set_state(self, st):
         """a third entry whose pressures are None ("not yet taken from the cells") sets the head model anew: the library then takes them from
         the cells at the next begin_iteration(0), as the host class does.  (Whether the bottom-hole pressures have been set is the library's
-        to keep: it cannot be handed in.)"""
+        to keep: it cannot be handed in.)  With groups the last entry's modes go back to the device; its NUPCOL rates do NOT: no entry point
+        sets them - the library keeps and rolls back its own (opmhip_advance_time_level / opmhip_update_failed).  A state handed to another
+        list, or one older than the last opmhip_advance_time_level, therefore leaves the device's NUPCOL rates as they are: from iteration >=
+        nupcol on its reductions differ from those of StandardWells.set_state until the next iteration < nupcol copies the rates anew."""
         self.x = st[0].copy()
         for w, c in zip(self.wells, st[1]):
             w.control = c
+        if self.has_groups and isinstance(st[-1], dict):     # the modes first: control 8 is checked against nothing of them, a mode needs its target
+            self.group_mode = list(st[-1]["group_mode"])
+            self.m.set_std_wells_group_targets(mode=self.group_mode)
         self._send()
         if self.head_model == "wellbore" and len(st) > 2:
             if st[2][0] is None:
