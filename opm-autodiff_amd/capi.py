@@ -302,6 +302,14 @@ def ms_wells_caps():
     return _header_define("OPMHIP_MS_WELLS_MAX_M"), _header_define("OPMHIP_MS_WELLS_MAX_KIB")
 
 
+MS_WELLS_FORMS = {"dense": 0, "tree": 1, "auto": 2}   # OPMHIP_MS_WELLS_DENSE / _TREE / _AUTO
+
+
+def ms_wells_tree_cap():
+    """the largest number of segments a well may have in the tree form: OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS of the header"""
+    return _header_define("OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS")
+
+
 def make_ms_wells(wells):
     """list of per-well dicts(Brows [Mb+1], Bcols [nblk], Bvals [nblk*12], Cvals [nblk*12], Dcolptr [4 Mb+1], Drows [nnz], Dvals [nnz]) - the
     constructor arguments of Opm::MultisegmentWellContribution, cells in natural order - -> (MsWells struct, keep-alive list).
@@ -384,6 +392,8 @@ def lib():
         L.opmhip_get_ilu_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
         L.opmhip_set_ms_wells.argtypes = [vp, C.POINTER(MsWells)]
         L.opmhip_get_ms_wells_info.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.opmhip_set_ms_wells_form.argtypes = [vp, C.c_int]
+        L.opmhip_get_ms_wells_form_info.argtypes = [vp, C.POINTER(C.c_int * 6)]
         L.opmhip_get_ilu_factors.argtypes = [vp, ip, ip, ip, ip, ip, dp, dp, dp]
         L.opmhip_time_kernel.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.opmhip_cpr_levels.argtypes = [vp, ip, ip, C.c_int]
@@ -627,11 +637,22 @@ class HipSolver:
     def set_ilu_fillin_level(self, n):
         self._check(lib().opmhip_set_ilu_fillin_level(self._h, int(n)))
 
-    def set_ms_wells(self, wells):
+    def set_ms_wells(self, wells, form="dense"):
         """opmhip_set_ms_wells: the multisegment wells (list of dicts, see make_ms_wells) on the device for every operator application that
-        follows; None or an empty list clears them"""
+        follows; None or an empty list clears them.  form: "dense", "tree" or "auto" (opmhip_set_ms_wells_form, set in front of a list; a
+        clearing call leaves the form as it is)"""
         ms, keep = make_ms_wells(wells)
+        if ms:
+            self._check(lib().opmhip_set_ms_wells_form(self._h, MS_WELLS_FORMS[form] if isinstance(form, str) else int(form)))
         self._check(lib().opmhip_set_ms_wells(self._h, C.byref(ms) if ms else None))
+
+    def ms_wells_form_info(self):
+        """opmhip_get_ms_wells_form_info: the form set, the list's wells by form, the largest tree well's segments and depth, KiB of tree blocks"""
+        info = (C.c_int * 6)()
+        self._check(lib().opmhip_get_ms_wells_form_info(self._h, C.byref(info)))
+        names = {v: k for k, v in MS_WELLS_FORMS.items()}
+        return {"form": names[int(info[0])], "dense": int(info[1]), "tree": int(info[2]), "tree_max_segments": int(info[3]), "tree_max_depth": int(info[4]),
+                "tree_kib": int(info[5])}
 
     def ms_wells_info(self):
         """opmhip_get_ms_wells_info: wells on the device, largest M = 4 Mb, device KiB held for them, inversions done so far"""

@@ -19,6 +19,7 @@
 
 #include <cfloat>
 
+#include "device_blocks.hpp"
 #include "fluid_tables.hpp"
 #include "internal.hpp"
 
@@ -1988,31 +1989,6 @@ __device__ __forceinline__ void sw_perf_rates(const double* __restrict__ iq, int
         }
     }
 }
-// wells.py invert4_stated: Gauss-Jordan on [D | I], partial pivoting (largest |entry| of the column, lowest row on ties), the pivot row
-// divided by the pivot, every other row updated as a - f * b.  -> 0, or 1 + the column without a pivot (inv is then left alone)
-__device__ int sw_invert4(const double* D, double* inv) {
-    double a[4][8];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) { a[i][j] = D[i * 4 + j]; a[i][4 + j] = i == j ? 1.0 : 0.0; }
-    for (int col = 0; col < 4; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < 4; ++r)
-            if (fabs(a[r][col]) > fabs(a[piv][col])) piv = r;
-        if (!(fabs(a[piv][col]) > 0.0)) return 1 + col;
-        if (piv != col)
-            for (int j = 0; j < 8; ++j) { const double t = a[col][j]; a[col][j] = a[piv][j]; a[piv][j] = t; }
-        const double p = a[col][col];
-        for (int j = 0; j < 8; ++j) a[col][j] = a[col][j] / p;
-        for (int r = 0; r < 4; ++r) {
-            if (r == col) continue;
-            const double f = a[r][col];
-            for (int j = 0; j < 8; ++j) a[r][j] = a[r][j] - f * a[col][j];
-        }
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) inv[i * 4 + j] = a[i][4 + j];
-    return 0;
-}
 struct SwArrays {
     int num;
     const int *vp, *cell, *wi;                  // perforation ranges, perforated cells (internal positions), per well: producer, injected phase, rate component
@@ -2293,7 +2269,7 @@ __global__ __launch_bounds__(64) void k_std_wells_eq(SwArrays W, SwThp H, SwLim 
             else { r[3] = xs[comp] - (producer ? -1.0 : 1.0) * W.wd[2 * w]; D[12 + comp] = 1.0; }
             // a well none of whose completions flows has no rate that answers to its bottom-hole pressure: it keeps the pressure
             if (D[3] == 0.0 && D[7] == 0.0 && D[11] == 0.0 && D[15] == 0.0) { r[3] = 0.0; D[12] = D[13] = D[14] = 0.0; D[15] = 1.0; }
-            const int sing = sw_invert4(D, inv);
+            const int sing = invert4_stated(D, inv);
             if (sing) *flag = (double)sing;   // sticky: cleared by the host once it has looked
             if (SOLVE) {
                 s_active = 0;

@@ -160,9 +160,28 @@ struct MsWellDesc {
     int blk0;          // first block
     int dcol0, dnz0;   // well's part of Dcol_pointers (4 Mb + 1 entries), first entry of D
     int inv0;          // first double of the dense D^-1
+    int well;          // its number in the list (the place of its pivot flag): a list may hold wells of both forms
+};
+// The tree form (opmhip_set_ms_wells_form; ms_wells_setup.hpp): D block-sparse over the segment tree, 48 doubles per segment
+// (S_i^-1 | E_i = D_pi S_i^-1 | D_ip).  The well's index lists lie one after the other in MsWellsDev::d_tint.
+struct MsTreeDesc {
+    int Mb, nblk, seg0, blk0, dcol0, dnz0, well;   // as MsWellDesc's
+    int depth, width;                              // levels; segments of the widest level
+    int par0, cptr0, child0, lptr0, lseg0, dest0;  // in d_tint: parent [Mb], child_ptr [Mb + 1], child, level_ptr [depth + 1], level_seg [Mb], dest [nnz]
+    int fac0;                                      // first double of the well's blocks in d_fac
 };
 struct MsWellsDev {
     int num = 0, maxM = 0;
+    int form = 0;                // OPMHIP_MS_WELLS_DENSE / _TREE / _AUTO: applies to the lists set after opmhip_set_ms_wells_form
+    int num_dense = 0, num_tree = 0;     // the list's wells by form: d_desc holds the dense ones, d_tdesc the others
+    int tree_max_seg = 0, tree_max_depth = 0;
+    size_t tree_bytes = 0;       // of `bytes`: the tree wells' blocks
+    int tree_lds_doubles = 0;    // dynamic LDS of k_ms_wells_tree_apply for this list (ms_wells_tree_plan)
+    bool have_structure = false; // the index arrays on the device belong to h_Mbp ... h_Dnzp
+    MsTreeDesc* d_tdesc = nullptr;
+    int* d_tint = nullptr;
+    double* d_fac = nullptr;
+    std::vector<int> h_form;     // per well of the list: 0 dense, 1 tree
     bool atomic = false;         // some cell is shared between two blocks of the list: y is updated by atomic adds
     bool flag_pending = false;   // an inversion was enqueued whose pivot flags have not been looked at yet
     int factorisations = 0;
@@ -170,7 +189,7 @@ struct MsWellsDev {
     MsWellDesc* d_desc = nullptr;
     int *d_Brows = nullptr, *d_cell = nullptr, *d_blkrow = nullptr, *d_Dcolp = nullptr, *d_Drows = nullptr, *d_flag = nullptr;
     double *d_B = nullptr, *d_C = nullptr, *d_Dvals = nullptr, *d_inv = nullptr;
-    int* h_flag = nullptr;       // pinned, one int per well: 0, or 1 + the column whose pivot was zero
+    int* h_flag = nullptr;       // pinned, one int per well: 0, or 1 + the column (dense form) / the segment (tree form) whose pivot was zero
     size_t cap_flag = 0;
     // the list as handed over last time (natural cell numbers): what arrives unchanged is not copied again
     std::vector<int> h_Mbp, h_Brows, h_blkp, h_Bcols, h_Dcolp, h_Drows, h_Dnzp;
@@ -776,6 +795,7 @@ void cpr_shutdown(opmhip_ctx* c);   // joins a structure build in flight (before
 bool cpr_coarse_pivot_failed(opmhip_ctx* c);
 int cpr_ilu_levels_in_force(const opmhip_ctx* c);   // opmhip_config.cpr_amg_ilu_levels with "< 0: the library's choice" resolved (0 without CPR)
 inline bool use_cpr(const opmhip_ctx* c) { return c->cfg.preconditioner == OPMHIP_PRECOND_CPR_QUASIIMPES || c->cfg.preconditioner == OPMHIP_PRECOND_CPR_TRUEIMPES; }
+void ms_wells_tree_plan(opmhip_ctx* c, const std::vector<MsTreeDesc>& tdesc);   // MsWellsDev::tree_lds_doubles of a new list: the dynamic LDS of k_ms_wells_tree_apply
 void launch_ms_wells_factor(opmhip_ctx* c);   // D -> D^-1 of every well of the device-resident multisegment list; pivot flags to MsWellsDev::d_flag
 int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs = 1.0);   // distributed wells: one all-reduce inside
 void launch_lu_to_natural(opmhip_ctx* c, double* d_out_internal_layout);

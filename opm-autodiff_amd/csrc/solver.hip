@@ -16,10 +16,13 @@
 #include <atomic>
 
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 
+#include "device_blocks.hpp"
 #include "internal.hpp"
+#include "ms_wells_setup.hpp"
 
 namespace opmhip {
 
@@ -1740,7 +1743,7 @@ __global__ __launch_bounds__(64) void k_wells_recover(const int* __restrict__ vp
 // the smaller row number where two are equal - and the columns are put back in the reverse order of the row exchanges, which leaves the
 // explicit inverse.  Per step: column k to LDS (the multipliers), the pivot search by the first wavefront, the pivot row scaled to LDS while
 // the old row k moves to its place, then every entry's update - wavefronts over the columns, lanes down a column.  A zero (or non-finite)
-// pivot ends the well's elimination: flag[w] = 1 + k, read by the host where it synchronises next; 0 otherwise.
+// pivot ends the well's elimination: flag[well] = 1 + k, read by the host where it synchronises next; 0 otherwise.
 constexpr int MSW_MAX_M = OPMHIP_MS_WELLS_MAX_M;
 constexpr int MSW_FACTOR_THREADS = 512, MSW_APPLY_THREADS = 1024;
 static_assert(MSW_MAX_M % 64 == 0 && MSW_MAX_M <= MSW_APPLY_THREADS, "k_ms_wells_apply: one thread per well equation and part of the columns");
@@ -1781,7 +1784,7 @@ __global__ __launch_bounds__(MSW_FACTOR_THREADS) void k_ms_wells_factor(const Ms
         __syncthreads();
         const int p = s_p;
         if (p < 0) {   // (the same for every thread)
-            if (t == 0) flag[blockIdx.x] = k + 1;
+            if (t == 0) flag[d.well] = k + 1;
             return;
         }
         const double pv = col[p];
@@ -1813,7 +1816,7 @@ __global__ __launch_bounds__(MSW_FACTOR_THREADS) void k_ms_wells_factor(const Ms
             W[p * M + i] = a;
         }
     }
-    if (t == 0) flag[blockIdx.x] = 0;
+    if (t == 0) flag[d.well] = 0;
 }
 // y -= C^T (D^-1 (B (xs x))) for the wells of the list, one workgroup per well, z1 and z2 in LDS:
 // z1 = B (xs x): per segment row its blocks in ascending order, each block's sum over k formed first (MultisegmentWellContribution.cpp:78-90);
@@ -1861,6 +1864,187 @@ __global__ __launch_bounds__(MSW_APPLY_THREADS) void k_ms_wells_apply(const MsWe
     for (int e = t; e < d.nblk * 3; e += MSW_APPLY_THREADS) {
         const int blk = d.blk0 + e / 3, j = e % 3;
         const double* zz = z2 + blkrow[blk] * 4;
+        double temp = 0.0;
+        for (int k = 0; k < 4; ++k) temp += C[(size_t)blk * 12 + j + k * 3] * zz[k];
+        double* yp = y + (size_t)cell[blk] * 3 + j;
+        if (ATOMIC) atomicAdd(yp, -temp);
+        else *yp -= temp;
+    }
+}
+
+// ---- the tree form of the same list (opmhip_set_ms_wells_form; ms_wells_setup.hpp; mswells.py tree_solve states the arithmetic) ----
+// D is block-sparse over the segment tree: 4 x 4 blocks on the diagonal and between a segment i and its parent p.  Eliminating the leaves
+// first leaves no fill: per segment S_i = D_ii - sum_c E_c D_ci over the children c of i, E_i = D_pi S_i^-1.  One workgroup per well, one
+// lane per segment of a level, levels separated by barriers; every sum in a stated order (the children ascending, inside a block
+// product k ascending from 0.0), no floating-point atomics.  The blocks live in global memory, 48 doubles per segment:
+// S_i^-1 | E_i | D_ip.  Pivoting stays INSIDE a segment's block (invert4_stated): a block without a non-zero finite pivot sets
+// flag[well] = 1 + the lowest such segment (an integer minimum in LDS: the same whatever the lanes' order).
+constexpr int MSW_TREE_THREADS = 256;
+constexpr int MSW_TREE_MAX_M = 4 * OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS;
+constexpr int MSW_SEG = opmhip::MS_TREE_SEG, MSW_UP = opmhip::MS_TREE_UP, MSW_DOWN = opmhip::MS_TREE_DOWN;
+static_assert(MSW_TREE_MAX_M * sizeof(double) <= 32768, "k_ms_wells_tree_apply: the well's z stays in LDS, half of the static limit");
+__global__ __launch_bounds__(MSW_TREE_THREADS) void k_ms_wells_tree_factor(const MsTreeDesc* __restrict__ desc, const int* __restrict__ Dcolp,
+                                                                           const int* __restrict__ tint, const double* __restrict__ Dvals,
+                                                                           double* facAll, int* __restrict__ flag) {
+    __shared__ int s_bad;
+    const MsTreeDesc d = desc[blockIdx.x];
+    const int M = 4 * d.Mb, t = threadIdx.x;
+    constexpr int T = MSW_TREE_THREADS;
+    double* fac = facAll + d.fac0;
+    const int *parent = tint + d.par0, *cptr = tint + d.cptr0, *child = tint + d.child0, *lptr = tint + d.lptr0, *lseg = tint + d.lseg0, *dest = tint + d.dest0;
+    if (t == 0) s_bad = INT_MAX;
+    for (int e = t; e < MSW_SEG * d.Mb; e += T) fac[e] = 0.0;
+    __syncthreads();
+    const int* cp = Dcolp + d.dcol0;
+    for (int c = t; c < M; c += T)   // one thread per column (two columns never share a place): entries that name the same place are added in their order
+        for (int k = cp[c]; k < cp[c + 1]; ++k) fac[dest[k]] += Dvals[d.dnz0 + k];
+    __syncthreads();
+    for (int l = d.depth - 1; l >= 0; --l) {
+        for (int q = lptr[l] + t; q < lptr[l + 1]; q += T) {
+            const int i = lseg[q];
+            double* F = fac + (size_t)i * MSW_SEG;
+            double S[16], Si[16];
+            for (int e = 0; e < 16; ++e) S[e] = F[e];
+            for (int k = cptr[i]; k < cptr[i + 1]; ++k) {   // S_i -= E_c D_ci, the children ascending
+                const double* G = fac + (size_t)child[k] * MSW_SEG;
+                for (int r = 0; r < 4; ++r)
+                    for (int c = 0; c < 4; ++c) {
+                        double p = 0.0;
+                        for (int m = 0; m < 4; ++m) p += G[MSW_UP + r * 4 + m] * G[MSW_DOWN + m * 4 + c];
+                        S[r * 4 + c] = S[r * 4 + c] - p;
+                    }
+            }
+            bool ok = invert4_stated(S, Si) == 0;
+            if (ok)
+                for (int e = 0; e < 16; ++e) ok = ok && fabs(Si[e]) <= 1.7976931348623157e308;
+            if (!ok) { atomicMin(&s_bad, i + 1); continue; }
+            for (int e = 0; e < 16; ++e) F[e] = Si[e];
+            if (parent[i] >= 0) {   // E_i = D_pi S_i^-1
+                double U[16];
+                for (int e = 0; e < 16; ++e) U[e] = F[MSW_UP + e];
+                for (int r = 0; r < 4; ++r)
+                    for (int c = 0; c < 4; ++c) {
+                        double p = 0.0;
+                        for (int m = 0; m < 4; ++m) p += U[r * 4 + m] * Si[m * 4 + c];
+                        F[MSW_UP + r * 4 + c] = p;
+                    }
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) flag[d.well] = s_bad == INT_MAX ? 0 : s_bad;
+}
+// The two sweeps of z2 = D^-1 z1 over the tree, z in LDS, in place.  Forward, from the deepest parents up: z_p -= E_c z_c over p's
+// children, ascending (pull: lane p alone writes z_p).  Backward, from the roots down: x_i = S_i^-1 (z_i - D_ip x_p).  A chain is
+// 2 x depth dependent steps, so what a step costs beside its arithmetic decides:
+//   - the tree's index lists (`ti`) are in LDS: a step's chain level -> segment -> children -> block is four dependent reads;
+//   - the blocks (`fac`) are in LDS too where the well's fit (STAGED; otherwise each step waits for global memory once);
+//   - WAVE - no level is wider than a wavefront - lets the first wavefront alone walk the levels, ordered by the LDS' own in-order
+//     execution (a wavefront-scope fence keeps the compiler from moving the accesses; no s_barrier); otherwise the whole workgroup
+//     does, with a barrier per level.
+template <bool WAVE>
+__device__ __forceinline__ void msw_tree_level_end() {
+    if (WAVE) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+template <bool WAVE>
+__device__ __forceinline__ void msw_tree_sweeps(const MsTreeDesc& d, const int* ti, const double* fac, double* z, int t) {
+    constexpr int T = WAVE ? 64 : MSW_TREE_THREADS;
+    const int *parent = ti, *cptr = ti + (d.cptr0 - d.par0), *child = ti + (d.child0 - d.par0), *lptr = ti + (d.lptr0 - d.par0), *lseg = ti + (d.lseg0 - d.par0);
+    for (int l = d.depth - 2; l >= 0; --l) {
+        for (int q = lptr[l] + t; q < lptr[l + 1]; q += T) {
+            const int i = lseg[q], k0 = cptr[i], k1 = cptr[i + 1];
+            if (k0 == k1) continue;
+            double zp[4];
+            for (int r = 0; r < 4; ++r) zp[r] = z[4 * i + r];
+            for (int k = k0; k < k1; ++k) {
+                const int c = child[k];
+                const double* E = fac + (size_t)c * MSW_SEG + MSW_UP;
+                for (int r = 0; r < 4; ++r) {
+                    double s = 0.0;
+                    for (int m = 0; m < 4; ++m) s += E[r * 4 + m] * z[4 * c + m];
+                    zp[r] = zp[r] - s;
+                }
+            }
+            for (int r = 0; r < 4; ++r) z[4 * i + r] = zp[r];
+        }
+        msw_tree_level_end<WAVE>();
+    }
+    for (int l = 0; l < d.depth; ++l) {
+        for (int q = lptr[l] + t; q < lptr[l + 1]; q += T) {
+            const int i = lseg[q], p = parent[i];
+            const double* F = fac + (size_t)i * MSW_SEG;
+            double v[4], x[4];
+            for (int r = 0; r < 4; ++r) v[r] = z[4 * i + r];
+            if (p >= 0)
+                for (int r = 0; r < 4; ++r) {
+                    double s = 0.0;
+                    for (int m = 0; m < 4; ++m) s += F[MSW_DOWN + r * 4 + m] * z[4 * p + m];
+                    v[r] = v[r] - s;
+                }
+            for (int r = 0; r < 4; ++r) {
+                double s = 0.0;
+                for (int m = 0; m < 4; ++m) s += F[r * 4 + m] * v[m];
+                x[r] = s;
+            }
+            for (int r = 0; r < 4; ++r) z[4 * i + r] = x[r];
+        }
+        msw_tree_level_end<WAVE>();
+    }
+}
+// y -= C^T (D^-1 (B (xs x))) for the tree wells of the list, one workgroup per well: z1 and y's update as k_ms_wells_apply forms them
+// (a well of more equations than threads loops), z2 by the sweeps above.  Dynamic LDS, ldsDoubles doubles: z [4 Mb] | the tree's index
+// lists [nint ints] | the well's blocks [48 Mb], the last only where they fit (msw_tree_lds_doubles: the host sizes the launch by it).
+__host__ __device__ inline size_t msw_tree_lds_doubles(int Mb, int nint, bool staged) {
+    return (size_t)4 * Mb + (size_t)(nint + 1) / 2 + (staged ? (size_t)MSW_SEG * Mb : 0);
+}
+template <bool ATOMIC>
+__global__ __launch_bounds__(MSW_TREE_THREADS) void k_ms_wells_tree_apply(const MsTreeDesc* __restrict__ desc, const int* __restrict__ Brows,
+                                                                          const int* __restrict__ cell, const int* __restrict__ blkrow,
+                                                                          const double* __restrict__ B, const double* __restrict__ C,
+                                                                          const int* __restrict__ tint, const double* __restrict__ facAll,
+                                                                          const double* __restrict__ x, double* __restrict__ y, double xs, int ldsDoubles) {
+    extern __shared__ double msw_lds[];
+    const MsTreeDesc d = desc[blockIdx.x];
+    const int M = 4 * d.Mb, t = threadIdx.x, nint = d.dest0 - d.par0;
+    const bool staged = msw_tree_lds_doubles(d.Mb, nint, true) <= (size_t)ldsDoubles;   // (the same for every thread)
+    double* z = msw_lds;
+    int* ti = reinterpret_cast<int*>(msw_lds + M);
+    double* sfac = msw_lds + M + (nint + 1) / 2;
+    for (int e = t; e < nint; e += MSW_TREE_THREADS) ti[e] = tint[d.par0 + e];
+    if (staged)
+        for (int e = t; e < MSW_SEG * d.Mb; e += MSW_TREE_THREADS) sfac[e] = facAll[d.fac0 + e];
+    const int* br = Brows + d.seg0;
+    for (int e = t; e < M; e += MSW_TREE_THREADS) {
+        const int row = e >> 2, j = e & 3;
+        double s = 0.0;
+        for (int blk = d.blk0 + br[row]; blk < d.blk0 + br[row + 1]; ++blk) {
+            const double* xb = x + (size_t)cell[blk] * 3;
+            double temp = 0.0;
+            for (int k = 0; k < 3; ++k) temp += B[(size_t)blk * 12 + j * 3 + k] * (xs * xb[k]);
+            s += temp;
+        }
+        z[e] = s;
+    }
+    __syncthreads();
+    if (d.width <= 64) {
+        if (t < 64) {
+            if (staged) msw_tree_sweeps<true>(d, ti, sfac, z, t);
+            else msw_tree_sweeps<true>(d, ti, facAll + d.fac0, z, t);
+        }
+        __syncthreads();
+    } else {
+        if (staged) msw_tree_sweeps<false>(d, ti, sfac, z, t);
+        else msw_tree_sweeps<false>(d, ti, facAll + d.fac0, z, t);
+    }
+    for (int e = t; e < d.nblk * 3; e += MSW_TREE_THREADS) {
+        const int blk = d.blk0 + e / 3, j = e % 3;
+        const double* zz = z + blkrow[blk] * 4;
         double temp = 0.0;
         for (int k = 0; k < 4; ++k) temp += C[(size_t)blk * 12 + j + k * 3] * zz[k];
         double* yp = y + (size_t)cell[blk] * 3 + j;
@@ -2360,7 +2544,10 @@ void launch_lu_to_natural(opmhip_ctx* c, double* d_out) {
 }
 void launch_ms_wells_factor(opmhip_ctx* c) {
     MsWellsDev& S = c->wells.ms;
-    hipLaunchKernelGGL(k_ms_wells_factor, dim3(S.num), dim3(MSW_FACTOR_THREADS), 0, c->stream, S.d_desc, S.d_Dcolp, S.d_Drows, S.d_Dvals, S.d_inv, S.d_flag);
+    if (S.num_dense > 0)
+        hipLaunchKernelGGL(k_ms_wells_factor, dim3(S.num_dense), dim3(MSW_FACTOR_THREADS), 0, c->stream, S.d_desc, S.d_Dcolp, S.d_Drows, S.d_Dvals, S.d_inv, S.d_flag);
+    if (S.num_tree > 0)
+        hipLaunchKernelGGL(k_ms_wells_tree_factor, dim3(S.num_tree), dim3(MSW_TREE_THREADS), 0, c->stream, S.d_tdesc, S.d_Dcolp, S.d_tint, S.d_Dvals, S.d_fac, S.d_flag);
     (void)hipMemcpyAsync(S.h_flag, S.d_flag, (size_t)S.num * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     S.flag_pending = true;
     S.factorisations++;
@@ -2368,10 +2555,38 @@ void launch_ms_wells_factor(opmhip_ctx* c) {
 // the device-resident multisegment wells, in the place of the host round trip: no copy, no synchronisation
 static void launch_ms_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
     const MsWellsDev& S = c->wells.ms;
-    if (S.atomic)
-        hipLaunchKernelGGL(k_ms_wells_apply<true>, dim3(S.num), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
-    else
-        hipLaunchKernelGGL(k_ms_wells_apply<false>, dim3(S.num), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
+    if (S.num_dense > 0) {
+        if (S.atomic)
+            hipLaunchKernelGGL(k_ms_wells_apply<true>, dim3(S.num_dense), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
+        else
+            hipLaunchKernelGGL(k_ms_wells_apply<false>, dim3(S.num_dense), dim3(MSW_APPLY_THREADS), 0, c->stream, S.d_desc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_inv, x, y, xs);
+    }
+    if (S.num_tree > 0) {
+        const size_t lds = (size_t)S.tree_lds_doubles * sizeof(double);
+        if (S.atomic)
+            hipLaunchKernelGGL(k_ms_wells_tree_apply<true>, dim3(S.num_tree), dim3(MSW_TREE_THREADS), lds, c->stream, S.d_tdesc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_tint, S.d_fac, x, y, xs, S.tree_lds_doubles);
+        else
+            hipLaunchKernelGGL(k_ms_wells_tree_apply<false>, dim3(S.num_tree), dim3(MSW_TREE_THREADS), lds, c->stream, S.d_tdesc, S.d_Brows, S.d_cell, S.d_blkrow, S.d_B, S.d_C, S.d_tint, S.d_fac, x, y, xs, S.tree_lds_doubles);
+    }
+}
+// The dynamic LDS of k_ms_wells_tree_apply for a list of tree wells: every well's z and index lists, and the blocks of the largest well
+// whose blocks fit beside them (wells that fit stage their blocks, the others read them from global memory).  More than 64 KiB per
+// workgroup has to be asked for; where the runtime declines, 64 KiB is the limit.
+void ms_wells_tree_plan(opmhip_ctx* c, const std::vector<MsTreeDesc>& tdesc) {
+    MsWellsDev& S = c->wells.ms;
+    S.tree_lds_doubles = 0;
+    if (tdesc.empty()) return;
+    constexpr int LARGE = 160 * 1024, SMALL = 64 * 1024;
+    const bool large = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ms_wells_tree_apply<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LARGE) == hipSuccess &&
+                       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ms_wells_tree_apply<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LARGE) == hipSuccess;
+    if (!large) (void)hipGetLastError();
+    const size_t cap = (size_t)(large ? LARGE : SMALL) / sizeof(double);
+    size_t need = 0;
+    for (const MsTreeDesc& d : tdesc) {
+        const size_t plain = msw_tree_lds_doubles(d.Mb, d.dest0 - d.par0, false), staged = msw_tree_lds_doubles(d.Mb, d.dest0 - d.par0, true);
+        need = std::max(need, staged <= cap ? staged : plain);
+    }
+    S.tree_lds_doubles = (int)need;
 }
 int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs) {
     const WellsDev& W = c->wells;

@@ -89,10 +89,12 @@ public:
     /// ISTLSolverEbos::getTrueImpesWeights (ISTLSolverEbos.hpp:466-475) to setCprWeights() before each solve.
     /// ms_wells_on_device: multisegment wells are handed to the library once per solve and applied on the device (opmhip_set_ms_wells) instead
     /// of through the host round trip after every product; a list the library refuses (its size cap) falls back to the callback.
+    /// ms_wells_form: the form of that device list (opmhip_set_ms_wells_form): OPMHIP_MS_WELLS_DENSE (default; wells of at most 64 segments),
+    /// OPMHIP_MS_WELLS_TREE (block elimination over the segment tree, up to 1024 segments) or OPMHIP_MS_WELLS_AUTO (tree above the dense cap).
     hipSolverBackend(int linear_solver_verbosity, int maxit_, double tolerance_, unsigned int deviceID_,
                      const std::string& ilu_reorder = "auto", double ilu_relaxation = 0.9,
                      const std::string& linsolver = "ilu0", int cpr_reuse_setup = 3, int cpr_amg_ilu_levels = -1, int cpr_gather_rows = 0,
-                     int ilu_fillin_level = 0, bool ms_wells_on_device = false)
+                     int ilu_fillin_level = 0, bool ms_wells_on_device = false, int ms_wells_form = OPMHIP_MS_WELLS_DENSE)
         : Base(linear_solver_verbosity, maxit_, tolerance_, deviceID_), msOnDevice(ms_wells_on_device) {
         static_assert(block_size == 3, "libopmhip handles 3x3 blocks (three-phase black-oil)");
         opmhip_config cfg;
@@ -127,6 +129,11 @@ public:
         if (rc != OPMHIP_SUCCESS) throw std::logic_error(std::string("hipSolverBackend: ") + opmhip_last_error(nullptr));
         // --ilu-fillin-level: block ILU(n) in place of ILU0 (ignored by the CPR configurations, whose fine smoother is ILU0)
         if (ilu_fillin_level != 0 && opmhip_set_ilu_fillin_level(ctx, ilu_fillin_level) != OPMHIP_SUCCESS) {
+            const std::string msg = std::string("hipSolverBackend: ") + opmhip_last_error(ctx);
+            opmhip_destroy(ctx);
+            throw std::logic_error(msg);
+        }
+        if (ms_wells_form != OPMHIP_MS_WELLS_DENSE && opmhip_set_ms_wells_form(ctx, ms_wells_form) != OPMHIP_SUCCESS) {
             const std::string msg = std::string("hipSolverBackend: ") + opmhip_last_error(ctx);
             opmhip_destroy(ctx);
             throw std::logic_error(msg);

@@ -31,6 +31,81 @@ def tree_D(Mb, rng, branch=0.2, offd=0.6):
     return D
 
 
+def D_from_parents(parents, rng, offd=0.6):
+    """D of a well whose segment i hangs on parents[i] (-1: a root) - any tree or forest, in any numbering; the blocks as tree_D draws
+    them: diagonal blocks U(-1, 1) plus +-4 on the diagonal, the two blocks between a segment and its parent offd * U(-1, 1)"""
+    Mb = len(parents)
+    D = np.zeros((4 * Mb, 4 * Mb))
+    for i in range(Mb):
+        blk = rng.uniform(-1, 1, (4, 4))
+        blk += np.diag(np.sign(np.diag(blk)) * 4.0)
+        D[4 * i:4 * i + 4, 4 * i:4 * i + 4] = blk
+        p = int(parents[i])
+        if p >= 0:
+            D[4 * i:4 * i + 4, 4 * p:4 * p + 4] = offd * rng.uniform(-1, 1, (4, 4))
+            D[4 * p:4 * p + 4, 4 * i:4 * i + 4] = offd * rng.uniform(-1, 1, (4, 4))
+    return D
+
+
+def _mm_stated(A, B):
+    """A @ B with every entry's sum taken over k ascending from 0.0, one rounding per operation (no fused multiply-add)"""
+    s = np.zeros((A.shape[0],) + B.shape[1:])
+    for k in range(A.shape[1]):
+        s = s + (A[:, k:k + 1] * B[k:k + 1] if B.ndim == 2 else A[:, k] * B[k])
+    return s
+
+
+def tree_solve(D, z, parents):
+    """D^-1 z by the block elimination over the segment tree that the device's tree form runs (csrc/solver.hip k_ms_wells_tree_factor and
+    k_ms_wells_tree_apply), in float64 and in the device's order of operations; the device roots every component at its lowest segment
+    number, so `parents` in that rooting gives its bits.
+      factor, from the deepest level up:   S_i = D_ii - sum_c E_c D_ci (children c ascending; each product's entries over k ascending
+                                           from 0.0), S_i^-1 by wells.invert4_stated (partial pivoting INSIDE the block), E_i = D_pi S_i^-1
+      forward, from the deepest level up:  z_p -= E_c z_c over the children of p, ascending
+      backward, from the roots down:       x_i = S_i^-1 (z_i - D_ip x_p)
+    No row is exchanged across blocks: a singular S_i raises wells.SingularWellEquations although D may be regular."""
+    from .wells import invert4_stated
+    parents = [int(p) for p in parents]
+    Mb = len(parents)
+    D = np.asarray(D, float)
+    blk = lambda i, j: D[4 * i:4 * i + 4, 4 * j:4 * j + 4]
+    level = [-1] * Mb
+    for i in range(Mb):
+        path = []
+        j = i
+        while level[j] < 0 and parents[j] >= 0:
+            path.append(j)
+            j = parents[j]
+        if level[j] < 0:
+            level[j] = 0
+        for q in reversed(path):
+            level[q] = level[parents[q]] + 1
+    depth = max(level) + 1
+    by_level = [[i for i in range(Mb) if level[i] == l] for l in range(depth)]
+    children = [[c for c in range(Mb) if parents[c] == i] for i in range(Mb)]
+    Sinv, E = [None] * Mb, [None] * Mb
+    for l in range(depth - 1, -1, -1):
+        for i in by_level[l]:
+            S = blk(i, i).copy()
+            for c in children[i]:
+                S = S - _mm_stated(E[c], blk(c, i))
+            Sinv[i] = invert4_stated(S)
+            if parents[i] >= 0:
+                E[i] = _mm_stated(blk(parents[i], i), Sinv[i])
+    x = np.array(z, float).reshape(Mb, 4).copy()
+    for l in range(depth - 2, -1, -1):
+        for p in by_level[l]:
+            for c in children[p]:
+                x[p] = x[p] - _mm_stated(E[c], x[c])
+    for l in range(depth):
+        for i in by_level[l]:
+            v = x[i]
+            if parents[i] >= 0:
+                v = v - _mm_stated(blk(i, parents[i]), x[parents[i]])
+            x[i] = _mm_stated(Sinv[i], v)
+    return x.reshape(-1)
+
+
 def well_from(D, seg_of_block, cells, Bvals, Cvals):
     """the per-well dict from D (dense), the segment of each block (ascending), its cell and the block values [nblk, 4, 3] in the reference's
     indexing: Bvals[blk, j, k] multiplies x[cell, k] into well equation j; Cvals[blk, k, j] multiplies z[k] into y[cell, j]"""

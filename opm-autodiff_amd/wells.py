@@ -175,7 +175,7 @@ class SingularWellEquations(ValueError):
 
 
 def invert4_stated(D):
-    """D^-1 of one 4 x 4 matrix in an order a kernel can follow (csrc/assemble.hip sw_invert4 is this routine): Gauss-Jordan on [D | I],
+    """D^-1 of one 4 x 4 matrix in an order a kernel can follow (csrc/device_blocks.hpp invert4_stated is this routine): Gauss-Jordan on [D | I],
     column by column; the pivot is the largest |entry| of the column at or below the diagonal, the lowest row on ties; the pivot row is
     divided by the pivot, every other row is updated as a - f * b - one rounding per operation.  A column without a non-zero pivot
     raises SingularWellEquations instead of dividing by it."""
