@@ -1106,7 +1106,7 @@ class HipModel(HipSolver):
 
     def _check(self, rc):
         """(a singular D reported by opmhip_get_std_wells / opmhip_solve_system clears the resident list: the sizes kept here follow.
-        The words looked for are those of std_wells_check's message in csrc/capi_asm.cpp: change both together)"""
+        The words looked for are those of std_wells_check's message in csrc/capi_std_wells.cpp: change both together)"""
         try:
             return HipSolver._check(self, rc)
         except OpmHipError as e:

@@ -1094,7 +1094,7 @@ int opmhip_get_split_assembly(opmhip_ctx* c, long long info[4], double* rest, do
     if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
     return guarded(c, [&]() -> int {
         if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "get_split_assembly before set_pattern");
-        info[0] = (c->split_asm && c->asmb.split_ok && !c->wells.sw.matrix_add) ? 1 : 0;
+        info[0] = (c->split_asm && c->asmb.split_ok && !c->wells.sw.ma.on) ? 1 : 0;
         info[1] = c->A_stale ? 1 : 0;
         info[2] = c->split_assemblies;
         info[3] = c->split_gathers;

@@ -861,7 +861,7 @@ static int upload_ell(opmhip_ctx* c, const CprHostLevel& H, CprLevelDev& L, int 
 // times 50e5, block^T w = e_p, w /= 1000 - from the intensive quantities of the state on the device.  The storage term is
 // the one of the assembly kernel's diagonal lane (assemble.hip: same statements, same order); the 3 x 3 solve is the pivoted
 // elimination of oracle/cpr.hpp: true_impes_weights_cell, statement by statement.  Field numbers and the field-major
-// addressing of the cache: assemble.hip (F_S .. F_RS, Lay<EXT>, iq_at).
+// addressing of the cache: fluid_device.hpp (F_S .. F_RS, Lay<EXT>, iq_at).
 struct WAd { double v, d[3]; };
 __device__ __forceinline__ WAd wad_load(const double* iq, int ncell, int f, int c) {
     const double* o = iq + ((size_t)f * ncell + c) * 4;

@@ -10,6 +10,7 @@
 #include <climits>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/opmhip.h"
@@ -203,6 +204,81 @@ struct MsWellsDev {
 // opmhip_advance_time_level.  h_wi / h_wd: what d_wi / d_wd hold.
 constexpr int SW_X = 0, SW_CONTROL = 4, SW_RW = 5, SW_FLAG = 9, SW_PACK = 10;   // where d_pack's fields begin and its length, in doubles per well
 constexpr int SW_SAVED = SW_RW;                                                 // d_saved's length: the fields in front of r_w
+// The list's features, one part each: its flags, its host copies and its device arrays.  A part is a plain aggregate whose device
+// arrays are named ONCE, in each_dev; dev_part_release and dev_part_install (below, beside dev_free) free, discard and install by that
+// list.  Nothing here owns memory: every array is registered in opmhip_ctx::allocs, which opmhip_destroy frees wholesale.
+// The heads from the well-bore density (opmhip_set_std_wells_head_model).  d_state: per perforation p_perf | q_o | q_w | q_g (4 nperf
+// doubles, field-major), d_saved its copy of the last opmhip_advance_time_level; d_out: density | p_avg | mixture (5 nperf, the
+// mixture 3 per perforation); d_scratch: 8 doubles per perforation for the two dependent passes of wells that do not fit the LDS
+struct SwWellboreDev {
+    bool on = false;
+    bool state_set = false, state_saved = false;   // p_perf has been taken from the cells (or handed in); ... at the last advance_time_level
+    bool initialised_saved = false;                // StdWellsDev::initialised at the last advance_time_level: under this model the bottom-hole pressure is an input of the heads, so a given-up first step goes back to 'not yet set'
+    double *d_depth = nullptr, *d_ref = nullptr, *d_state = nullptr, *d_saved = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    int* d_pref = nullptr;       // per well: the preferred phase
+    template <class F> void each_dev(F f) { f(&d_depth); f(&d_ref); f(&d_state); f(&d_saved); f(&d_out); f(&d_scratch); f(&d_pref); }
+};
+// Crossflow in producers (opmhip_set_std_wells_crossflow): on only while some well of the list has the switch; d_allow: per well 0 / 1,
+// d_dq: per perforation d rate_c / d q_j of the last assemble (9 doubles)
+struct SwCrossflowDev {
+    bool on = false;
+    int* d_allow = nullptr;
+    double* d_dq = nullptr;
+    template <class F> void each_dev(F f) { f(&d_allow); f(&d_dq); }
+};
+// Vaporised oil in the rate model (opmhip_set_std_wells_vaporised_oil): d_sol: per well the dissolved gas [num] | the vaporised oil
+// [num] of the last assemble; allocated while the switch is on
+struct SwVaporisedOilDev {
+    bool on = false;
+    double* d_sol = nullptr;
+    template <class F> void each_dev(F f) { f(&d_sol); }
+};
+// THP limits (opmhip_set_std_wells_thp): on only while some well of the list has one.  d_table: per well the index of its VFP table
+// (-1: no limit), h_table its host copy; d_wd: per well limit, alq, dh; d_out: thp of the last controls | dp of this time step |
+// V - dp of the last assemble (3 num doubles, field-major)
+struct SwThpDev {
+    bool on = false;
+    std::vector<int> h_table;
+    int* d_table = nullptr;
+    double *d_wd = nullptr, *d_out = nullptr;
+    template <class F> void each_dev(F f) { f(&d_table); f(&d_wd); f(&d_out); }
+};
+// Further rate limits (opmhip_set_std_wells_limits): on only while some well of the list has one (or use_list_target = 0).  d_lim: per
+// well oil, water, gas, liquid, resv (+infinity: none), h_lim its host copy; d_use / h_use: per well use_list_target; d_out:
+// coeff [3 num] | resv_current [num] | the averages the coefficients were formed at [5]; resv: some well has a RESV limit
+struct SwLimitsDev {
+    bool on = false, resv = false;
+    std::vector<double> h_lim;
+    std::vector<int> h_use;
+    double *d_lim = nullptr, *d_out = nullptr;
+    int* d_use = nullptr;
+    template <class F> void each_dev(F f) { f(&d_lim); f(&d_use); f(&d_out); }
+};
+// The matrix-add form (opmhip_set_std_wells_matrix_add): d_target [targets]: the distinct blocks of the device's block-CSR the pairs
+// write; d_tptr [targets + 1] / d_contrib [3 pairs]: per block its contributions (well, a, b) in the order of the host path; h_*: what
+// they hold.  (Whether the wells ARE in the matrix is a fact about the matrix, not about this part: StdWellsDev::in_matrix.)
+struct SwMatrixAddDev {
+    bool on = false;
+    int targets = 0, pairs = 0;
+    int *d_target = nullptr, *d_tptr = nullptr, *d_contrib = nullptr;
+    std::vector<int> h_target, h_tptr, h_contrib;
+    template <class F> void each_dev(F f) { f(&d_target); f(&d_tptr); f(&d_contrib); }
+};
+// Group production control (opmhip_set_std_wells_groups): on only while groups are in force.  d_ptr [num + 1] / d_idx: per group its
+// producers, wells ascending; d_of / d_avail / d_resv: per well its group (-1: none), available, a producer in a group with a RESV
+// target; d_guide: 5 per well; d_target: 5 per group; d_state: mode [num] | NUPCOL rates [3 wells], d_saved its copy of the last
+// opmhip_advance_time_level; d_rec: per group rates [3], voidage, reduction [3], guide_sum of the last group data; d_out: what
+// SwLimitsDev::d_out holds (coeff | resv_current | averages), for a list without further limits; h: the host's copy
+struct SwGroupsDev {
+    bool on = false, resv = false;
+    int num = 0, nupcol = 0;
+    int *d_ptr = nullptr, *d_idx = nullptr, *d_of = nullptr, *d_avail = nullptr, *d_resv = nullptr;
+    double *d_guide = nullptr, *d_target = nullptr, *d_state = nullptr, *d_saved = nullptr, *d_rec = nullptr, *d_out = nullptr;
+    StdWellsGroupsLists h;
+    template <class F> void each_dev(F f) {
+        f(&d_ptr); f(&d_idx); f(&d_of); f(&d_avail); f(&d_resv); f(&d_guide); f(&d_target); f(&d_state); f(&d_saved); f(&d_rec); f(&d_out);
+    }
+};
 struct StdWellsDev {
     int num = 0, nperf = 0, nd = 0;
     bool initialised = false;    // the first begin_iteration(0) has set the bottom-hole pressures
@@ -216,56 +292,15 @@ struct StdWellsDev {
     int *d_cpos = nullptr, *d_cptr = nullptr, *d_cperf = nullptr;   // distinct perforated cells: position, range into d_cperf, their perforations in perforation order
     double* d_save = nullptr;    // per distinct cell: the caller's 3 source and 9 dsource entries
     std::vector<double> h_flag;  // opmhip_solve_system: the flags' copy, queued in front of the synchronisation it does anyway
-    // the heads from the well-bore density (opmhip_set_std_wells_head_model).  d_wbstate: per perforation p_perf | q_o | q_w | q_g (4 nperf
-    // doubles, field-major), d_wbsaved its copy of the last opmhip_advance_time_level; d_wbout: density | p_avg | mixture (5 nperf, the
-    // mixture 3 per perforation); d_wbscratch: 8 doubles per perforation for the two dependent passes of wells that do not fit the LDS
-    bool wellbore = false;
-    bool wb_state_set = false, wb_state_saved = false;   // p_perf has been taken from the cells (or handed in); ... at the last advance_time_level
-    bool wb_initialised_saved = false;                   // `initialised` at the last advance_time_level: under this model the bottom-hole pressure is an input of the heads, so a given-up first step goes back to 'not yet set'
-    double *d_wbdepth = nullptr, *d_wbref = nullptr, *d_wbstate = nullptr, *d_wbsaved = nullptr, *d_wbout = nullptr, *d_wbscratch = nullptr;
-    int* d_wbpref = nullptr;     // per well: the preferred phase
-    // crossflow in producers (opmhip_set_std_wells_crossflow): set only while some well of the list has the switch; d_cf: per well 0 / 1,
-    // d_dq: per perforation d rate_c / d q_j of the last assemble (9 doubles)
-    bool crossflow = false;
-    int* d_cf = nullptr;
-    double* d_dq = nullptr;
-    // vaporised oil in the rate model (opmhip_set_std_wells_vaporised_oil): d_sol: per well the dissolved gas [num] | the vaporised oil
-    // [num] of the last assemble; allocated while the switch is on
-    bool vaporised_oil = false;
-    double* d_sol = nullptr;
-    // THP limits (opmhip_set_std_wells_thp): set only while some well of the list has one.  d_thp_table: per well the index of its VFP
-    // table (-1: no limit), h_thp_table its host copy; d_thp_wd: per well limit, alq, dh; d_thp_out: thp of the last controls | dp of this
-    // time step | V - dp of the last assemble (3 num doubles, field-major)
-    bool thp = false;
-    std::vector<int> h_thp_table;
-    int* d_thp_table = nullptr;
-    double *d_thp_wd = nullptr, *d_thp_out = nullptr;
-    // further rate limits (opmhip_set_std_wells_limits): set only while some well of the list has one (or use_list_target = 0).  d_lim: per
-    // well oil, water, gas, liquid, resv (+infinity: none), h_lim its host copy; d_lim_use / h_lim_use: per well use_list_target; d_lim_out:
-    // coeff [3 num] | resv_current [num] | the averages the coefficients were formed at [5]; resv: some well has a RESV limit
-    bool limits = false, resv = false;
-    std::vector<double> h_lim;
-    std::vector<int> h_lim_use;
-    double *d_lim = nullptr, *d_lim_out = nullptr;
-    int* d_lim_use = nullptr;
-    // the matrix-add form (opmhip_set_std_wells_matrix_add): d_ma_target [ma_targets]: the distinct blocks of the device's block-CSR the
-    // pairs write; d_ma_tptr [ma_targets + 1] / d_ma_contrib [3 ma_pairs]: per block its contributions (well, a, b) in the order of the host
-    // path; h_ma_*: what they hold.  in_matrix: opmhip_std_wells_add_to_matrix has run since the last assemble - the solve then installs no
-    // operator form.  h_vp / h_pos: the list's ranges and the internal positions of its perforated cells (the schedule is built from them)
-    bool matrix_add = false, in_matrix = false;
-    int ma_targets = 0, ma_pairs = 0;
-    int *d_ma_target = nullptr, *d_ma_tptr = nullptr, *d_ma_contrib = nullptr;
-    std::vector<int> h_ma_target, h_ma_tptr, h_ma_contrib, h_vp, h_pos;
-    // group production control (opmhip_set_std_wells_groups): set only while groups are in force.  d_grp_ptr [ng + 1] / d_grp_idx: per group
-    // its producers, wells ascending; d_grp_of / d_grp_avail / d_grp_resv: per well its group (-1: none), available, a producer in a group
-    // with a RESV target; d_grp_guide: 5 per well; d_grp_target: 5 per group; d_grp_state: mode [ng] | NUPCOL rates [3 num], d_grp_saved its
-    // copy of the last opmhip_advance_time_level; d_grp_rec: per group rates [3], voidage, reduction [3], guide_sum of the last group data;
-    // d_grp_out: what d_lim_out holds (coeff | resv_current | averages), for a list without further limits; grp_h: the host's copy
-    bool groups = false, grp_resv = false;
-    int grp_num = 0, grp_nupcol = 0;
-    int *d_grp_ptr = nullptr, *d_grp_idx = nullptr, *d_grp_of = nullptr, *d_grp_avail = nullptr, *d_grp_resv = nullptr;
-    double *d_grp_guide = nullptr, *d_grp_target = nullptr, *d_grp_state = nullptr, *d_grp_saved = nullptr, *d_grp_rec = nullptr, *d_grp_out = nullptr;
-    StdWellsGroupsLists grp_h;
+    std::vector<int> h_vp, h_pos;   // the list's ranges and the internal positions of its perforated cells (the matrix-add schedule is built from them)
+    bool in_matrix = false;      // opmhip_std_wells_add_to_matrix has run since the last assemble - the solve then installs no operator form
+    SwWellboreDev wb;
+    SwCrossflowDev cf;
+    SwVaporisedOilDev vo;
+    SwThpDev thp;
+    SwLimitsDev lim;
+    SwMatrixAddDev ma;
+    SwGroupsDev grp;
     double* x() const { return d_pack + (size_t)SW_X * num; }
     double* control() const { return d_pack + (size_t)SW_CONTROL * num; }
     double* rw() const { return d_pack + (size_t)SW_RW * num; }
@@ -305,7 +340,7 @@ struct StdWellsOperatorForm {
     StdWellsOperatorForm& operator=(const StdWellsOperatorForm&) = delete;
 };
 
-// The intensive-quantity record (assemble.hip): fields of value + 3 derivatives, the first of each group; phases, equations, gravity
+// The intensive-quantity record (fluid_device.hpp): fields of value + 3 derivatives, the first of each group; phases, equations, gravity
 enum { F_S = 0, F_P = 3, F_B = 6, F_MOB = 9, F_RHO = 12, F_RS = 15 };
 enum { WATER = 0, OIL = 1, GAS = 2 };
 enum { EQ_OIL = 0, EQ_WATER = 1, EQ_GAS = 2 };
@@ -333,10 +368,12 @@ struct AquifersDev {
 };
 
 // VFP tables (opmhip_set_vfp_tables): the packed host form (vfp_tables.hpp) and its two device arrays, resident for the context's life
+// (a part as the standard wells' are: its device arrays named once, in each_dev)
 struct VfpDev {
     VfpPacked h;
     int* d_desc = nullptr;
     double* d_dbl = nullptr;
+    template <class F> void each_dev(F f) { f(&d_desc); f(&d_dbl); }
 };
 
 // opmhip_reservoir_averages (assemble.hip, k_resv_avg_part / k_resv_avg_final): the first stage runs cdiv(cells, 256) workgroups of 256 lanes,
@@ -671,6 +708,19 @@ void dev_free(opmhip_ctx* c, T** p) {
     (void)hipFree((void*)*p);
     *p = nullptr;
 }
+// A part of the device state (SwThpDev, VfpDev, ...: its device arrays are what its each_dev names).  Release: every array given back,
+// the part as default-constructed - also how a half-built replacement is discarded.  Install: the part in force released, the
+// finished one moved in; a replacement is built apart first, so that a refused call leaves the previous setting in force.
+template <class P>
+void dev_part_release(opmhip_ctx* c, P& part) {
+    part.each_dev([c](auto** p) { dev_free(c, p); });
+    part = P();
+}
+template <class P>
+void dev_part_install(opmhip_ctx* c, P& in_force, P& fresh) {
+    dev_part_release(c, in_force);
+    in_force = std::move(fresh);
+}
 template <class T>
 int dev_upload(opmhip_ctx* c, T** p, const std::vector<T>& h) {
     int rc = dev_alloc(c, p, h.size());
@@ -819,8 +869,11 @@ void launch_aquifer_begin(opmhip_ctx* c);    // pressure_previous_ = p_w of the 
 void launch_aquifer_apply(opmhip_ctx* c);    // Qai_ of every connection; saved and raised source rows of the connected cells (in front of k_assemble)
 void launch_aquifer_restore(opmhip_ctx* c);  // the caller's source rows back (behind k_assemble)
 void launch_aquifer_end(opmhip_ctx* c, double dt);
-// standard wells on the device (opmhip_set_std_wells; assemble.hip)
-int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_asm.cpp: the zero-pivot flags as the caller has just read them back; a singular D clears the list
+// standard wells on the device (opmhip_set_std_wells; kernels and launchers: std_wells.hip, entry points: capi_std_wells.cpp)
+int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_std_wells.cpp: the zero-pivot flags as the caller has just read them back; a singular D clears the list
+// capi_std_wells.cpp: the list's part of opmhip_advance_time_level / opmhip_update_failed, on the context's stream
+int std_wells_save_state(opmhip_ctx* c);
+int std_wells_restore_state(opmhip_ctx* c);
 void launch_std_wells_solve(opmhip_ctx* c, bool first);   // heads, then the wells alone against the frozen reservoir (iteration 0)
 void launch_std_wells_wellbore(opmhip_ctx* c, bool first, bool init);   // the heads from the well-bore density, in front of launch_std_wells_solve
 void launch_std_wells_controls(opmhip_ctx* c);            // updateWellControls
@@ -840,6 +893,7 @@ void launch_hyst_update(opmhip_ctx* c, const double* d_sw_ow = nullptr, const do
 int launch_relative_change(opmhip_ctx* c);   // -> asmb.d_rc[512 .. 514)
 int launch_convergence(opmhip_ctx* c, double dt, double tol_cnv);
 void launch_reservoir_averages(opmhip_ctx* c);   // -> asmb.d_resv[RESV_MAX_PARTS * 8 .. + RESV_OUT)
+double* resv_avg_kernels(opmhip_ctx* c);         // its two kernels without a profiling scope of their own (launch_std_wells_resv); returns where the RESV_OUT results go
 void launch_u8_to_internal(opmhip_ctx* c, const unsigned char* nat, unsigned char* internal);
 void launch_u8_to_natural(opmhip_ctx* c, const unsigned char* internal, unsigned char* nat);
 void launch_iq_to_natural(opmhip_ctx* c, double* d_nat);
@@ -848,7 +902,7 @@ void launch_source_scatter(opmhip_ctx* c, int n, const int* d_pos, const double*
 int iq_doubles_per_cell(const opmhip_ctx* c);
 int asm_max_rows();
 int launch_fluid_probe(opmhip_ctx* c, int pr, int sr, int n, const double* d_in, double* d_out);
-// opmhip_vfp_probe: table = the index into the packed set; d_in = aqua | liquid | vapour | thp | alq | bhp_target (n each), d_out 10 per point
+// opmhip_vfp_probe (std_wells.hip): table = the index into the packed set; d_in = aqua | liquid | vapour | thp | alq | bhp_target (n each), d_out 10 per point
 int launch_vfp_probe(opmhip_ctx* c, int table, int n, const double* d_in, bool has_target, double* d_out);
 int launch_gas_probe(opmhip_ctx* c, int pr, int n, const double* d_in, double* d_out);
 int launch_sat_probe(opmhip_ctx* c, int sr, int cfg, const double* d_eps, int n, const double* d_in, double* d_out);

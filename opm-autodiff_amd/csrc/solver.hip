@@ -2612,10 +2612,10 @@ void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const
 }
 void launch_std_wells_add_to_matrix(opmhip_ctx* c) {
     const WellsDev& W = c->wells;
-    const StdWellsDev& S = W.sw;
+    const SwMatrixAddDev& M = W.sw.ma;
     ensure_A(c);
     const int ps = prof_begin(c, PROF_ASSEMBLE);   // (the well model's, as the standard wells' other launches: one scope)
-    hipLaunchKernelGGL(k_std_wells_add_to_matrix, dim3((S.ma_targets + 63) / 64), dim3(64), 0, c->stream, S.ma_targets, S.d_ma_target, S.d_ma_tptr, S.d_ma_contrib,
+    hipLaunchKernelGGL(k_std_wells_add_to_matrix, dim3((M.targets + 63) / 64), dim3(64), 0, c->stream, M.targets, M.d_target, M.d_tptr, M.d_contrib,
                        W.d_val_pointers, W.d_C, W.d_D, W.d_B, c->d_A);
     prof_end(c, ps);
 }

@@ -1,4 +1,4 @@
-// Host set-up of the VFP tables and of the resident standard wells' THP limits (vfp_tables.hpp).  No HIP call: capi_asm.cpp uploads what
+// Host set-up of the VFP tables and of the resident standard wells' THP limits (vfp_tables.hpp).  No HIP call: capi_std_wells.cpp uploads what
 // is built here.
 #include <cmath>
 #include <cstdarg>

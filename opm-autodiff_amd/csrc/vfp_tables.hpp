@@ -1,6 +1,6 @@
 // Host set-up of the VFP tables (opmhip_set_vfp_tables) and of the THP limits of the resident standard wells (opmhip_set_std_wells_thp):
 // every check of what the caller hands over and the packing of the arrays the kernels read.  Pure host work on its arguments, no context
-// and no HIP call, so that it is built and checked without a device (tests/san/vfp_tables_san.cpp).  capi_asm.cpp allocates, uploads and
+// and no HIP call, so that it is built and checked without a device (tests/san/vfp_tables_san.cpp).  capi_std_wells.cpp allocates, uploads and
 // launches.  A refusal is a code other than OPMHIP_SUCCESS with its text in `msg`, for the caller's fail(); the outputs are then untouched.
 #pragma once
 #include <string>

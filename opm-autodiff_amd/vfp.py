@@ -1,6 +1,6 @@
 """Vertical-flow-performance tables (VFPPROD / VFPINJ): the bottom-hole pressure of a well as a function of its rates and its tubing-head
 pressure, and the inverse look-up - stated on the host in an order a kernel can follow, operation by operation.  The device functions
-(csrc/assemble.hip vfp_*, opmhip_vfp_probe) are this file, bit for bit; NumPy's elementwise arithmetic is IEEE arithmetic without
+(csrc/std_wells.hip vfp_*, opmhip_vfp_probe) are this file, bit for bit; NumPy's elementwise arithmetic is IEEE arithmetic without
 contraction, so every function below takes arrays (one entry per point) as well as plain floats.
 
 What of the reference this restates:

@@ -147,7 +147,7 @@ import numpy as np
 
 from . import vfp as vfp_mod
 
-OIL, WATER, GAS = 0, 1, 2          # equation / component order of the blocks (csrc/assemble.hip: EQ_OIL, EQ_WATER, EQ_GAS)
+OIL, WATER, GAS = 0, 1, 2          # equation / component order of the blocks (csrc/internal.hpp: EQ_OIL, EQ_WATER, EQ_GAS)
 PH_W, PH_O, PH_G = 0, 1, 2         # phase order of the intensive-quantity record (opmhip_get_iq)
 F_S, F_P, F_B, F_MOB, F_RHO, F_RS = 0, 3, 6, 9, 12, 15
 F_RV = 16                          # in the 19-field record only (a fluid with PVTG, ROCKTAB or pc_scaling)
