@@ -50,6 +50,8 @@ __device__ __forceinline__ Ad ad_max(const Ad& a, const Ad& b) { return (a.v > b
 __device__ __forceinline__ Ad ad_min(const Ad& a, const Ad& b) { return (a.v < b.v) ? a : b; }
 __device__ __forceinline__ double val(const Ad& a) { return a.v; }
 __device__ __forceinline__ double val(double a) { return a; }
+__device__ __forceinline__ void set_val(Ad& a, double v) { a.v = v; }
+__device__ __forceinline__ void set_val(double& a, double v) { a = v; }
 template <class E> __device__ __forceinline__ E mk(double x, int idx);
 template <> __device__ __forceinline__ Ad mk<Ad>(double x, int idx) { return ad_var(x, idx); }
 template <> __device__ __forceinline__ double mk<double>(double x, int) { return x; }
@@ -93,7 +95,11 @@ template <class DP> __device__ __forceinline__ int seg_right(DP x, int n, double
 template <class E, class DP> __device__ __forceinline__ E tab1(DP x, DP y, int n, const E& xv) {
     const int s = seg_right(x, n, val(xv));
     const double x0 = x[s], x1 = x[s + 1], y0 = y[s], y1 = y[s + 1];
-    return y0 + (y1 - y0) * (xv - x0) / (x1 - x0);
+    E r = y0 + (y1 - y0) * (xv - x0) / (x1 - x0);
+    // the right end of a segment is met only on the table's last node (an interior node belongs to the segment on its right); there
+    // the product and the sum above can miss the sample by an ulp, so the value is the sample itself and the slope stays the segment's
+    if (val(xv) == x1) set_val(r, y1);
+    return r;
 }
 // plain bilinear interpolation in (x, y) with per-column y grids (UniformXTabulated2DFunction; the policy the Norne PVT
 // points select): oil (x = Rs, y = p_o)

@@ -21,6 +21,8 @@ struct Ev {
 };
 inline double value(const Ev& a) { return a.v; }
 inline double value(double a) { return a; }
+inline void setValue(Ev& a, double v) { a.v = v; }
+inline void setValue(double& a, double v) { a = v; }
 
 inline Ev operator-(const Ev& a) { Ev r; r.v = -a.v; for (int i = 0; i < 3; ++i) r.d[i] = -a.d[i]; return r; }
 inline Ev operator+(const Ev& a, const Ev& b) { Ev r; r.v = a.v + b.v; for (int i = 0; i < 3; ++i) r.d[i] = a.d[i] + b.d[i]; return r; }

@@ -34,7 +34,9 @@ struct Tab1D {
     template <class E> E eval(const E& xv) const {
         const int s = segment(value(xv));
         const double x0 = x[s], x1 = x[s + 1], y0 = y[s], y1 = y[s + 1];
-        return y0 + (y1 - y0) * (xv - x0) / (x1 - x0);
+        E r = y0 + (y1 - y0) * (xv - x0) / (x1 - x0);
+        if (value(xv) == x1) setValue(r, y1);   // the last node: the sample itself (the sum above can miss it by an ulp); as the device's tab1
+        return r;
     }
 };
 
