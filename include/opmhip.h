@@ -623,7 +623,11 @@ typedef struct opmhip_endpoint_scaling {
                                              * cell's SATNUM tables (opmhip_sat_end_points) */
 } opmhip_endpoint_scaling;
 /* Needs a fluid with pc_scaling set, and set_static.  eps == NULL: scaling off.  Recomputes the cached intensive quantities
- * if a state is set.  Not to be combined with opmhip_set_pcw (PCW then is points[OPMHIP_EPS_MAXPCOW] with pcw = 1). */
+ * if a state is set.  Not to be combined with opmhip_set_pcw (PCW then is points[OPMHIP_EPS_MAXPCOW] with pcw = 1).
+ * Refused with OPMHIP_INVALID_ARGUMENT, naming the cell and its saturation region, before anything changes: with sat_scaling, points
+ * that leave a curve no saturation interval (the maps divide by its length); a vertical mode for a curve whose table denominator is 0
+ * - the table's maximum in mode 1, its value at the displacing phase's critical saturation in mode 2.  With opmhip_set_hysteresis
+ * in force the imbibition points and regions are held to the same; opmhip_set_hysteresis checks them under the options in force. */
 int opmhip_set_endpoint_scaling(opmhip_ctx* ctx, const opmhip_endpoint_scaling* eps);
 /* the end points of the tables of saturation region sat_region (opm-common's satfunc end-point extraction, restated):
  * out[OPMHIP_EPS_COUNT].  Needs opmhip_set_fluid only. */

@@ -361,6 +361,18 @@ int opmhip_set_endpoint_scaling(opmhip_ctx* c, const opmhip_endpoint_scaling* e)
                 OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
                 OPMHIP_HIP(c, hipMemcpy(satnum.data(), A.d_satnum, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
             }
+            // with hysteresis in force the imbibition curves are scaled by the same options: their points are checked again
+            std::vector<int> imbnum;
+            std::vector<double> imbpts;
+            if (A.d_hyst) {
+                imbnum.resize(N);
+                OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
+                OPMHIP_HIP(c, hipMemcpy(imbnum.data(), A.d_imbnum, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+                if (A.d_eps_imb) {
+                    imbpts.resize((size_t)EPS_COUNT * N);
+                    OPMHIP_HIP(c, hipMemcpy(imbpts.data(), A.d_eps_imb, imbpts.size() * sizeof(double), hipMemcpyDeviceToHost));
+                }
+            }
             std::vector<double> v((size_t)EPS_COUNT * N);   // field-major, internal order
             for (int pos = 0; pos < N; ++pos) {
                 const int i = P.fromOrder[pos];   // natural id (ghost cells keep their place behind the owned ones)
@@ -370,10 +382,17 @@ int opmhip_set_endpoint_scaling(opmhip_ctx* c, const opmhip_endpoint_scaling* e)
                     if (!std::isfinite(s[f])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_endpoint_scaling: end point %d of cell %d is not finite", f, i);
                     v[(size_t)f * N + pos] = s[f];
                 }
-                // the scaling maps [first, last] point of every curve onto the table's: the scaled intervals must not be empty
-                const bool ok = s[EPS_SWL] < s[EPS_SWU] && s[EPS_SGL] < s[EPS_SGU] && s[EPS_SWCR] < s[EPS_SWU] && s[EPS_SGCR] < s[EPS_SGU] &&
-                                s[EPS_SWL] + s[EPS_SGL] < 1.0 - s[EPS_SOWCR] && s[EPS_SOGCR] < 1.0 - s[EPS_SWL] - s[EPS_SGL];
-                if (e->sat_scaling && !ok) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_endpoint_scaling: the end points of cell %d leave a curve no saturation interval", i);
+                const std::string why = end_points_refusal(s, &A.sat_eps[(size_t)satnum[pos] * EPS_COUNT], e->sat_scaling != 0, e->krw, e->kro, e->krg);
+                if (!why.empty())
+                    return fail(c, OPMHIP_INVALID_ARGUMENT, "set_endpoint_scaling: the end points of cell %d (saturation region %d) %s", i, satnum[pos], why.c_str());
+                if (A.d_hyst) {
+                    const double* uI = &A.sat_eps[(size_t)imbnum[pos] * EPS_COUNT];
+                    if (!imbpts.empty())
+                        for (int f = 0; f < EPS_COUNT; ++f) s[f] = imbpts[(size_t)f * N + pos];
+                    const std::string whyI = end_points_refusal(imbpts.empty() ? uI : s, uI, e->sat_scaling != 0, e->krw, e->kro, e->krg);
+                    if (!whyI.empty())
+                        return fail(c, OPMHIP_INVALID_ARGUMENT, "set_endpoint_scaling: the imbibition end points of cell %d (saturation region %d) %s", i, imbnum[pos], whyI.c_str());
+                }
             }
             int rc;
             if (!A.d_eps && (rc = dev_alloc(c, &A.d_eps, v.size()))) return rc;
@@ -753,17 +772,27 @@ int opmhip_set_hysteresis(opmhip_ctx* c, int kr_model, const int* imbnum, const 
             for (int i = 0; i < N; ++i)
                 if (imbnum[i] < 0 || imbnum[i] >= A.num_sat) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_hysteresis: imbnum[%d] out of range", i);
             int rc;
-            if ((rc = upload_cells(c, &A.d_imbnum, imbnum))) return rc;
-            if (imb) {
-                std::vector<double> v((size_t)EPS_COUNT * N);   // field-major, internal order
+            // every refusal comes before the first upload: a refused call leaves the previous settings in force
+            std::vector<double> v(imb ? (size_t)EPS_COUNT * N : 0);   // field-major, internal order
+            if (A.d_eps) {   // the imbibition curves are scaled by the options of opmhip_set_endpoint_scaling: the same checks
+                const bool satScaling = (A.epscfg & 1) != 0;
+                const int mKrw = (A.epscfg >> 2) & 3, mKro = (A.epscfg >> 4) & 3, mKrg = (A.epscfg >> 6) & 3;
                 for (int pos = 0; pos < N; ++pos) {
                     const int i = P.fromOrder[pos];
+                    const double* u = &A.sat_eps[(size_t)imbnum[i] * EPS_COUNT];
+                    double s[EPS_COUNT];
                     for (int f = 0; f < EPS_COUNT; ++f) {
-                        const double x = imb->points[f] ? imb->points[f][i] : A.sat_eps[(size_t)imbnum[i] * EPS_COUNT + f];
-                        if (!std::isfinite(x)) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_hysteresis: imbibition end point %d of cell %d is not finite", f, i);
-                        v[(size_t)f * N + pos] = x;
+                        s[f] = imb && imb->points[f] ? imb->points[f][i] : u[f];
+                        if (!std::isfinite(s[f])) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_hysteresis: imbibition end point %d of cell %d is not finite", f, i);
+                        if (imb) v[(size_t)f * N + pos] = s[f];
                     }
+                    const std::string why = end_points_refusal(s, u, satScaling, mKrw, mKro, mKrg);
+                    if (!why.empty())
+                        return fail(c, OPMHIP_INVALID_ARGUMENT, "set_hysteresis: the imbibition end points of cell %d (saturation region %d) %s", i, imbnum[i], why.c_str());
                 }
+            }
+            if ((rc = upload_cells(c, &A.d_imbnum, imbnum))) return rc;
+            if (imb) {
                 if (!A.d_eps_imb && (rc = dev_alloc(c, &A.d_eps_imb, v.size()))) return rc;
                 OPMHIP_HIP(c, hipMemcpy(A.d_eps_imb, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
             } else dev_free(c, &A.d_eps_imb);

@@ -314,4 +314,20 @@ void sat_end_points(const FluidTables& T, int s, double* out) {
     for (int f = 0; f < EPS_COUNT; ++f) out[f] = T.dbl[sd[s].eps + f];
 }
 
+std::string end_points_refusal(const double* s, const double* u, bool sat_scaling, int krw, int kro, int krg) {
+    // the scaling maps [first, last] point of every curve onto the table's: the scaled intervals must not be empty
+    const bool ok = s[EPS_SWL] < s[EPS_SWU] && s[EPS_SGL] < s[EPS_SGU] && s[EPS_SWCR] < s[EPS_SWU] && s[EPS_SGCR] < s[EPS_SGU] &&
+                    s[EPS_SWL] + s[EPS_SGL] < 1.0 - s[EPS_SOWCR] && s[EPS_SOGCR] < 1.0 - s[EPS_SWL] - s[EPS_SGL];
+    if (sat_scaling && !ok) return "leave a curve no saturation interval";
+    // eps_vertical_krw / eps_vertical_krn: mode 1 forms fm / fmax, mode 2 fr / fdisp, both out of the table
+    const struct { const char* curve; int mode, fmax, fdisp; } V[4] = {{"krw", krw, EPS_MAXKRW, EPS_KRWR}, {"krow", kro, EPS_MAXKROW, EPS_KRORW},
+                                                                      {"krog", kro, EPS_MAXKROG, EPS_KRORG}, {"krg", krg, EPS_MAXKRG, EPS_KRGR}};
+    for (const auto& v : V) {
+        if (v.mode == 1 && !(u[v.fmax] != 0.0)) return std::string("scale ") + v.curve + " vertically (mode 1) by a table maximum of 0";
+        if (v.mode == 2 && !(u[v.fdisp] != 0.0))
+            return std::string("scale ") + v.curve + " vertically (mode 2) by a table value of 0 at the displacing phase's critical saturation";
+    }
+    return "";
+}
+
 }  // namespace opmhip

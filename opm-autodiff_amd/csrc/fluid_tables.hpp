@@ -42,6 +42,11 @@ enum EpsField { EPS_SWL = 0, EPS_SWCR, EPS_SWU, EPS_SOWCR, EPS_SGL, EPS_SGCR, EP
                 EPS_KRWR, EPS_KRORW, EPS_KRGR, EPS_KRORG, EPS_COUNT };
 // the end points of saturation region s of a table set built by build_fluid_tables (host copy of the blob)
 void sat_end_points(const struct FluidTables& T, int s, double* out);
+// what keeps a cell's scaled end points s[EPS_COUNT] over a region's own u[EPS_COUNT] from being used ("" = nothing): with
+// sat_scaling, a curve whose scaled saturation interval is empty (the horizontal maps divide by its length); for each curve under
+// vertical scaling, a table denominator of 0 - the table's maximum in mode 1, its value at the displacing phase's critical
+// saturation in mode 2 (krw, kro, krg: the modes, 0 | 1 | 2).  Host only, no HIP.
+std::string end_points_refusal(const double* s, const double* u, bool sat_scaling, int krw, int kro, int krg);
 
 struct FluidTables {
     std::vector<double> dbl;

@@ -308,10 +308,13 @@ def _rel_perms(S, sw, sg, num):
     return krw, kro, krg
 
 
-def exact(fluid, rows, extras=None, num=Fr, T=None):
+def exact(fluid, rows, extras=None, num=Fr, T=None, sat_law=None):
     """-> (probe (N, 8), sat (N, 5), iq (N, 6), mu) as arrays of `num` objects (None where the exact statement divides by zero):
     the columns of capi.HipFluid.probe(p, x3 as Rs, Sw, Sg), of sat_probe(Sw, Sg), and 1/B and the mobilities of the cache; mu: per
-    cell the three exact viscosities behind the mobilities"""
+    cell the three exact viscosities behind the mobilities.
+    sat_law: another law of relative permeability and capillary pressure (tests/sat_states.py: scaled end points, hysteresis):
+    sat_law(cell, S, sw, sg, num) -> (krw, kro, krg, pcow, pcgo) in `num`; asked with num = float for the capillary pressures behind
+    the phase pressures, which are doubles the code forms"""
     T = T or tables(fluid)
     rows = np.asarray(rows, np.float64)
     N = len(rows)
@@ -353,9 +356,13 @@ def exact(fluid, rows, extras=None, num=Fr, T=None):
         P[c, 3] = guard(rs_sat, D, p)
         oil = None if sat_f is None else guard(_oil, D, p, rs_probe, bool(sat_f))
         P[c, 2], P[c, 6] = (None, None) if oil is None else oil
-        P[c, 4] = pwlin(S["sw"], S["pcow"], sw, num)
-        P[c, 5] = pwlin(S["so"], S["pcgo"], 1.0 - swco - sg_probe, num)
-        kr = guard(_rel_perms, S, sw, sg_probe)
+        if sat_law is None:
+            P[c, 4] = pwlin(S["sw"], S["pcow"], sw, num)
+            P[c, 5] = pwlin(S["so"], S["pcgo"], 1.0 - swco - sg_probe, num)
+            kr = guard(_rel_perms, S, sw, sg_probe)
+        else:
+            law = sat_law(c, S, sw, sg_probe, num)
+            kr, P[c, 4], P[c, 5] = law[:3], law[3], law[4]
         Sx[c, :3] = kr
         Sx[c, 3], Sx[c, 4] = P[c, 4], P[c, 5]
         # -- the cache: update_iq's own decisions, on the doubles it forms --
@@ -366,8 +373,11 @@ def exact(fluid, rows, extras=None, num=Fr, T=None):
         else:
             sg = 0.0
         so = 1.0 - sw - sg
-        pcw_f = pwlin(S["sw"], S["pcow"], sw)
-        pcg_f = pwlin(S["so"], S["pcgo"], 1.0 - swco - sg)
+        if sat_law is None:
+            pcw_f = pwlin(S["sw"], S["pcow"], sw)
+            pcg_f = pwlin(S["so"], S["pcgo"], 1.0 - swco - sg)
+        else:
+            pcw_f, pcg_f = (float(v) for v in sat_law(c, S, sw, sg, float)[3:5])
         pC = (-pcw_f, 0.0, pcg_f)
         ref = 2 if m == SW_PG_RV else 1
         pph = [p + (pC[k] - pC[ref]) for k in range(3)]
@@ -391,7 +401,7 @@ def exact(fluid, rows, extras=None, num=Fr, T=None):
         except ZeroDivisionError:
             Q[c, :] = None
             continue
-        krc = guard(_rel_perms, S, sw, sg)
+        krc = guard(_rel_perms, S, sw, sg) if sat_law is None else sat_law(c, S, sw, sg, num)[:3]
         w = guard(_water, D, pph[0])
         o = guard(_oil, D, pph[1], rs, bool(saturated)) if math.isfinite(rs) else None
         g = guard(_gas, D, pph[2], rv, bool(gsat))

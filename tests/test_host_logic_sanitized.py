@@ -6,7 +6,9 @@ runtime calls of reorder.cpp from the host heap.  The GPU sanitizers are not ava
 to run them on.  The CPR pressure-AMG set-up (csrc/cpr_setup.cpp) is built the same way, linked alone (tests/san/cpr_setup_san.cpp: level
 invariants on every hierarchy, the oracle's hierarchy alongside).  So is the host set-up of the resident standard wells and analytic
 aquifers (csrc/source_lists.cpp, linked alone; tests/san/source_lists_san.cpp: the grouping by distinct cell against a quadratic restatement,
-every refusal with its code and its text, the aquifers' tables, step scalars and sums)."""
+every refusal with its code and its text, the aquifers' tables, step scalars and sums).  So is the check of scaled saturation end
+points that opmhip_set_endpoint_scaling and opmhip_set_hysteresis share (end_points_refusal in csrc/fluid_tables.cpp, linked alone;
+tests/san/end_points_san.cpp: accepted and refused inputs over three saturation regions built by build_fluid_tables)."""
 import os
 import shutil
 import subprocess
@@ -74,3 +76,22 @@ def test_source_lists_under_asan_ubsan(tmp_path):
     lines = out.splitlines()   # every case of the lists ran
     assert sum(l.startswith("ok  group_by_cell: ") for l in lines) == 30 and sum(l.startswith("ok  refused: ") for l in lines) == 50
     assert sum(l.startswith("ok  ") for l in lines) == 93
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_end_points_refusal_under_asan_ubsan(tmp_path):
+    # the check of scaled end points (end_points_refusal, csrc/fluid_tables.cpp) that opmhip_set_endpoint_scaling and opmhip_set_hysteresis
+    # share; fluid_tables.cpp alone, no HIP stand-ins
+    exe = str(tmp_path / "end_points_san")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           "-D_GLIBCXX_ASSERTIONS", "-ffp-contract=off", os.path.join(ROOT, "tests", "san", "end_points_san.cpp"), os.path.join(CSRC, "fluid_tables.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-4000:]
+    assert "all checks passed" in out and "FAILED" not in out
+    assert "runtime error" not in out and "AddressSanitizer" not in out and "LeakSanitizer" not in out, out[-4000:]
+    lines = out.splitlines()   # every case of the list ran
+    assert sum(l.startswith("ok  accepted: ") for l in lines) == 11 and sum(l.startswith("ok  refused: ") for l in lines) == 15
