@@ -789,6 +789,74 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * over the aquifer's connections in connection order; fluxValue_ = W_flux_; aquifer_pressure_ = pa0_ - W_flux_ / (total_compr *
  * initial_watvolume).  opmhip_update_failed leaves the aquifers alone: a rolled-back step never reaches endTimeStep. */
 
+/* ---- passive tracers, resident on the device.  Additive to ABI 11 ------------------------------------------------------------
+ * EclTracerModel (ebos/ecltracermodel.hh:113-134, 156-439; ebos/eclgenerictracermodel.cc:86-281): tracers carried by one phase each,
+ * advanced once per time step by one scalar transport solve per phase from the converged state - the cached intensive quantities, the
+ * transmissibilities, areas, THPRES, depths and volumes of opmhip_set_static, all of them in HBM already.  The tracers of one phase share
+ * their matrix and differ in their right-hand sides (ecltracermodel.hh:476-479); the reference solves them one after the other
+ * (eclgenerictracermodel.cc:272-277), here they advance in lock step, their vectors interleaved per cell, so that every product and
+ * sweep reads a matrix or factor entry once for all of them.
+ * The equations, per phase and cell I (assembleTracerEquations_, :216-337), every sum sequential in this order:
+ *   storage  r_t[I] = ((vol c_t[I] - storage1_t[I]) V) / dt,  M[I][I] = (vol V) / dt,  vol = max(S b porosity, 1e-10) (computeVolume_, :158-179);
+ *   faces in ascending natural column index (the stencil's own face order is opm-grid's and not in the reference tree: UNVERIFIED):
+ *            f = A v b_up with v the phase's volumeFlux evaluated with I as the interior cell - the value arithmetic of the assembly's
+ *            face flux (ebos/eclfluxmodule.hh:212-357) -, r_t[I] += f c_t[up]; where I is upstream M[I][I] += f and M[J][I] = -f
+ *            (:285-288), the entry (I, J) being filled from a second evaluation with J as the interior cell;
+ *   wells    per connection, in list order, with q the phase's component surface rate, positive into the reservoir
+ *            (volumetricSurfaceRateForConnection, wells/WellInterface_impl.hpp:434-445): q > 0: r_t[I] -= q c_inj[t]; q < 0:
+ *            r_t[I] -= q c_t[I] and M[I][I] -= q (:293-336).
+ * The solver (eclgenerictracermodel.cc:248-281): ILU0 with relaxation 1 and BiCGStab from x = 0, defect reduction 1e-2, at most 100
+ * iterations.  Dune's BiCGSTABSolver and SeqILU are not in the reference tree: the recurrence is the block solver's (right-preconditioned,
+ * the stopping test at each half iteration, bda/cusparseSolverBackend.cu:60-184) and the factorisation an exact ILU0 of the matrix in the
+ * context's ordering, scheduled by the level sets of its lower triangle.  Iteration counts are UNVERIFIED against Dune's.
+ * NOT covered: gas tracers (refused: the library's fluid always carries dissolved gas and the reference refuses gas tracers under DISGAS,
+ * ecltracermodel.hh:465-467), oil tracers on a fluid with PVTG (refused, :455-457), decomposed contexts (refused, as doInit gives up
+ * on parallel runs, eclgenerictracermodel.cc:105-111), restart output, partitioned or adsorbing tracers, the TBLK / TVDPF parsing
+ * (opm-common's: the caller hands in concentrations). */
+#define OPMHIP_TRACERS_MAX_PER_PHASE 32
+typedef struct opmhip_tracer_result {
+    int converged;      /* 0: the stopping rule was not met within maxit iterations, or a pivot of the ILU0 was zero or not finite */
+    double iterations;  /* half iterations count 0.5 (bda/cusparseSolverBackend.cu:90, 131, 172) */
+    double reduction;   /* norm / norm_0 (:173); 0 where the right-hand side was zero */
+} opmhip_tracer_result;
+/* replaces: EclTracerModel::init -> doInit + prepareTracerBatches (eclgenerictracermodel.cc:86-245, ecltracermodel.hh:441-479).
+ * phase[t]: 0 water, 1 oil, 2 gas; concentration[t * Nb + cell], natural cell order.  num_tracers = 0 clears.  Also computes, on the
+ * host, the level sets of the ordering's lower triangle and the rows' faces in natural column order.  OPMHIP_NOT_READY before
+ * opmhip_set_static; OPMHIP_INVALID_ARGUMENT (the text names the reason) for a gas tracer, an oil tracer on a PVTG fluid, a decomposed
+ * context or one with ghost cells, a phase outside 0 .. 2, more than OPMHIP_TRACERS_MAX_PER_PHASE tracers of one phase, a null array,
+ * a concentration that is not finite.  A refused call leaves no tracers set. */
+int opmhip_set_tracers(opmhip_ctx* ctx, int num_tracers, const int* phase, const double* concentration);
+/* replaces: the constants of linearSolve_ (eclgenerictracermodel.cc:256-262).  Defaults 1e-2, 100.  tolerance > 0 and finite, maxit >= 1 */
+int opmhip_set_tracer_solver(opmhip_ctx* ctx, double tolerance, int maxit);
+/* replaces: the well loop's inputs of assembleTracerEquations_ (:293-336).  cell[i]: natural cell of connection i (a cell may appear
+ * several times: its connections are applied in list order); rate[3 i + phase]: the component surface rate of water, oil, gas, positive
+ * into the reservoir; injected[t * n + i]: the concentration of tracer t in what connection i injects (WTRACER).  n = 0 clears; the list
+ * stays until it is replaced.  Needs opmhip_set_tracers.  OPMHIP_INVALID_ARGUMENT for a cell outside [0, Nb), a null array, a value that
+ * is not finite. */
+int opmhip_set_tracer_connections(opmhip_ctx* ctx, int n, const int* cell, const double* rate, const double* injected);
+/* replaces: EclTracerModel::beginTimeStep -> updateStorageCache (:340-359): c_initial = c, storage1 = vol(state now present) c_initial.
+ * Calling it again without an end (a chopped step) reproduces the first call's values from the rolled-back state.
+ * OPMHIP_NOT_READY before opmhip_set_state.  A no-op without tracers. */
+int opmhip_tracers_begin_time_step(opmhip_ctx* ctx);
+/* replaces: EclTracerModel::endTimeStep -> advanceTracerFields (:362-383) with linearSolveBatchwise_ (eclgenerictracermodel.cc:264-281):
+ * assembles at the state now present (the converged one: the record cache is current after the last opmhip_update), solves
+ * M dx_t = r_t for every tracer from x = 0 and sets c_t -= dx_t.  A solve that did not converge is applied all the same and reported,
+ * as the reference does.  res: NULL or num_tracers records.  A zero or non-finite pivot of the ILU0 is replaced by 1, reported as
+ * converged = 0 on every tracer of the phase and named in opmhip_last_error (the call still returns OPMHIP_SUCCESS).
+ * OPMHIP_NOT_READY before the first opmhip_tracers_begin_time_step; OPMHIP_INVALID_ARGUMENT unless dt > 0.  A no-op without tracers. */
+int opmhip_tracers_end_time_step(opmhip_ctx* ctx, double dt, opmhip_tracer_result* res);
+/* what EclTracerModel::tracerConcentration reports: concentration[t * Nb + cell], natural order */
+int opmhip_get_tracers(opmhip_ctx* ctx, double* concentration);
+/* for tests: the system assembleTracerEquations_ forms for one phase at the state now present - matrix[nnzb] in the order of the
+ * pattern handed to opmhip_set_pattern, residual[j * Nb + cell] for the phase's j-th tracer - nothing solved, nothing changed.
+ * OPMHIP_NOT_READY before the first opmhip_tracers_begin_time_step */
+int opmhip_get_tracer_system(opmhip_ctx* ctx, int phase, double dt, double* matrix, double* residual);
+/* for tests: storageOfTimeIndex1_ and concentrationInitial_ of the last opmhip_tracers_begin_time_step, [t * Nb + cell] each (either may be NULL) */
+int opmhip_get_tracer_storage(opmhip_ctx* ctx, double* storage1, double* concentration_initial);
+/* for measurements: device milliseconds of the last opmhip_tracers_end_time_step, summed over the phases (HIP events on the context's
+ * stream): ms[0] system, ms[1] ILU0 factorisation, ms[2] BiCGStab; info[0] levels of the sweeps' schedule, info[1] BiCGStab launches */
+int opmhip_get_tracer_timings(opmhip_ctx* ctx, double* ms, int* info);
+
 /* ---- standard wells, resident on the device.  Additive to ABI 11 -----------------------------------------------------------
  * The well model the Python package states on the host (wells.py StandardWells: vertical standard wells, 4 unknowns per well - the
  * surface rates of oil, water and gas INTO the reservoir and the bottom-hole pressure -, rate or BHP control with one BHP limit,

@@ -89,6 +89,11 @@ class Aquifers(C.Structure):
                 ("initial_watvolume", C.c_void_p), ("has_restart", C.c_void_p), ("restart_W_flux", C.c_void_p), ("restart_pressure", C.c_void_p)]
 
 
+class TracerResult(C.Structure):
+    """opmhip_tracer_result"""
+    _fields_ = [("converged", C.c_int), ("iterations", C.c_double), ("reduction", C.c_double)]
+
+
 class StdWells(C.Structure):
     """opmhip_std_wells: standard wells for the device-resident form (opmhip_set_std_wells)"""
     _fields_ = [("num_wells", C.c_int), ("perf_pointers", C.c_void_p), ("cell", C.c_void_p), ("tw", C.c_void_p), ("dz", C.c_void_p),
@@ -805,6 +810,15 @@ def _bind_assembly(L):
     L.opmhip_aquifers_begin_time_step.argtypes = [vp, C.c_double, C.c_double]
     L.opmhip_get_aquifers.argtypes = [vp, vp, vp, vp, vp]
     L.opmhip_get_aquifer_rates.argtypes = [vp, vp]
+    L.opmhip_set_tracers.argtypes = [vp, C.c_int, vp, vp]
+    L.opmhip_set_tracer_solver.argtypes = [vp, C.c_double, C.c_int]
+    L.opmhip_set_tracer_connections.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.opmhip_tracers_begin_time_step.argtypes = [vp]
+    L.opmhip_tracers_end_time_step.argtypes = [vp, C.c_double, C.POINTER(TracerResult)]
+    L.opmhip_get_tracers.argtypes = [vp, vp]
+    L.opmhip_get_tracer_system.argtypes = [vp, C.c_int, C.c_double, vp, vp]
+    L.opmhip_get_tracer_storage.argtypes = [vp, vp, vp]
+    L.opmhip_get_tracer_timings.argtypes = [vp, vp, vp]
     L.opmhip_set_std_wells.argtypes = [vp, C.POINTER(StdWells)]
     L.opmhip_std_wells_begin_iteration.argtypes = [vp, C.c_int]
     L.opmhip_std_wells_apply_residual.argtypes = [vp]
@@ -1304,6 +1318,66 @@ class HipModel(HipSolver):
                    xw=np.zeros((n, 4)))
         self._check(lib().opmhip_get_std_wells_blocks(self._h, *[_ptr(out[k]) for k in ("head", "D", "Dinv", "B", "C", "rates", "xw")]))
         return out
+
+    # ---- passive tracers (opmhip_set_tracers ...; tracers.DeviceTracers) ----
+    def set_tracers(self, phase, concentration):
+        """phase: per tracer 0 water, 1 oil, 2 gas; concentration (num_tracers, Nb), natural order; no tracers clears.  Ragged input raises
+        ValueError; what the library refuses (a gas tracer, an oil tracer on a PVTG fluid, a decomposed context, a value that is not
+        finite) raises OpmHipError with its text"""
+        ph = _i32(np.asarray(phase).reshape(-1))
+        nt = len(ph)
+        cc = _f64(np.asarray(concentration, float).reshape(-1)) if nt else _f64(np.zeros(1))
+        if nt and len(cc) != nt * self.Nb:
+            raise ValueError("set_tracers: concentration needs num_tracers x Nb = %d x %d values, has %d" % (nt, self.Nb, len(cc)))
+        self._ntracers = 0     # a refused call leaves none set
+        self._check(lib().opmhip_set_tracers(self._h, nt, _ptr(ph) if nt else None, _ptr(cc) if nt else None))
+        self._ntracers = nt
+
+    def set_tracer_solver(self, tolerance=1e-2, maxit=100):
+        self._check(lib().opmhip_set_tracer_solver(self._h, tolerance, maxit))
+
+    def set_tracer_connections(self, cells, rates, injected):
+        """cells [n]; rates [n, 3]: water, oil, gas component surface rates, positive into the reservoir; injected [num_tracers, n]"""
+        cl = _i32(np.asarray(cells).reshape(-1))
+        n, nt = len(cl), getattr(self, "_ntracers", 0)
+        r, j = _f64(np.asarray(rates, float).reshape(-1)), _f64(np.asarray(injected, float).reshape(-1))
+        if len(r) != 3 * n or len(j) != nt * n:
+            raise ValueError("set_tracer_connections: %d cells need %d rates and %d injected concentrations, got %d and %d" % (n, 3 * n, nt * n, len(r), len(j)))
+        self._check(lib().opmhip_set_tracer_connections(self._h, n, _ptr(cl) if n else None, _ptr(r) if n else None, _ptr(j) if n else None))
+
+    def tracers_begin_time_step(self):
+        self._check(lib().opmhip_tracers_begin_time_step(self._h))
+
+    def tracers_end_time_step(self, dt):
+        """-> per tracer dict(converged, iterations, reduction)"""
+        nt = getattr(self, "_ntracers", 0)
+        res = (TracerResult * max(nt, 1))()
+        self._check(lib().opmhip_tracers_end_time_step(self._h, dt, res))
+        return [dict(converged=bool(res[t].converged), iterations=res[t].iterations, reduction=res[t].reduction) for t in range(nt)]
+
+    def get_tracers(self):
+        out = np.zeros((getattr(self, "_ntracers", 0), self.Nb))
+        self._check(lib().opmhip_get_tracers(self._h, _ptr(out)))
+        return out
+
+    def tracer_system(self, phase, dt, num_phase_tracers):
+        """for tests: (M [nnzb] in the pattern's order, residual [tracers of the phase, Nb]) at the state now present"""
+        M, r = np.zeros(self.nnzb), np.zeros((num_phase_tracers, self.Nb))
+        self._check(lib().opmhip_get_tracer_system(self._h, phase, dt, _ptr(M), _ptr(r)))
+        return M, r
+
+    def tracer_storage(self):
+        """for tests: (storage1, c_initial) of the last tracers_begin_time_step, (num_tracers, Nb) each"""
+        nt = getattr(self, "_ntracers", 0)
+        s, c0 = np.zeros((nt, self.Nb)), np.zeros((nt, self.Nb))
+        self._check(lib().opmhip_get_tracer_storage(self._h, _ptr(s), _ptr(c0)))
+        return s, c0
+
+    def tracer_timings(self):
+        """device milliseconds of the last tracers_end_time_step: dict(system, factor, solve, levels, launches)"""
+        ms, info = np.zeros(3), np.zeros(2, np.int32)
+        self._check(lib().opmhip_get_tracer_timings(self._h, _ptr(ms), _ptr(info)))
+        return dict(system=ms[0], factor=ms[1], solve=ms[2], levels=int(info[0]), launches=int(info[1]))
 
     def set_source(self, source, dsource=None):
         s, d = _f64(source), _f64(dsource)

@@ -400,6 +400,9 @@ void opmhip_destroy(opmhip_ctx* c) {
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->asmb.aq.h_step) (void)hipHostFree(c->asmb.aq.h_step);
     if (c->asmb.aq.ev_step) (void)hipEventDestroy(c->asmb.aq.ev_step);
+    if (c->asmb.tr.h_rec) (void)hipHostFree(c->asmb.tr.h_rec);
+    for (hipEvent_t e : c->asmb.tr.ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->prof.ev) (void)hipEventDestroy(e);

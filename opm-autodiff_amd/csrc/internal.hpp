@@ -367,6 +367,49 @@ struct AquifersDev {
     hipEvent_t ev_step = nullptr;                                     // "h_step has been read"
 };
 
+// Passive tracers on the device (opmhip_set_tracers; kernels and the solve: tracers.hip, entry points: capi_tracers.cpp, host set-up:
+// tracers_setup.hpp).  One batch per phase; a batch's per-cell arrays are interleaved [cell][tracer of the batch], internal cell order.
+// The matrix, the factors and the solver's vectors are shared by the batches (they are solved one after the other) and sized for the
+// largest one.
+constexpr int TRACER_PHASES = 3;
+struct TracerMembers { int g[OPMHIP_TRACERS_MAX_PER_PHASE]; };   // a batch's tracers by their number in the caller's list (kernel argument)
+struct TracerBatchDev {
+    int nt = 0;
+    TracerMembers members{};
+    double *d_c = nullptr, *d_c0 = nullptr, *d_s1 = nullptr;   // concentration_, concentrationInitial_, storageOfTimeIndex1_
+    template <class F> void each_dev(F f) { f(&d_c); f(&d_c0); f(&d_s1); }
+};
+struct TracersDev {
+    int num = 0, maxnt = 0;
+    bool begun = false;          // an opmhip_tracers_begin_time_step has been seen
+    double tol = 1e-2;           // eclgenerictracermodel.cc:256-262
+    int maxit = 100;
+    std::vector<int> phase, slot;   // per tracer: its batch, its place there
+    TracerBatchDev b[TRACER_PHASES];
+    // the sweeps' schedule: rows of level l = d_lvrows[lvptr[l] .. lvptr[l + 1]); d_ford: per row its entries in ascending natural column order
+    std::vector<int> lvptr;
+    int *d_lvrows = nullptr, *d_ford = nullptr, *d_flag = nullptr;
+    double *d_M = nullptr, *d_LU = nullptr, *d_invd = nullptr;                  // [nnzb], [nnzb], [Nb]
+    double *d_res = nullptr, *d_x = nullptr, *d_r = nullptr, *d_rw = nullptr, *d_p = nullptr, *d_v = nullptr, *d_s = nullptr, *d_t = nullptr,
+           *d_y = nullptr, *d_pw = nullptr;                                     // [Nb * maxnt]
+    double *d_sc = nullptr, *d_part = nullptr;                                  // per-tracer BiCGStab scalars; the reductions' partial sums
+    int nblk = 0, cellsPerBlock = 0;                                            // first stage of a reduction: workgroups, cells of each
+    double *h_rec = nullptr, *d_rec = nullptr;                                  // pinned: tracers done, -, -, sequence number (written last); the same through the device's eyes
+    double seq = 0.0;
+    // connections (opmhip_set_tracer_connections): grouped by distinct cell as the aquifers' are
+    int nconn = 0, nd = 0;
+    int *d_cpos = nullptr, *d_cptr = nullptr, *d_cconn = nullptr;
+    double *d_rate = nullptr, *d_inj = nullptr;                                 // [3 nconn], [num * nconn]
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms[3] = {0.0, 0.0, 0.0};
+    int launches = 0;
+    template <class F> void each_conn(F f) { f(&d_cpos); f(&d_cptr); f(&d_cconn); f(&d_rate); f(&d_inj); }
+    template <class F> void each_dev(F f) {
+        f(&d_lvrows); f(&d_ford); f(&d_flag); f(&d_M); f(&d_LU); f(&d_invd); f(&d_res); f(&d_x); f(&d_r); f(&d_rw); f(&d_p); f(&d_v); f(&d_s); f(&d_t);
+        f(&d_y); f(&d_pw); f(&d_sc); f(&d_part);
+    }
+};
+
 // VFP tables (opmhip_set_vfp_tables): the packed host form (vfp_tables.hpp) and its two device arrays, resident for the context's life
 // (a part as the standard wells' are: its device arrays named once, in each_dev)
 struct VfpDev {
@@ -384,6 +427,7 @@ constexpr int RESV_MAX_PARTS = 1024, RESV_FINAL_THREADS = 256, RESV_OUT = 6;
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
 struct AsmDev {
     AquifersDev aq;
+    TracersDev tr;
     VfpDev vfp;
     bool fluid_set = false, static_set = false, state_set = false, assembled = false;
     double *d_tab_dbl = nullptr;
@@ -899,6 +943,10 @@ void launch_u8_to_natural(opmhip_ctx* c, const unsigned char* internal, unsigned
 void launch_iq_to_natural(opmhip_ctx* c, double* d_nat);
 void launch_iq_gather(opmhip_ctx* c, int n, const int* d_pos, double* d_out);                                    // records of n cells (internal positions)
 void launch_source_scatter(opmhip_ctx* c, int n, const int* d_pos, const double* d_src, const double* d_dsrc);   // d_dsrc nullable
+// passive tracers (tracers.hip)
+void launch_tracer_begin(opmhip_ctx* c, int phase);                        // updateStorageCache of one batch
+void launch_tracer_system(opmhip_ctx* c, int phase, double dt);            // assembleTracerEquations_ of one batch -> TracersDev::d_M, d_res
+int tracer_solve_batch(opmhip_ctx* c, int phase, opmhip_tracer_result* res_batch, bool* pivot_failed);   // ILU0, BiCGStab -> d_x; c -= x
 int iq_doubles_per_cell(const opmhip_ctx* c);
 int asm_max_rows();
 int launch_fluid_probe(opmhip_ctx* c, int pr, int sr, int n, const double* d_in, double* d_out);

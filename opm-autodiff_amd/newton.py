@@ -64,8 +64,10 @@ class ModelParameters:
 class BlackoilModelHip:
     """model = capi.HipModel (device context) ; one instance drives one grid on one GPU."""
 
-    def __init__(self, model, param=None, well_model=None, aquifer_model=None):
-        """aquifer_model (aquifers.DeviceAquifers, aquifers.HostAquifers or None): the analytic aquifers - aquiferModel_ of EclProblem
+    def __init__(self, model, param=None, well_model=None, aquifer_model=None, tracer_model=None):
+        """tracer_model (tracers.DeviceTracers, tracers.HostTracers or None): the passive tracers - tracerModel_ of EclProblem, advanced once
+        per accepted time step (beginTimeStep / endTimeStep below) with the connection rates of well_model; None: the loop is unchanged.
+        aquifer_model (aquifers.DeviceAquifers, aquifers.HostAquifers or None): the analytic aquifers - aquiferModel_ of EclProblem
         (initialSolutionApplied here, beginTimeStep / addToSource / endTimeStep below); the model's state must be set.
         well_model (wells.StandardWells, wells.DeviceStandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
         reservoir's linearisation (BlackoilModelEbos::assembleReservoir -> wellModel().assemble, flow/BlackoilModelEbos.hpp:418-428),
@@ -80,6 +82,7 @@ class BlackoilModelHip:
         self.aquifers = aquifer_model
         if aquifer_model is not None:
             aquifer_model.initial_solution_applied(model)
+        self.tracers = tracer_model
 
     # -- BlackoilModelEbos::getReservoirConvergence ------------------------------------------------------------
     def get_convergence(self, dt, iteration):
@@ -229,6 +232,8 @@ class BlackoilModelHip:
             self._well_saved = self.wells.state()      # the well state of the last accepted step (WellState copy of a failed step's restart)
 
     def update_failed(self):
+        # (the tracers need no hook here: nothing of theirs moved - they advance in end_time_step only, and the next begin_time_step
+        #  forms their storage cache again from the rolled-back state)
         self.m.update_failed()
         if self.wells is not None and self._well_saved is not None:
             self.wells.set_state(self._well_saved)
@@ -244,12 +249,18 @@ class BlackoilModelHip:
             self.m.begin_time_step(dt)
         if self.aquifers is not None:
             self.aquifers.begin_time_step(self.m, time, dt)   # aquiferModel_.beginTimeStep (ebos/eclproblem.hh:1042-1075)
+        if self.tracers is not None:
+            self.tracers.on_begin_time_step(self.m)           # tracerModel_.beginTimeStep (ebos/eclproblem.hh:1042-1075): updateStorageCache
 
     # -- EclProblem::endTimeStep (ebos/eclproblem.hh:1101-1135): the drift of the accepted step ------------------
     def end_time_step(self, dt):
         self.m.end_time_step(dt)      # with aquifers on the device: their endTimeStep too
         if self.aquifers is not None and not self.aquifers.on_device:
             self.aquifers.end_time_step(dt)
+        if self.tracers is not None:                          # tracerModel_.endTimeStep (ebos/eclproblem.hh:1101-1135): advanceTracerFields
+            from . import tracers as _tracers
+            conn = _tracers.connection_rates(self.wells) if self.wells is not None else None
+            self.tracers.on_end_time_step(self.m, dt, conn)
 
 
 @dataclass

@@ -1178,6 +1178,7 @@ class StandardWells:
         if dq is not None:
             C[:, :3, :] = 0.0 - dq.transpose(0, 2, 1)    # C[j][c]: d r_cell[c] / d q_j
         self.rate_dq = np.zeros((nperf, 3, 3)) if dq is None else dq
+        self.last_perf_rates = pr[:, :, 0].copy()    # the connections' component rates of this assemble (tracers.connection_rates)
         return r, D, B, C, pr[:, :, 0], pr[:, :, 1:4]
 
     def solve_well_equations(self, iq, iterations=20):
