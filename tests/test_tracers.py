@@ -344,3 +344,145 @@ def test_connection_rates_of_a_host_well_model(pkg):
         class Fresh:
             cells = np.array([0])
         pkg.tracers.connection_rates(Fresh())
+
+
+# ---- the cases of tests/test_gpu_tracer_edges.py: what each is for, shown on the oracle's records ------------------------------------------
+def records(orc, case, pv):
+    o = oracle_bind.OracleModel(orc, case)
+    o.set_state(pv, case["meaning"])
+    return o.iq()
+
+
+def host_at(pkg, orc, sc, **kw):
+    """the host form of a solve case, begun at the case's own state and standing at pv1"""
+    case = sc["case"]
+    h = pkg.tracers.HostTracers(case, sc["phase"], sc["c"], **kw)
+    h.begin_time_step(records(orc, case, case["pv"]))
+    h.set_records(records(orc, case, sc["pv1"]))
+    h.set_connections(sc["cells"], sc["rates"], sc["injected"])
+    return h
+
+
+def test_wide_batches_cross_the_chunks(pkg, orc):
+    TR_CH = 8
+    case, _ = S.system_case(pkg, (9, 9, 2))
+    assert S.WIDTHS == (8, 9, 17, 32)
+    for nt in S.WIDTHS:
+        for wide in (WATER, OIL):
+            phase, c = S.wide_tracers(case, nt, wide)
+            members = [t for t, p in enumerate(phase) if p == wide]
+            assert len(members) == nt and len(phase) == nt + 1 and members != list(range(nt))
+            assert phase.count(WATER if wide == OIL else OIL) == 1
+            assert len({row.tobytes() for row in c}) == nt + 1
+    # the 17 copies: each chunk holds every prototype that fits, the zero tracer in the last slot and below the first chunk's end
+    p = S.PROTO_17
+    assert len(p) == 17 and p[16] == 2 and 2 in p[:TR_CH]
+    assert set(p[:TR_CH]) == set(p[TR_CH:2 * TR_CH]) == {0, 1, 2}
+    assert sorted(S.PERM_17) == list(range(17)) and all(a != b for a, b in enumerate(S.PERM_17))
+    assert [p[s] for s in S.PERM_17] != list(p)
+    assert sorted(S.PROTO_9) == [0, 0, 0, 1, 1, 1, 2, 2, 2] and any(S.PROTO_9[s] != S.PROTO_9[s % 3] for s in range(9))
+    # the prototypes stop at three different half iterations, every decision clear
+    sc = S.proto_solve_case(pkg, (9, 9, 2), (0, 1, 2))
+    res = host_at(pkg, orc, sc).end_time_step(DT)
+    its = [r["iterations"] for r in res]
+    assert S.clear_decisions(res, 1e-2) and all(r["converged"] for r in res)
+    assert its[2] == 0.0 and len(set(its)) == 3, its
+
+
+def reduction_layout(Nb):
+    """opmhip_set_tracers (csrc/capi_tracers.cpp): nblk = max(1, min(256, ceil(Nb / 256))), cellsPerBlock = ceil(Nb / nblk); k_tracer_dot:
+    workgroup b sums the cells [b cells, min(Nb, b cells + cells))"""
+    nblk = max(1, min(256, (Nb + 255) // 256))
+    cells = (Nb + nblk - 1) // nblk
+    return nblk, cells, [(b * cells, min(Nb, b * cells + cells)) for b in range(nblk)]
+
+
+def test_reduction_grids_take_more_than_one_workgroup():
+    want = {(17, 17, 1): (2, 145, [145, 144]), (23, 23, 1): (3, 177, [177, 177, 175])}
+    assert set(S.REDUCTION_GRIDS) == set(want)
+    for dims, (nblk, cells, sizes) in want.items():
+        Nb = dims[0] * dims[1] * dims[2]
+        n, c, ranges = reduction_layout(Nb)
+        assert (n, c) == (nblk, cells) and [b - a for a, b in ranges] == sizes
+        assert all(b > a for a, b in ranges) and ranges[0][0] == 0 and ranges[-1][1] == Nb
+        assert all(ranges[i][1] == ranges[i + 1][0] for i in range(n - 1))
+        assert sizes[-1] < cells                                 # a ragged last workgroup
+    assert reduction_layout(162)[0] == 1                         # the grids of the older tests stay in one
+    for nt, W in ((3, 255), (9, 252), (17, 255), (32, 256)):
+        assert 256 - 256 % nt == W
+
+
+def test_dry_case_sits_on_the_clamp_and_has_one_sided_faces(pkg, orc):
+    T = pkg.tracers
+    sc = S.dry_case(pkg)
+    case, dry = sc["case"], sc["dry"]
+    assert len(dry) == 13 and case["Nb"] == 90
+    rows = np.repeat(np.arange(case["Nb"]), np.diff(case["rowptr"]))
+    cols = np.asarray(case["col"])
+    isolated = dry[-1]
+    assert not np.isin(cols[rows == isolated], dry[:-1]).any()   # no neighbour of the isolated cell is dry
+    wet = np.ones(case["Nb"], bool)
+    wet[dry] = False
+    for pv in (case["pv"], sc["pv1"]):
+        iq = records(orc, case, pv)
+        assert np.all(iq[dry, T.F_MOB + WATER, 0] == 0.0) and np.all(iq[wet, T.F_MOB + WATER, 0] > 0.0)
+        vol = T.phase_volume(iq, WATER)
+        assert np.all(vol[dry] == 1e-10) and np.all(vol[wet] > 1e-10)
+        assert np.all(T.phase_volume(iq, OIL) > 1e-10)
+    f, up = T.face_values(case, iq, WATER)
+    off = rows != cols
+    mob = iq[:, T.F_MOB + WATER, 0] > 0.0
+    both_dry = off & ~mob[rows] & ~mob[cols]
+    assert both_dry.sum() >= 2 and np.all(f[both_dry] == 0.0)
+    one_in = off & ~mob[rows] & mob[cols]                       # the interior cell is the immobile one
+    one_ex = off & mob[rows] & ~mob[cols]
+    for one in (one_in, one_ex):
+        assert (one & up).sum() > 0 and (one & ~up).sum() > 0    # each upwind direction occurs
+    # an immobile upstream side carries nothing; a mobile one carries water into the dry cell
+    assert np.all(f[one_in & up] == 0.0) and np.all(f[one_ex & ~up] == 0.0)
+    assert np.all(f[one_in & ~up] != 0.0) and np.all(f[one_ex & up] != 0.0)
+    # a producing connection inside the dry column, an injecting one outside
+    q = sc["rates"][:, WATER]
+    assert any(q[n] < 0 and sc["cells"][n] in dry[:-1] for n in range(len(q))) and any(q[n] > 0 and wet[sc["cells"][n]] for n in range(len(q)))
+    h = host_at(pkg, orc, sc)
+    assert np.all(h.storage1[0, dry] == 1e-10 * sc["c"][0, dry])
+    res = h.end_time_step(DT)
+    assert S.clear_decisions(res, 1e-2) and all(r["converged"] for r in res)
+
+
+def test_pivot_case_is_reported_bad_by_the_host_form(pkg, orc):
+    T = pkg.tracers
+    sc = S.pivot_case(pkg)
+    case, cell = sc["case"], sc["cell"]
+    assert np.isfinite(sc["rates"]).all() and list(sc["cells"]).count(cell) == 2 and sc["c"][0, cell] == 0.0
+    h = host_at(pkg, orc, sc, maxit=2)
+    with np.errstate(all="ignore"):
+        M, r = h.system(OIL, DT)
+        assert M[S.entry(case, cell, cell)] == np.inf and np.isfinite(np.delete(M, S.entry(case, cell, cell))).all()
+        assert np.isfinite(r[0]).all()                           # the tracer that is absent from the cell keeps a finite residual
+        rp, ci, va, dg = T.permute_csr(case["Nb"], h.rowptr, h.col, M)
+        lu, invd, bad = T.ilu0(rp, ci, va, dg)
+        assert bad and np.isfinite(lu).all() and np.isfinite(invd).all()      # nothing that is not finite is stored
+        res = h.end_time_step(DT)
+    assert [q["converged"] for q in res] == [False, True, False]
+    assert res[0]["iterations"] == 2.0 and res[2]["iterations"] == 2.0 and 0.0 < res[1]["iterations"] < 2.0
+    assert S.clear_decisions([res[1]], 1e-2) and np.isfinite(h.c[1]).all()
+    # a step later, with a sane list: the water tracer is solved as ever
+    h.begin_time_step()
+    h.set_connections(*sc["sane"])
+    with np.errstate(all="ignore"):
+        res2 = h.end_time_step(DT)
+    assert res2[1]["converged"] and S.clear_decisions([res2[1]], 1e-2) and np.isfinite(h.c[1]).all()
+
+
+def test_wave_connections_name_71_cells_and_one_of_them_five_times():
+    case = dict(Nb=162)
+    cells, rates, inj, many = S.wave_connections(case, 11)
+    assert len(cells) == 75 and rates.shape == (75, 3) and inj.shape == (11, 75)
+    assert len(set(cells.tolist())) == 71 > 64 and list(cells).count(many) == 5
+    once = cells != many
+    assert list(cells[once]) != sorted(cells[once])              # shuffled cell order
+    for ph in (WATER, OIL):
+        assert (np.sign(rates[~once, ph]) == [1, -1, 0, -1, 1]).all()
+        assert (rates[once, ph] > 0).sum() > 10 and (rates[once, ph] < 0).sum() > 10
+    assert 0 <= cells.min() and cells.max() < 162
