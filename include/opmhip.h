@@ -1330,6 +1330,68 @@ int opmhip_convergence(opmhip_ctx* ctx, double dt, double tol_cnv, double* out);
  * not part of this) and for a field whose pore volume is not > 0 (nothing is divided; out stays untouched).  Additive to ABI 11 */
 int opmhip_reservoir_averages(opmhip_ctx* ctx, double* out);
 
+/* ---- fluids in place and region pressures per FIP region, reduced on the device.  Additive to ABI 11 ---------------------------
+ * The fluid-in-place report Flow forms at every report step (ebos/ecloutputblackoilmodule.hh:610-697 updateFluidInPlace_;
+ * ebos/eclgenericoutputblackoilmodule.cc:712-737 regionSum, :1240-1250 pressureAverage_, :1412-1571 update / makeRegionSum /
+ * accumulateRegionSums / updateSummaryRegionValues), from the cached intensive quantities, the cell volumes and the reference porosity
+ * of opmhip_set_static - all in HBM already - instead of a copy of every record (opmhip_get_iq) and a loop on the host.
+ * Per cell twelve terms, values only, in this order (the OPMHIP_FIP_* slots) and with these statements:
+ *    0 DynamicPoreVolume      pv = volume * porosity(record)
+ *    1 PoreVolume             volume * reference porosity
+ *    2 HydroCarbonPV          pv * hc,  hc = S_o + S_g   (not 1 - S_w)
+ *    3 PressurePV             p_o * pv
+ *    4 PressureHydroCarbonPV  PressurePV * hc
+ *    5 OilInLiquidPhase       fip_o = (b_o * S_o) * pv
+ *    6 GasInGasPhase          fip_g = (b_g * S_g) * pv
+ *    7 GasInLiquidPhase       Rs * fip_o
+ *    8 OilInGasPhase          Rv * fip_g   (Rv = 0 in the 17-field record)
+ *    9 WATER                  (b_w * S_w) * pv
+ *   10 OIL                    fip_o + OilInGasPhase
+ *   11 GAS                    fip_g + GasInLiquidPhase
+ * Per region the twelve sums over its cells; cells with an id <= 0 belong to no region and are left out everywhere, field totals
+ * included (regionSum, :724-727).  The sums use no floating-point atomics and have ONE stated order, which depends on the region
+ * array and the natural cell numbering alone (not on the context's ordering, a launch's grid or the call): a region's cells by
+ * ascending natural index, cut into chunks of 256 consecutive items (a missing item of the last chunk counts as 0.0); in a chunk
+ * lane l of one wavefront forms (((0.0 + x[l]) + x[l + 64]) + x[l + 128]) + x[l + 192], the 64 lanes are combined by the tree
+ * v[l] += v[l + o], o = 32, 16, ..., 1; the chunk results of a region, ascending, form a new list under the same rule until one
+ * value is left.  (The reference adds in cell order; the two differ by rounding.)  Field totals: the regions' totals added from 0.0
+ * in ascending id, as `update` does (:1420-1426).  An id in 1 .. max that no cell carries gives zeros.
+ * A row of results has OPMHIP_FIP_ROW = 14 doubles: the twelve sums, then pressureAverage_ with hydrocarbon = true (RPR / FPR) and
+ * with hydrocarbon = false (RPRP / FPRP): hydrocarbon && HydroCarbonPV > 1e-10 ? PressureHydroCarbonPV / HydroCarbonPV :
+ * PressurePV / PoreVolume.  A region or field without pore volume gives the reference's 0.0 / 0.0, a NaN, and no status.
+ * UNVERIFIED: Inplace::add(phase, sum) is opm-common's and not in the reference tree - whether Flow's field value accumulates over
+ * several region sets cannot be read there.  Here every set has field totals of its own, and set 0's are "the field's".
+ * NOT covered: decomposed contexts (the region sums are comm.sums over the ranks, :733-734), the text layout of the report
+ * (outputRegionFluidInPlace_) and unit conversion - the caller's -, inter-region flows (the reference at this version has none). */
+#define OPMHIP_FIP_MAX_SETS 16
+#define OPMHIP_FIP_TERMS 12
+#define OPMHIP_FIP_ROW 14
+/* replaces: createLocalRegion_ / regionMax and the region arrays of EclGenericOutputBlackoilModule (regions_, :1405-1410).
+ * region[s][cell], s < num_sets, Nb ids each in the natural cell order; set 0 is FIPNUM.  num_sets = 0 releases everything.  The host
+ * builds per set the list of its cells by (id, natural index) and the chunk descriptors of every level, and uploads them.
+ * OPMHIP_NOT_READY before set_static.  OPMHIP_INVALID_ARGUMENT with a text, before anything is uploaded and with the sets in force
+ * untouched: a NULL array, num_sets outside 0 .. OPMHIP_FIP_MAX_SETS, a largest id above Nb, a decomposed context (the sums over
+ * the ranks are not formed). */
+int opmhip_set_fip_regions(opmhip_ctx* ctx, int num_sets, const int* const* region);
+/* replaces: the element loop of EclWriter::evalSummaryState over updateFluidInPlace_, accumulateRegionSums and the pressure part of
+ * updateSummaryRegionValues, for one set, from the state now present.  regions[max_id * OPMHIP_FIP_ROW] (row r - 1 = region r; nullable),
+ * field[OPMHIP_FIP_ROW] (nullable).  One launch for the per-cell terms, one per level of the reduction, one for the totals; the call
+ * waits for the stream to read (max_id + 1) * 12 doubles back.  The same state gives the same bits from call to call and in every
+ * ordering of the context.  The first evaluation of a set after opmhip_set_fip_regions is kept as its "originally in place", as
+ * initialInplace_ is (:1487-1488) - with the flaws the reference's own comment lists: it is the first REPORTED state, not the initial one.
+ * OPMHIP_NOT_READY before set_state or before regions are set; OPMHIP_INVALID_ARGUMENT for a set out of range. */
+int opmhip_fluid_in_place(opmhip_ctx* ctx, int set, double* regions, double* field);
+/* that record (what FOE divides by, :1514-1517); OPMHIP_NOT_READY before the set's first opmhip_fluid_in_place */
+int opmhip_get_fluid_in_place_initial(opmhip_ctx* ctx, int set, double* regions, double* field);
+/* the per-cell arrays Flow writes to the restart file (ecloutputblackoilmodule.hh:632-637, 666-693) at the state now present:
+ * out[slot * Nb + cell], natural cell order.  Needs regions to be set (the arrays are allocated with them). */
+int opmhip_get_fluid_in_place_cells(opmhip_ctx* ctx, double* out);
+/* info[4]: the set's largest id, its cells in regions, its chunks at level 0, its levels (launches of the reduction) */
+int opmhip_get_fip_info(opmhip_ctx* ctx, int set, int* info);
+/* device milliseconds of the last opmhip_fluid_in_place, by HIP events on the context's stream: ms[0] the per-cell terms, ms[1] the
+ * reduction's launches and the totals */
+int opmhip_get_fip_timings(opmhip_ctx* ctx, double* ms);
+
 /* replaces: BlackoilModelEbos::updateSolution (flow/BlackoilModelEbos.hpp:549-563) = BlackOilNewtonMethod::update_
  * (dp <= 0.3 p, dS <= 0.2, primary-variable switching) + invalidateAndUpdateIntensiveQuantities, preceded by
  * NonlinearSolverEbos::stabilizeNonlinearUpdate "dampen" (flow/NonlinearSolverEbos.hpp:307-353): dx *= relax.

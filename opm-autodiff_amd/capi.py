@@ -781,6 +781,12 @@ def _bind_assembly(L):
     L.opmhip_convergence.argtypes = [vp, C.c_double, C.c_double, vp]
     L.opmhip_update.argtypes = [vp, vp, C.c_double, C.POINTER(C.c_int)]
     L.opmhip_reservoir_averages.argtypes = [vp, vp]
+    L.opmhip_set_fip_regions.argtypes = [vp, C.c_int, vp]
+    L.opmhip_fluid_in_place.argtypes = [vp, C.c_int, vp, vp]
+    L.opmhip_get_fluid_in_place_initial.argtypes = [vp, C.c_int, vp, vp]
+    L.opmhip_get_fluid_in_place_cells.argtypes = [vp, vp]
+    L.opmhip_get_fip_info.argtypes = [vp, C.c_int, vp]
+    L.opmhip_get_fip_timings.argtypes = [vp, vp]
     L.opmhip_set_pattern_dd.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.opmhip_comm_unique_id.argtypes = [C.c_char_p]
     L.opmhip_comm_init_rccl.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
@@ -1420,6 +1426,66 @@ class HipModel(HipSolver):
         out = np.empty(5)
         self._check(lib().opmhip_reservoir_averages(self._h, _ptr(out)))
         return out
+
+    # ---- fluids in place per FIP region (opmhip_set_fip_regions ...; fip.py states the arithmetic) ----
+    def set_fip_regions(self, regions):
+        """regions: {"FIPNUM": ids, "FIPABC": ids, ...}, Nb ids each in the natural cell order; the first name is set 0 ("the field's").
+        None or {} releases.  Ragged input raises ValueError; what the library refuses (more than 16 sets, an id above Nb, a decomposed
+        context) raises OpmHipError with its text and leaves the sets in force"""
+        regions = dict(regions or {})
+        keep = [_i32(np.asarray(v).reshape(-1)) for v in regions.values()]
+        for name, a in zip(regions, keep):
+            if len(a) != self.Nb:
+                raise ValueError("set_fip_regions: %s needs Nb = %d ids, has %d" % (name, self.Nb, len(a)))
+        ptrs = (C.c_void_p * max(len(keep), 1))(*[a.ctypes.data for a in keep])
+        self._check(lib().opmhip_set_fip_regions(self._h, len(keep), ptrs if keep else None))
+        self._fip_names = list(regions)
+
+    def _fip_set(self, name):
+        names = getattr(self, "_fip_names", [])
+        if isinstance(name, str):
+            if name not in names:
+                raise KeyError("no region set %r (set: %s)" % (name, ", ".join(names) or "none"))
+            return names.index(name)
+        return int(name)
+
+    def fip_info(self, name="FIPNUM"):
+        """dict(max_id, cells, chunks, levels) of a set: its largest id, its cells in regions, its chunks at level 0, its levels"""
+        info = np.zeros(4, np.int32)
+        self._check(lib().opmhip_get_fip_info(self._h, self._fip_set(name), _ptr(info)))
+        return dict(max_id=int(info[0]), cells=int(info[1]), chunks=int(info[2]), levels=int(info[3]))
+
+    def _fip_rows(self, fn, name):
+        s = self._fip_set(name)
+        info = np.zeros(4, np.int32)
+        if lib().opmhip_get_fip_info(self._h, s, _ptr(info)) != SUCCESS:
+            info[:] = 0   # no such set: fn refuses below, with its own code and text
+        reg, field = np.zeros((int(info[0]), 14)), np.zeros(14)
+        self._check(fn(self._h, s, _ptr(reg), _ptr(field)))
+        return dict(regions=reg, field=field)
+
+    def fluid_in_place(self, name="FIPNUM"):
+        """opmhip_fluid_in_place of one set (a name of set_fip_regions, or its number) at the state now present:
+        dict(regions=(max_id, 14), field=(14,)) - the twelve sums in fip.TERMS' order, then RPR / FPR and RPRP / FPRP"""
+        if not getattr(self, "_fip_names", []) and isinstance(name, str):
+            name = 0   # the library's own status says that no regions are set
+        return self._fip_rows(lib().opmhip_fluid_in_place, name)
+
+    def fluid_in_place_initial(self, name="FIPNUM"):
+        """the set's first fluid_in_place since set_fip_regions (initialInplace_): what FOE divides by"""
+        return self._fip_rows(lib().opmhip_get_fluid_in_place_initial, name)
+
+    def fluid_in_place_cells(self):
+        """(12, Nb): the per-cell terms at the state now present, rows as fip.TERMS, natural cell order"""
+        out = np.zeros((12, self.Nb))
+        self._check(lib().opmhip_get_fluid_in_place_cells(self._h, _ptr(out)))
+        return out
+
+    def fip_timings(self):
+        """device milliseconds of the last fluid_in_place: dict(cells, reduce)"""
+        ms = np.zeros(2)
+        self._check(lib().opmhip_get_fip_timings(self._h, _ptr(ms)))
+        return dict(cells=float(ms[0]), reduce=float(ms[1]))
 
     def solve_jacobian_system(self, wells=None):
         """solveJacobianSystem on the device-resident Jacobian and residual (no host copies)."""

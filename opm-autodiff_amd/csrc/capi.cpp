@@ -403,6 +403,8 @@ void opmhip_destroy(opmhip_ctx* c) {
     if (c->asmb.tr.h_rec) (void)hipHostFree(c->asmb.tr.h_rec);
     for (hipEvent_t e : c->asmb.tr.ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->asmb.fip_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->prof.ev) (void)hipEventDestroy(e);

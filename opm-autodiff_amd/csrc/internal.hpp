@@ -410,6 +410,33 @@ struct TracersDev {
     }
 };
 
+// Fluids in place per FIP region (opmhip_set_fip_regions; kernels: fip.hip, entry points: capi_fip.cpp, host set-up: fip_setup.hpp).
+// The twelve per-cell terms and region sums, in the order of the reference's statements (include/opmhip.h "fluids in place")
+enum { FIP_DYNAMIC_PV = 0, FIP_PORE_VOLUME, FIP_HC_PV, FIP_PRESSURE_PV, FIP_PRESSURE_HC_PV, FIP_OIL_IN_LIQUID, FIP_GAS_IN_GAS, FIP_GAS_IN_LIQUID,
+       FIP_OIL_IN_GAS, FIP_WATER, FIP_OIL, FIP_GAS, FIP_TERMS };
+static_assert(FIP_TERMS == OPMHIP_FIP_TERMS && FIP_TERMS + 2 == OPMHIP_FIP_ROW, "the header's row of results");
+// One region set: its plan's arrays on the device (FipPlan: items, chunk descriptors, the regions' result slots), the plan's numbers,
+// and the first evaluation's rows ((max_id + 1) x OPMHIP_FIP_ROW, the field's last)
+struct FipSetDev {
+    int max_id = 0, ncells = 0, npart = 0;
+    std::vector<int> level_ptr;
+    int *d_items = nullptr, *d_desc = nullptr, *d_result = nullptr;
+    std::vector<double> initial;
+    template <class F> void each_dev(F f) { f(&d_items); f(&d_desc); f(&d_result); }
+};
+// d_terms [FIP_TERMS][Nloc] field-major, internal cell order; d_part [FIP_TERMS][npart] the chunk results of the set under way, d_out
+// [(max_id + 1)][FIP_TERMS] its regions' and field's sums - both sized for the largest set
+struct FipDev {
+    std::vector<FipSetDev> sets;
+    int npart = 0, max_id = 0;
+    double *d_terms = nullptr, *d_part = nullptr, *d_out = nullptr;
+    bool timed = false;          // the events of AsmDev::fip_ev belong to a finished opmhip_fluid_in_place
+    template <class F> void each_dev(F f) {
+        for (FipSetDev& s : sets) s.each_dev(f);
+        f(&d_terms); f(&d_part); f(&d_out);
+    }
+};
+
 // VFP tables (opmhip_set_vfp_tables): the packed host form (vfp_tables.hpp) and its two device arrays, resident for the context's life
 // (a part as the standard wells' are: its device arrays named once, in each_dev)
 struct VfpDev {
@@ -429,6 +456,8 @@ struct AsmDev {
     AquifersDev aq;
     TracersDev tr;
     VfpDev vfp;
+    FipDev fip;
+    hipEvent_t fip_ev[3] = {nullptr, nullptr, nullptr};   // opmhip_fluid_in_place: start, the per-cell terms done, the totals done (created with the first regions)
     bool fluid_set = false, static_set = false, state_set = false, assembled = false;
     double *d_tab_dbl = nullptr;
     int* d_tab_idx = nullptr;
@@ -947,6 +976,9 @@ void launch_source_scatter(opmhip_ctx* c, int n, const int* d_pos, const double*
 void launch_tracer_begin(opmhip_ctx* c, int phase);                        // updateStorageCache of one batch
 void launch_tracer_system(opmhip_ctx* c, int phase, double dt);            // assembleTracerEquations_ of one batch -> TracersDev::d_M, d_res
 int tracer_solve_batch(opmhip_ctx* c, int phase, opmhip_tracer_result* res_batch, bool* pivot_failed);   // ILU0, BiCGStab -> d_x; c -= x
+// fluids in place (fip.hip)
+void launch_fip_cells(opmhip_ctx* c);                      // the twelve per-cell terms of the state now present -> FipDev::d_terms
+void launch_fip_reduce(opmhip_ctx* c, const FipSetDev& S);   // every level of the set's reduction, then the regions' and the field's sums -> FipDev::d_out
 int iq_doubles_per_cell(const opmhip_ctx* c);
 int asm_max_rows();
 int launch_fluid_probe(opmhip_ctx* c, int pr, int sr, int n, const double* d_in, double* d_out);
