@@ -9,8 +9,8 @@
 #include <new>
 #include <optional>
 
+#include "capi_guard.hpp"
 #include "internal.hpp"
-#include "ms_wells_setup.hpp"
 
 using namespace opmhip;
 
@@ -124,11 +124,9 @@ static int upload_wells_local(opmhip_ctx* c, const opmhip_wells* w) {
     // device arrays grow geometrically and are then reused: wells are rebuilt for every solve
     // (linalg/ISTLSolverEbos.hpp:265-272)
     // what of the list differs from what the device already holds (a Newton iteration hands the same list over three times)
-    auto same_i = [](const std::vector<int>& h, const int* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(int)) == 0); };
-    auto same_d = [](const std::vector<double>& h, const double* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(double)) == 0); };
-    const bool sVp = same_i(W.h_vp, w->val_pointers, (size_t)nw + 1), sD = same_d(W.h_D, w->Dnnzs, (size_t)nw * 16);
-    const bool sCc = same_i(W.h_cc, cc.data(), (size_t)np), sBc = same_i(W.h_bc, bc.data(), (size_t)np);
-    const bool sC = same_d(W.h_C, w->Cnnzs, (size_t)np * 12), sB = same_d(W.h_B, w->Bnnzs, (size_t)np * 12);
+    const bool sVp = record_same(W.h_vp, w->val_pointers, (size_t)nw + 1), sD = record_same(W.h_D, w->Dnnzs, (size_t)nw * 16);
+    const bool sCc = record_same(W.h_cc, cc.data(), (size_t)np), sBc = record_same(W.h_bc, bc.data(), (size_t)np);
+    const bool sC = record_same(W.h_C, w->Cnnzs, (size_t)np * 12), sB = record_same(W.h_B, w->Bnnzs, (size_t)np * 12);
     if (sVp && sD && sCc && sBc && sC && sB && (size_t)nw <= W.cap_wells && (size_t)np <= W.cap_perf) {
         W.nperf = np;
         return OPMHIP_SUCCESS;
@@ -158,68 +156,14 @@ static int upload_wells_local(opmhip_ctx* c, const opmhip_wells* w) {
         W.cap_perf = cap;
         W.h_cc.clear(); W.h_bc.clear(); W.h_C.clear(); W.h_B.clear();
     }
-    // a failed copy leaves the record of that array empty: the next call copies it again
-    auto put_i = [&](int* d, std::vector<int>& h, const int* p, size_t n) -> int {
-        h.clear();
-        if (n > 0) OPMHIP_HIP(c, hipMemcpy(d, p, n * sizeof(int), hipMemcpyHostToDevice));
-        h.assign(p, p + n);
-        return OPMHIP_SUCCESS;
-    };
-    auto put_d = [&](double* d, std::vector<double>& h, const double* p, size_t n) -> int {
-        h.clear();
-        if (n > 0) OPMHIP_HIP(c, hipMemcpy(d, p, n * sizeof(double), hipMemcpyHostToDevice));
-        h.assign(p, p + n);
-        return OPMHIP_SUCCESS;
-    };
-    if (!same_i(W.h_vp, w->val_pointers, (size_t)nw + 1) && (rc = put_i(W.d_val_pointers, W.h_vp, w->val_pointers, (size_t)nw + 1))) return rc;
-    if (!same_d(W.h_D, w->Dnnzs, (size_t)nw * 16) && (rc = put_d(W.d_D, W.h_D, w->Dnnzs, (size_t)nw * 16))) return rc;
-    if (!same_i(W.h_cc, cc.data(), (size_t)np) && (rc = put_i(W.d_Ccols, W.h_cc, cc.data(), (size_t)np))) return rc;
-    if (!same_i(W.h_bc, bc.data(), (size_t)np) && (rc = put_i(W.d_Bcols, W.h_bc, bc.data(), (size_t)np))) return rc;
-    if (!same_d(W.h_C, w->Cnnzs, (size_t)np * 12) && (rc = put_d(W.d_C, W.h_C, w->Cnnzs, (size_t)np * 12))) return rc;
-    if (!same_d(W.h_B, w->Bnnzs, (size_t)np * 12) && (rc = put_d(W.d_B, W.h_B, w->Bnnzs, (size_t)np * 12))) return rc;
+    // (the records are asked again: a larger array above has emptied its own)
+    if (!record_same(W.h_vp, w->val_pointers, (size_t)nw + 1) && (rc = dev_put_recorded(c, W.d_val_pointers, W.h_vp, w->val_pointers, (size_t)nw + 1))) return rc;
+    if (!record_same(W.h_D, w->Dnnzs, (size_t)nw * 16) && (rc = dev_put_recorded(c, W.d_D, W.h_D, w->Dnnzs, (size_t)nw * 16))) return rc;
+    if (!record_same(W.h_cc, cc.data(), (size_t)np) && (rc = dev_put_recorded(c, W.d_Ccols, W.h_cc, cc.data(), (size_t)np))) return rc;
+    if (!record_same(W.h_bc, bc.data(), (size_t)np) && (rc = dev_put_recorded(c, W.d_Bcols, W.h_bc, bc.data(), (size_t)np))) return rc;
+    if (!record_same(W.h_C, w->Cnnzs, (size_t)np * 12) && (rc = dev_put_recorded(c, W.d_C, W.h_C, w->Cnnzs, (size_t)np * 12))) return rc;
+    if (!record_same(W.h_B, w->Bnnzs, (size_t)np * 12) && (rc = dev_put_recorded(c, W.d_B, W.h_B, w->Bnnzs, (size_t)np * 12))) return rc;
     W.nperf = np;
-    return OPMHIP_SUCCESS;
-}
-
-// ---- multisegment wells on the device (opmhip_set_ms_wells) ----
-static void ms_wells_clear(opmhip_ctx* c) {
-    MsWellsDev& S = c->wells.ms;
-    S.num = S.maxM = 0;
-    S.flag_pending = false;
-}
-static void ms_wells_release(opmhip_ctx* c) {
-    MsWellsDev& S = c->wells.ms;
-    ms_wells_clear(c);
-    S.atomic = false;
-    S.have_structure = false;
-    S.num_dense = S.num_tree = S.tree_max_seg = S.tree_max_depth = 0;
-    S.tree_bytes = 0;
-    S.tree_lds_doubles = 0;
-    S.h_form.clear();
-    dev_free(c, &S.d_tdesc); dev_free(c, &S.d_tint); dev_free(c, &S.d_fac);
-    dev_free(c, &S.d_desc); dev_free(c, &S.d_Brows); dev_free(c, &S.d_cell); dev_free(c, &S.d_blkrow); dev_free(c, &S.d_Dcolp); dev_free(c, &S.d_Drows);
-    dev_free(c, &S.d_flag); dev_free(c, &S.d_B); dev_free(c, &S.d_C); dev_free(c, &S.d_Dvals); dev_free(c, &S.d_inv);
-    S.bytes = 0;
-    S.h_Mbp.clear(); S.h_Brows.clear(); S.h_blkp.clear(); S.h_Bcols.clear(); S.h_Dcolp.clear(); S.h_Drows.clear(); S.h_Dnzp.clear();
-    S.h_Bvals.clear(); S.h_Cvals.clear(); S.h_Dvals.clear();
-}
-// The pivot flags of the last inversion, looked at where the host waits for the stream anyway (the caller has just synchronised, or this
-// does): a singular D clears the list and is INVALID_ARGUMENT - the operator is never applied with a broken inverse.
-static int ms_wells_check(opmhip_ctx* c) {
-    MsWellsDev& S = c->wells.ms;
-    if (!S.flag_pending) return OPMHIP_SUCCESS;
-    OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-    S.flag_pending = false;
-    for (int w = 0; w < S.num; ++w)
-        if (S.h_flag[w] != 0) {
-            const int col = S.h_flag[w] - 1;
-            const bool tree = (size_t)w < S.h_form.size() && S.h_form[w] != 0;
-            ms_wells_release(c);
-            if (tree)
-                return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: D of multisegment well %d: the 4 x 4 block of segment %d is singular after its children are eliminated (no non-zero finite pivot); "
-                            "the tree form pivots inside a segment's block only, the dense form pivots over the whole column and does not have this limit; the list is cleared", w, col);
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: D of multisegment well %d is singular (no non-zero pivot in column %d of its elimination); the list is cleared", w, col);
-        }
     return OPMHIP_SUCCESS;
 }
 
@@ -312,18 +256,6 @@ int vec_out(opmhip_ctx* c, const double* d_internal, double* h) {
     return OPMHIP_SUCCESS;
 }
 
-template <class F>
-int guarded(opmhip_ctx* c, F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        return fail(c, OPMHIP_UNKNOWN_ERROR, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(c, OPMHIP_UNKNOWN_ERROR, "exception: %s", e.what());
-    } catch (...) {
-        return fail(c, OPMHIP_UNKNOWN_ERROR, "unknown exception");
-    }
-}
 }  // namespace
 
 extern "C" {
@@ -796,245 +728,6 @@ int opmhip_get_ordering_info(opmhip_ctx* c, int info[4]) {
     info[2] = P.numColors;
     info[3] = cpr_ilu_levels_in_force(c);
     return OPMHIP_SUCCESS;
-}
-
-int opmhip_set_ms_wells(opmhip_ctx* c, const opmhip_ms_wells* ms) {
-    if (!c) return OPMHIP_INVALID_ARGUMENT;
-    return guarded(c, [&]() -> int {
-        MsWellsDev& S = c->wells.ms;
-        if (!ms || ms->num_ms_wells == 0) {   // cleared: the arrays stay for the next list
-            OPMHIP_HIP(c, hipSetDevice(c->device));
-            if (S.flag_pending) OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-            ms_wells_clear(c);
-            S.h_Dvals.clear();   // (a list that comes back is inverted again)
-            return OPMHIP_SUCCESS;
-        }
-        if (!c->pattern_set) return fail(c, OPMHIP_NOT_READY, "set_ms_wells before the pattern is set (the cells are translated to the ILU ordering)");
-        if (c->comm.nranks > 1) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: multisegment wells on the device are not supported in decomposed runs");
-        const int nw = ms->num_ms_wells;
-        if (nw < 0) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: negative well count");
-        if (ms->dim != 3 || ms->dim_wells != 4) return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: dim = %d, dim_wells = %d; only 3 and 4 are supported", ms->dim, ms->dim_wells);
-        if (!ms->Mb_pointers || !ms->Brows || !ms->block_pointers || !ms->Bcols || !ms->Bvals || !ms->Cvals || !ms->Dcol_pointers || !ms->Drows || !ms->Dvals || !ms->Dnnz_pointers)
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: null array");
-        // a refused list leaves none in force: the caller falls back to the callback form
-        auto refuse = [&](int rc) { ms_wells_clear(c); S.h_Dvals.clear(); return rc; };
-        if (ms->Mb_pointers[0] != 0 || ms->block_pointers[0] != 0 || ms->Dnnz_pointers[0] != 0)
-            return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (Mb_pointers, block_pointers and Dnnz_pointers start at 0)"));
-        // all: every well's descriptor, in list order; wform: its form - 0 dense, 1 tree (opmhip_set_ms_wells_form; under AUTO a well above
-        // the dense caps is a candidate for the tree form, settled where the structure is analysed)
-        std::vector<MsWellDesc> all(nw);
-        std::vector<int> wform(nw, 0);
-        size_t invDoubles = 0;
-        int maxM = 0;
-        auto over_M = [&](int w, int Mb) {
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d has %d segments, M = %lld > OPMHIP_MS_WELLS_MAX_M = %d: above the size cap of the device form (use the callback form)",
-                        w, Mb, 4 * (long long)Mb, OPMHIP_MS_WELLS_MAX_M);
-        };
-        for (int w = 0; w < nw; ++w) {
-            const int Mb = ms->Mb_pointers[w + 1] - ms->Mb_pointers[w], nblk = ms->block_pointers[w + 1] - ms->block_pointers[w];
-            const int nnz = ms->Dnnz_pointers[w + 1] - ms->Dnnz_pointers[w];
-            if (Mb < 1 || nblk < 0 || nnz < 0) return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (well %d: %d segments, %d blocks, %d entries of D)", w, Mb, nblk, nnz));
-            const bool overM = 4 * (long long)Mb > OPMHIP_MS_WELLS_MAX_M;
-            if (overM && S.form == OPMHIP_MS_WELLS_DENSE) return refuse(over_M(w, Mb));
-            wform[w] = S.form == OPMHIP_MS_WELLS_TREE || (S.form == OPMHIP_MS_WELLS_AUTO && overM);
-            if (wform[w] && Mb > OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS)
-                return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d has %d segments > OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS = %d: above the size cap of the tree form (use the callback form)",
-                                   w, Mb, OPMHIP_MS_WELLS_TREE_MAX_SEGMENTS));
-            MsWellDesc& d = all[w];
-            d.Mb = Mb; d.nblk = nblk;
-            d.seg0 = ms->Mb_pointers[w] + w; d.blk0 = ms->block_pointers[w];
-            d.dcol0 = 4 * ms->Mb_pointers[w] + w; d.dnz0 = ms->Dnnz_pointers[w];
-            d.inv0 = 0;
-            d.well = w;
-            if (!wform[w]) {
-                d.inv0 = (int)invDoubles;
-                invDoubles += (size_t)16 * Mb * Mb;
-                if (invDoubles * sizeof(double) > (size_t)OPMHIP_MS_WELLS_MAX_KIB * 1024)
-                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: the dense D^-1 of the list exceed OPMHIP_MS_WELLS_MAX_KIB = %d KiB at well %d: above the size cap of the device form (use the callback form)",
-                                       OPMHIP_MS_WELLS_MAX_KIB, w));
-            }
-            maxM = std::max(maxM, 4 * Mb);
-            const int* br = ms->Brows + d.seg0;
-            bool ok = br[0] == 0 && br[Mb] == nblk;
-            for (int r = 0; r < Mb && ok; ++r) ok = br[r] <= br[r + 1];
-            const int* cp = ms->Dcol_pointers + d.dcol0;
-            ok = ok && cp[0] == 0 && cp[4 * Mb] == nnz;
-            for (int q = 0; q < 4 * Mb && ok; ++q) ok = cp[q] <= cp[q + 1];
-            if (!ok) return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: inconsistent pointers (Brows or Dcol_pointers of well %d)", w));
-            for (int k = 0; k < nnz; ++k) {
-                if (ms->Drows[d.dnz0 + k] < 0 || ms->Drows[d.dnz0 + k] >= 4 * Mb)
-                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d, entry %d of D: row %d outside [0, %d)", w, k, ms->Drows[d.dnz0 + k], 4 * Mb));
-                if (!std::isfinite(ms->Dvals[d.dnz0 + k]))
-                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: well %d, entry %d of D is not finite", w, k));
-            }
-        }
-        const size_t nseg = (size_t)ms->Mb_pointers[nw], nblk = (size_t)ms->block_pointers[nw], nnz = (size_t)ms->Dnnz_pointers[nw];
-        for (size_t k = 0; k < nblk; ++k)
-            if (ms->Bcols[k] < 0 || ms->Bcols[k] >= c->pat.Nb)
-                return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: block %zu: cell %d out of range [0, %d)", k, ms->Bcols[k], c->pat.Nb));
-        OPMHIP_HIP(c, hipSetDevice(c->device));
-        auto same_i = [](const std::vector<int>& h, const int* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(int)) == 0); };
-        auto same_d = [](const std::vector<double>& h, const double* p, size_t n) { return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(double)) == 0); };
-        const bool structure = S.have_structure && same_i(S.h_Mbp, ms->Mb_pointers, (size_t)nw + 1) && same_i(S.h_Brows, ms->Brows, nseg + nw) && same_i(S.h_blkp, ms->block_pointers, (size_t)nw + 1) &&
-                               same_i(S.h_Bcols, ms->Bcols, nblk) && same_i(S.h_Dcolp, ms->Dcol_pointers, 4 * nseg + nw) && same_i(S.h_Drows, ms->Drows, nnz) &&
-                               same_i(S.h_Dnzp, ms->Dnnz_pointers, (size_t)nw + 1);
-        const bool sB = structure && same_d(S.h_Bvals, ms->Bvals, nblk * 12), sC = structure && same_d(S.h_Cvals, ms->Cvals, nblk * 12);
-        const bool sD = structure && same_d(S.h_Dvals, ms->Dvals, nnz);
-        int rc;
-        if (!(structure && sB && sC && sD)) OPMHIP_HIP(c, hipStreamSynchronize(c->stream));   // earlier kernels on the stream may still read what the copies below replace
-        if (!structure) {
-            // a new list: the index arrays anew, cells in the internal order, per block its segment row, and whether two blocks meet in a cell
-            ms_wells_release(c);
-            // the tree wells: the segment tree and the entries' places (ms_wells_setup.cpp), the index lists one after the other
-            std::vector<MsWellDesc> desc;
-            std::vector<MsTreeDesc> tdesc;
-            std::vector<int> tint;
-            size_t facDoubles = 0;
-            int treeSeg = 0, treeDepth = 0;
-            for (int w = 0; w < nw; ++w) {
-                if (!wform[w]) { desc.push_back(all[w]); continue; }
-                const MsWellDesc& d = all[w];
-                opmhip::MsTreeWell t;
-                std::string msg;
-                if (opmhip::ms_wells_tree_analyse(w, d.Mb, ms->Dcol_pointers + d.dcol0, ms->Drows + d.dnz0, t, msg)) {
-                    if (S.form == OPMHIP_MS_WELLS_AUTO) return refuse(over_M(w, d.Mb));   // (neither form takes it)
-                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "%s", msg.c_str()));
-                }
-                MsTreeDesc td{};
-                td.Mb = d.Mb; td.nblk = d.nblk; td.seg0 = d.seg0; td.blk0 = d.blk0; td.dcol0 = d.dcol0; td.dnz0 = d.dnz0; td.well = w;
-                td.depth = t.depth; td.width = t.width;
-                auto put = [&](const std::vector<int>& v) { const int at = (int)tint.size(); tint.insert(tint.end(), v.begin(), v.end()); return at; };
-                if (tint.size() + 4 * (size_t)d.Mb + 2 + t.dest.size() > (size_t)INT_MAX || (facDoubles + (size_t)opmhip::MS_TREE_SEG * d.Mb) > (size_t)INT_MAX)
-                    return refuse(fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells: the tree wells' index lists exceed 2^31 entries at well %d: above the size cap of the tree form", w));
-                td.par0 = put(t.parent); td.cptr0 = put(t.child_ptr); td.child0 = put(t.child); td.lptr0 = put(t.level_ptr); td.lseg0 = put(t.level_seg);
-                td.dest0 = put(t.dest);
-                td.fac0 = (int)facDoubles;
-                facDoubles += (size_t)opmhip::MS_TREE_SEG * d.Mb;
-                treeSeg = std::max(treeSeg, d.Mb);
-                treeDepth = std::max(treeDepth, t.depth);
-                tdesc.push_back(td);
-            }
-            std::vector<int> cell(nblk), blkrow(nblk);
-            std::vector<char> seen((size_t)c->pat.Nb, 0);
-            bool shared = false;
-            for (int w = 0; w < nw; ++w) {
-                const int* br = ms->Brows + all[w].seg0;
-                for (int r = 0; r < all[w].Mb; ++r)
-                    for (int k = br[r]; k < br[r + 1]; ++k) blkrow[(size_t)all[w].blk0 + k] = r;
-            }
-            for (size_t k = 0; k < nblk; ++k) {
-                cell[k] = c->pat.toOrder[ms->Bcols[k]];
-                if (seen[(size_t)ms->Bcols[k]]) shared = true;
-                seen[(size_t)ms->Bcols[k]] = 1;
-            }
-            if (!S.h_flag || S.cap_flag < (size_t)nw) {
-                if (S.h_flag) (void)hipHostFree(S.h_flag);
-                S.h_flag = nullptr;
-                OPMHIP_HIP(c, hipHostMalloc((void**)&S.h_flag, (size_t)nw * sizeof(int)));
-                S.cap_flag = (size_t)nw;
-            }
-            auto up_i = [&](int** d, const int* p, size_t n) -> int {
-                int r = dev_alloc(c, d, n);
-                if (r) return r;
-                if (n > 0) OPMHIP_HIP(c, hipMemcpy(*d, p, n * sizeof(int), hipMemcpyHostToDevice));
-                return OPMHIP_SUCCESS;
-            };
-            if ((rc = dev_alloc(c, &S.d_desc, desc.size()))) { ms_wells_release(c); return refuse(rc); }
-            if (!desc.empty()) OPMHIP_HIP(c, hipMemcpy(S.d_desc, desc.data(), desc.size() * sizeof(MsWellDesc), hipMemcpyHostToDevice));
-            if ((rc = up_i(&S.d_Brows, ms->Brows, nseg + nw)) || (rc = up_i(&S.d_cell, cell.data(), nblk)) || (rc = up_i(&S.d_blkrow, blkrow.data(), nblk)) ||
-                (rc = up_i(&S.d_Dcolp, ms->Dcol_pointers, 4 * nseg + nw)) || (rc = up_i(&S.d_Drows, ms->Drows, nnz)) || (rc = dev_alloc(c, &S.d_flag, (size_t)nw)) ||
-                (rc = dev_alloc(c, &S.d_B, nblk * 12)) || (rc = dev_alloc(c, &S.d_C, nblk * 12)) || (rc = dev_alloc(c, &S.d_Dvals, nnz)) || (rc = dev_alloc(c, &S.d_inv, invDoubles))) {
-                ms_wells_release(c);
-                return rc;
-            }
-            // the tree wells' arrays behind the others, and only where the list has such wells: a dense list allocates what it always did
-            if (!tdesc.empty()) {
-                if ((rc = dev_alloc(c, &S.d_tdesc, tdesc.size())) || (rc = up_i(&S.d_tint, tint.data(), tint.size())) || (rc = dev_alloc(c, &S.d_fac, facDoubles))) {
-                    ms_wells_release(c);
-                    return rc;
-                }
-                OPMHIP_HIP(c, hipMemcpy(S.d_tdesc, tdesc.data(), tdesc.size() * sizeof(MsTreeDesc), hipMemcpyHostToDevice));
-            }
-            S.tree_bytes = sizeof(double) * facDoubles;
-            S.bytes = desc.size() * sizeof(MsWellDesc) + tdesc.size() * sizeof(MsTreeDesc) + sizeof(int) * (nseg + nw + 2 * nblk + 4 * nseg + nw + nnz + nw + tint.size()) +
-                      sizeof(double) * (nblk * 24 + nnz + invDoubles) + S.tree_bytes;
-            S.atomic = shared;
-            S.num_dense = (int)desc.size(); S.num_tree = (int)tdesc.size();
-            S.tree_max_seg = treeSeg; S.tree_max_depth = treeDepth;
-            S.h_form = wform;
-            ms_wells_tree_plan(c, tdesc);
-            S.have_structure = true;
-            S.h_Mbp.assign(ms->Mb_pointers, ms->Mb_pointers + nw + 1); S.h_Brows.assign(ms->Brows, ms->Brows + nseg + nw);
-            S.h_blkp.assign(ms->block_pointers, ms->block_pointers + nw + 1); S.h_Bcols.assign(ms->Bcols, ms->Bcols + nblk);
-            S.h_Dcolp.assign(ms->Dcol_pointers, ms->Dcol_pointers + 4 * nseg + nw); S.h_Drows.assign(ms->Drows, ms->Drows + nnz);
-            S.h_Dnzp.assign(ms->Dnnz_pointers, ms->Dnnz_pointers + nw + 1);
-        }
-        // a failed copy leaves the record of that array empty: the next call copies it again
-        auto put_d = [&](double* d, std::vector<double>& h, const double* p, size_t n) -> int {
-            h.clear();
-            if (n > 0) OPMHIP_HIP(c, hipMemcpy(d, p, n * sizeof(double), hipMemcpyHostToDevice));
-            h.assign(p, p + n);
-            return OPMHIP_SUCCESS;
-        };
-        if (!sB && (rc = put_d(S.d_B, S.h_Bvals, ms->Bvals, nblk * 12))) return refuse(rc);
-        if (!sC && (rc = put_d(S.d_C, S.h_Cvals, ms->Cvals, nblk * 12))) return refuse(rc);
-        if (!sD && (rc = put_d(S.d_Dvals, S.h_Dvals, ms->Dvals, nnz))) return refuse(rc);
-        S.num = nw;
-        S.maxM = maxM;
-        if (!sD) {
-            launch_ms_wells_factor(c);
-            OPMHIP_HIP(c, hipGetLastError());
-        }
-        return OPMHIP_SUCCESS;
-    });
-}
-
-int opmhip_get_ms_wells_info(opmhip_ctx* c, int info[4]) {
-    if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
-    return guarded(c, [&]() -> int {
-        int rc;
-        if ((rc = ms_wells_check(c))) return rc;
-        const MsWellsDev& S = c->wells.ms;
-        info[0] = S.num;
-        info[1] = S.maxM;
-        info[2] = S.num > 0 ? (int)((S.bytes + 1023) / 1024) : 0;
-        info[3] = S.factorisations;
-        return OPMHIP_SUCCESS;
-    });
-}
-
-int opmhip_set_ms_wells_form(opmhip_ctx* c, int form) {
-    if (!c) return OPMHIP_INVALID_ARGUMENT;
-    return guarded(c, [&]() -> int {
-        if (form != OPMHIP_MS_WELLS_DENSE && form != OPMHIP_MS_WELLS_TREE && form != OPMHIP_MS_WELLS_AUTO)
-            return fail(c, OPMHIP_INVALID_ARGUMENT, "set_ms_wells_form: form = %d; OPMHIP_MS_WELLS_DENSE (0), _TREE (1) or _AUTO (2)", form);
-        MsWellsDev& S = c->wells.ms;
-        if (form == S.form) return OPMHIP_SUCCESS;
-        if (S.have_structure || S.flag_pending) {   // a list set under the other form is cleared; kernels on the stream may still read its arrays
-            OPMHIP_HIP(c, hipSetDevice(c->device));
-            OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
-        }
-        ms_wells_release(c);
-        S.form = form;
-        return OPMHIP_SUCCESS;
-    });
-}
-
-int opmhip_get_ms_wells_form_info(opmhip_ctx* c, int info[6]) {
-    if (!c || !info) return OPMHIP_INVALID_ARGUMENT;
-    return guarded(c, [&]() -> int {
-        int rc;
-        if ((rc = ms_wells_check(c))) return rc;
-        const MsWellsDev& S = c->wells.ms;
-        const bool set = S.num > 0;
-        info[0] = S.form;
-        info[1] = set ? S.num_dense : 0;
-        info[2] = set ? S.num_tree : 0;
-        info[3] = set ? S.tree_max_seg : 0;
-        info[4] = set ? S.tree_max_depth : 0;
-        info[5] = set ? (int)((S.tree_bytes + 1023) / 1024) : 0;
-        return OPMHIP_SUCCESS;
-    });
 }
 
 int opmhip_set_ilu_fillin_level(opmhip_ctx* c, int n) {

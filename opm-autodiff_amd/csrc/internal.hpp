@@ -17,6 +17,7 @@
 #include "cpr_setup.hpp"
 #include "vfp_tables.hpp"
 #include "source_lists.hpp"
+#include "ms_wells_setup.hpp"
 
 namespace opmhip {
 
@@ -153,24 +154,7 @@ struct Pattern {
 constexpr int ILUN_BUDGET_FACTOR = 8;
 
 // Multisegment wells in their device-resident form (opmhip_set_ms_wells): a list that stays until it is replaced or cleared, beside the
-// per-solve WellsDev.  Per well one descriptor; D^-1 dense and COLUMN-major (element (i, j) of well w at inv[inv0 + j * M + i]) - the
-// elimination's lanes and the product's threads both run down a column.
-struct MsWellDesc {
-    int Mb, nblk;      // segments, blocks
-    int seg0;          // well's part of Brows (Mb + 1 entries)
-    int blk0;          // first block
-    int dcol0, dnz0;   // well's part of Dcol_pointers (4 Mb + 1 entries), first entry of D
-    int inv0;          // first double of the dense D^-1
-    int well;          // its number in the list (the place of its pivot flag): a list may hold wells of both forms
-};
-// The tree form (opmhip_set_ms_wells_form; ms_wells_setup.hpp): D block-sparse over the segment tree, 48 doubles per segment
-// (S_i^-1 | E_i = D_pi S_i^-1 | D_ip).  The well's index lists lie one after the other in MsWellsDev::d_tint.
-struct MsTreeDesc {
-    int Mb, nblk, seg0, blk0, dcol0, dnz0, well;   // as MsWellDesc's
-    int depth, width;                              // levels; segments of the widest level
-    int par0, cptr0, child0, lptr0, lseg0, dest0;  // in d_tint: parent [Mb], child_ptr [Mb + 1], child, level_ptr [depth + 1], level_seg [Mb], dest [nnz]
-    int fac0;                                      // first double of the well's blocks in d_fac
-};
+// per-solve WellsDev.  Per well one descriptor (MsWellDesc, MsTreeDesc: ms_wells_setup.hpp).
 struct MsWellsDev {
     int num = 0, maxM = 0;
     int form = 0;                // OPMHIP_MS_WELLS_DENSE / _TREE / _AUTO: applies to the lists set after opmhip_set_ms_wells_form
@@ -795,10 +779,28 @@ void dev_part_install(opmhip_ctx* c, P& in_force, P& fresh) {
     in_force = std::move(fresh);
 }
 template <class T>
-int dev_upload(opmhip_ctx* c, T** p, const std::vector<T>& h) {
-    int rc = dev_alloc(c, p, h.size());
+int dev_upload(opmhip_ctx* c, T** p, const T* h, size_t n) {
+    int rc = dev_alloc(c, p, n);
     if (rc) return rc;
-    if (!h.empty()) OPMHIP_HIP(c, hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (n > 0) OPMHIP_HIP(c, hipMemcpy(*p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return OPMHIP_SUCCESS;
+}
+template <class T>
+int dev_upload(opmhip_ctx* c, T** p, const std::vector<T>& h) {
+    return dev_upload(c, p, h.data(), h.size());
+}
+// A list that is handed over again and again (the wells of a Newton iteration): the host keeps a record of what each device array holds, and
+// what arrives unchanged is not copied.  record_same: the record holds exactly the caller's n entries.  dev_put_recorded: the caller's
+// array to the device and into the record; a failed copy leaves the record empty, so that the next call copies it again.
+template <class T>
+bool record_same(const std::vector<T>& h, const T* p, size_t n) {
+    return h.size() == n && (n == 0 || std::memcmp(h.data(), p, n * sizeof(T)) == 0);
+}
+template <class T>
+int dev_put_recorded(opmhip_ctx* c, T* d, std::vector<T>& h, const T* p, size_t n) {
+    h.clear();
+    if (n > 0) OPMHIP_HIP(c, hipMemcpy(d, p, n * sizeof(T), hipMemcpyHostToDevice));
+    h.assign(p, p + n);
     return OPMHIP_SUCCESS;
 }
 
@@ -901,9 +903,6 @@ int launch_spmv(opmhip_ctx* c, double* x, double* y, int ndot, const double* w0,
 bool split_asm_wanted(const opmhip_ctx* c);      // solver.hip: half_product in force, ILU0 without CPR, no ghost columns, the assembly's entry records carry the places; OPMHIP_SPLIT_ASM=0 (tuning) forces it off
 void ensure_A(opmhip_ctx* c);                    // solver.hip: A_stale -> d_A gathered from d_R / d_U on the context's stream; in front of every reader of d_A
 bool half_product_wanted(const opmhip_ctx* c);   // solver.hip: opmhip_config.half_product resolved for the pattern in hand (asked once, when the system's buffers are allocated)
-void launch_wells_residual(opmhip_ctx* c, const double* d_resWell, double* r);
-void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const int* d_pair_ptr, const int* d_entry);
-int launch_wells_recover(opmhip_ctx* c, const double* d_resWell, const double* x, double* d_xw);   // distributed wells: one all-reduce inside
 void launch_ilu_factor(opmhip_ctx* c, bool fix_zero_diagonal = false, const FactorRider* rider = nullptr);
 int cpr_factor_rider(opmhip_ctx* c, FactorRider* r);   // cpr.hip: level 0 in place, this solve's weights where they do not come from the matrix; r->mode = 0: no rider this time
 void launch_ilu_apply(opmhip_ctx* c, const double* d, double* v, double w_override = -1.0, double* unscaled = nullptr, const double* addp = nullptr, double* work = nullptr, double* usum = nullptr);
@@ -918,9 +917,6 @@ void cpr_shutdown(opmhip_ctx* c);   // joins a structure build in flight (before
 bool cpr_coarse_pivot_failed(opmhip_ctx* c);
 int cpr_ilu_levels_in_force(const opmhip_ctx* c);   // opmhip_config.cpr_amg_ilu_levels with "< 0: the library's choice" resolved (0 without CPR)
 inline bool use_cpr(const opmhip_ctx* c) { return c->cfg.preconditioner == OPMHIP_PRECOND_CPR_QUASIIMPES || c->cfg.preconditioner == OPMHIP_PRECOND_CPR_TRUEIMPES; }
-void ms_wells_tree_plan(opmhip_ctx* c, const std::vector<MsTreeDesc>& tdesc);   // MsWellsDev::tree_lds_doubles of a new list: the dynamic LDS of k_ms_wells_tree_apply
-void launch_ms_wells_factor(opmhip_ctx* c);   // D -> D^-1 of every well of the device-resident multisegment list; pivot flags to MsWellsDev::d_flag
-int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs = 1.0);   // distributed wells: one all-reduce inside
 void launch_lu_to_natural(opmhip_ctx* c, double* d_out_internal_layout);
 int bicgstab(opmhip_ctx* c, opmhip_result* res);
 // comm.hip
@@ -955,7 +951,17 @@ void launch_std_wells_resv(opmhip_ctx* c);                // the field's average
 void launch_std_wells_assemble(opmhip_ctx* c);            // rates, r_w, D, D^-1, B, C; saved and raised source rows (in front of k_assemble)
 void launch_std_wells_restore(opmhip_ctx* c);             // the caller's source rows back (behind k_assemble)
 void launch_std_wells_axpy(opmhip_ctx* c, double relax);  // x -= relax * x_w
-void launch_std_wells_add_to_matrix(opmhip_ctx* c);       // solver.hip: A -= C^T D^-1 B by StdWellsDev's schedule (the matrix-add form), one launch
+// wells_operator.hip: the well operator y -= C^T (D^-1 (B (xs x))) behind launch_spmv's product, and the wells added to the matrix
+int launch_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs = 1.0);   // the solve's standard wells; distributed wells: one all-reduce inside
+void launch_ms_wells_apply(opmhip_ctx* c, const double* x, double* y, double xs);     // the device-resident multisegment list: no copy, no synchronisation
+int ms_wells_apply_callback(opmhip_ctx* c, const double* x, double* y, double xs);    // multisegment wells behind opmhip_wells.ms_apply: the host round trip
+void launch_wells_residual(opmhip_ctx* c, const double* d_resWell, double* r);
+int launch_wells_recover(opmhip_ctx* c, const double* d_resWell, const double* x, double* d_xw);   // distributed wells: one all-reduce inside
+void launch_wells_add_to_matrix(opmhip_ctx* c, int w0, int nw, int serial, const int* d_pair_ptr, const int* d_entry);
+void launch_std_wells_add_to_matrix(opmhip_ctx* c);       // A -= C^T D^-1 B by StdWellsDev's schedule (the matrix-add form), one launch
+void ms_wells_tree_plan(opmhip_ctx* c, const std::vector<MsTreeDesc>& tdesc);   // MsWellsDev::tree_lds_doubles of a new list: the dynamic LDS of k_ms_wells_tree_apply
+void launch_ms_wells_factor(opmhip_ctx* c);   // D -> D^-1 of every well of the device-resident multisegment list; pivot flags to MsWellsDev::d_flag
+int ms_wells_check(opmhip_ctx* c);   // capi_ms_wells.cpp: the pivot flags of the last inversion, looked at where the host waits for the stream; a singular D clears the list
 void launch_last_rs_rv(opmhip_ctx* c);
 void launch_set_limits(opmhip_ctx* c, double dt);
 void launch_min_pressure(opmhip_ctx* c, bool init);

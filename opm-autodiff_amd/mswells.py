@@ -56,7 +56,7 @@ def _mm_stated(A, B):
 
 
 def tree_solve(D, z, parents):
-    """D^-1 z by the block elimination over the segment tree that the device's tree form runs (csrc/solver.hip k_ms_wells_tree_factor and
+    """D^-1 z by the block elimination over the segment tree that the device's tree form runs (csrc/wells_operator.hip k_ms_wells_tree_factor and
     k_ms_wells_tree_apply), in float64 and in the device's order of operations; the device roots every component at its lowest segment
     number, so `parents` in that rooting gives its bits.
       factor, from the deepest level up:   S_i = D_ii - sum_c E_c D_ci (children c ascending; each product's entries over k ascending

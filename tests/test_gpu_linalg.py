@@ -269,7 +269,7 @@ def test_wells_operator(pkg, orc):
 
 
 def test_wells_with_more_completions_than_a_wavefront_has_lanes(pkg, orc):
-    """B x of a well is formed 64 completions at a time (well_Bx in csrc/solver.hip: the products in parallel, their sum in the CPU loop's
+    """B x of a well is formed 64 completions at a time (well_Bx in csrc/wells_operator.hip: the products in parallel, their sum in the CPU loop's
     order): wells of 150, 64, 65 and 1 completions - the solve stops where the oracle's does with its solution, and x_w = D^-1 (r_w - B x),
     whose subtractions run through the same code, equals the oracle's bit for bit on the same x"""
     rng = np.random.default_rng(21)
