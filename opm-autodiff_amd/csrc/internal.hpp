@@ -349,6 +349,9 @@ struct AquifersDev {
     double* d_save = nullptr;                                         // per distinct cell: the caller's source water row and its three derivatives
     double* h_step = nullptr;                                         // pinned staging of d_step
     hipEvent_t ev_step = nullptr;                                     // "h_step has been read"
+    template <class F> void each_dev(F f) {
+        f(&d_ptr); f(&d_of); f(&d_pos); f(&d_alpha); f(&d_pprev); f(&d_q); f(&d_par); f(&d_step); f(&d_state); f(&d_cpos); f(&d_cptr); f(&d_cconn); f(&d_save);
+    }
 };
 
 // Passive tracers on the device (opmhip_set_tracers; kernels and the solve: tracers.hip, entry points: capi_tracers.cpp, host set-up:
@@ -978,6 +981,17 @@ void launch_u8_to_natural(opmhip_ctx* c, const unsigned char* internal, unsigned
 void launch_iq_to_natural(opmhip_ctx* c, double* d_nat);
 void launch_iq_gather(opmhip_ctx* c, int n, const int* d_pos, double* d_out);                                    // records of n cells (internal positions)
 void launch_source_scatter(opmhip_ctx* c, int n, const int* d_pos, const double* d_src, const double* d_dsrc);   // d_dsrc nullable
+// capi_asm.cpp: internal positions of n named cells on the device (AsmDev::d_cell_pos, grown on demand); the host copy stays valid until the caller's synchronise
+int stage_cell_positions(opmhip_ctx* c, const std::vector<int>& pos);
+// `pos` staged, then what `enqueue` puts on the stream - copies that read host vectors of the caller among it.  The stream is drained on
+// the way out whatever happened: those vectors (and `pos`) may end with the caller's scope, no copy may still be reading them
+template <class F>
+int with_cell_positions(opmhip_ctx* c, const char* who, const std::vector<int>& pos, F&& enqueue) {
+    int rc = stage_cell_positions(c, pos);
+    if (!rc) rc = enqueue();
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) return fail(c, OPMHIP_DEVICE_ERROR, "%s: hipStreamSynchronize failed", who);
+    return rc;
+}
 // passive tracers (tracers.hip)
 void launch_tracer_begin(opmhip_ctx* c, int phase);                        // updateStorageCache of one batch
 void launch_tracer_system(opmhip_ctx* c, int phase, double dt);            // assembleTracerEquations_ of one batch -> TracersDev::d_M, d_res

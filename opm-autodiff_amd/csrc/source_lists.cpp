@@ -1,4 +1,4 @@
-// Host set-up of the resident standard wells and analytic aquifers (source_lists.hpp).  No HIP call: capi_std_wells.cpp and capi_asm.cpp upload what is
+// Host set-up of the resident standard wells and analytic aquifers (source_lists.hpp).  No HIP call: capi_std_wells.cpp and capi_aquifers.cpp upload what is
 // built here.
 #include <algorithm>
 #include <cmath>

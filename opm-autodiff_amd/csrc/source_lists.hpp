@@ -1,7 +1,7 @@
 // Host set-up of the two resident source lists - standard wells (opmhip_set_std_wells and its setters) and analytic aquifers
 // (opmhip_set_aquifers, opmhip_aquifers_begin_time_step, opmhip_get_aquifers): every check of what the caller hands over, the packing
 // of the arrays the kernels read, the grouping by distinct cell.  Pure host work on its arguments, no context and no HIP call, so that
-// it is built and checked without a device (tests/san/source_lists_san.cpp).  capi_std_wells.cpp (wells) and capi_asm.cpp (aquifers) allocate, upload and launch.
+// it is built and checked without a device (tests/san/source_lists_san.cpp).  capi_std_wells.cpp (wells) and capi_aquifers.cpp (aquifers) allocate, upload and launch.
 // A refusal is a code other than OPMHIP_SUCCESS with its text in `msg`, for the caller's fail(); the outputs are then untouched.
 #pragma once
 #include <string>
