@@ -789,6 +789,64 @@ int opmhip_get_aquifer_rates(opmhip_ctx* ctx, double* q4);
  * over the aquifer's connections in connection order; fluxValue_ = W_flux_; aquifer_pressure_ = pa0_ - W_flux_ / (total_compr *
  * initial_watvolume).  opmhip_update_failed leaves the aquifers alone: a rolled-back step never reaches endTimeStep. */
 
+/* ---- open boundaries (the BC keyword: FREE and RATE faces), resident on the device.  Additive to ABI 11 ----------------------
+ * replaces: EclProblem::boundary (ebos/eclproblem.hh:1602-1671) with the lists readBoundaryConditions_ (:2686-2830) builds, the
+ * boundary gradients of the flux module (calculateBoundaryGradients_, ebos/eclfluxmodule.hh:362-468) and what the local residual
+ * does with a boundary rate vector (evalBoundary_: rate times the face's area, ADDED to the interior cell's residual).
+ * A FREE face's flux depends on the interior cell's present pressures, densities and mobilities and carries a 3 x 3 derivative, so
+ * it is formed anew in front of every linearisation - on the device, from the cached intensive quantities.
+ * The list: one entry per boundary face, in any order; the faces of one cell are applied in list order.
+ * SIGN: a boundary rate is positive OUT of the domain.  boundary() passes the deck's RATE on without a sign change, so a positive
+ * rate of a RATE face leaves the domain and an influx is negative.
+ * FREE: the exterior fluid state is initialFluidStates_[globalDofIdx] - the interior cell's own state at the moment of
+ * opmhip_set_boundary_conditions, values only: phase pressures, densities, mobilities, 1/B, Rs (and Rv on the extended record).
+ * Per phase, in the reference's statement order: rhoAvg = (rhoIn + rhoEx) / 2; pEx += rhoAvg * (distZ * g), distZ = zIn - zFace;
+ * dp = pEx - pIn; dp > 0: the exterior is upstream, q = dp * mobEx * (-trans / area) with the captured mobility as a plain number
+ * (the reference re-evaluates the relative permeabilities of the exterior state with the cell's material parameters: without
+ * hysteresis that IS the captured mobility); otherwise q = dp * mobIn * (-(trans * tmult) / area), tmult the value of the cell's
+ * ROCKTAB transmissibility multiplier (rockCompTransMultiplier<double>, 1 without tables).  Derivatives: the interior cell's.
+ * From phase volume fluxes to the three equations (BlackOilBoundaryRateVector::setFreeFlow / setMassRate and evalPhaseFluxes_ are
+ * opm-models', not in the reference tree: restated from the published form, UNVERIFIED): per phase the RAW phase pressures
+ * pBoundary (captured) and pInside, without the gravity term, choose the fluid state that supplies 1/B, Rs and Rv - pBoundary <
+ * pInside: the interior's, with derivatives; pBoundary > pInside: the captured one's; equal: the phase adds nothing -, surface
+ * volume flux = 1/B * q into the phase's own equation, Rs times it into the gas equation (oil phase), Rv times it into the oil
+ * equation (gas phase, wet gas).  On a Z face the two direction tests may disagree (gravity): each then decides what the
+ * published form lets it decide, the mobility by dp, the composition by the raw pressures.
+ * RATE: rate[3] is a MASS rate per area in the equation order of opmhip_set_source (oil, water, gas); setMassRate divides each by
+ * the component's reference density in the cell's PVT region (Flow conserves surface volumes); no derivative.
+ * NOT covered: decomposed contexts; relative-permeability hysteresis with a FREE face; water-induced compaction tables; the
+ * thermal boundary (setThermalFlow); solvent and polymer; the deck's unit conversion and the BC keyword's boxes (the caller's:
+ * area, the boundary half transmissibility - ebos/ecltransmissibility.cc:241-282, the interior cell's half transmissibility alone,
+ * no NTG or MULT* - and the depth of the face centre, scvf.integrationPos()[2], are handed in). */
+#define OPMHIP_BC_RATE 0
+#define OPMHIP_BC_FREE 1
+typedef struct opmhip_boundary_conditions {
+    int num_faces;
+    const int* cell;        /* natural id of an owned cell */
+    const int* direction;   /* indexInInside: 0 X-, 1 X+, 2 Y-, 3 Y+, 4 Z-, 5 Z+; a (cell, direction) pair at most once */
+    const int* type;        /* OPMHIP_BC_RATE | OPMHIP_BC_FREE */
+    const double* area;     /* scvf.area(), > 0 */
+    const double* trans;    /* transmissibilityBoundary, >= 0 and finite */
+    const double* depth;    /* depth of the face centre */
+    const double* rate;     /* [3 num_faces]: RATE faces' mass rate per area (oil, water, gas), positive out of the domain; a FREE face's
+                             * entries are ignored */
+} opmhip_boundary_conditions;
+/* Call it after opmhip_set_static and opmhip_set_state: the exterior state of the FREE faces is captured here, on the device, from
+ * the intensive-quantity cache; a second call captures again.  NULL or num_faces == 0 clears the list.
+ * OPMHIP_NOT_READY before static / state; OPMHIP_INVALID_ARGUMENT (the text names the reason) for a null array, a cell outside
+ * [0, Nb), a direction outside 0..5, the same (cell, direction) twice, an area that is not positive, a transmissibility that is
+ * negative or not finite, an unknown type, a decomposed context, a FREE face in a context with relative-permeability hysteresis,
+ * a context with water-induced compaction tables.  A refused call leaves no list set.
+ * With a list set, every opmhip_assemble forms the faces' rates from the state now present and SUBTRACTS them (the source is a rate
+ * into the cell) from the source and its derivative of the boundary cells, behind the wells' and the aquifers' terms; the caller's
+ * source arrays hold exactly what the caller put there afterwards (12 doubles per distinct boundary cell are saved and restored
+ * around the assembly kernel).  Without a list nothing is launched. */
+int opmhip_set_boundary_conditions(opmhip_ctx* ctx, const opmhip_boundary_conditions* bc);
+/* for tests and reports: per face the last assemble's contribution to the interior cell's residual, area included, positive out of
+ * the cell: q12[12 f + e] the three equations (oil, water, gas), q12[12 f + 3 + 3 e + v] their derivatives with respect to the cell's
+ * primary variables */
+int opmhip_get_boundary_rates(opmhip_ctx* ctx, double* q12);
+
 /* ---- passive tracers, resident on the device.  Additive to ABI 11 ------------------------------------------------------------
  * EclTracerModel (ebos/ecltracermodel.hh:113-134, 156-439; ebos/eclgenerictracermodel.cc:86-281): tracers carried by one phase each,
  * advanced once per time step by one scalar transport solve per phase from the converged state - the cached intensive quantities, the

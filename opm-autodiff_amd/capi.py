@@ -89,6 +89,12 @@ class Aquifers(C.Structure):
                 ("initial_watvolume", C.c_void_p), ("has_restart", C.c_void_p), ("restart_W_flux", C.c_void_p), ("restart_pressure", C.c_void_p)]
 
 
+class BoundaryConditions(C.Structure):
+    """opmhip_boundary_conditions: the FREE and RATE faces for the device-resident form (opmhip_set_boundary_conditions)"""
+    _fields_ = [("num_faces", C.c_int), ("cell", C.c_void_p), ("direction", C.c_void_p), ("type", C.c_void_p), ("area", C.c_void_p),
+                ("trans", C.c_void_p), ("depth", C.c_void_p), ("rate", C.c_void_p)]
+
+
 class TracerResult(C.Structure):
     """opmhip_tracer_result"""
     _fields_ = [("converged", C.c_int), ("iterations", C.c_double), ("reduction", C.c_double)]
@@ -293,6 +299,39 @@ def make_aquifers(aquifers):
                td=_f64(np.concatenate(td)), pd=_f64(np.concatenate(pd)))
     s = Aquifers(len(aquifers))
     for name, _ in Aquifers._fields_[1:]:
+        setattr(s, name, arr[name].ctypes.data)
+    return s, arr
+
+
+BOUNDARY_TYPES = {"rate": 0, "free": 1}
+
+
+def make_boundary_conditions(records):
+    """list of face-group dicts (boundary.rate / boundary.free: type, cells, direction, area, trans, depth and, for "rate", rate (n, 3)),
+    cells in natural order; the faces are listed in the order of the records -> (BoundaryConditions struct, keep-alive dict).
+    Ragged input (lengths that do not fit each other, an unknown type, a missing entry) raises ValueError."""
+    if not records:
+        return None, {}
+    col = {k: [] for k in ("cell", "direction", "type", "area", "trans", "depth", "rate")}
+    for n, r in enumerate(records):
+        try:
+            kind = BOUNDARY_TYPES[r["type"]]
+            cl = np.asarray(r["cells"]).reshape(-1)
+            m = len(cl)
+            per = {k: np.asarray(r[k], float).reshape(-1) for k in ("area", "trans", "depth")}
+            per["direction"] = np.asarray(r["direction"]).reshape(-1)
+            rt = np.asarray(r["rate"], float).reshape(-1, 3) if kind == 0 else np.zeros((m, 3))
+            if any(len(v) != m for v in per.values()) or len(rt) != m:
+                raise ValueError("boundary record %d: %d cells, arrays of other lengths" % (n, m))
+        except KeyError as e:
+            raise ValueError("boundary record %d: missing entry or unknown type %s" % (n, e))
+        col["cell"].append(cl); col["type"].append(np.full(m, kind)); col["rate"].append(rt)
+        for k, v in per.items():
+            col[k].append(v)
+    i32 = ("cell", "direction", "type")
+    arr = {k: (_i32(np.concatenate(v)) if k in i32 else _f64(np.concatenate(v).reshape(-1))) for k, v in col.items()}
+    s = BoundaryConditions(len(arr["cell"]))
+    for name, _ in BoundaryConditions._fields_[1:]:
         setattr(s, name, arr[name].ctypes.data)
     return s, arr
 
@@ -816,6 +855,8 @@ def _bind_assembly(L):
     L.opmhip_aquifers_begin_time_step.argtypes = [vp, C.c_double, C.c_double]
     L.opmhip_get_aquifers.argtypes = [vp, vp, vp, vp, vp]
     L.opmhip_get_aquifer_rates.argtypes = [vp, vp]
+    L.opmhip_set_boundary_conditions.argtypes = [vp, C.POINTER(BoundaryConditions)]
+    L.opmhip_get_boundary_rates.argtypes = [vp, vp]
     L.opmhip_set_tracers.argtypes = [vp, C.c_int, vp, vp]
     L.opmhip_set_tracer_solver.argtypes = [vp, C.c_double, C.c_int]
     L.opmhip_set_tracer_connections.argtypes = [vp, C.c_int, vp, vp, vp]
@@ -1122,6 +1163,23 @@ class HipModel(HipSolver):
         """Qai_ of the last assemble per connection: (connections, 4) = value, d/dSw, d/dp, d/dX"""
         q = np.zeros((getattr(self, "_naqconn", 0), 4))
         self._check(lib().opmhip_get_aquifer_rates(self._h, _ptr(q)))
+        return q
+
+    def set_boundary_conditions(self, records):
+        """opmhip_set_boundary_conditions: the FREE and RATE faces (list of boundary.free / boundary.rate records, see
+        make_boundary_conditions) on the device; the exterior state of the FREE faces is the state now present.  None or an empty list
+        clears them"""
+        bc, keep = make_boundary_conditions(records)
+        self._nbcfaces = 0      # a refused call leaves no list set
+        self._check(lib().opmhip_set_boundary_conditions(self._h, C.byref(bc) if bc else None))
+        if bc:
+            self._nbcfaces = bc.num_faces
+
+    def boundary_rates(self):
+        """the last assemble's contribution of every face to its cell's residual, positive out of the cell: (faces, 12) = the three equations
+        (oil, water, gas), then their 3 x 3 derivative, row by row"""
+        q = np.zeros((getattr(self, "_nbcfaces", 0), 12))
+        self._check(lib().opmhip_get_boundary_rates(self._h, _ptr(q)))
         return q
 
     def _check(self, rc):

@@ -448,14 +448,6 @@ __device__ __forceinline__ void update_iq(const TablesT<DP>& T, const CellStatic
     }
 }
 
-__device__ __forceinline__ void store_ad(double* o, const Ad& a) {
-    *reinterpret_cast<double2*>(o) = make_double2(a.v, a.d0);
-    *reinterpret_cast<double2*>(o + 2) = make_double2(a.d1, a.d2);
-}
-__device__ __forceinline__ Ad load_ad(const double* o) {
-    const double2 a = *reinterpret_cast<const double2*>(o), b = *reinterpret_cast<const double2*>(o + 2);
-    return Ad{a.x, a.y, b.x, b.y};
-}
 // the convergence check needs 1/b of the three phases and nothing else of the record (flow/BlackoilModelEbos.hpp:650-664):
 // a packed copy (24 B per cell) spares it a 544-byte-strided walk through the cache (PMC: 232 MB of traffic for 56 MB of data)
 __device__ __forceinline__ void store_invb(double* invb, int c, const Iq<Ad>& q) {

@@ -787,13 +787,18 @@ int opmhip_assemble(opmhip_ctx* c, double dt, int iteration, double* jac, double
         StdWellsDev& SW = c->wells.sw;
         if (Q.num > 0 && !Q.stepped) return fail(c, OPMHIP_NOT_READY, "assemble: aquifers are set but opmhip_aquifers_begin_time_step was not called");
         if (Q.num > 0 && dt != Q.step_dt) return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: dt = %.17g, the aquifers' time step was begun with dt = %.17g", dt, Q.step_dt);
+        const BoundaryDev& BC = c->asmb.bc;
+        if (BC.nf > 0 && ((BC.nfc > 0 && c->asmb.hyst_model >= 0) || c->asmb.d_maxsw))
+            return fail(c, OPMHIP_INVALID_ARGUMENT, "assemble: hysteresis or water-induced compaction was set behind opmhip_set_boundary_conditions, which refuses them");
         OPMHIP_HIP(c, hipSetDevice(c->device));
         c->asmb.last_dt = dt;
         c->asmb.last_iteration = iteration;
         SW.in_matrix = false;   // a new Jacobian: the matrix-add form's wells are not in it yet
         if (SW.num > 0) { launch_std_wells_assemble(c); SW.assembled = true; }   // wellModel().assemble: rates first, then the aquifers (the host order)
         if (Q.nd > 0) launch_aquifer_apply(c);     // aquiferModel_.addToSource (ebos/eclproblem.hh:1843)
+        if (BC.nd > 0) launch_boundary_apply(c);   // EclProblem::boundary (ebos/eclproblem.hh:1602-1671): the faces' rates out of the boundary cells' source
         launch_assemble(c, dt, iteration);
+        if (BC.nd > 0) launch_boundary_restore(c); // innermost: the save areas nest
         if (Q.nd > 0) launch_aquifer_restore(c);   // the caller's source arrays as the caller left them
         if (SW.num > 0) launch_std_wells_restore(c);
         OPMHIP_HIP(c, hipGetLastError());

@@ -185,6 +185,15 @@ template <class DP> __device__ __forceinline__ double rv_sat_value(const TablesT
 // records, whose 544-byte stride gave every lane of a gather its own lines.  (F_S .. F_RS, the phases, the equations: internal.hpp)
 __device__ __forceinline__ const double* iq_at(const double* iq, int ncell, int f, int c) { return iq + ((size_t)f * ncell + c) * 4; }
 __device__ __forceinline__ double* iq_at(double* iq, int ncell, int f, int c) { return iq + ((size_t)f * ncell + c) * 4; }
+// one field (value + 3 derivatives, 16-byte aligned) as two 16-byte accesses
+__device__ __forceinline__ void store_ad(double* o, const Ad& a) {
+    *reinterpret_cast<double2*>(o) = make_double2(a.v, a.d0);
+    *reinterpret_cast<double2*>(o + 2) = make_double2(a.d1, a.d2);
+}
+__device__ __forceinline__ Ad load_ad(const double* o) {
+    const double2 a = *reinterpret_cast<const double2*>(o), b = *reinterpret_cast<const double2*>(o + 2);
+    return Ad{a.x, a.y, b.x, b.y};
+}
 template <bool EXT> struct Lay {
     static constexpr int F_RV = 16, F_TMULT = 17;                    // EXT only
     static constexpr int F_PORO = EXT ? 18 : 16;

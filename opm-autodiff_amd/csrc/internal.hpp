@@ -354,6 +354,25 @@ struct AquifersDev {
     }
 };
 
+// Open boundaries on the device (opmhip_set_boundary_conditions; kernels: boundary.hip, entry points: capi_boundary.cpp, host set-up:
+// boundary_setup.hpp).  nf faces, nd distinct boundary cells, nfc of them with a FREE face.  Per face BC_GEO doubles (area,
+// transmissibility, depth of the face centre) and the RATE faces' three rates; per distinct cell with a FREE face one captured
+// exterior record of BC_EXT doubles: p, rho, mobility, 1/B of the three phases, Rs, Rv.
+enum { BC_AREA = 0, BC_TRANS, BC_DEPTH, BC_GEO };
+enum { BX_P = 0, BX_RHO = 3, BX_MOB = 6, BX_B = 9, BX_RS = 12, BX_RV = 13, BC_EXT = 14 };
+constexpr int BC_Q = 12;   // a face's residual contribution: three equations and their 3 x 3 derivative
+struct BoundaryDev {
+    int nf = 0, nd = 0, nfc = 0;
+    int *d_type = nullptr;                                            // per face
+    double *d_geo = nullptr, *d_rate = nullptr, *d_q = nullptr;       // per face: BC_GEO, 3, BC_Q
+    int *d_cpos = nullptr, *d_cptr = nullptr, *d_cconn = nullptr;     // distinct cells: position, range into d_cconn, their faces in list order
+    int *d_slot = nullptr, *d_fcell = nullptr;                        // per distinct cell: its exterior record or -1; per record: its distinct cell
+    double *d_ext = nullptr, *d_save = nullptr;                       // [nfc * BC_EXT]; per distinct cell: the caller's source row and dsource block
+    template <class F> void each_dev(F f) {
+        f(&d_type); f(&d_geo); f(&d_rate); f(&d_q); f(&d_cpos); f(&d_cptr); f(&d_cconn); f(&d_slot); f(&d_fcell); f(&d_ext); f(&d_save);
+    }
+};
+
 // Passive tracers on the device (opmhip_set_tracers; kernels and the solve: tracers.hip, entry points: capi_tracers.cpp, host set-up:
 // tracers_setup.hpp).  One batch per phase; a batch's per-cell arrays are interleaved [cell][tracer of the batch], internal cell order.
 // The matrix, the factors and the solver's vectors are shared by the batches (they are solved one after the other) and sized for the
@@ -441,6 +460,7 @@ constexpr int RESV_MAX_PARTS = 1024, RESV_FINAL_THREADS = 256, RESV_OUT = 6;
 // assembly-side device state (all per-cell / per-entry arrays in the INTERNAL order)
 struct AsmDev {
     AquifersDev aq;
+    BoundaryDev bc;
     TracersDev tr;
     VfpDev vfp;
     FipDev fip;
@@ -941,6 +961,10 @@ void launch_aquifer_begin(opmhip_ctx* c);    // pressure_previous_ = p_w of the 
 void launch_aquifer_apply(opmhip_ctx* c);    // Qai_ of every connection; saved and raised source rows of the connected cells (in front of k_assemble)
 void launch_aquifer_restore(opmhip_ctx* c);  // the caller's source rows back (behind k_assemble)
 void launch_aquifer_end(opmhip_ctx* c, double dt);
+// open boundaries (boundary.hip)
+void launch_boundary_capture(opmhip_ctx* c);  // the exterior records of the cells with a FREE face, from the intensive-quantity cache
+void launch_boundary_apply(opmhip_ctx* c);    // every face's rates; saved and lowered source rows / dsource blocks of the boundary cells (in front of k_assemble)
+void launch_boundary_restore(opmhip_ctx* c);  // the caller's rows and blocks back (behind k_assemble)
 // standard wells on the device (opmhip_set_std_wells; kernels and launchers: std_wells.hip, entry points: capi_std_wells.cpp)
 int std_wells_check(opmhip_ctx* c, const double* flags);   // capi_std_wells.cpp: the zero-pivot flags as the caller has just read them back; a singular D clears the list
 // capi_std_wells.cpp: the list's part of opmhip_advance_time_level / opmhip_update_failed, on the context's stream

@@ -64,11 +64,14 @@ class ModelParameters:
 class BlackoilModelHip:
     """model = capi.HipModel (device context) ; one instance drives one grid on one GPU."""
 
-    def __init__(self, model, param=None, well_model=None, aquifer_model=None, tracer_model=None):
+    def __init__(self, model, param=None, well_model=None, aquifer_model=None, tracer_model=None, boundary_model=None):
         """tracer_model (tracers.DeviceTracers, tracers.HostTracers or None): the passive tracers - tracerModel_ of EclProblem, advanced once
         per accepted time step (beginTimeStep / endTimeStep below) with the connection rates of well_model; None: the loop is unchanged.
         aquifer_model (aquifers.DeviceAquifers, aquifers.HostAquifers or None): the analytic aquifers - aquiferModel_ of EclProblem
         (initialSolutionApplied here, beginTimeStep / addToSource / endTimeStep below); the model's state must be set.
+        boundary_model (boundary.DeviceBoundary, boundary.HostBoundary or None): the open boundaries of the BC keyword - EclProblem::boundary;
+        the exterior state of the FREE faces is the model's state now.  The host form stands alone: beside a well model or HostAquifers its
+        source rows would replace theirs.
         well_model (wells.StandardWells, wells.DeviceStandardWells or None): the host-side well equations of BlackoilWellModel - assembled in front of the
         reservoir's linearisation (BlackoilModelEbos::assembleReservoir -> wellModel().assemble, flow/BlackoilModelEbos.hpp:418-428),
         eliminated from the linear system by the device (wells/StandardWell_impl.hpp:1254-1311) and updated with the reservoir"""
@@ -83,6 +86,11 @@ class BlackoilModelHip:
         if aquifer_model is not None:
             aquifer_model.initial_solution_applied(model)
         self.tracers = tracer_model
+        self.boundary = boundary_model
+        if boundary_model is not None:
+            if not boundary_model.on_device and (well_model is not None or (aquifer_model is not None and not aquifer_model.on_device)):
+                raise NotImplementedError("HostBoundary beside a well model or HostAquifers: its source rows would replace theirs")
+            boundary_model.initial_solution_applied(model)
 
     # -- BlackoilModelEbos::getReservoirConvergence ------------------------------------------------------------
     def get_convergence(self, dt, iteration):
@@ -162,6 +170,10 @@ class BlackoilModelHip:
                 self.aquifers.add_to_source(self.m, wa["cells"], wa["source_cells"], wa["dsource_cells"])
             else:
                 self.aquifers.add_to_source(self.m)
+        if self.boundary is not None and not self.boundary.on_device:
+            # EclProblem::boundary (ebos/eclproblem.hh:1602-1671) on the host: the boundary cells' records come down, the faces' rates go up.
+            # The device form (opmhip_set_boundary_conditions) needs nothing here: opmhip_assemble forms them itself
+            self.boundary.add_to_source(self.m)
         self.m.assemble(dt, iteration, fetch=False)          # assembleReservoir -> linearizeDomain (asynchronous)
         conv, norms = self.get_convergence(dt, iteration)    # synchronises: reads the reduced scalars back
         if wa is not None:
