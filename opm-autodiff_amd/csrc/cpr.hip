@@ -27,6 +27,7 @@
 #include <thread>
 
 #include "internal.hpp"
+#include "device_blocks.hpp"
 
 namespace opmhip {
 
@@ -34,22 +35,6 @@ constexpr int CPR_P = 1;             // pressure index inside a block (BlackOilI
 
 // ---------------------------------------------------------------- kernels -----------------------------------------------
 #define CPR_DONE_CHECK if (*done != 0.0) return;
-// closed-form 3x3 inverse, expression tree of Opm::Detail::Inverter<3> (linalg/MatrixBlock.hpp:722-747); same as solver.hip
-__device__ __forceinline__ void inv3(const double* m, double* inv) {
-    const double t4 = m[0] * m[4], t6 = m[0] * m[5], t8 = m[1] * m[3];
-    const double t10 = m[2] * m[3], t12 = m[1] * m[6], t14 = m[2] * m[6];
-    const double det = (t4 * m[8] - t6 * m[7] - t8 * m[8] + t10 * m[7] + t12 * m[5] - t14 * m[4]);
-    const double t17 = 1.0 / det;
-    inv[0] = (m[4] * m[8] - m[5] * m[7]) * t17;
-    inv[1] = -(m[1] * m[8] - m[2] * m[7]) * t17;
-    inv[2] = (m[1] * m[5] - m[2] * m[4]) * t17;
-    inv[3] = -(m[3] * m[8] - m[5] * m[6]) * t17;
-    inv[4] = (m[0] * m[8] - t14) * t17;
-    inv[5] = -(t6 - t10) * t17;
-    inv[6] = (m[3] * m[7] - m[4] * m[6]) * t17;
-    inv[7] = -(m[0] * m[7] - t12) * t17;
-    inv[8] = (t4 - t8) * t17;
-}
 // quasi-IMPES weights: w_i = D_ii^-T e_p / max|.| (getQuasiImpesWeights.hpp:46-85)
 __global__ __launch_bounds__(256) void k_cpr_weights(int Nb, const int* __restrict__ diag, const double* __restrict__ A, double* __restrict__ w) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -58,7 +43,7 @@ __global__ __launch_bounds__(256) void k_cpr_weights(int Nb, const int* __restri
     double Dt[BB], inv[BB];
     for (int r = 0; r < BS; ++r)
         for (int c = 0; c < BS; ++c) Dt[r * BS + c] = D[c * BS + r];
-    inv3(Dt, inv);
+    blk_invert(Dt, inv);
     double bw[BS], mx = 0.0;
     for (int r = 0; r < BS; ++r) { bw[r] = inv[r * BS + CPR_P]; mx = fmax(mx, fabs(bw[r])); }
     for (int r = 0; r < BS; ++r) w[(size_t)i * BS + r] = bw[r] / mx;

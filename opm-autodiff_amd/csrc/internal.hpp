@@ -33,6 +33,14 @@ constexpr int BB = 9;
 #endif
 constexpr int TILE_ROWS = OPMHIP_TILE_ROWS;
 constexpr int TILE_CAP_BLOCKS = 7 * TILE_ROWS;  // a full tile of a Cartesian 7-point stencil
+// ---- what reorder.cpp builds and the kernels of solver.hip read: the limits both sides go by ----
+constexpr int CHAIN_MAX_STEPS = 128;       // steps of a chain-tile (its descriptor record lives in LDS)
+constexpr int STENCIL_ROW_ENTRIES = 8;     // the stencil form (StencilForm): 4-bit table indices in a row's word = entries of a row
+constexpr int STENCIL_MAX_OFFSETS = 15;    // ... offsets in a tile's table; the index 15 says "no entry"
+constexpr int STENCIL_TABLE_SLOTS = 16;    // ... numbers a tile's table takes in StencilForm::table
+constexpr int STENCIL_MAX_KOFF = 255;      // ... a row's first entry behind its tile's first entry (one byte)
+constexpr int DESC_HEAD = 4;               // descriptor record of a chain kernel's launch position (TileSet::ctDesc): numbers in front of its three lists
+constexpr int desc_stride(int S1) { return 4 * ((DESC_HEAD + 3 * S1 + 3) / 4); }   // ... its size with three lists of S1 numbers, a multiple of 16 bytes
 
 struct DevBuf {
     void* p = nullptr;

@@ -295,16 +295,16 @@ void tile_offsets(const std::vector<int>& rowptr, const std::vector<int>& col, i
 void reset_stencil(StencilForm& S, int Nb, size_t tables) {
     S.word.assign(Nb, 0xFFFFFFFFu);
     S.koff.assign(Nb, 0);
-    S.table.assign(16 * tables, 0);
+    S.table.assign(STENCIL_TABLE_SLOTS * tables, 0);
 }
 bool encode_stencil(const std::vector<int>& rowptr, const std::vector<int>& col, int r0, int r1, int slot, StencilForm& S) {
     std::vector<int> offs;
     tile_offsets(rowptr, col, r0, r1, offs);
-    if (offs.size() > 15) return false;
-    for (size_t q = 0; q < offs.size(); ++q) S.table[(size_t)16 * slot + q] = offs[q];
+    if (offs.size() > STENCIL_MAX_OFFSETS) return false;
+    for (size_t q = 0; q < offs.size(); ++q) S.table[(size_t)STENCIL_TABLE_SLOTS * slot + q] = offs[q];
     for (int r = r0; r < r1; ++r) {
         const int len = rowptr[r + 1] - rowptr[r], ko = rowptr[r] - rowptr[r0];
-        if (len > 8 || ko > 255) return false;
+        if (len > STENCIL_ROW_ENTRIES || ko > STENCIL_MAX_KOFF) return false;
         unsigned w = 0xFFFFFFFFu;
         for (int u = 0; u < len; ++u) {
             const int idx = (int)(std::lower_bound(offs.begin(), offs.end(), col[rowptr[r] + u] - r) - offs.begin());
@@ -368,7 +368,7 @@ void build_rest_schedule(Pattern& P, const std::vector<int>& order) {
                 if (r1 <= r0) continue;
                 if (cur.r1 > cur.r0 && r0 == cur.r1 && r1 - cur.r0 <= 64 && P.rrowptr[r1] - P.rrowptr[cur.r0] <= TILE_CAP_BLOCKS) {
                     tile_offsets(P.rrowptr, P.rcol, cur.r0, r1, offs);
-                    if (offs.size() <= 15) { cur.r1 = r1; continue; }
+                    if (offs.size() <= STENCIL_MAX_OFFSETS) { cur.r1 = r1; continue; }
                 }
                 if (cur.r1 > cur.r0) lists[k].push_back(cur);
                 cur = Rt{r0, r1};
@@ -441,7 +441,7 @@ void build_schedules(Pattern& P, int G) {
         int S = 1;
         for (size_t q = 0; q + 1 < T.ctFirst.size(); ++q) S = std::max(S, T.ctFirst[q + 1] - T.ctFirst[q]);
         T.descS1 = S + 1;
-        T.descStride = 4 * ((4 + 3 * T.descS1 + 3) / 4);
+        T.descStride = desc_stride(T.descS1);
         T.ctDesc.assign((size_t)T.ctSched.size() * T.descStride, 0);
         for (size_t pos = 0; pos < T.ctSched.size(); ++pos) {
             int* rec = &T.ctDesc[pos * T.descStride];
@@ -453,9 +453,9 @@ void build_schedules(Pattern& P, int G) {
             rec[2] = q0;   // first tile of the chain-tile: where its steps' stencil tables start
             for (int i = 0; i <= n; ++i) {
                 const int r = T.row0[q0 + i];
-                rec[4 + i] = r;
-                rec[4 + T.descS1 + i] = P.lrowptr[r];
-                rec[4 + 2 * T.descS1 + i] = P.urowptr[r];
+                rec[DESC_HEAD + i] = r;
+                rec[DESC_HEAD + T.descS1 + i] = P.lrowptr[r];
+                rec[DESC_HEAD + 2 * T.descS1 + i] = P.urowptr[r];
             }
         }
     }
@@ -668,13 +668,13 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
         bool regular = Nb >= AUTO_LINE_MIN_ROWS;
         std::vector<int> offs;
         for (int i = 0; i < Nb && regular; ++i) {
-            if (rows[i + 1] - rows[i] > 8) regular = false;
+            if (rows[i + 1] - rows[i] > STENCIL_ROW_ENTRIES) regular = false;
             for (int k = rows[i]; k < rows[i + 1] && regular; ++k) {
                 if (cols[k] >= Nb) continue;
                 const int o = cols[k] - i;
                 if (std::find(offs.begin(), offs.end(), o) == offs.end()) {
                     offs.push_back(o);
-                    if (offs.size() > 15) regular = false;
+                    if (offs.size() > STENCIL_MAX_OFFSETS) regular = false;
                 }
             }
         }
@@ -905,8 +905,8 @@ int build_pattern(opmhip_ctx* c, int Nb, int Nghost, int nnzb, const int* rows, 
         T.ctFirst.push_back((int)T.row0.size());
         T.row0.push_back(Nb);
         for (size_t q = 0; q + 1 < T.ctFirst.size(); ++q)
-            if (T.ctFirst[q + 1] - T.ctFirst[q] > 128)
-                return fail(c, OPMHIP_ANALYSIS_FAILED, "line colouring: a chain-tile has %d steps (limit 128); lower the chain length", T.ctFirst[q + 1] - T.ctFirst[q]);
+            if (T.ctFirst[q + 1] - T.ctFirst[q] > CHAIN_MAX_STEPS)
+                return fail(c, OPMHIP_ANALYSIS_FAILED, "line colouring: a chain-tile has %d steps (limit %d); lower the chain length", T.ctFirst[q + 1] - T.ctFirst[q], CHAIN_MAX_STEPS);
     }
 
     build_schedules(P, OPMHIP_XCD_GROUP_DEFAULT);   // chain-tiles per XCD group of the launch schedules (0 = identity map), see DESIGN.md

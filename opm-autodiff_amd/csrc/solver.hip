@@ -15,12 +15,14 @@
 #include <hip/hip_ext.h>
 #include <atomic>
 
+#include <cassert>
 #include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
 
 #include "internal.hpp"
+#include "device_blocks.hpp"
 
 namespace opmhip {
 
@@ -82,77 +84,6 @@ __device__ __forceinline__ void stage_ints(const int* __restrict__ src, int* __r
 // matrix through all 8 L2s at once and was faster (SpMV 0.112 vs 0.125 ms at 100^3) than an XCD-contiguous map that keeps
 // each XCD on one contiguous eighth of the tile range so that gathered vector entries stay in one 4 MB L2.
 
-// y -= A x, y += A x, y = A x in dune-common DenseMatrix order (row outer, column inner)
-__device__ __forceinline__ void blk_mmv(const double* A, const double x0, const double x1, const double x2, double* y) {
-    y[0] -= A[0] * x0; y[0] -= A[1] * x1; y[0] -= A[2] * x2;
-    y[1] -= A[3] * x0; y[1] -= A[4] * x1; y[1] -= A[5] * x2;
-    y[2] -= A[6] * x0; y[2] -= A[7] * x1; y[2] -= A[8] * x2;
-}
-// The same with the block known to live in LDS.  The pointer carries its address space in its type, so that the compiler
-// can neither treat it as "flat" nor merge this path with the global-memory one behind a single flat pointer (it does
-// that to two branches that differ in nothing but the pointer): a flat load makes the wavefront wait for EVERY outstanding
-// memory access - in the pipelined sweeps that is the prefetch of the next step.
-typedef __attribute__((address_space(3))) const double lds_cdouble;
-__device__ __forceinline__ void blk_mmv_lds(const double* Agen, const double x0, const double x1, const double x2, double* y) {
-    lds_cdouble* A = (lds_cdouble*)Agen;
-    y[0] -= A[0] * x0; y[0] -= A[1] * x1; y[0] -= A[2] * x2;
-    y[1] -= A[3] * x0; y[1] -= A[4] * x1; y[1] -= A[5] * x2;
-    y[2] -= A[6] * x0; y[2] -= A[7] * x1; y[2] -= A[8] * x2;
-}
-// y -= A x and, beside it, u += A x from the SAME rounded products: the backward sweep's row sums u_i = sum_{j>i} U_ij x_j (Pattern::ualias)
-__device__ __forceinline__ void blk_mmv_u(const double* A, const double x0, const double x1, const double x2, double* y, double* u) {
-    double p;
-    p = A[0] * x0; y[0] -= p; u[0] += p; p = A[1] * x1; y[0] -= p; u[0] += p; p = A[2] * x2; y[0] -= p; u[0] += p;
-    p = A[3] * x0; y[1] -= p; u[1] += p; p = A[4] * x1; y[1] -= p; u[1] += p; p = A[5] * x2; y[1] -= p; u[1] += p;
-    p = A[6] * x0; y[2] -= p; u[2] += p; p = A[7] * x1; y[2] -= p; u[2] += p; p = A[8] * x2; y[2] -= p; u[2] += p;
-}
-__device__ __forceinline__ void blk_mmv_lds_u(const double* Agen, const double x0, const double x1, const double x2, double* y, double* u) {
-    lds_cdouble* A = (lds_cdouble*)Agen;
-    double p;
-    p = A[0] * x0; y[0] -= p; u[0] += p; p = A[1] * x1; y[0] -= p; u[0] += p; p = A[2] * x2; y[0] -= p; u[0] += p;
-    p = A[3] * x0; y[1] -= p; u[1] += p; p = A[4] * x1; y[1] -= p; u[1] += p; p = A[5] * x2; y[1] -= p; u[1] += p;
-    p = A[6] * x0; y[2] -= p; u[2] += p; p = A[7] * x1; y[2] -= p; u[2] += p; p = A[8] * x2; y[2] -= p; u[2] += p;
-}
-__device__ __forceinline__ void blk_umv_lds(const double* Agen, const double x0, const double x1, const double x2, double* y) {
-    lds_cdouble* A = (lds_cdouble*)Agen;
-    y[0] += A[0] * x0; y[0] += A[1] * x1; y[0] += A[2] * x2;
-    y[1] += A[3] * x0; y[1] += A[4] * x1; y[1] += A[5] * x2;
-    y[2] += A[6] * x0; y[2] += A[7] * x1; y[2] += A[8] * x2;
-}
-__device__ __forceinline__ void blk_umv(const double* A, const double x0, const double x1, const double x2, double* y) {
-    y[0] += A[0] * x0; y[0] += A[1] * x1; y[0] += A[2] * x2;
-    y[1] += A[3] * x0; y[1] += A[4] * x1; y[1] += A[5] * x2;
-    y[2] += A[6] * x0; y[2] += A[7] * x1; y[2] += A[8] * x2;
-}
-// C = A * B with the inner sum starting from 0.0 (DenseMatrix::rightmultiply / leftmultiply)
-__device__ __forceinline__ void blk_mul(const double* A, const double* B, double* C) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s = 0.0;
-            s += A[i * 3 + 0] * B[0 * 3 + j];
-            s += A[i * 3 + 1] * B[1 * 3 + j];
-            s += A[i * 3 + 2] * B[2 * 3 + j];
-            C[i * 3 + j] = s;
-        }
-}
-// closed-form inverse, expression tree of Opm::Detail::Inverter<3> (linalg/MatrixBlock.hpp:722-747)
-__device__ __forceinline__ void blk_invert(const double* m, double* inv) {
-    const double t4 = m[0] * m[4], t6 = m[0] * m[5], t8 = m[1] * m[3];
-    const double t10 = m[2] * m[3], t12 = m[1] * m[6], t14 = m[2] * m[6];
-    const double det = (t4 * m[8] - t6 * m[7] - t8 * m[8] + t10 * m[7] + t12 * m[5] - t14 * m[4]);
-    const double t17 = 1.0 / det;
-    inv[0] = (m[4] * m[8] - m[5] * m[7]) * t17;
-    inv[1] = -(m[1] * m[8] - m[2] * m[7]) * t17;
-    inv[2] = (m[1] * m[5] - m[2] * m[4]) * t17;
-    inv[3] = -(m[3] * m[8] - m[5] * m[6]) * t17;
-    inv[4] = (m[0] * m[8] - t14) * t17;
-    inv[5] = -(t6 - t10) * t17;
-    inv[6] = (m[3] * m[7] - m[4] * m[6]) * t17;
-    inv[7] = -(m[0] * m[7] - t12) * t17;
-    inv[8] = (t4 - t8) * t17;
-}
 // The tile kernels run ONE wavefront per workgroup.  A wavefront's LDS instructions execute in issue order and its
 // global stores are visible to its own later loads once they have left the wave (same CU, write-through L1), so no
 // s_barrier is needed between "lanes wrote LDS" and "other lanes read it" - only the compiler must keep the order.
@@ -196,16 +127,6 @@ __device__ __forceinline__ TileCtx tile_stage_values(int t, const int* __restric
     if (T.staged && T.nb > 0) stage_doubles(val + (size_t)T.k0e * BB, sval, T.nb * BB, lane);
     wave_sync();
     return T;
-}
-
-// y -= A x / y += A x per block, see blk_mmv / blk_umv
-template <bool SUB>
-__device__ __forceinline__ void blk_apply(const double* A, const double* xx, double* acc) {
-    if (SUB) blk_mmv(A, xx[0], xx[1], xx[2], acc); else blk_umv(A, xx[0], xx[1], xx[2], acc);
-}
-template <bool SUB>
-__device__ __forceinline__ void blk_apply_lds(const double* A, const double* xx, double* acc) {
-    if (SUB) blk_mmv_lds(A, xx[0], xx[1], xx[2], acc); else blk_umv_lds(A, xx[0], xx[1], xx[2], acc);
 }
 
 // Accumulates acc (+/-)= sum_k A_k x[col_k] over the lane's row of tile t, blocks taken in ascending (or, with
@@ -430,6 +351,7 @@ __global__ __launch_bounds__(64) void k_spmv(const int4* __restrict__ sched, con
 // product gets 4 % longer (a third operand stream of 24 MB), the two k_dots launches and their kernel boundaries go, +1.3 %
 // Newton iterations/s at equal iteration counts.  (Per-tile wavefront reductions, the first way this was tried, cost 8 %.)
 constexpr int PGCH = 8;
+static_assert(PGCH == STENCIL_ROW_ENTRIES, "k_spmv_pipe_st decodes one word of PGCH table indices per row");
 constexpr int PIPE_MAX_STEPS = 128;   // schedule entries of one workgroup, kept in LDS (2 KiB: eight workgroups per CU must still fit; the host sizes the grid accordingly)
 // Written by the rules listed at chain_sweep (which see): the tile's schedule entries come out of LDS (one round of loads
 // at the start instead of a scalar load per tile at the head of every dependency chain); stages A (row bounds, 3 tiles
@@ -798,7 +720,6 @@ __global__ __launch_bounds__(64) void k_ilu_sweep(int tile_begin, int ntc, int n
 __device__ __forceinline__ double coherent_load(const double* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-constexpr int CHAIN_MAX_STEPS = 128;
 #ifndef OPMHIP_CHAIN_GATHER
 #define OPMHIP_CHAIN_GATHER 6
 #endif
@@ -811,8 +732,8 @@ constexpr int CHAIN_STAGE = OPMHIP_CHAIN_STAGE;
 // coalesced load: [0] steps (0 = padding) [1] chain-tile [4 ..] first row of step 0..steps, then the first L entry and the
 // first U entry of those rows (S1 = longest chain-tile + 1 numbers each).  Everything the sweep needs to issue its first
 // loads - the old chain  schedule -> chain-tile -> tile -> row -> entry  cost four dependent round trips per workgroup.
-constexpr int DESC_HEAD = 4;
 constexpr int DESC_MAX = DESC_HEAD + 3 * (CHAIN_MAX_STEPS + 1) + 3;
+static_assert(DESC_MAX >= desc_stride(CHAIN_MAX_STEPS + 1), "the LDS image holds the record of the longest chain-tile the host lets through");
 __device__ __forceinline__ int load_desc(const int* __restrict__ desc, int dstride, int lane, int* sdesc) {
     const int* rec = desc + (size_t)blockIdx.x * dstride;
     for (int i = lane; i < dstride; i += 64) sdesc[i] = rec[i];
@@ -2119,6 +2040,13 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
     int es = -1, ee = -1;
     const bool timed = prof_kernel_scope(c, cls, &es, &ee);
     hipEvent_t e0 = timed ? c->prof.ev[es] : nullptr, e1 = timed ? c->prof.ev[ee] : nullptr;
+    // the instantiations by [uadd != nullptr][ndot] and by [ndot]; three sums ride in the stencil kernel alone (launch_spmv: rides3)
+    static decltype(&k_spmv_pipe_st<0, false>) const pipeSt[2][4] = {
+        {k_spmv_pipe_st<0, false>, k_spmv_pipe_st<1, false>, k_spmv_pipe_st<2, false>, k_spmv_pipe_st<3, false>},
+        {k_spmv_pipe_st<0, true>, k_spmv_pipe_st<1, true>, k_spmv_pipe_st<2, true>, k_spmv_pipe_st<3, true>}};
+    static decltype(&k_spmv_pipe<0>) const pipe[3] = {k_spmv_pipe<0>, k_spmv_pipe<1>, k_spmv_pipe<2>};
+    static decltype(&k_spmv<0>) const tile[3] = {k_spmv<0>, k_spmv<1>, k_spmv<2>};
+    const double* w1r = ndot == 3 ? w1 : (const double*)nullptr;   // the third sum's operand: passed with NDOT == 3 alone
     if (uadd) {
         // the rest product (Pattern::ualias): the pipelined kernel on the schedule, the index streams and the values of the matrix WITHOUT
         // its U part, the row sums of the backward sweep added at the end of every row.  The grid as for the full product: every workgroup
@@ -2128,15 +2056,8 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
         const int pipeWgs = std::max(8, spmv_pipe_wgs(c));
         const int steps = std::min((np + pipeWgs - 1) / pipeWgs, PIPE_MAX_STEPS);
         const int grid = 8 * (((np + steps - 1) / steps + 7) / 8);
-        const int* tab = R.d_table + (size_t)p0 * 16;
-        if (ndot == 0)
-            hipExtLaunchKernelGGL((k_spmv_pipe_st<0, true>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, rsched, R.d_word, R.d_koff, tab, c->d_R, x, y, w0, part, c->npart, c->d_done, xs, uadd, (const double*)nullptr);
-        else if (ndot == 1)
-            hipExtLaunchKernelGGL((k_spmv_pipe_st<1, true>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, rsched, R.d_word, R.d_koff, tab, c->d_R, x, y, w0, part, c->npart, c->d_done, xs, uadd, (const double*)nullptr);
-        else if (ndot == 2)
-            hipExtLaunchKernelGGL((k_spmv_pipe_st<2, true>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, rsched, R.d_word, R.d_koff, tab, c->d_R, x, y, w0, part, c->npart, c->d_done, xs, uadd, (const double*)nullptr);
-        else
-            hipExtLaunchKernelGGL((k_spmv_pipe_st<3, true>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, rsched, R.d_word, R.d_koff, tab, c->d_R, x, y, w0, part, c->npart, c->d_done, xs, uadd, w1);
+        const int* tab = R.d_table + (size_t)p0 * STENCIL_TABLE_SLOTS;
+        hipExtLaunchKernelGGL(pipeSt[1][ndot], dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, rsched, R.d_word, R.d_koff, tab, c->d_R, x, y, w0, part, c->npart, c->d_done, xs, uadd, w1r);
         return ndot > 0 ? grid : 0;
     }
     const int4* sched = reinterpret_cast<const int4*>(P.tiles.d_spmvSched) + p0;
@@ -2149,31 +2070,16 @@ static int launch_spmv_part(opmhip_ctx* c, int p0, int np, const double* x, doub
         const bool inInt = p0 < P.tiles.nschedInt, inBnd = p0 + np > P.tiles.nschedInt;   // which parts of the schedule this launch covers
         if ((!inInt || P.tiles.stencilPart[0]) && (!inBnd || P.tiles.stencilPart[1])) {
             const StencilForm& S = P.tiles.st;
-            const int* tab = S.d_table + (size_t)p0 * 16;
-            if (ndot == 0)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<0, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
-            else if (ndot == 1)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<1, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
-            else if (ndot == 2)
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<2, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, (const double*)nullptr);
-            else
-                hipExtLaunchKernelGGL((k_spmv_pipe_st<3, false>), dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, w1);
+            const int* tab = S.d_table + (size_t)p0 * STENCIL_TABLE_SLOTS;
+            hipExtLaunchKernelGGL(pipeSt[0][ndot], dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, S.d_word, S.d_koff, tab, c->d_A, x, y, w0, part, c->npart, c->d_done, xs, (const double*)nullptr, w1r);
             return ndot > 0 ? grid : 0;
         }
-        if (ndot == 0)
-            hipExtLaunchKernelGGL(k_spmv_pipe<0>, dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
-        else if (ndot == 1)
-            hipExtLaunchKernelGGL(k_spmv_pipe<1>, dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
-        else
-            hipExtLaunchKernelGGL(k_spmv_pipe<2>, dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
+        assert(ndot < 3);   // launch_spmv (rides3) hands three sums to the stencil kernel alone
+        hipExtLaunchKernelGGL(pipe[ndot], dim3(grid), dim3(64), 0, c->stream, e0, e1, 0, np, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
         return ndot > 0 ? grid : 0;
     }
-    if (ndot == 0)
-        hipExtLaunchKernelGGL(k_spmv<0>, dim3(np), dim3(64), 0, c->stream, e0, e1, 0, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
-    else if (ndot == 1)
-        hipExtLaunchKernelGGL(k_spmv<1>, dim3(np), dim3(64), 0, c->stream, e0, e1, 0, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
-    else
-        hipExtLaunchKernelGGL(k_spmv<2>, dim3(np), dim3(64), 0, c->stream, e0, e1, 0, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
+    assert(ndot < 3);
+    hipExtLaunchKernelGGL(tile[ndot], dim3(np), dim3(64), 0, c->stream, e0, e1, 0, sched, P.d_rowptr, P.d_col, c->d_A, x, y, w0, part, c->npart, c->d_done, xs);
     return ndot > 0 ? np : 0;
 }
 // y = A x (+ wells) and the partial sums of the scalar products: ndot 0 none, 1 y.w0, 2 y.w0 and y.y.
