@@ -19,9 +19,8 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <numeric>
+#include <cstring>
 #include <atomic>
-#include <map>
 #include <memory>
 #include <string>
 #include <thread>
@@ -792,6 +791,35 @@ struct CprAsyncJob {
     CprHostCoarse result;
     ~CprAsyncJob() { if (th.joinable()) th.join(); }
 };
+// ---- policy: what the configuration and the communicator put in force ---------------------------------------------------------------
+// Decomposed runs, the hierarchy continued across the ranks.  The reference's parallel CPR keeps a coarse pressure problem that spans
+// the processes (Dune's parallel AMG behind linalg/OwningTwoLevelPreconditioner.hpp; aggregates never cross a process boundary, the
+// coarse operators carry the couplings between the processes).  Here: every rank coarsens its own subdomain down to its first level of
+// at most opmhip_config.cpr_gather_rows rows (couplings to ghost cells left out of those levels: they smooth, and smoothing is local);
+// that level's matrix rows - its own entries plus the Galerkin sums of the fine couplings between the aggregates of different subdomains -
+// are gathered into ONE system that every rank holds, coarsens further and cycles on redundantly: one all-gather of a right-hand side
+// per application, one of matrix values per solve.  oracle: orc_cpr_solve_blocks with gather_rows.
+// cpr_gather_rows = 0 ("the default") means ON over the loopback communicator and OFF over RCCL: the spanning stage's collectives
+// (ncclAllGather on the context stream, the w = 1 / w = 2 halo exchanges inside launch_cpr_apply, the joined level's set-up exchanges) have
+// only ever run as threads on one GPU - no record of any round takes them with nranks > 1 over RCCL - and a default must not be a path
+// that was never executed.  A positive cpr_gather_rows asks for it explicitly on either communicator.
+static bool cpr_gathering(const opmhip_ctx* c) {
+    if (c->comm.nranks <= 1 || c->comm.kind == COMM_NONE) return false;
+    const int g = c->cfg.cpr_gather_rows;
+    return g > 0 || (g == 0 && c->comm.kind != COMM_RCCL);
+}
+static int cpr_stop_rows(const opmhip_ctx* c) { return cpr_gathering(c) ? (c->cfg.cpr_gather_rows > 0 ? c->cfg.cpr_gather_rows : 100000) : CPR_COARSE_DIRECT; }
+// opmhip_config.cpr_amg_ilu_levels as it is in force: < 0 = the library's choice - level 0 where the block ILU0's ordering has few colours
+// (a sweep of level 0 is one launch per colour: four launches per application with two colours, +5 ... +8 % Newton iterations/s on the
+// 10^6-cell case; with the seven colours of a greedy-coloured corner-point grid 28, and Jacobi is 1.5 x faster there), Jacobi otherwise
+static int cpr_ilu_levels(const opmhip_ctx* c) {
+    const int v = c->cfg.cpr_amg_ilu_levels;
+    return v >= 0 ? v : (c->pat.numColors <= 3 ? 1 : 0);
+}
+int cpr_ilu_levels_in_force(const opmhip_ctx* c) { return use_cpr(c) ? (cpr_gathering(c) ? 0 : cpr_ilu_levels(c)) : 0; }
+// is level l smoothed with its ILU0 (a level that has the schedule and is not the coarsest)?
+static bool cpr_ilu_active(const CprDev& R, size_t l) { return l + 1 < R.lv.size() && R.lv[l].ilu; }
+
 static int cpr_upload_ilu(opmhip_ctx* c, const CprIluHost& S, CprLevelDev& L) {
     if (!S.error.empty()) return fail(c, OPMHIP_ANALYSIS_FAILED, "%s", S.error.c_str());
     int rc;
@@ -929,58 +957,15 @@ static int cpr_weights(opmhip_ctx* c) {
     hipLaunchKernelGGL(k_cpr_weights, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, P.d_diag, c->d_A, R.d_w);
     return OPMHIP_SUCCESS;
 }
-// The rider of this solve's factorisation (FactorRider, solver.hip: k_ilu_factor<RIDER>): level 0's image is set up if it is not yet,
-// weights that do not come from the matrix (true-IMPES from the state, or handed in) are formed now, quasi-IMPES weights ride along.
-// OPMHIP_CPR_PVALS_SEPARATE=1 (measurement switch): the passes of their own, as before.
-static int cpr_setup_level0(opmhip_ctx* c);
-static bool cpr_gathering(const opmhip_ctx* c);
-int cpr_factor_rider(opmhip_ctx* c, FactorRider* r) {
-    CprDev& R = c->cpr;
-    *r = FactorRider();
-    static const bool separate = tuning_env("OPMHIP_CPR_PVALS_SEPARATE") != nullptr;
-    if (separate || !use_cpr(c)) return OPMHIP_SUCCESS;
-    int rc;
-    if (!R.level0 && (rc = cpr_setup_level0(c))) return rc;
-    const bool fromMatrix = !R.w_given && c->cfg.preconditioner != OPMHIP_PRECOND_CPR_TRUEIMPES;
-    if (!fromMatrix && (rc = cpr_weights(c))) return rc;
-    r->mode = fromMatrix ? 2 : 1;
-    r->w = R.d_w;
-    r->ap = R.lv[0].d_val;
-    r->pcol = R.d_pcol;
-    r->W = R.lv[0].W;
-    r->ghostFrom = (c->pat.Nghost > 0 && !cpr_gathering(c)) ? c->pat.Nb : INT_MAX;
-    // (CprDev::pvals_fresh is raised by the caller once the factorisation that carries this rider has run without an error: a solve that
-    //  leaves before that must not make the next cpr_update skip its own pass over the matrix)
-    return OPMHIP_SUCCESS;
+// A set-up that fails half way (an ILU schedule the level cannot take, a failed allocation) gives back what it allocated: the retry of
+// the next solve starts from a clean slate and nothing piles up in the context.  Every allocation since `mark` (c->allocs.size() before the
+// set-up began) goes back; the caller then forgets the pointers it held to them.  Valid only while nothing between the mark and here called
+// dev_free, which moves the last entry of allocs into the freed one's place: cpr_host_allgather takes its buffers with hipMalloc for that.
+static void cpr_rollback_allocs(opmhip_ctx* c, size_t mark) {
+    (void)hipStreamSynchronize(c->stream);
+    while (c->allocs.size() > mark) { (void)hipFree(c->allocs.back()); c->allocs.pop_back(); }
 }
-static bool cpr_gathering(const opmhip_ctx* c);
-// opmhip_config.cpr_amg_ilu_levels as it is in force: < 0 = the library's choice - level 0 where the block ILU0's ordering has few colours
-// (a sweep of level 0 is one launch per colour: four launches per application with two colours, +5 ... +8 % Newton iterations/s on the
-// 10^6-cell case; with the seven colours of a greedy-coloured corner-point grid 28, and Jacobi is 1.5 x faster there), Jacobi otherwise
-static int cpr_ilu_levels(const opmhip_ctx* c) {
-    const int v = c->cfg.cpr_amg_ilu_levels;
-    return v >= 0 ? v : (c->pat.numColors <= 3 ? 1 : 0);
-}
-int cpr_ilu_levels_in_force(const opmhip_ctx* c) { return use_cpr(c) ? (cpr_gathering(c) ? 0 : cpr_ilu_levels(c)) : 0; }
 // ---- level 0: belongs to the PATTERN (image, stencil form, block-vector work space): built once per context ------------------
-static int cpr_setup_level0_body(opmhip_ctx* c);
-// a set-up that fails half way (an ILU schedule the level cannot take, a failed allocation) gives back what it allocated: the retry of
-// the next solve starts from a clean slate and nothing piles up in the context
-static int cpr_setup_level0(opmhip_ctx* c) {
-    CprDev& R = c->cpr;
-    const size_t mark = c->allocs.size();
-    const bool hadW = R.d_w != nullptr;
-    const int rc = cpr_setup_level0_body(c);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        while (c->allocs.size() > mark) { (void)hipFree(c->allocs.back()); c->allocs.pop_back(); }
-        if (!hadW) R.d_w = nullptr;
-        R.d_r = R.d_y = R.d_z = R.d_pcol = nullptr;
-        R.lv.clear();
-        R.level0 = false;
-    }
-    return rc;
-}
 static int cpr_setup_level0_body(opmhip_ctx* c) {
     const Pattern& P = c->pat;
     CprDev& R = c->cpr;
@@ -1015,17 +1000,49 @@ static int cpr_setup_level0_body(opmhip_ctx* c) {
         }
     }
     if (cpr_ilu_levels(c) > 0 && !spans) {   // ILU0 smoothing of level 0: in the stored order, the block ILU0's colours are this one's
-        std::vector<int> posv(P.Nb), colour(P.Nb);
-        for (int cc = 0; cc < P.numColors; ++cc)
-            for (int p = P.colorPrefix[cc]; p < P.colorPrefix[cc + 1]; ++p) colour[p] = cc;
-        std::iota(posv.begin(), posv.end(), 0);
         CprIluHost S;
-        cpr_ilu_schedule(H0, posv, colour, P.numColors, S);
+        cpr_level0_ilu_schedule(H0, P.colorPrefix, P.numColors, S);
         if ((rc = cpr_upload_ilu(c, S, R.lv[0]))) return rc;
     }
     if ((rc = dev_alloc(c, &R.d_pcol, (size_t)3 * R.lv[0].W * P.Nb))) return rc;     // pressure columns of the blocks, ELL, component-major
     OPMHIP_HIP(c, hipMemsetAsync(R.d_pcol, 0, (size_t)3 * R.lv[0].W * P.Nb * sizeof(double), c->stream));   // the padding stays 0
     R.level0 = true;
+    return OPMHIP_SUCCESS;
+}
+static int cpr_setup_level0(opmhip_ctx* c) {
+    CprDev& R = c->cpr;
+    const size_t mark = c->allocs.size();
+    const bool hadW = R.d_w != nullptr;
+    const int rc = cpr_setup_level0_body(c);
+    if (rc) {
+        cpr_rollback_allocs(c, mark);
+        if (!hadW) R.d_w = nullptr;
+        R.d_r = R.d_y = R.d_z = R.d_pcol = nullptr;
+        R.lv.clear();
+        R.level0 = false;
+    }
+    return rc;
+}
+// The rider of this solve's factorisation (FactorRider, solver.hip: k_ilu_factor<RIDER>): level 0's image is set up if it is not yet,
+// weights that do not come from the matrix (true-IMPES from the state, or handed in) are formed now, quasi-IMPES weights ride along.
+// OPMHIP_CPR_PVALS_SEPARATE=1 (measurement switch): the passes of their own, as before.
+int cpr_factor_rider(opmhip_ctx* c, FactorRider* r) {
+    CprDev& R = c->cpr;
+    *r = FactorRider();
+    static const bool separate = tuning_env("OPMHIP_CPR_PVALS_SEPARATE") != nullptr;
+    if (separate || !use_cpr(c)) return OPMHIP_SUCCESS;
+    int rc;
+    if (!R.level0 && (rc = cpr_setup_level0(c))) return rc;
+    const bool fromMatrix = !R.w_given && c->cfg.preconditioner != OPMHIP_PRECOND_CPR_TRUEIMPES;
+    if (!fromMatrix && (rc = cpr_weights(c))) return rc;
+    r->mode = fromMatrix ? 2 : 1;
+    r->w = R.d_w;
+    r->ap = R.lv[0].d_val;
+    r->pcol = R.d_pcol;
+    r->W = R.lv[0].W;
+    r->ghostFrom = (c->pat.Nghost > 0 && !cpr_gathering(c)) ? c->pat.Nb : INT_MAX;
+    // (CprDev::pvals_fresh is raised by the caller once the factorisation that carries this rider has run without an error: a solve that
+    //  leaves before that must not make the next cpr_update skip its own pass over the matrix)
     return OPMHIP_SUCCESS;
 }
 // ---- the device side of it: transfer arrays of every level, images of the levels below level 0 --------------------------------
@@ -1097,29 +1114,67 @@ static int cpr_download_level0(opmhip_ctx* c, std::vector<double>& ell) {
     OPMHIP_HIP(c, hipStreamSynchronize(c->stream));
     return OPMHIP_SUCCESS;
 }
-static int cpr_update_values(opmhip_ctx* c, CprDev& R);
-static int cpr_upload_coarse(opmhip_ctx* c, CprDev& R, const CprHostCoarse& H, bool gathered);
-
-// ---- decomposed runs: the hierarchy continued across the ranks ------------------------------------------------------------------
-// The reference's parallel CPR keeps a coarse pressure problem that spans the processes (Dune's parallel AMG behind
-// linalg/OwningTwoLevelPreconditioner.hpp; aggregates never cross a process boundary, the coarse operators carry the couplings between
-// the processes).  Here: every rank coarsens its own subdomain down to its first level of at most opmhip_config.cpr_gather_rows rows
-// (couplings to ghost cells left out of those levels: they smooth, and smoothing is local); that level's matrix rows - its own entries
-// plus the Galerkin sums of the fine couplings between the aggregates of different subdomains - are gathered into ONE system that every
-// rank holds, coarsens further and cycles on redundantly: one all-gather of a right-hand side per application, one of matrix values per
-// solve.  oracle: orc_cpr_solve_blocks with gather_rows.
-// cpr_gather_rows = 0 ("the default") means ON over the loopback communicator and OFF over RCCL: the spanning stage's collectives
-// (ncclAllGather on the context stream, the w = 1 / w = 2 halo exchanges inside launch_cpr_apply, the joined level's set-up exchanges) have
-// only ever run as threads on one GPU - no record of any round takes them with nranks > 1 over RCCL - and a default must not be a path
-// that was never executed.  A positive cpr_gather_rows asks for it explicitly on either communicator.
-static bool cpr_gathering(const opmhip_ctx* c) {
-    if (c->comm.nranks <= 1 || c->comm.kind == COMM_NONE) return false;
-    const int g = c->cfg.cpr_gather_rows;
-    return g > 0 || (g == 0 && c->comm.kind != COMM_RCCL);
+// forgets a coarse structure whose upload failed half way: what was allocated since `mark` goes back (cpr_rollback_allocs), level 0
+// keeps its image and loses its transfer arrays, the levels below it and the joined level go
+static void cpr_forget_coarse(opmhip_ctx* c, CprDev& R, size_t mark) {
+    cpr_rollback_allocs(c, mark);
+    for (CprLevelDev& L : R.lv) L.d_agg = L.d_mptr = L.d_midx = L.d_mem4 = L.d_gptr = L.d_gidx = L.d_cpos = nullptr;
+    if (!R.lv.empty()) R.lv.resize(1);
+    R.d_lu = nullptr;
+    R.structured = false;
+    R.gather = CprGatherDev();
 }
-static int cpr_stop_rows(const opmhip_ctx* c) { return cpr_gathering(c) ? (c->cfg.cpr_gather_rows > 0 ? c->cfg.cpr_gather_rows : 100000) : CPR_COARSE_DIRECT; }
-// `bytes` bytes of every rank, in rank order, on every rank (set-up only: staged through device buffers of its own)
-static int cpr_host_allgather(opmhip_ctx* c, const void* src, size_t bytes, std::vector<char>& dst) {
+static void launch_cpr_ilu_factor(opmhip_ctx* c, const CprLevelDev& L, size_t cc) {
+    if (L.rm) hipLaunchKernelGGL(k_cpr_ilu_factor<true>, g256(L.iluNseq[cc]), dim3(256), 0, c->stream, L.iluNseq[cc], L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, L.W, L.iluMW, L.iluWL, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_lorder, L.d_fval);
+    else hipLaunchKernelGGL(k_cpr_ilu_factor<false>, g256(L.iluNseq[cc]), dim3(256), 0, c->stream, L.iluNseq[cc], L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, L.W, L.iluMW, L.iluWL, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_lorder, L.d_fval);
+}
+// the values of a hierarchy below its level 0 (whose image holds the matrix already): 1 / diagonal, the ILU0 factors of the levels that
+// smooth with them, Galerkin values level by level, the dense LU of the coarsest level
+static int cpr_update_values(opmhip_ctx* c, CprDev& R) {
+    for (size_t l = 0; l < R.lv.size(); ++l) {
+        CprLevelDev& L = R.lv[l];
+        hipLaunchKernelGGL(k_cpr_dinv, g256(L.n), dim3(256), 0, c->stream, L.n, L.d_diag, L.d_val, L.d_dinv);
+        if (cpr_ilu_active(R, l) && L.iluSimple) {   // scalar ILU0 of a level without triangles: the sweeps' images straight from the matrix, then the recurrence
+            hipLaunchKernelGGL(k_cpr_ilu_pack, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.iluMW, 0, L.iluWL, L.iluWU, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_val,
+                               L.d_ilv, L.d_ilc, L.d_iuv, L.d_iuc, L.d_iud);
+            for (size_t cc = 0; cc < L.iluNseq.size(); ++cc) {
+                const int nseq = L.iluNseq[cc], wq = L.iluWl[cc];
+                if (nseq == 0) continue;
+                const dim3 grid((nseq + 63) / 64);
+#define CPR_FS(WQ, G) hipLaunchKernelGGL((k_cpr_ilu_factor_simple<WQ, G>), grid, dim3(64), 0, c->stream, nseq, L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, wq, L.d_val, L.d_diag, L.d_ilc, L.d_tpos, L.d_ilv, (const double*)L.d_iud, L.d_iud)
+                if (wq <= 1) CPR_FS(1, 12); else if (wq <= 2) CPR_FS(2, 12); else if (wq <= 4) CPR_FS(4, 10); else if (wq <= 6) CPR_FS(6, 8); else CPR_FS(8, 6);
+#undef CPR_FS
+            }
+        } else
+        if (cpr_ilu_active(R, l)) {   // scalar ILU0 of the level, colour by colour
+            OPMHIP_HIP(c, hipMemcpyAsync(L.d_fval, L.d_val, (size_t)L.W * L.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            for (size_t cc = 0; cc < L.iluNseq.size(); ++cc)
+                if (L.iluNseq[cc] > 0) launch_cpr_ilu_factor(c, L, cc);
+            hipLaunchKernelGGL(k_cpr_ilu_pack, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.iluMW, L.rm ? 1 : 0, L.iluWL, L.iluWU, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_fval,
+                               L.d_ilv, L.d_ilc, L.d_iuv, L.d_iuc, L.d_iud);
+        }
+        if (l + 1 < R.lv.size()) {
+            CprLevelDev& C = R.lv[l + 1];
+            hipLaunchKernelGGL(k_cpr_galerkin, g256(C.nnz), dim3(256), 0, c->stream, C.nnz, L.d_gptr, L.d_gidx, L.d_cpos, L.d_val, C.d_val);
+        }
+    }
+    if (R.coarse_direct) {
+        const CprLevelDev& C = R.lv.back();
+        // in LDS where the device grants n x n doubles of dynamic shared memory (gfx950: yes, up to n = 128), else in place in global memory
+        static const bool ldsOk = hipFuncSetAttribute(reinterpret_cast<const void*>(k_cpr_dense_lu_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      CPR_COARSE_DIRECT * CPR_COARSE_DIRECT * (int)sizeof(double)) == hipSuccess;
+        if (ldsOk) hipLaunchKernelGGL(k_cpr_dense_lu_lds, dim3(1), dim3(CPR_LU_THREADS), (size_t)C.n * C.n * sizeof(double), c->stream, C.n, C.W, C.rm ? 1 : 0, C.d_ecol, C.d_rlen, C.d_val, R.d_lu);
+        else hipLaunchKernelGGL(k_cpr_dense_lu, dim3(1), dim3(256), 0, c->stream, C.n, C.W, C.rm ? 1 : 0, C.d_ecol, C.d_rlen, C.d_val, R.d_lu);
+    }
+    return OPMHIP_SUCCESS;
+}
+
+// ---- decomposed runs: the hierarchy continued across the ranks (what and when: cpr_gathering, above) --------------------------------
+// `count` values of every rank, in rank order, on every rank (set-up only: staged through device buffers of its own - raw hipMalloc,
+// not dev_alloc / dev_free: cpr_rollback_allocs)
+template <class T>
+static int cpr_host_allgather(opmhip_ctx* c, const T* src, size_t count, std::vector<T>& dst) {
+    const size_t bytes = count * sizeof(T);
     const int nr = c->comm.nranks;
     const size_t cnt = std::max<size_t>((bytes + 7) / 8, 1);
     std::vector<double> sb(cnt, 0.0), rb(cnt * nr, 0.0);
@@ -1141,9 +1196,18 @@ static int cpr_host_allgather(opmhip_ctx* c, const void* src, size_t bytes, std:
     }();
     (void)hipFree(d_s); (void)hipFree(d_r);
     if (rc) return rc;
-    dst.resize(bytes * nr);
+    dst.resize(count * nr);
     for (int r = 0; r < nr; ++r)
-        if (bytes) std::memcpy(dst.data() + (size_t)r * bytes, rb.data() + (size_t)r * cnt, bytes);
+        if (bytes) std::memcpy(dst.data() + (size_t)r * count, rb.data() + (size_t)r * cnt, bytes);
+    return OPMHIP_SUCCESS;
+}
+// The error protocol of the set-up exchanges.  A failure of ONE rank between two exchanges must not leave the others waiting in the next
+// one: the rank notes its first error (text in c->err), goes on through every exchange with what it has, and the error flag travels with
+// the next payload - all ranks then leave together, the failed one with its own status (`mine`), the others with a status that names it.
+// b: every rank's record of `stride` ints, the flag at `at`
+static int cpr_first_failed(opmhip_ctx* c, const std::vector<int>& b, size_t stride, size_t at, int mine, const char* what) {
+    for (int r = 0; r < c->comm.nranks; ++r)
+        if (const int f = b[(size_t)r * stride + at]) return mine ? mine : fail(c, f, "cpr: rank %d failed %s", r, what);
     return OPMHIP_SUCCESS;
 }
 // after the rank's own hierarchy is on the device (its last level = the one that is gathered; H: the host side of it, with that level's matrix)
@@ -1152,45 +1216,33 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
     CprDev& R = c->cpr;
     CprGatherDev& G = R.gather;
     const int nr = c->comm.nranks, me = c->comm.rank;
-    // A failure of ONE rank between two exchanges must not leave the others waiting in the next one: the rank notes its first error
-    // (text in c->err), goes on through every exchange with what it has, and the error flag travels with the next payload - all ranks
-    // then leave together, the failed one with its own status, the others with a status that names it.
+    // the error protocol: cpr_first_failed.  A HIP call between two exchanges goes through note() as well (OPMHIP_HIP would return at once, alone)
     int lerr = 0, rc;
     auto note = [&](int e) { if (e && !lerr) lerr = e; };
-    // a HIP call between two exchanges goes through note() as well (OPMHIP_HIP would return at once, alone)
-    auto hipnote = [&](hipError_t e, const char* what) { if (e != hipSuccess) note(fail(c, OPMHIP_DEVICE_ERROR, "%s failed: %s (cpr_gather_setup)", what, hipGetErrorString(e))); };
-    auto first_failed = [&](const std::vector<char>& b, size_t stride, size_t at, const char* where) -> int {   // the flag at byte `at` of every rank's record
-        for (int r = 0; r < nr; ++r) {
-            int f;
-            std::memcpy(&f, b.data() + (size_t)r * stride + at, sizeof f);
-            if (f) return lerr ? lerr : fail(c, f, "cpr: rank %d failed in the set-up of the joined level (%s)", r, where);
-        }
-        return OPMHIP_SUCCESS;
+    auto hipcode = [&](hipError_t e, const char* what) { return e == hipSuccess ? 0 : fail(c, OPMHIP_DEVICE_ERROR, "%s failed: %s (cpr_gather_setup)", what, hipGetErrorString(e)); };
+    auto hipnote = [&](hipError_t e, const char* what) { note(hipcode(e, what)); };
+    // values of every rank, `count` each (mine padded with zeros), on every rank
+    auto gather = [&](const auto& v, size_t count, auto& all) {
+        auto t = v;
+        t.resize(count);
+        return cpr_host_allgather(c, t.data(), count, all);
     };
     if (P.Nghost > 0 && !c->comm.halo_set) note(fail(c, OPMHIP_NOT_READY, "cpr: the joined coarse level needs the halo lists (opmhip_set_halo) before the first solve"));
-    std::vector<char> buf;
-    const size_t g = R.lv.size() - 1;
-    const int nloc = R.lv[g].n;
+    std::vector<int> buf;
+    const int nloc = R.lv.back().n;
     // 1. sizes of everybody's slice, of everybody's subdomain
     const int mine[3] = {nloc, P.Nb, lerr};
-    if ((rc = cpr_host_allgather(c, mine, sizeof mine, buf))) return rc;
-    if ((rc = first_failed(buf, sizeof mine, 2 * sizeof(int), "halo lists"))) return rc;
+    if ((rc = cpr_host_allgather(c, mine, 3, buf))) return rc;
+    if ((rc = cpr_first_failed(c, buf, 3, 2, lerr, "in the set-up of the joined level (halo lists)"))) return rc;
     std::vector<int> offs(nr + 1, 0), foffs(nr + 1, 0);
     int maxn = 1;
     for (int r = 0; r < nr; ++r) {
-        int v[3];
-        std::memcpy(v, buf.data() + (size_t)r * sizeof v, sizeof v);
-        offs[r + 1] = offs[r] + v[0];
-        foffs[r + 1] = foffs[r] + v[1];
-        maxn = std::max(maxn, v[0]);
+        offs[r + 1] = offs[r] + buf[3 * r];
+        foffs[r + 1] = foffs[r] + buf[3 * r + 1];
+        maxn = std::max(maxn, buf[3 * r]);
     }
     // 2. aggregate (on the gathered level) of every owned cell
-    std::vector<int> cagg(P.Nb);
-    std::iota(cagg.begin(), cagg.end(), 0);
-    for (size_t l = 0; l < g; ++l) {
-        const std::vector<int>& a = l == 0 ? H.l0.agg : H.lv[l - 1].agg;
-        for (int i = 0; i < P.Nb; ++i) cagg[i] = a[cagg[i]];
-    }
+    const std::vector<int> cagg = cpr_joined_aggregates(P.Nb, H);
     // 3. the same for the ghost cells, from their owners: row of the joined level, and the owner-side place of the cell (what orders the
     //    fine couplings inside one joined entry: subdomain by subdomain, each in its rank's internal order)
     std::vector<double> hv((size_t)2 * P.Nloc, 0.0);
@@ -1202,23 +1254,18 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
         hipnote(hipMemcpyAsync(hv.data(), d_hv, hv.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
         hipnote(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     }
+    std::vector<int> ghostRow(P.Nloc - P.Nb);
+    std::vector<long long> ghostPlace(P.Nloc - P.Nb);
+    for (int gh = P.Nb; gh < P.Nloc; ++gh) { ghostRow[gh - P.Nb] = (int)hv[(size_t)2 * gh]; ghostPlace[gh - P.Nb] = (long long)hv[(size_t)2 * gh + 1]; }
     // 4. my rows of the joined level: my last level's entries, and one entry per pair (my aggregate, an aggregate of another rank) that a
-    //    fine coupling joins
-    std::vector<int> qrow, qentry;
-    struct Fine { int i; long long gf; int q; };
-    std::vector<std::map<int, std::vector<Fine>>> cross(nloc);
-    for (int i = 0; i < P.Nb; ++i)
-        for (int k = P.rowptr[i]; k < P.rowptr[i + 1]; ++k) {
-            const int gh = P.col[k];
-            if (gh < P.Nb) continue;
-            const int q = (int)qrow.size();
-            qrow.push_back(i); qentry.push_back(k);
-            cross[cagg[i]][(int)hv[(size_t)2 * gh]].push_back(Fine{i, (long long)hv[(size_t)2 * gh + 1], q});
-        }
-    G.nq = (int)qrow.size();
+    //    fine coupling joins; the values of this first matrix on the host, by the rule the device forms every later one with
+    CprJoinedRows Q;
+    cpr_joined_rows(P.Nb, P.rowptr, P.col, cagg, ghostRow, ghostPlace, offs[me], H.lastA, H.lastPos, Q);
+    G.nq = (int)Q.qrow.size();
+    G.nnzloc = (int)Q.cols.size();
     std::vector<double> apg(std::max(G.nq, 1), 0.0);
-    note(dev_upload(c, &G.d_qrow, qrow));
-    note(dev_upload(c, &G.d_qentry, qentry));
+    note(dev_upload(c, &G.d_qrow, Q.qrow));
+    note(dev_upload(c, &G.d_qentry, Q.qentry));
     note(dev_alloc(c, &G.d_apg, (size_t)std::max(G.nq, 1)));
     if (G.nq > 0 && !lerr) {
         ensure_A(c);
@@ -1226,69 +1273,24 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
         hipnote(hipMemcpyAsync(apg.data(), G.d_apg, (size_t)G.nq * sizeof(double), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
         hipnote(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     }
-    const HCsr& LA = H.lastA;
-    std::vector<int> rowlen(nloc, 0), cols, src, xptr(1, 0), xidx;
-    std::vector<double> vals;
-    for (int I = 0; I < nloc; ++I) {
-        auto cr = cross[I].begin();
-        auto emit_cross = [&](int upto) {   // the entries towards other ranks whose joined column lies below `upto`
-            for (; cr != cross[I].end() && cr->first < upto; ++cr) {
-                std::vector<Fine>& f = cr->second;
-                std::sort(f.begin(), f.end(), [](const Fine& a, const Fine& b) { return a.i != b.i ? a.i < b.i : a.gf < b.gf; });
-                double sum = 0.0;
-                for (const Fine& e : f) { sum += apg[e.q]; xidx.push_back(e.q); }
-                cols.push_back(cr->first); vals.push_back(sum);
-                src.push_back(-1 - (int)(xptr.size() - 1));
-                xptr.push_back((int)xidx.size());
-                ++rowlen[I];
-            }
-        };
-        for (int k = LA.rowptr[I]; k < LA.rowptr[I + 1]; ++k) {
-            emit_cross(offs[me] + LA.col[k]);
-            cols.push_back(offs[me] + LA.col[k]); vals.push_back(LA.val[k]); src.push_back(H.lastPos[k]);
-            ++rowlen[I];
-        }
-        emit_cross(INT_MAX);
-    }
-    G.nnzloc = (int)cols.size();
-    // 5. everybody's rows
+    const std::vector<double> vals = cpr_joined_values(Q, apg, H.lastA.val);
+    // 5. everybody's rows, into one matrix
     const int mine5[2] = {G.nnzloc, lerr};
-    if ((rc = cpr_host_allgather(c, mine5, sizeof mine5, buf))) return rc;
-    if ((rc = first_failed(buf, sizeof mine5, sizeof(int), "boundary couplings"))) return rc;
+    if ((rc = cpr_host_allgather(c, mine5, 2, buf))) return rc;
+    if ((rc = cpr_first_failed(c, buf, 2, 1, lerr, "in the set-up of the joined level (boundary couplings)"))) return rc;
     std::vector<int> nnzs(nr);
     int maxnnz = 1;
-    for (int r = 0; r < nr; ++r) { std::memcpy(&nnzs[r], buf.data() + (size_t)r * sizeof mine5, sizeof(int)); maxnnz = std::max(maxnnz, nnzs[r]); }
-    std::vector<char> bl, bc, bv;
-    {
-        std::vector<int> t(maxn, 0);
-        std::copy(rowlen.begin(), rowlen.end(), t.begin());
-        if ((rc = cpr_host_allgather(c, t.data(), (size_t)maxn * sizeof(int), bl))) return rc;
-        std::vector<int> tc(maxnnz, 0);
-        std::copy(cols.begin(), cols.end(), tc.begin());
-        if ((rc = cpr_host_allgather(c, tc.data(), (size_t)maxnnz * sizeof(int), bc))) return rc;
-        std::vector<double> tv(maxnnz, 0.0);
-        std::copy(vals.begin(), vals.end(), tv.begin());
-        if ((rc = cpr_host_allgather(c, tv.data(), (size_t)maxnnz * sizeof(double), bv))) return rc;
-    }
-    HCsr J;
-    const int NG = offs[nr];
-    J.n = NG;
-    J.rowptr.assign(1, 0);
-    std::vector<int> unpad, vunpad;
-    for (int r = 0; r < nr; ++r) {
-        const int* rl = reinterpret_cast<const int*>(bl.data() + (size_t)r * maxn * sizeof(int));
-        const int* rcs = reinterpret_cast<const int*>(bc.data() + (size_t)r * maxnnz * sizeof(int));
-        const double* rv = reinterpret_cast<const double*>(bv.data() + (size_t)r * maxnnz * sizeof(double));
-        int e = 0;
-        for (int I = 0; I < offs[r + 1] - offs[r]; ++I) {
-            for (int t = 0; t < rl[I]; ++t, ++e) {
-                if (rcs[e] < 0 || rcs[e] >= NG || e >= nnzs[r]) return fail(c, OPMHIP_ANALYSIS_FAILED, "cpr: the joined level's rows of rank %d are inconsistent", r);   // the same data on every rank: all leave here
-                J.col.push_back(rcs[e]); J.val.push_back(rv[e]); vunpad.push_back(r * maxnnz + e);
-            }
-            J.rowptr.push_back((int)J.col.size());
-            unpad.push_back(r * maxn + I);
-        }
-    }
+    for (int r = 0; r < nr; ++r) { nnzs[r] = buf[2 * r]; maxnnz = std::max(maxnnz, nnzs[r]); }
+    std::vector<int> bl, bc;
+    std::vector<double> bv;
+    if ((rc = gather(Q.rowlen, (size_t)maxn, bl))) return rc;
+    if ((rc = gather(Q.cols, (size_t)maxnnz, bc))) return rc;
+    if ((rc = gather(vals, (size_t)maxnnz, bv))) return rc;
+    CprJoined JR;
+    cpr_join_rows(bl, bc, bv, nnzs, offs, maxn, maxnnz, JR);
+    if (!JR.error.empty()) return fail(c, OPMHIP_ANALYSIS_FAILED, "%s", JR.error.c_str());   // the same data on every rank: all leave here
+    const HCsr& J = JR.J;
+    const int NG = J.n;
     // 6. the hierarchy all ranks share: level 0 = the joined level (the same matrix on every rank, hence the same hierarchy)
     G.glob = std::make_shared<CprDev>();
     CprDev& JD = *G.glob;
@@ -1301,24 +1303,26 @@ static int cpr_gather_setup(opmhip_ctx* c, const CprHostCoarse& H) {
     note(upload_ell(c, img0, JD.lv[0]));
     CprHostCoarse HJ;
     cpr_coarsen_host(J, posg, nullptr, nullptr, R.beta, CPR_LPR_ROWS, 0, CPR_COARSE_DIRECT, HJ);
-    if (!lerr) note(cpr_upload_coarse(c, JD, HJ, false));
-    // 7. what the solves need on the device
+    // 7. what the solves need on the device: the first failure ends the uploads
     G.nloc = nloc; G.off = offs[me]; G.NG = NG; G.maxn = maxn; G.maxnnz = maxnnz; G.nnzG = (int)J.col.size();
-    if (!lerr) note(dev_alloc(c, &G.d_recv, (size_t)nr * maxn));
-    if (!lerr) note(dev_alloc(c, &G.d_vsend, (size_t)maxnnz));
-    if (!lerr) hipnote(hipMemsetAsync(G.d_vsend, 0, (size_t)maxnnz * sizeof(double), c->stream), "hipMemsetAsync");
-    if (!lerr) note(dev_alloc(c, &G.d_vrecv, (size_t)nr * maxnnz));
-    if (!lerr) note(dev_upload(c, &G.d_unpad, unpad));
-    if (!lerr) note(dev_upload(c, &G.d_vunpad, vunpad));
-    if (!lerr) note(dev_upload(c, &G.d_vpos, posg));
-    if (!lerr) note(dev_upload(c, &G.d_src, src));
-    if (!lerr) note(dev_upload(c, &G.d_xptr, xptr));
-    if (!lerr) note(dev_upload(c, &G.d_xidx, xidx));
-    if (!lerr) note(dev_upload(c, &G.d_cagg, cagg));
-    if (!lerr) note(dev_alloc(c, &G.d_send, (size_t)maxn));   // my slice of the joined level's right-hand side: room for the largest slice
-    if (!lerr) hipnote(hipMemsetAsync(G.d_send, 0, (size_t)maxn * sizeof(double), c->stream), "hipMemsetAsync");
-    if ((rc = cpr_host_allgather(c, &lerr, sizeof lerr, buf))) return rc;
-    if ((rc = first_failed(buf, sizeof lerr, 0, "uploads of the joined level"))) return rc;
+    if (!lerr) note([&]() -> int {
+        if ((rc = cpr_upload_coarse(c, JD, HJ, false))) return rc;
+        if ((rc = dev_alloc(c, &G.d_recv, (size_t)nr * maxn))) return rc;
+        if ((rc = dev_alloc(c, &G.d_vsend, (size_t)maxnnz))) return rc;
+        if ((rc = hipcode(hipMemsetAsync(G.d_vsend, 0, (size_t)maxnnz * sizeof(double), c->stream), "hipMemsetAsync"))) return rc;
+        if ((rc = dev_alloc(c, &G.d_vrecv, (size_t)nr * maxnnz))) return rc;
+        if ((rc = dev_upload(c, &G.d_unpad, JR.unpad))) return rc;
+        if ((rc = dev_upload(c, &G.d_vunpad, JR.vunpad))) return rc;
+        if ((rc = dev_upload(c, &G.d_vpos, posg))) return rc;
+        if ((rc = dev_upload(c, &G.d_src, Q.src))) return rc;
+        if ((rc = dev_upload(c, &G.d_xptr, Q.xptr))) return rc;
+        if ((rc = dev_upload(c, &G.d_xidx, Q.xidx))) return rc;
+        if ((rc = dev_upload(c, &G.d_cagg, cagg))) return rc;
+        if ((rc = dev_alloc(c, &G.d_send, (size_t)maxn))) return rc;   // my slice of the joined level's right-hand side: room for the largest slice
+        return hipcode(hipMemsetAsync(G.d_send, 0, (size_t)maxn * sizeof(double), c->stream), "hipMemsetAsync");
+    }());
+    if ((rc = cpr_host_allgather(c, &lerr, 1, buf))) return rc;
+    if ((rc = cpr_first_failed(c, buf, 1, 0, lerr, "in the set-up of the joined level (uploads of the joined level)"))) return rc;
     G.on = true;
     return OPMHIP_SUCCESS;
 }
@@ -1350,76 +1354,16 @@ static int cpr_setup_coarse_now(opmhip_ctx* c) {
     const bool gathered = cpr_gathering(c);
     rc = cpr_upload_coarse(c, R, H, gathered);
     if (gathered) {   // a rank whose own hierarchy failed must not leave its peers waiting in the joined level's set-up: agree first
-        std::vector<char> flags;
-        const int mine = rc;
-        int r2 = cpr_host_allgather(c, &mine, sizeof mine, flags);
-        for (int r = 0; !r2 && !rc && r < c->comm.nranks; ++r) {
-            int f;
-            std::memcpy(&f, flags.data() + (size_t)r * sizeof f, sizeof f);
-            if (f) rc = fail(c, f, "cpr: rank %d failed to build its pressure hierarchy", r);
-        }
-        if (!rc) rc = r2;
+        std::vector<int> flags;
+        const int mine = rc, r2 = cpr_host_allgather(c, &mine, 1, flags);
+        rc = r2 ? (mine ? mine : r2) : cpr_first_failed(c, flags, 1, 0, mine, "to build its pressure hierarchy");
     }
     if (!rc && gathered) rc = cpr_gather_setup(c, H);
     if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        R.gather = CprGatherDev();
-        while (c->allocs.size() > mark) { (void)hipFree(c->allocs.back()); c->allocs.pop_back(); }
-        for (size_t l = 0; l < R.lv.size(); ++l) {
-            CprLevelDev& L = R.lv[l];
-            L.d_agg = L.d_mptr = L.d_midx = L.d_mem4 = L.d_gptr = L.d_gidx = L.d_cpos = nullptr;
-        }
-        if (!R.lv.empty()) R.lv.resize(1);
-        R.d_lu = nullptr;
-        R.structured = false;
+        cpr_forget_coarse(c, R, mark);
         return rc;
     }
     if (timing) std::fprintf(stderr, "opmhip cpr set-up: %.3f s (matching %.3f, Galerkin %.3f, level images %.3f, uploads %.3f), %zu levels\n", now() - t0, H.tAgg, H.tGal, H.tImg, now() - t1, R.lv.size());
-    return OPMHIP_SUCCESS;
-}
-static int cpr_gather_values(opmhip_ctx* c);
-// the values of a hierarchy below its level 0 (whose image holds the matrix already): 1 / diagonal, the ILU0 factors of the levels that
-// smooth with them, Galerkin values level by level, the dense LU of the coarsest level
-static bool cpr_ilu_active(const CprDev& R, size_t l);
-static int cpr_update_values(opmhip_ctx* c, CprDev& R) {
-    for (size_t l = 0; l < R.lv.size(); ++l) {
-        CprLevelDev& L = R.lv[l];
-        hipLaunchKernelGGL(k_cpr_dinv, g256(L.n), dim3(256), 0, c->stream, L.n, L.d_diag, L.d_val, L.d_dinv);
-        if (cpr_ilu_active(R, l) && L.iluSimple) {   // scalar ILU0 of a level without triangles: the sweeps' images straight from the matrix, then the recurrence
-            hipLaunchKernelGGL(k_cpr_ilu_pack, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.iluMW, 0, L.iluWL, L.iluWU, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_val,
-                               L.d_ilv, L.d_ilc, L.d_iuv, L.d_iuc, L.d_iud);
-            for (size_t cc = 0; cc < L.iluNseq.size(); ++cc) {
-                const int nseq = L.iluNseq[cc], wq = L.iluWl[cc];
-                if (nseq == 0) continue;
-                const dim3 grid((nseq + 63) / 64);
-#define CPR_FS(WQ, G) hipLaunchKernelGGL((k_cpr_ilu_factor_simple<WQ, G>), grid, dim3(64), 0, c->stream, nseq, L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, wq, L.d_val, L.d_diag, L.d_ilc, L.d_tpos, L.d_ilv, (const double*)L.d_iud, L.d_iud)
-                if (wq <= 1) CPR_FS(1, 12); else if (wq <= 2) CPR_FS(2, 12); else if (wq <= 4) CPR_FS(4, 10); else if (wq <= 6) CPR_FS(6, 8); else CPR_FS(8, 6);
-#undef CPR_FS
-            }
-        } else
-        if (cpr_ilu_active(R, l)) {   // scalar ILU0 of the level, colour by colour
-            OPMHIP_HIP(c, hipMemcpyAsync(L.d_fval, L.d_val, (size_t)L.W * L.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            for (size_t cc = 0; cc < L.iluNseq.size(); ++cc) {
-                if (L.iluNseq[cc] == 0) continue;
-                if (L.rm) hipLaunchKernelGGL(k_cpr_ilu_factor<true>, g256(L.iluNseq[cc]), dim3(256), 0, c->stream, L.iluNseq[cc], L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, L.W, L.iluMW, L.iluWL, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_lorder, L.d_fval);
-                else hipLaunchKernelGGL(k_cpr_ilu_factor<false>, g256(L.iluNseq[cc]), dim3(256), 0, c->stream, L.iluNseq[cc], L.iluNsteps[cc], L.d_rowAt + L.iluOff[cc], L.n, L.W, L.iluMW, L.iluWL, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_lorder, L.d_fval);
-            }
-            hipLaunchKernelGGL(k_cpr_ilu_pack, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.iluMW, L.rm ? 1 : 0, L.iluWL, L.iluWU, L.d_ecol, L.d_rlen, L.d_diag, L.d_imask, L.d_fval,
-                               L.d_ilv, L.d_ilc, L.d_iuv, L.d_iuc, L.d_iud);
-        }
-        if (l + 1 < R.lv.size()) {
-            CprLevelDev& C = R.lv[l + 1];
-            hipLaunchKernelGGL(k_cpr_galerkin, g256(C.nnz), dim3(256), 0, c->stream, C.nnz, L.d_gptr, L.d_gidx, L.d_cpos, L.d_val, C.d_val);
-        }
-    }
-    if (R.coarse_direct) {
-        const CprLevelDev& C = R.lv.back();
-        // in LDS where the device grants n x n doubles of dynamic shared memory (gfx950: yes, up to n = 128), else in place in global memory
-        static const bool ldsOk = hipFuncSetAttribute(reinterpret_cast<const void*>(k_cpr_dense_lu_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      CPR_COARSE_DIRECT * CPR_COARSE_DIRECT * (int)sizeof(double)) == hipSuccess;
-        if (ldsOk) hipLaunchKernelGGL(k_cpr_dense_lu_lds, dim3(1), dim3(CPR_LU_THREADS), (size_t)C.n * C.n * sizeof(double), c->stream, C.n, C.W, C.rm ? 1 : 0, C.d_ecol, C.d_rlen, C.d_val, R.d_lu);
-        else hipLaunchKernelGGL(k_cpr_dense_lu, dim3(1), dim3(256), 0, c->stream, C.n, C.W, C.rm ? 1 : 0, C.d_ecol, C.d_rlen, C.d_val, R.d_lu);
-    }
     return OPMHIP_SUCCESS;
 }
 void cpr_shutdown(opmhip_ctx* c) { c->cpr.job.reset(); }
@@ -1440,12 +1384,9 @@ int cpr_update(opmhip_ctx* c, bool solveBoundary) {
                 const size_t mark = c->allocs.size();
                 rc = cpr_upload_coarse(c, R, R.job->result, false);
                 R.job.reset();
-                if (rc) {   // (cannot happen for a pattern that was set up once; if it does: back to a synchronous set-up below)
-                    (void)hipStreamSynchronize(c->stream);
-                    while (c->allocs.size() > mark) { (void)hipFree(c->allocs.back()); c->allocs.pop_back(); }
-                    for (CprLevelDev& L : R.lv) L.d_agg = L.d_mptr = L.d_midx = L.d_mem4 = L.d_gptr = L.d_gidx = L.d_cpos = nullptr;
-                    R.lv.resize(1); R.d_lu = nullptr; R.structured = false;
-                }
+                // (cannot happen for a pattern that was set up once; if it does: back to a synchronous set-up below.  That this also resets
+                //  R.gather changes nothing here: the branch requires !cpr_gathering(c), so there is no joined level)
+                if (rc) cpr_forget_coarse(c, R, mark);
             } else if (anew && !R.job) startAsync = true;
             anew = false;
         }
@@ -1483,8 +1424,35 @@ int cpr_update(opmhip_ctx* c, bool solveBoundary) {
     return OPMHIP_SUCCESS;
 }
 
-// is level l smoothed with its ILU0 (a level that has the schedule and is not the coarsest)?
-static bool cpr_ilu_active(const CprDev& R, size_t l) { return l + 1 < R.lv.size() && R.lv[l].ilu; }
+// ---------------------------------------------------------------- application --------------------------------------------
+// One launch statement per kernel with a stencil-form or a fused variant: the choice and the argument list stand here once.
+// S: the level's ELL columns in stencil form (level 0 of a single domain, where the pattern has it), else {NULL, NULL}
+static EllStencil cpr_stencil(const CprLevelDev& L) { return EllStencil{L.d_sword, L.d_stable}; }
+// r = b - A x on level L
+static void launch_cpr_resid(opmhip_ctx* c, const CprLevelDev& L, const EllStencil& S, const double* x, double* r) {
+    if (S.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, x, r, c->d_done, S);
+    else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, x, r, c->d_done, S);
+}
+// post-smoothing of level L: x2 = x' + omega D^-1 (b - A x'), x' in the residual buffer
+static void launch_cpr_post(opmhip_ctx* c, const CprDev& R, const CprLevelDev& L, const EllStencil& S) {
+    if (S.word) hipLaunchKernelGGL(k_cpr_post<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, c->d_done, S);
+    else hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, c->d_done, S);
+}
+// R.d_r = d - A (0, x_p, 0): the residual the fine smoother takes
+static void launch_cpr_presid(opmhip_ctx* c, const CprDev& R, const EllStencil& S, const double* d, const double* xp) {
+    const int Nb = c->pat.Nb;
+    if (S.word) hipLaunchKernelGGL(k_cpr_presid<true>, g256(Nb), dim3(256), 0, c->stream, Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, c->d_done, S);
+    else hipLaunchKernelGGL(k_cpr_presid<false>, g256(Nb), dim3(256), 0, c->stream, Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, c->d_done, S);
+}
+// lane-group levels; fused: b is formed on the way from the finer level's residual rf by its member records mem4f (both NULL otherwise)
+static void launch_cpr_jacobi_lpr(opmhip_ctx* c, const CprDev& R, const CprLevelDev& L, bool fused, const double* xin, double* xout, const int4* mem4f, const double* rf) {
+    if (fused) hipLaunchKernelGGL(k_cpr_jacobi_lpr<true>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, xin, xout, mem4f, rf, c->d_done);
+    else hipLaunchKernelGGL(k_cpr_jacobi_lpr<false>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, xin, xout, mem4f, rf, c->d_done);
+}
+static void launch_cpr_down_lpr(opmhip_ctx* c, const CprDev& R, const CprLevelDev& L, bool fused, const int4* mem4f, const double* rf) {
+    if (fused) hipLaunchKernelGGL(k_cpr_down_lpr<true>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_x, L.d_r, mem4f, rf, c->d_done);
+    else hipLaunchKernelGGL(k_cpr_down_lpr<false>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_x, L.d_r, mem4f, rf, c->d_done);
+}
 // v = (U^-1 L^-1) d with the level's ILU0: forward colour by colour, backward in reverse; out != NULL: out = add + v as the
 // backward sweeps store
 template <bool BWD, int WQ>
@@ -1547,8 +1515,8 @@ static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l) {
         if (!havex && !fused) hipLaunchKernelGGL(k_cpr_presmooth, g256(L.n), dim3(256), 0, c->stream, L.n, R.omega, L.d_dinv, L.d_b, L.d_x, done);
         double *xin = L.d_x, *xout = L.d_x2;
         for (int sweep = 0; sweep < 4; ++sweep) {
-            if (L.rm && fused && sweep == 0) hipLaunchKernelGGL(k_cpr_jacobi_lpr<true>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, xin, xout, mem4f, rf, done);
-            else if (L.rm) hipLaunchKernelGGL(k_cpr_jacobi_lpr<false>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, xin, xout, (const int4*)nullptr, (const double*)nullptr, done);
+            const bool first = fused && sweep == 0;   // the sweep that forms b; the later ones read it
+            if (L.rm) launch_cpr_jacobi_lpr(c, R, L, first, xin, xout, first ? mem4f : nullptr, first ? rf : nullptr);
             else hipLaunchKernelGGL(k_cpr_jacobi, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, xin, xout, done);
             std::swap(xin, xout);
         }
@@ -1556,21 +1524,15 @@ static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l) {
     }
     CprLevelDev& C = R.lv[l + 1];
     const bool ilu = cpr_ilu_active(R, l);
-    const EllStencil S0{L.d_sword, L.d_stable};
+    const EllStencil S = cpr_stencil(L);
     if (ilu) {   // pre-smoothing from x = 0 with the level's ILU0, then the residual
         cpr_ilu_smooth(c, L, L.d_b, L.d_x, nullptr, nullptr);
-        if (S0.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S0);
-        else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S0);
+        launch_cpr_resid(c, L, S, L.d_x, L.d_r);
     } else
-    if (L.rm && fused) hipLaunchKernelGGL(k_cpr_down_lpr<true>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_x, L.d_r, mem4f, rf, done);
-    else if (L.rm) hipLaunchKernelGGL(k_cpr_down_lpr<false>, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_x, L.d_r, (const int4*)nullptr, (const double*)nullptr, done);
+    if (L.rm) launch_cpr_down_lpr(c, R, L, fused, mem4f, rf);
     else {   // large levels: x first (it rides in the kernel that produced b), then the residual with ONE gathered value per entry (0.250 -> 0.243 ms per cycle against the fused form, which gathers dinv and b)
         if (!havex) hipLaunchKernelGGL(k_cpr_presmooth, g256(L.n), dim3(256), 0, c->stream, L.n, R.omega, L.d_dinv, L.d_b, L.d_x, done);
-        {
-            const EllStencil S{L.d_sword, L.d_stable};
-            if (S.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S);
-            else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S);
-        }
+        launch_cpr_resid(c, L, S, L.d_x, L.d_r);
     }
     if (!cpr_forms_rhs(R, l + 1)) {
         const bool ride = cpr_presmooth_rides(R, l + 1);
@@ -1580,19 +1542,14 @@ static const double* cpr_vcycle(opmhip_ctx* c, CprDev& R, size_t l) {
     const double* xc = cpr_vcycle(c, R, l + 1);
     if (ilu) {   // x' = x + damp P xc; r = b - A x'; x = x' + ILU0(r)
         hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, R.damp, L.d_agg, xc, L.d_x, L.d_r, done);
-        if (S0.word) hipLaunchKernelGGL(k_cpr_resid<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_r, L.d_x, done, S0);
-        else hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_r, L.d_x, done, S0);
+        launch_cpr_resid(c, L, S, L.d_r, L.d_x);
         cpr_ilu_smooth(c, L, L.d_x, L.d_t, L.d_r, L.d_x2);
         return L.d_x2;
     }
     if (L.rm) hipLaunchKernelGGL(k_cpr_up_lpr, g256(L.n * CPR_LPR), dim3(256), 0, c->stream, L.n, L.W, R.omega, R.damp, L.d_ecol, L.d_val, L.d_dinv, L.d_agg, xc, L.d_b, L.d_x, L.d_x2, done);
     else {   // large levels: the prolonged iterate first (into the residual buffer, free by now), then one gathered value per entry
         hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, R.damp, L.d_agg, xc, L.d_x, L.d_r, done);
-        {
-            const EllStencil S{L.d_sword, L.d_stable};
-            if (S.word) hipLaunchKernelGGL(k_cpr_post<true>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
-            else hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
-        }
+        launch_cpr_post(c, R, L, S);
     }
     return L.d_x2;
 }
@@ -1612,8 +1569,8 @@ static const double* cpr_gathered_cycle(opmhip_ctx* c, const double* d) {
     auto keep = [&](int rc) { if (rc && !R.apply_rc) R.apply_rc = rc; };
     hipLaunchKernelGGL(k_cpr_restrict_fine, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, d, R.d_w, L.d_b, R.omega, L.d_dinv, L.d_x, done);   // b = r_p, x = omega D^-1 b
     keep(comm_halo_f64(c, L.d_x, 1));
-    const EllStencil S{nullptr, nullptr};
-    hipLaunchKernelGGL(k_cpr_resid<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, L.d_ecol, L.d_val, L.d_b, L.d_x, L.d_r, done, S);
+    const EllStencil S{nullptr, nullptr};   // level 0 keeps its couplings to ghost cells here: no stencil form
+    launch_cpr_resid(c, L, S, L.d_x, L.d_r);
     const size_t g = R.lv.size() - 1;
     const double* rl = L.d_r;
     for (size_t l = 0; l < g; ++l) {   // sums over the aggregates, level by level (no smoothing in between)
@@ -1634,7 +1591,7 @@ static const double* cpr_gathered_cycle(opmhip_ctx* c, const double* d) {
     prof_span_end(c, span);
     hipLaunchKernelGGL(k_cpr_prolong, g256(L.n), dim3(256), 0, c->stream, L.n, 1.0, G.d_cagg, xG + G.off, L.d_x, L.d_r, done);   // x' = x + (the joined level's result, per aggregate)
     keep(comm_halo_f64(c, L.d_r, 1));
-    hipLaunchKernelGGL(k_cpr_post<false>, g256(L.n), dim3(256), 0, c->stream, L.n, L.W, R.omega, L.d_ecol, L.d_val, L.d_dinv, L.d_b, L.d_r, L.d_x2, done, S);
+    launch_cpr_post(c, R, L, S);
     keep(comm_halo_f64(c, L.d_x2, 1));
     return L.d_x2;
 }
@@ -1649,8 +1606,7 @@ void launch_cpr_apply(opmhip_ctx* c, const double* d, double* v) {
         const double* xp = cpr_gathered_cycle(c, d);
         prof_end(c, ps);
         ps = prof_begin(c, PROF_VECTOR);
-        const EllStencil S{nullptr, nullptr};
-        hipLaunchKernelGGL(k_cpr_presid<false>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, done, S);
+        launch_cpr_presid(c, R, EllStencil{nullptr, nullptr}, d, xp);
         prof_end(c, ps);
         launch_ilu_apply(c, R.d_r, v, 1.0, nullptr, xp, R.d_z);
         return;
@@ -1667,11 +1623,7 @@ void launch_cpr_apply(opmhip_ctx* c, const double* d, double* v) {
     prof_end(c, ps);
     // post-smoothing on the updated residual r = d - A (0, x_p, 0)
     ps = prof_begin(c, PROF_VECTOR);
-    {
-        const EllStencil S{R.lv[0].d_sword, R.lv[0].d_stable};
-        if (S.word) hipLaunchKernelGGL(k_cpr_presid<true>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, done, S);
-        else hipLaunchKernelGGL(k_cpr_presid<false>, g256(P.Nb), dim3(256), 0, c->stream, P.Nb, R.lv[0].W, R.lv[0].d_ecol, R.d_pcol, d, xp, R.d_r, done, S);
-    }
+    launch_cpr_presid(c, R, cpr_stencil(R.lv[0]), d, xp);
     prof_end(c, ps);
     launch_ilu_apply(c, R.d_r, v, 1.0, nullptr, xp, R.d_z);               // fine smoother: ILU0, relaxation 1; v = (0, x_p, 0) + its result
 }

@@ -1,9 +1,13 @@
 // Host side of the CPR pressure-AMG set-up (cpr_setup.hpp): two passes of pairwise matching per level, Galerkin gather lists, ELL
 // images of the levels, ILU0 smoothing schedules and colourings.  Mirrors oracle/cpr.hpp (CprAmg::setup_structure: same matching, same
-// lists, same stops).  No HIP call: cpr.hip uploads what is built here.
+// lists, same stops), and the index work of the level that joins the ranks of a decomposed run.  No HIP call: cpr.hip uploads what is
+// built here.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <map>
+#include <numeric>
+#include <string>
 #include <thread>
 #include <utility>
 
@@ -353,6 +357,100 @@ void cpr_build_coarse_host(const Pattern& P, const std::vector<double>& ell0, do
     A.val.resize(nnz0);
     for (int k = 0; k < nnz0; ++k) A.val[k] = ell0[pos[k]];
     cpr_coarsen_host(std::move(A), std::move(pos), P.fromOrder.data(), P.toOrder.data(), beta, lprRows, iluLevels, stopRows, out);
+}
+void cpr_level0_ilu_schedule(const CprHostLevel& L0, const std::vector<int>& colourPrefix, int ncol, CprIluHost& S) {
+    std::vector<int> posv(L0.n), colour(L0.n);
+    for (int cc = 0; cc < ncol; ++cc)
+        for (int p = colourPrefix[cc]; p < colourPrefix[cc + 1]; ++p) colour[p] = cc;
+    std::iota(posv.begin(), posv.end(), 0);
+    cpr_ilu_schedule(L0, posv, colour, ncol, S);
+}
+
+// ---- the joined level of a decomposed run (cpr_setup.hpp) -----------------------------------------------------------------------------
+std::vector<int> cpr_joined_aggregates(int nb, const CprHostCoarse& H) {
+    std::vector<int> cagg(nb);
+    std::iota(cagg.begin(), cagg.end(), 0);
+    for (size_t l = 0; l < H.lv.size(); ++l) {   // (H.lv.size() levels below level 0: as many transfers)
+        const std::vector<int>& a = l == 0 ? H.l0.agg : H.lv[l - 1].agg;
+        for (int i = 0; i < nb; ++i) cagg[i] = a[cagg[i]];
+    }
+    return cagg;
+}
+void cpr_joined_rows(int nb, const std::vector<int>& rowptr, const std::vector<int>& col, const std::vector<int>& cagg, const std::vector<int>& ghostRow,
+                     const std::vector<long long>& ghostPlace, int off, const HCsr& LA, const std::vector<int>& lastPos, CprJoinedRows& out) {
+    out = CprJoinedRows();
+    const int nloc = LA.n;
+    // the fine couplings of every pair (my aggregate, joined row of a ghost cell's aggregate); q: the coupling's number in entry order
+    struct Fine { int i; long long gf; int q; };
+    std::vector<std::map<int, std::vector<Fine>>> cross(nloc);
+    for (int i = 0; i < nb; ++i)
+        for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+            const int gh = col[k] - nb;
+            if (gh < 0) continue;
+            const int q = (int)out.qrow.size();
+            out.qrow.push_back(i); out.qentry.push_back(k);
+            cross[cagg[i]][ghostRow[gh]].push_back(Fine{i, ghostPlace[gh], q});
+        }
+    out.rowlen.assign(nloc, 0);
+    out.xptr.assign(1, 0);
+    for (int I = 0; I < nloc; ++I) {
+        auto cr = cross[I].begin();
+        auto emit_cross = [&](int upto) {   // the entries towards other ranks whose joined column lies below `upto`
+            for (; cr != cross[I].end() && cr->first < upto; ++cr) {
+                std::vector<Fine>& f = cr->second;
+                std::sort(f.begin(), f.end(), [](const Fine& a, const Fine& b) { return a.i != b.i ? a.i < b.i : a.gf < b.gf; });
+                for (const Fine& e : f) out.xidx.push_back(e.q);
+                out.cols.push_back(cr->first);
+                out.src.push_back(-1 - (int)(out.xptr.size() - 1));
+                out.xptr.push_back((int)out.xidx.size());
+                ++out.rowlen[I];
+            }
+        };
+        for (int k = LA.rowptr[I]; k < LA.rowptr[I + 1]; ++k) {
+            emit_cross(off + LA.col[k]);
+            out.cols.push_back(off + LA.col[k]); out.src.push_back(lastPos[k]);
+            ++out.rowlen[I];
+        }
+        emit_cross(INT_MAX);
+    }
+}
+std::vector<double> cpr_joined_values(const CprJoinedRows& Q, const std::vector<double>& apg, const std::vector<double>& lastval) {
+    std::vector<double> vals(Q.src.size());
+    size_t k = 0;   // own entries stand in the last level's entry order
+    for (size_t e = 0; e < Q.src.size(); ++e) {
+        if (Q.src[e] >= 0) { vals[e] = lastval[k++]; continue; }
+        const int x = -1 - Q.src[e];
+        double s = 0.0;
+        for (int t = Q.xptr[x]; t < Q.xptr[x + 1]; ++t) s += apg[Q.xidx[t]];
+        vals[e] = s;
+    }
+    return vals;
+}
+void cpr_join_rows(const std::vector<int>& bl, const std::vector<int>& bc, const std::vector<double>& bv, const std::vector<int>& nnzs, const std::vector<int>& offs,
+                   int maxn, int maxnnz, CprJoined& out) {
+    out = CprJoined();
+    const int nr = (int)nnzs.size(), NG = offs[nr];
+    HCsr& J = out.J;
+    J.n = NG;
+    J.rowptr.assign(1, 0);
+    for (int r = 0; r < nr; ++r) {
+        const size_t l0 = (size_t)r * maxn, e0 = (size_t)r * maxnnz;
+        const int rows = offs[r + 1] - offs[r], nnz = nnzs[r];
+        bool ok = rows >= 0 && rows <= maxn && nnz >= 0 && nnz <= maxnnz && l0 + maxn <= bl.size() && e0 + maxnnz <= bc.size() && e0 + maxnnz <= bv.size();
+        int e = 0;
+        for (int I = 0; I < rows && ok; ++I) {
+            const int len = bl[l0 + I];
+            ok = len >= 0 && len <= nnz - e;   // a row that would leave the rank's entries is not followed
+            for (int t = 0; t < len && ok; ++t, ++e) {
+                const int cj = bc[e0 + e];
+                ok = cj >= 0 && cj < NG;
+                J.col.push_back(cj); J.val.push_back(bv[e0 + e]); out.vunpad.push_back(r * maxnnz + e);
+            }
+            J.rowptr.push_back((int)J.col.size());
+            out.unpad.push_back(r * maxn + I);
+        }
+        if (!ok) { out.error = "cpr: the joined level's rows of rank " + std::to_string(r) + " are inconsistent"; return; }
+    }
 }
 
 }  // namespace opmhip

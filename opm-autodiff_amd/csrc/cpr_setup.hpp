@@ -1,7 +1,9 @@
 // Host side of the CPR pressure-AMG set-up (cpr_setup.cpp): the hierarchy's matching, Galerkin gather lists, ELL images, ILU0
 // smoothing schedules and colourings - pure host work on copies, no HIP call, so that it can run on a thread of its own beside the
 // solves (cpr.hip: --cpr-reuse-setup=2 with opmhip_config.cpr_async_setup) and be built and checked without a device
-// (tests/san/cpr_setup_san.cpp).  cpr.hip uploads what it produces.
+// (tests/san/cpr_setup_san.cpp).  cpr.hip uploads what it produces.  The joined level of a decomposed run (cpr.hip: cpr_gather_setup) has its
+// index work here as well - aggregates composed down the levels, a rank's rows, their values, everybody's rows into one matrix - as
+// functions of plain vectors: no context, no communicator; a refusal comes back as an error string.
 #pragma once
 #include <climits>
 #include <string>
@@ -74,5 +76,38 @@ void cpr_coarsen_host(HCsr A, std::vector<int> pos, const int* natOf, const int*
 // Pure host work on its arguments (no context, no HIP call): may run on a thread of its own.  ell0: level 0's value image
 // (W0 x Nb, as on the device) of the pressure matrix the structure is built from.
 void cpr_build_coarse_host(const Pattern& P, const std::vector<double>& ell0, double beta, int lprRows, int iluLevels, int stopRows, CprHostCoarse& out);
+// Level 0's ILU0 smoothing schedule in the stored order: the block ILU0's colours (rows of colour c: [colourPrefix[c], colourPrefix[c + 1]))
+// are this one's, the elimination position of a row is its index
+void cpr_level0_ilu_schedule(const CprHostLevel& L0, const std::vector<int>& colourPrefix, int ncol, CprIluHost& S);
+
+// ---- the joined level of a decomposed run: the index work between cpr_gather_setup's exchanges (cpr.hip) --------------------------------
+// Rank r's last level (n_r rows) becomes rows [offs[r], offs[r + 1]) of ONE matrix that every rank holds.  Its entries: the last
+// level's own (columns shifted by offs[r]), and per pair (my aggregate, an aggregate of another rank) that fine couplings to ghost
+// cells join the sum of their pressure values.
+// The aggregate, on the rank's last level, of every owned cell: H.l0.agg and H.lv[*].agg composed (the identity where level 0 is the last)
+std::vector<int> cpr_joined_aggregates(int nb, const CprHostCoarse& H);
+struct CprJoinedRows {
+    std::vector<int> qrow, qentry;   // the pattern's couplings to ghost cells in entry order: owned row, entry (k_cpr_ghost_pvals forms apg from them)
+    std::vector<int> rowlen, cols;   // my rows: lengths, joined columns (ascending in a row)
+    // value of entry e (k_cpr_gather_vals, cpr_joined_values): src[e] >= 0: the last level's entry at that place of its image (H.lastPos),
+    // else the sum of apg[xidx[t]] over t in [xptr[x], xptr[x + 1]), x = -1 - src[e], in list order = by (owned row, owner-side place)
+    std::vector<int> src, xptr, xidx;
+};
+// My rows, structure only.  rowptr / col: the local pattern (nb owned rows, columns >= nb: ghost cells); per ghost cell (column - nb)
+// what its owner says of it: its row of the joined level, and the owner-side global place of the cell; off = offs[me]
+void cpr_joined_rows(int nb, const std::vector<int>& rowptr, const std::vector<int>& col, const std::vector<int>& cagg, const std::vector<int>& ghostRow,
+                     const std::vector<long long>& ghostPlace, int off, const HCsr& lastA, const std::vector<int>& lastPos, CprJoinedRows& out);
+// Their values: k_cpr_gather_vals's statement with the last level's values in entry order (own entries appear in that order)
+std::vector<double> cpr_joined_values(const CprJoinedRows& Q, const std::vector<double>& apg, const std::vector<double>& lastval);
+// Everybody's rows into one CSR.  bl / bc / bv: per rank maxn row lengths, maxnnz columns and values (padded); nnzs[r]: entries of
+// rank r.  unpad / vunpad: the place of row I / entry e of J in the padded buffers.  Every index is bounded before it is used; the
+// refusal names the rank (the same data on every rank: all refuse alike)
+struct CprJoined {
+    HCsr J;
+    std::vector<int> unpad, vunpad;
+    std::string error;
+};
+void cpr_join_rows(const std::vector<int>& bl, const std::vector<int>& bc, const std::vector<double>& bv, const std::vector<int>& nnzs, const std::vector<int>& offs,
+                   int maxn, int maxnnz, CprJoined& out);
 
 }  // namespace opmhip

@@ -7,8 +7,13 @@
 // entry of the finer level once (as places in its ELL image, each inside the right pair of aggregates), every image decodes back to its CSR
 // matrix, and every ILU0 schedule is an elimination order its sweeps may run in parallel.  The hierarchy is compared with the oracle's
 // (oracle/cpr.hpp: CprAmg::setup_structure on the same matrix): the same levels, sizes and aggregates, the same coarsest matrix bit for bit.
+// The joined level of a decomposed run (cpr_joined_aggregates, cpr_joined_rows, cpr_joined_values, cpr_join_rows) is run on small worlds of
+// ranks and compared with the Galerkin product of the whole system's matrix; cpr_join_rows is fed buffers a peer has spoiled (run_world, refuses).
 #include <algorithm>
+#include <climits>
+#include <cmath>
 #include <cstdio>
+#include <map>
 #include <numeric>
 #include <random>
 #include <set>
@@ -316,13 +321,8 @@ static bool run(const Case& cs, int iluLevels, int lprRows, int stopRows, int& l
     std::vector<double> ell0((size_t)I0.W * n, 0.0);
     for (int k = 0; k < (int)A.col.size(); ++k) ell0[pos0[k]] = A.val[k];
     if (!cs.colourPrefix.empty() && iluLevels > 0) {   // level 0's ILU0 schedule in the stored order, with the block ILU0's colours (cpr_setup_level0)
-        const int ncol = (int)cs.colourPrefix.size() - 1;
-        std::vector<int> posv(n), colour(n);
-        for (int cc = 0; cc < ncol; ++cc)
-            for (int p = cs.colourPrefix[cc]; p < cs.colourPrefix[cc + 1]; ++p) colour[p] = cc;
-        std::iota(posv.begin(), posv.end(), 0);
         CprIluHost S;
-        opmhip::cpr_ilu_schedule(I0, posv, colour, ncol, S);
+        opmhip::cpr_level0_ilu_schedule(I0, cs.colourPrefix, (int)cs.colourPrefix.size() - 1, S);
         std::snprintf(what, sizeof what, "%s level 0 ILU0", cs.name.c_str());
         if (!check_ilu(what, I0, S)) return false;
     }
@@ -406,6 +406,269 @@ static bool run(const Case& cs, int iluLevels, int lprRows, int stopRows, int& l
     return true;
 }
 
+// ---- the joined level of a decomposed run: cpr_joined_aggregates, cpr_joined_rows, cpr_joined_values, cpr_join_rows ---------------------
+// A world: a whole system's pressure matrix (natural order) and the rank that owns every cell.  Every rank numbers its owned cells in
+// ascending natural id (reversedLast: the last rank in descending id - its internal order is then not the natural one) and its ghost cells
+// behind them, coarsens its owned part down to stopRows and forms its rows of the joined level; the ghost information is taken straight
+// from the owners, which is what the halo exchange of cpr_gather_setup delivers.
+// Summation order of a joined entry between two ranks: the product's rule is (owned row in my internal order, owner-side place of the
+// column).  The oracle (oracle_capi.cpp: orc_cpr_solve_blocks) sums in ascending (row, column) of the matrix it is handed; the GPU tests
+// hand it the whole system numbered rank by rank in each rank's internal order (tests/test_gpu_dd.py: frg), where the two orders are one.
+// The restatement below numbers the whole system the same way (place = first place of the owner + internal index) and sums in ascending
+// (row place, column place): the product's rule holds, and the reversed world shows that it is the place, not the natural id, that orders.
+struct World {
+    std::string name;
+    Mat A;
+    std::vector<int> owner;
+    int nr = 0, stopRows = 8;
+    bool reversedLast = false;
+    int wantLevels = -1;        // 0: level 0 itself is joined; 2: at least two transfers are composed; -1: whatever comes
+    bool wantShared = false;    // some joined entry sums several fine couplings
+    bool wantNoCoupling = false;
+};
+static World box_world(const std::string& name, int nx, int ny, int nz, std::vector<int> xcuts, std::vector<int> ycuts, unsigned seed, int stopRows) {
+    World w;
+    w.name = name;
+    w.A = grid7(nx, ny, nz, true, seed);
+    w.stopRows = stopRows;
+    auto part = [](const std::vector<int>& cuts, int v) { int p = 0; for (int c : cuts) p += v >= c; return p; };
+    const int npx = (int)xcuts.size() + 1;
+    w.nr = npx * ((int)ycuts.size() + 1);
+    w.owner.resize(w.A.n);
+    for (int k = 0; k < nz; ++k)
+        for (int j = 0; j < ny; ++j)
+            for (int i = 0; i < nx; ++i) w.owner[i + nx * (j + ny * k)] = part(xcuts, i) + npx * part(ycuts, j);
+    return w;
+}
+static World two_slabs(const std::string& name, unsigned seed) {
+    World w;
+    w.name = name;
+    const Mat a = grid7(3, 4, 3, true, seed), b = grid7(4, 3, 3, true, seed + 1);
+    std::vector<std::vector<std::pair<int, double>>> rows(a.n + b.n);
+    for (int i = 0; i < a.n; ++i)
+        for (int k = a.rowptr[i]; k < a.rowptr[i + 1]; ++k) rows[i].push_back({a.col[k], a.val[k]});
+    for (int i = 0; i < b.n; ++i)
+        for (int k = b.rowptr[i]; k < b.rowptr[i + 1]; ++k) rows[a.n + i].push_back({a.n + b.col[k], b.val[k]});
+    w.A = from_rows(a.n + b.n, 0, rows);
+    w.owner.assign(a.n + b.n, 1);
+    std::fill(w.owner.begin(), w.owner.begin() + a.n, 0);
+    w.nr = 2;
+    w.wantNoCoupling = true;
+    return w;
+}
+struct RankSide {
+    Mat M;                       // the local pattern with values
+    std::vector<int> cells, ghosts;   // natural id of every owned cell (internal order) and of every ghost cell
+    CprHostCoarse H;
+    std::vector<int> cagg;
+    opmhip::CprJoinedRows Q;
+    std::vector<double> vals;
+};
+// the padded buffers every rank holds after the exchanges of step 5
+struct Gathered {
+    std::vector<int> bl, bc, nnzs, offs;
+    std::vector<double> bv;
+    int maxn = 1, maxnnz = 1;
+};
+static bool run_world(const World& w, Gathered& out, int& lines) {
+    const Mat& A = w.A;
+    const int N = A.n, nr = w.nr;
+    const char* what = w.name.c_str();
+    std::vector<RankSide> R(nr);
+    std::vector<int> local(N);
+    for (int i = 0; i < N; ++i) R[w.owner[i]].cells.push_back(i);
+    if (w.reversedLast) std::reverse(R[nr - 1].cells.begin(), R[nr - 1].cells.end());
+    for (int r = 0; r < nr; ++r)
+        for (int q = 0; q < (int)R[r].cells.size(); ++q) local[R[r].cells[q]] = q;
+    int levelsMax = 0, levelsMin = INT_MAX;
+    for (int r = 0; r < nr; ++r) {   // every rank's subdomain and hierarchy
+        RankSide& S = R[r];
+        const int n = (int)S.cells.size();
+        CHECK(n > 0, "%s: rank %d owns nothing", what, r);
+        std::set<int> gs;
+        for (int i : S.cells)
+            for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
+                if (w.owner[A.col[k]] != r) gs.insert(A.col[k]);
+        S.ghosts.assign(gs.begin(), gs.end());
+        std::vector<std::vector<std::pair<int, double>>> rows(n);
+        for (int q = 0; q < n; ++q)
+            for (int k = A.rowptr[S.cells[q]]; k < A.rowptr[S.cells[q] + 1]; ++k) {
+                const int j = A.col[k];
+                const int lc = w.owner[j] == r ? local[j] : n + (int)(std::lower_bound(S.ghosts.begin(), S.ghosts.end(), j) - S.ghosts.begin());
+                rows[q].push_back({lc, A.val[k]});
+            }
+        S.M = from_rows(n, (int)S.ghosts.size(), rows);
+        opmhip::Pattern P;
+        P.Nb = n; P.Nghost = S.M.nghost; P.Nloc = n + S.M.nghost;
+        P.rowptr = S.M.rowptr; P.col = S.M.col;
+        opmhip::HCsr A0;
+        A0.n = n; A0.rowptr = S.M.rowptr; A0.col = S.M.col;
+        CprHostLevel I0;
+        std::vector<int> pos0;
+        CHECK(opmhip::ell_image(A0, I0, pos0, false, n), "%s: level 0 of rank %d refused", what, r);
+        std::vector<double> ell0((size_t)I0.W * n, 0.0);
+        for (int k = 0; k < (int)S.M.col.size(); ++k) ell0[pos0[k]] = S.M.val[k];
+        opmhip::cpr_build_coarse_host(P, ell0, 0.25, opmhip::CPR_LPR_ROWS, 0, w.stopRows, S.H);
+        CHECK(S.H.error.empty(), "%s: rank %d: %s", what, r, S.H.error.c_str());
+        const int g = (int)S.H.lv.size(), nlast = S.H.lastA.n;
+        levelsMax = std::max(levelsMax, g); levelsMin = std::min(levelsMin, g);
+        S.cagg = opmhip::cpr_joined_aggregates(n, S.H);
+        CHECK((int)S.cagg.size() == n, "%s: cagg size of rank %d", what, r);
+        std::vector<int> members(nlast, 0);
+        for (int q = 0; q < n; ++q) {   // the transfers applied one after the other, restated cell by cell
+            int a = q;
+            for (int l = 0; l < g; ++l) a = (l == 0 ? S.H.l0.agg : S.H.lv[l - 1].agg)[a];
+            CHECK(S.cagg[q] == a && a >= 0 && a < nlast, "%s: cagg[%d] of rank %d is %d, not %d", what, q, r, S.cagg[q], a);
+            ++members[a];
+        }
+        for (int I = 0; I < nlast; ++I) CHECK(members[I] > 0, "%s: row %d of rank %d's last level has no cell", what, I, r);
+    }
+    CHECK(w.wantLevels != 0 || levelsMax == 0, "%s: level 0 was to be the joined one, %d transfers", what, levelsMax);
+    CHECK(w.wantLevels != 2 || levelsMin >= 2, "%s: at least two transfers were to be composed, %d", what, levelsMin);
+    Gathered& G = out;
+    G = Gathered();
+    G.offs.assign(nr + 1, 0);
+    std::vector<int> foffs(nr + 1, 0);
+    for (int r = 0; r < nr; ++r) {
+        G.offs[r + 1] = G.offs[r] + R[r].H.lastA.n;
+        foffs[r + 1] = foffs[r] + (int)R[r].cells.size();
+        G.maxn = std::max(G.maxn, R[r].H.lastA.n);
+    }
+    const int NG = G.offs[nr];
+    auto place = [&](int i) { return foffs[w.owner[i]] + local[i]; };                        // of a cell in the whole system, rank by rank
+    auto joined = [&](int i) { return G.offs[w.owner[i]] + R[w.owner[i]].cagg[local[i]]; };   // its row of the joined level
+    int nqAll = 0, longest = 0;
+    for (int r = 0; r < nr; ++r) {   // every rank's rows of the joined level
+        RankSide& S = R[r];
+        const Mat& M = S.M;
+        const int n = M.n, nlast = S.H.lastA.n;
+        std::vector<int> ghostRow(S.ghosts.size());
+        std::vector<long long> ghostPlace(S.ghosts.size());
+        for (size_t gI = 0; gI < S.ghosts.size(); ++gI) { ghostRow[gI] = joined(S.ghosts[gI]); ghostPlace[gI] = place(S.ghosts[gI]); }
+        opmhip::CprJoinedRows& Q = S.Q;
+        opmhip::cpr_joined_rows(n, M.rowptr, M.col, S.cagg, ghostRow, ghostPlace, G.offs[r], S.H.lastA, S.H.lastPos, Q);
+        const int nq = (int)Q.qrow.size(), nnzloc = (int)Q.cols.size();
+        nqAll += nq;
+        // the couplings to ghost cells, in entry order
+        CHECK(Q.qentry.size() == Q.qrow.size(), "%s: rank %d: qrow / qentry sizes", what, r);
+        int q = 0;
+        for (int i = 0; i < n; ++i)
+            for (int k = M.rowptr[i]; k < M.rowptr[i + 1]; ++k)
+                if (M.col[k] >= n) { CHECK(q < nq && Q.qrow[q] == i && Q.qentry[q] == k, "%s: rank %d: ghost coupling %d", what, r, q); ++q; }
+        CHECK(q == nq, "%s: rank %d: %d ghost couplings listed, the pattern has %d", what, r, nq, q);
+        CHECK((int)Q.rowlen.size() == nlast && (int)Q.src.size() == nnzloc && !Q.xptr.empty() && Q.xptr[0] == 0 && Q.xptr.back() == (int)Q.xidx.size(),
+              "%s: rank %d: sizes of its rows", what, r);
+        CHECK(std::accumulate(Q.rowlen.begin(), Q.rowlen.end(), 0) == nnzloc, "%s: rank %d: rowlen does not sum to nnzloc", what, r);
+        std::vector<int> seen(nq, 0);
+        int e = 0, x = 0;
+        for (int I = 0; I < nlast; ++I) {
+            int k = S.H.lastA.rowptr[I];
+            for (int t = 0; t < Q.rowlen[I]; ++t, ++e) {
+                CHECK(t == 0 || Q.cols[e] > Q.cols[e - 1], "%s: rank %d row %d: columns do not ascend", what, r, I);
+                CHECK(Q.cols[e] >= 0 && Q.cols[e] < NG, "%s: rank %d row %d: column %d", what, r, I, Q.cols[e]);
+                if (Q.src[e] >= 0) {   // an entry of my last level: the next one of its row, at its place in the level's image
+                    CHECK(k < S.H.lastA.rowptr[I + 1] && Q.src[e] == S.H.lastPos[k] && Q.cols[e] == G.offs[r] + S.H.lastA.col[k], "%s: rank %d row %d: own entry %d", what, r, I, t);
+                    ++k;
+                    continue;
+                }
+                CHECK(Q.src[e] == -1 - x && x + 1 < (int)Q.xptr.size() && Q.xptr[x + 1] > Q.xptr[x], "%s: rank %d row %d: cross entry %d", what, r, I, x);
+                CHECK(Q.cols[e] < G.offs[r] || Q.cols[e] >= G.offs[r + 1], "%s: rank %d row %d: a cross entry inside my slice", what, r, I);
+                longest = std::max(longest, Q.xptr[x + 1] - Q.xptr[x]);
+                for (int u = Q.xptr[x]; u < Q.xptr[x + 1]; ++u) {
+                    const int qq = Q.xidx[u];
+                    CHECK(qq >= 0 && qq < nq && !seen[qq], "%s: rank %d: xidx[%d] = %d twice or out of range", what, r, u, qq);
+                    seen[qq] = 1;
+                    const int gh = M.col[Q.qentry[qq]] - n;
+                    CHECK(S.cagg[Q.qrow[qq]] == I && ghostRow[gh] == Q.cols[e], "%s: rank %d: coupling %d in the wrong joined entry", what, r, qq);
+                    if (u > Q.xptr[x]) {
+                        const int qp = Q.xidx[u - 1];
+                        const long long pp = ghostPlace[M.col[Q.qentry[qp]] - n], pn = ghostPlace[gh];
+                        CHECK(Q.qrow[qp] < Q.qrow[qq] || (Q.qrow[qp] == Q.qrow[qq] && pp < pn), "%s: rank %d: couplings of cross entry %d out of order", what, r, x);
+                    }
+                }
+                ++x;
+            }
+            CHECK(k == S.H.lastA.rowptr[I + 1], "%s: rank %d row %d: own entries missing", what, r, I);
+        }
+        CHECK(x + 1 == (int)Q.xptr.size(), "%s: rank %d: cross entries", what, r);
+        for (int qq = 0; qq < nq; ++qq) CHECK(seen[qq], "%s: rank %d: ghost coupling %d is in no joined entry", what, r, qq);
+        // values: the pressure value of a coupling of this scalar system is the entry itself
+        std::vector<double> apg(std::max(nq, 1), 0.0);
+        for (int qq = 0; qq < nq; ++qq) apg[qq] = M.val[Q.qentry[qq]];
+        S.vals = opmhip::cpr_joined_values(Q, apg, S.H.lastA.val);
+        CHECK((int)S.vals.size() == nnzloc, "%s: rank %d: values", what, r);
+        G.nnzs.push_back(nnzloc);
+        G.maxnnz = std::max(G.maxnnz, nnzloc);
+    }
+    CHECK(!w.wantNoCoupling || nqAll == 0, "%s: %d couplings between the slabs", what, nqAll);
+    CHECK(w.wantNoCoupling || nqAll > 0, "%s: no coupling between the ranks", what);
+    CHECK(!w.wantShared || longest >= 2, "%s: no joined entry sums more than one coupling", what);
+    // step 5's buffers, and the joined matrix from them
+    G.bl.assign((size_t)nr * G.maxn, 0); G.bc.assign((size_t)nr * G.maxnnz, 0); G.bv.assign((size_t)nr * G.maxnnz, 0.0);
+    for (int r = 0; r < nr; ++r) {
+        std::copy(R[r].Q.rowlen.begin(), R[r].Q.rowlen.end(), G.bl.begin() + (size_t)r * G.maxn);
+        std::copy(R[r].Q.cols.begin(), R[r].Q.cols.end(), G.bc.begin() + (size_t)r * G.maxnnz);
+        std::copy(R[r].vals.begin(), R[r].vals.end(), G.bv.begin() + (size_t)r * G.maxnnz);
+    }
+    opmhip::CprJoined JR;
+    opmhip::cpr_join_rows(G.bl, G.bc, G.bv, G.nnzs, G.offs, G.maxn, G.maxnnz, JR);
+    CHECK(JR.error.empty(), "%s: %s", what, JR.error.c_str());
+    const opmhip::HCsr& J = JR.J;
+    CHECK(J.n == NG && (int)J.rowptr.size() == NG + 1 && (int)JR.unpad.size() == NG && JR.vunpad.size() == J.col.size() && J.val.size() == J.col.size(), "%s: sizes of the joined matrix", what);
+    for (int r = 0; r < nr; ++r)   // unpad / vunpad invert the padding
+        for (int I = 0, e = 0; I < G.offs[r + 1] - G.offs[r]; ++I) {
+            CHECK(JR.unpad[G.offs[r] + I] == r * G.maxn + I, "%s: unpad of row %d of rank %d", what, I, r);
+            for (int k = J.rowptr[G.offs[r] + I]; k < J.rowptr[G.offs[r] + I + 1]; ++k, ++e)
+                CHECK(JR.vunpad[k] == r * G.maxnnz + e && J.col[k] == R[r].Q.cols[e] && J.val[k] == R[r].vals[e], "%s: vunpad of entry %d of rank %d", what, e, r);
+        }
+    // the Galerkin product of the whole system's matrix with the composed aggregates, map of maps, rows and columns in ascending place
+    struct Sum { double v, abs; int terms; bool cross; };
+    std::vector<std::map<int, Sum>> prod(NG);
+    std::vector<int> cellAt(N);
+    for (int i = 0; i < N; ++i) cellAt[place(i)] = i;
+    for (int p = 0; p < N; ++p) {
+        const int i = cellAt[p];
+        std::vector<std::pair<int, int>> ent;
+        for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) ent.push_back({place(A.col[k]), k});
+        std::sort(ent.begin(), ent.end());
+        for (const auto& en : ent) {
+            const int j = A.col[en.second];
+            const double a = A.val[en.second];
+            auto it = prod[joined(i)].find(joined(j));
+            if (it == prod[joined(i)].end()) prod[joined(i)][joined(j)] = Sum{0.0 + a, std::fabs(a), 1, w.owner[i] != w.owner[j]};
+            else { it->second.v += a; it->second.abs += std::fabs(a); ++it->second.terms; }
+        }
+    }
+    int nCross = 0;
+    for (int I = 0; I < NG; ++I) {
+        CHECK(J.rowptr[I + 1] - J.rowptr[I] == (int)prod[I].size(), "%s: row %d of the joined matrix has %d entries, the product %zu", what, I, J.rowptr[I + 1] - J.rowptr[I], prod[I].size());
+        int k = J.rowptr[I];
+        for (const auto& en : prod[I]) {
+            CHECK(J.col[k] == en.first, "%s: row %d of the joined matrix: column %d, the product's %d", what, I, J.col[k], en.first);
+            const Sum& s = en.second;
+            // between two ranks: the same additions in the same order, bit for bit.  Inside a rank the entry is the last level's, a sum of
+            // the partial sums of every level in between: equal up to the rounding of `terms` additions of numbers summing to `abs` in size
+            if (s.cross) { CHECK(J.val[k] == s.v, "%s: joined entry (%d, %d): %.17g, the product in the stated order %.17g", what, I, en.first, J.val[k], s.v); ++nCross; }
+            else CHECK(std::fabs(J.val[k] - s.v) <= s.terms * 2.220446049250313e-16 * s.abs, "%s: joined entry (%d, %d): %.17g, the product %.17g", what, I, en.first, J.val[k], s.v);
+            ++k;
+        }
+    }
+    std::printf("ok  joined level of %-44s ranks %d, transfers %d..%d, rows %d, entries %zu (%d between ranks, longest sum %d), ghost couplings %d: pattern and values are the whole system's Galerkin product\n",
+                what, nr, levelsMin, levelsMax, NG, J.col.size(), nCross, longest, nqAll);
+    ++lines;
+    return true;
+}
+// cpr_join_rows on buffers a peer has spoiled: refused with the rank named, no index followed out of its slice
+static bool refuses(const char* what, const Gathered& G, int rank, int& lines) {
+    opmhip::CprJoined JR;
+    opmhip::cpr_join_rows(G.bl, G.bc, G.bv, G.nnzs, G.offs, G.maxn, G.maxnnz, JR);
+    const std::string want = "cpr: the joined level's rows of rank " + std::to_string(rank) + " are inconsistent";
+    CHECK(JR.error == want, "%s: \"%s\", not \"%s\"", what, JR.error.c_str(), want.c_str());
+    std::printf("ok  refused: %s (rank %d)\n", what, rank);
+    ++lines;
+    return true;
+}
+
 int main() {
     std::vector<Case> cases;
     for (int s : {1, 2, 3, 5, 8, 13}) cases.push_back({"grid " + std::to_string(s) + "^3", grid7(s, s, s, true, 10u + s), {}, {}});
@@ -437,6 +700,55 @@ int main() {
                     run(cs, ilu, lpr, stop, lines);
                 }
     std::printf("%d of %d set-ups checked\n", lines, runs);
-    if (g_fail == 0 && lines == runs) std::printf("all checks passed\n");
-    return g_fail == 0 && lines == runs ? 0 : 1;
+    // the joined level: the smallest worlds that reach every branch
+    std::vector<World> worlds;
+    worlds.push_back(box_world("6x4x3 cut in two along x", 6, 4, 3, {3}, {}, 21u, 8));
+    worlds.push_back(box_world("8x4x3 cut at x = 5", 8, 4, 3, {5}, {}, 22u, 8));                 // uneven slices: both paddings are real
+    worlds.push_back(box_world("8x4x3 cut at x = 3", 8, 4, 3, {3}, {}, 22u, 8));                 // the last rank has the largest slice
+    worlds.push_back(box_world("8x8x4 in 2 x 2 ranks", 8, 8, 4, {4}, {4}, 23u, 8));              // two neighbours per rank, shared joined entries
+    worlds.back().wantShared = true;
+    worlds.push_back(worlds.back());
+    worlds.back().name = "8x8x4 in 2 x 2 ranks, last rank reversed";
+    worlds.back().reversedLast = true;
+    worlds.push_back(two_slabs("two slabs without a coupling", 24u));
+    worlds.push_back(box_world("6x4x3, stopRows above the subdomains", 6, 4, 3, {3}, {}, 25u, 1000));
+    worlds.back().wantLevels = 0;
+    worlds.push_back(box_world("8x8x4 in 2 x 2 ranks, stopRows 4", 8, 8, 4, {4}, {4}, 26u, 4));
+    worlds.back().wantLevels = 2;
+    int wlines = 0, rlines = 0;
+    Gathered uneven, mirrored;
+    for (const World& w : worlds) {
+        Gathered G;
+        run_world(w, G, wlines);
+        if (w.name == "8x4x3 cut at x = 5") uneven = G;
+        if (w.name == "8x4x3 cut at x = 3") mirrored = G;
+    }
+    std::printf("%d of %zu joined levels checked\n", wlines, worlds.size());
+    const int nrefusals = 6;
+    if (uneven.nnzs.size() == 2 && uneven.nnzs[0] != uneven.nnzs[1] && mirrored.nnzs.size() == 2 && mirrored.nnzs[1] == mirrored.maxnnz) {
+        const int big = uneven.nnzs[0] > uneven.nnzs[1] ? 0 : 1, small = 1 - big;   // big fills its slice: behind rank 1's lies the end of the buffer
+        const int lastRow = mirrored.offs[2] - mirrored.offs[1] - 1;
+        Gathered G = uneven;
+        G.bc[(size_t)small * G.maxnnz + 1] = G.offs[2];
+        refuses("a column >= NG", G, small, rlines);
+        G = uneven;
+        G.bc[(size_t)big * G.maxnnz] = -1;
+        refuses("a negative column", G, big, rlines);
+        G = uneven;
+        G.bl[(size_t)small * G.maxn] += 1;   // (still inside the padded slice: only nnzs tells)
+        refuses("a row length running past nnzs[r]", G, small, rlines);
+        G = mirrored;
+        G.bl[(size_t)1 * G.maxn + lastRow] += G.maxnnz;   // the last row of the last rank, which fills its slice: followed, it leaves the gathered buffer
+        refuses("a row length running past maxnnz", G, 1, rlines);
+        G = uneven;
+        G.bl[(size_t)big * G.maxn] = -1;
+        refuses("a negative row length", G, big, rlines);
+        G = uneven;
+        G.nnzs[small] = G.maxnnz + 1;
+        refuses("more entries than the slice holds", G, small, rlines);
+    }
+    std::printf("%d of %d spoiled buffers refused\n", rlines, nrefusals);
+    const bool all = g_fail == 0 && lines == runs && wlines == (int)worlds.size() && rlines == nrefusals;
+    if (all) std::printf("all checks passed\n");
+    return all ? 0 : 1;
 }

@@ -4,7 +4,7 @@ decomposed subdomains with ghost columns, irregular patterns with rows of up to 
 (tests/san/host_logic_san.cpp, which also checks the invariants every ordering must keep).  No GPU: the harness serves the three HIP
 runtime calls of reorder.cpp from the host heap.  The GPU sanitizers are not available on the pool; this is the CPU build the brief asks
 to run them on.  The CPR pressure-AMG set-up (csrc/cpr_setup.cpp) is built the same way, linked alone (tests/san/cpr_setup_san.cpp: level
-invariants on every hierarchy, the oracle's hierarchy alongside).  So is the host set-up of the resident standard wells and analytic
+invariants on every hierarchy, the oracle's hierarchy alongside; the joined level of decomposed runs on small worlds of ranks).  So is the host set-up of the resident standard wells and analytic
 aquifers (csrc/source_lists.cpp, linked alone; tests/san/source_lists_san.cpp: the grouping by distinct cell against a quadratic restatement,
 every refusal with its code and its text, the aquifers' tables, step scalars and sums).  So is the check of scaled saturation end
 points that opmhip_set_endpoint_scaling and opmhip_set_hysteresis share (end_points_refusal in csrc/fluid_tables.cpp, linked alone;
@@ -56,6 +56,12 @@ def test_cpr_setup_under_asan_ubsan(tmp_path):
     assert out.count("; oracle agrees: levels, n, nc, agg, coarsest matrix\n") == 104   # every set-up of the list, each against the oracle
     for stop in ("rows", "stall", "width"):   # every rule that ends a hierarchy was met
         assert "(last: %s)" % stop in out
+    # the joined level of a decomposed run (cpr_joined_aggregates / _rows / _values, cpr_join_rows): eight worlds of two and four ranks, each
+    # against the whole system's Galerkin product; six spoiled buffers, each refused with its rank named
+    assert out.count(": pattern and values are the whole system's Galerkin product\n") == 8 and "8 of 8 joined levels checked" in out
+    assert out.count("\nok  refused: ") == 6 and "6 of 6 spoiled buffers refused" in out
+    for world in ("transfers 0..0", "transfers 3..3", "ghost couplings 0:"):   # level 0 joined, several transfers composed, no coupling at all
+        assert world in out
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
