@@ -6,55 +6,14 @@ heads from stored injecting rates, the refusals and the launch counts."""
 import numpy as np
 import pytest
 
-import helpers
+import std_wells_harness as H
+from std_wells_harness import make_case, moved, same_state
 from test_std_wells_crossflow import make_wells, median_bhp
 
 pytestmark = pytest.mark.gpu
 
 DAY = 86400.0
 INJECTED_DURING_THE_RUN = False     # test c: no perforation injected during the SPE9-shaped report step (see its docstring)
-
-
-def make_case(pkg, ext):
-    """ext: a fluid with pc_scaling - the extended (19-field) intensive-quantity record"""
-    if ext:
-        return helpers.hysteresis_case(pkg, 2, 2, 150, heterogeneous=True, dz=1.0)
-    return pkg.decks.cartesian_case(2, 2, 150, state="mixed", heterogeneous=True, dz=1.0)
-
-
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
-
-
-def pair(pkg, case, crossflow=True, head_model="cell_oil", model_kw=None):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state"""
-    out = []
-    props = pkg.capi.HipFluid(case["fluid"]) if head_model == "wellbore" else None
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        wl = make_wells(pkg, case, crossflow)
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(wl, case["depth"], m, head_model=head_model)
-        else:
-            w = pkg.wells.StandardWells(wl, case["depth"], arithmetic="stated", head_model=head_model, props=props)
-        out.append((m, w))
-    return out
-
-
-def begin(md, wd, mh, wh, iteration):
-    """beginIteration on both sides; -> the host's records"""
-    iq = wh.records(mh)
-    if iteration == 0:
-        wh.calculate_explicit_quantities(iq)
-        wh.solve_well_equations(iq)
-    wh.update_well_controls()
-    wd.begin_iteration(iteration)
-    return iq
 
 
 def force_reversal(md, mh, wh, iq):
@@ -66,37 +25,18 @@ def force_reversal(md, mh, wh, iq):
     return x0
 
 
-def host_assemble(mh, wh, iq):
-    wa = wh.assemble(iq)
-    mh.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
-
-
-def compare_wells(md, wa, wh, iq, what):
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    r, D, B, C, src, dsrc = wh._assemble_wells(iq)                       # (the same state: the same bits as inside assemble)
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), D=D, Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), rates=wh._perf_rates(iq, wh.x[:, 3]), dq=wh.rate_dq, ctl=[int(w.control[0] == "bhp") for w in wh.wells])
-    got = dict(x=x, head=blk["head"], rw=rw, D=blk["D"], Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], rates=blk["rates"], dq=md.std_wells_rate_dq(), ctl=list(ctl))
-    assert np.array_equal(want["rw"], r) and np.array_equal(want["C"], C)
-    for k in want:
-        assert np.array_equal(got[k], want[k]), (what, k, np.abs(np.asarray(got[k], float) - np.asarray(want[k], float)).max())
-    assert all(np.all(np.isfinite(np.asarray(v, float))) for v in got.values())
-    return got
-
-
-def same_state(a, b):
-    (pa, ma), (pb, mb) = a.get_state(), b.get_state()
-    return np.array_equal(ma, mb) and np.array_equal(pa, pb)
+def assembles_what_assemble_wells_forms(wh, wa, iq):
+    """on the host alone: assemble's r_w and C are _assemble_wells' (the same state: the same bits as inside assemble), from which the
+    comparison forms D and the rates once more"""
+    r, _, _, C, _, _ = wh._assemble_wells(iq)
+    assert np.array_equal(wa["res_well"].reshape(-1, 4), r) and np.array_equal(wa["wells"]["Cnnzs"].reshape(len(wh.cells), 4, 3), C)
 
 
 # ---- a. one assembly -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ext", [False, True])
 def test_one_assembly(pkg, ext):
     case = make_case(pkg, ext)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case), head_model="cell_oil", props="wellbore")
     assert md.iq().shape[1] == (19 if ext else 17) and list(np.diff(wh.vp)) == [150, 64, 65, 1]
     assert [bool(f) for f in wh.allow_crossflow] == [True, False, True, True]
     dt = 5.0 * DAY
@@ -104,14 +44,15 @@ def test_one_assembly(pkg, ext):
         if state is not None:
             for m in (md, mh):
                 m.set_state(state, case["meaning"])
-        iq = begin(md, wd, mh, wh, it)
+        iq = H.begin(wd, mh, wh, it)
         if it == 0:
             assert np.array_equal(md.get_std_wells()[0], wh.x) and np.all(wh.x[[0, 2, 3], :3] < 0.0)      # the wells alone, crossflow inside their loop
             force_reversal(md, mh, wh, iq)
-        wa = host_assemble(mh, wh, iq)
+        wa = H.host_assemble(mh, wh, iq)
         jh, rh = mh.assemble(dt, it)
         jd, rd = md.assemble(dt, it)
-        got = compare_wells(md, wa, wh, iq, it)
+        assembles_what_assemble_wells_forms(wh, wa, iq)
+        got = H.compare_wells(pkg, md, wh, wa, it, extra=("D", "rates", "dq"), iq=iq, all_finite=True)
         assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it              # the reservoir's J and r equal the host path's
         injecting = (got["rates"][:150, :, 0] > 0.0).any(axis=1)
         assert 10 <= injecting.sum() <= 140, (it, injecting.sum())
@@ -125,11 +66,11 @@ def test_operator_and_update(pkg):
     """(wells that share no cell: where two wells meet in a cell the existing operator kernels add their two contributions atomically,
     in either order - with a host list as with the resident one)"""
     case = make_case(pkg, False)
-    (md, wd), (mh, wh) = pair(pkg, case, model_kw=dict(tolerance=1e-4))
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case), head_model="cell_oil", props="wellbore", model_kw=dict(tolerance=1e-4))
     dt = 5.0 * DAY
-    iq = begin(md, wd, mh, wh, 0)
+    iq = H.begin(wd, mh, wh, 0)
     force_reversal(md, mh, wh, iq)
-    wa = host_assemble(mh, wh, iq)
+    wa = H.host_assemble(mh, wh, iq)
     mh.assemble(dt, 0, fetch=False)
     md.assemble(dt, 0, fetch=False)
     assert np.any(wa["wells"]["Cnnzs"].reshape(-1, 4, 3)[:, :3, :] != 0.0)
@@ -197,10 +138,10 @@ def test_spe9_shaped_first_report_step(pkg):
 def test_wellbore_heads_from_stored_injecting_rates(pkg):
     """two time-step starts: the second forms the well-bore density from the rates the first assembly stored, injecting signs included"""
     case = make_case(pkg, False)
-    (md, wd), (mh, wh) = pair(pkg, case, head_model="wellbore")
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case), head_model="wellbore", props="wellbore")
     dt = 5.0 * DAY
     for start in (0, 1):
-        iq = begin(md, wd, mh, wh, 0)
+        iq = H.begin(wd, mh, wh, 0)
         wb, blk = md.std_wells_wellbore(), md.std_wells_blocks()
         for k in ("density", "p_avg", "mixture"):
             assert np.array_equal(wb[k], wh.wellbore[k]), (start, k)
@@ -208,10 +149,11 @@ def test_wellbore_heads_from_stored_injecting_rates(pkg):
         if start == 0:
             force_reversal(md, mh, wh, iq)
             heads0 = wh.head.copy()
-        wa = host_assemble(mh, wh, iq)
+        wa = H.host_assemble(mh, wh, iq)
         mh.assemble(dt, 0, fetch=False)
         md.assemble(dt, 0, fetch=False)
-        compare_wells(md, wa, wh, iq, start)
+        assembles_what_assemble_wells_forms(wh, wa, iq)
+        H.compare_wells(pkg, md, wh, wa, start, extra=("D", "rates", "dq"), iq=iq, all_finite=True)
         wb = md.std_wells_wellbore()
         assert np.array_equal(wb["perf_rates"], wh.perf_rates) and np.array_equal(wb["perf_pressure"], wh.perf_pressure), start
         if start == 0:
@@ -233,8 +175,8 @@ def test_refusals_and_the_previous_flags(pkg):
     m.set_state(case["pv"], case["meaning"])
     rc, msg = raw(m, [1, 0, 1, 1])
     assert rc == C.NOT_READY and "no resident list" in msg                  # before a list
-    (md, wd), (mh, wh) = pair(pkg, case)
-    iq = begin(md, wd, mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case), head_model="cell_oil", props="wellbore")
+    iq = H.begin(wd, mh, wh, 0)
     force_reversal(md, mh, wh, iq)
     md.assemble(DAY, 0, fetch=False)
     dq0, blk0 = md.std_wells_rate_dq(), md.std_wells_blocks()
@@ -291,7 +233,7 @@ def test_flags_off_launch_and_compute_what_they_did(pkg):
         wd.update(1.0)
         m.update(None, 1.0)
         m.synchronize()
-        seen.append(dict(counts={k: v[0] for k, v in m.profile().items()}, j=j, r=r, blk=blk, it=res.it, x=m.get_std_wells()[0], state=m.get_state()[0]))
+        seen.append(dict(counts=H.launch_counts(m), j=j, r=r, blk=blk, it=res.it, x=m.get_std_wells()[0], state=m.get_state()[0]))
     never, zeros, on = seen
     assert never["counts"] == zeros["counts"] and never["counts"]["assemble"] >= 5
     assert np.array_equal(never["j"], zeros["j"]) and np.array_equal(never["r"], zeros["r"]) and never["it"] == zeros["it"]

@@ -10,22 +10,13 @@ import uuid
 import numpy as np
 import pytest
 
-import helpers
+import std_wells_harness as H
+from std_wells_harness import make_case, moved, same_state
 
 pytestmark = pytest.mark.gpu
 
 DAY = 86400.0
-
-
-def make_case(pkg, ext):
-    """ext: a fluid with pc_scaling - the extended (19-field) intensive-quantity record"""
-    if ext:
-        return helpers.hysteresis_case(pkg, 2, 2, 150, heterogeneous=True, dz=1.0)
-    return pkg.decks.cartesian_case(2, 2, 150, state="mixed", heterogeneous=True, dz=1.0)
-
-
-def column(i, j, ks):
-    return [i + 2 * (j + 2 * k) for k in ks]
+column = H.column(2, 2)
 
 
 def make_wells(pkg, case, shared=True, bad=False):
@@ -45,61 +36,11 @@ def make_wells(pkg, case, shared=True, bad=False):
     return out
 
 
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
-
-
-def pair(pkg, case, wells_kw=None, model_kw=None):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state"""
-    out = []
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        wl = make_wells(pkg, case, **(wells_kw or {}))
-        w = pkg.wells.DeviceStandardWells(wl, case["depth"], m) if form == "device" else pkg.wells.StandardWells(wl, case["depth"], arithmetic="stated")
-        out.append((m, w))
-    return out
-
-
-def host_begin_and_assemble(m, w, iteration):
-    """newton.py's host branch: records down, the wells, rates up -> the assembled dict"""
-    iq = w.records(m)
-    if iteration == 0:
-        w.calculate_explicit_quantities(iq)
-        w.solve_well_equations(iq)
-    w.update_well_controls()
-    wa = w.assemble(iq)
-    m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
-
-
-def compare_wells(md, wa, wh, what):
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), ctl=[int(w.control[0] == "bhp") for w in wh.wells])
-    got = dict(x=x, head=blk["head"], rw=rw, Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], ctl=list(ctl))
-    for k in want:
-        assert np.array_equal(got[k], want[k]), (what, k, np.abs(np.asarray(got[k], float) - np.asarray(want[k], float)).max())
-    assert np.all(np.isfinite(blk["Dinv"])) and np.all(np.isfinite(x))
-    return x, blk
-
-
-def same_state(a, b):
-    (pa, ma), (pb, mb) = a.get_state(), b.get_state()
-    return np.array_equal(ma, mb) and np.array_equal(pa, pb)
-
-
 # ---- 1. one assembly ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ext", [False, True])
 def test_one_assembly(pkg, ext):
     case = make_case(pkg, ext)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case))
     assert md.iq().shape[1] == (19 if ext else 17)
     assert list(np.diff(wh.vp)) == [150, 64, 65, 1, 3, 2] and len(wh.ucells) == len(wh.cells) - 1
     dt = 5.0 * DAY
@@ -107,11 +48,12 @@ def test_one_assembly(pkg, ext):
         if state is not None:
             for m in (md, mh):
                 m.set_state(state, case["meaning"])
-        wa = host_begin_and_assemble(mh, wh, it)
+        wa = H.host_begin_and_assemble(mh, wh, it)
         jh, rh = mh.assemble(dt, it)
         wd.begin_iteration(it)
         jd, rd = md.assemble(dt, it)
-        x, blk = compare_wells(md, wa, wh, it)
+        blk = H.compare_wells(pkg, md, wh, wa, it)
+        x = blk["x"]
         assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it              # the reservoir's J and r equal the host path's
         assert np.all(x[:, 3] > 100e5) and np.all(blk["head"][wh.vp[0] + 1:wh.vp[1]] > 0.0)
         assert np.count_nonzero(blk["rates"][:, :, 0]) > 50 and np.all(blk["B"][:, 3, :] == 0.0) and np.all(blk["C"][:, :3, :] == 0.0)
@@ -128,14 +70,10 @@ def test_one_assembly(pkg, ext):
 # ---- 2. closed completions, the guard ----------------------------------------------------------------------------------------------------------
 def test_closed_completions_and_a_well_without_a_flowing_completion(pkg):
     case = make_case(pkg, False)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case))
     for m in (md, mh):
         m.set_state(moved(case, 11), case["meaning"])
-    iq = wh.records(mh)
-    wh.calculate_explicit_quantities(iq)
-    wh.solve_well_equations(iq)
-    wh.update_well_controls()
-    wd.begin_iteration(0)
+    iq = H.begin(wd, mh, wh, 0)
     x0 = wh.x.copy()
     po = wh.records(mh).rows(wh.cells)[:, 4, 0]
     inflow = (po - wh.head)[:150]
@@ -143,11 +81,10 @@ def test_closed_completions_and_a_well_without_a_flowing_completion(pkg):
     x0[3, 3] = po[wh.vp[3]] + 50e5                     # the one-completion producer: nothing flows, the guard keeps its equations regular
     wh.x = x0.copy()
     md.set_std_wells_state(x=x0)
-    wa = wh.assemble(iq)
-    mh.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
+    wa = H.host_assemble(mh, wh, iq)
     jh, rh = mh.assemble(DAY, 0)
     jd, rd = md.assemble(DAY, 0)
-    x, blk = compare_wells(md, wa, wh, "closed")       # get_std_wells inside: no flag is reported
+    blk = H.compare_wells(pkg, md, wh, wa, "closed")   # get_std_wells inside: no flag is reported
     assert np.array_equal(jd, jh) and np.array_equal(rd, rh)
     flowing = np.any(blk["rates"][:150, :, 0] != 0.0, axis=1)
     assert 10 < flowing.sum() < 140 and np.array_equal(flowing, inflow - x0[0, 3] > 0.0)
@@ -192,9 +129,9 @@ def test_operator_and_update(pkg):
     """(the four wells that share no cell: where two wells meet in a cell the existing operator kernels add their two contributions
     atomically, in either order - with a host list as with the resident one)"""
     case = make_case(pkg, False)
-    (md, wd), (mh, wh) = pair(pkg, case, wells_kw=dict(shared=False), model_kw=dict(tolerance=1e-4))
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case, shared=False), model_kw=dict(tolerance=1e-4))
     dt = 5.0 * DAY
-    wa = host_begin_and_assemble(mh, wh, 0)
+    wa = H.host_begin_and_assemble(mh, wh, 0)
     mh.assemble(dt, 0, fetch=False)
     wd.begin_iteration(0)
     md.assemble(dt, 0, fetch=False)
@@ -341,12 +278,7 @@ def test_aquifer_and_well_in_one_cell(pkg):
         if state is not None:
             for m in (md, mh):
                 m.set_state(state, case["meaning"])
-        iq = wh.records(mh)
-        if it == 0:
-            wh.calculate_explicit_quantities(iq)
-            wh.solve_well_equations(iq)
-        wh.update_well_controls()
-        wa = wh.assemble(iq)
+        wa = wh.assemble(H.host_begin(mh, wh, it))
         cells = np.concatenate([wa["cells"], [7]])                        # the host order: the wells' rates, then the aquifers' influx
         ha.add_to_source(mh, cells, np.vstack([wa["source_cells"].reshape(-1, 3), src[7:8]]), np.vstack([wa["dsource_cells"].reshape(-1, 9), np.zeros((1, 9))]))
         jh, rh = mh.assemble(dt, it)
@@ -459,7 +391,7 @@ def test_no_list_no_launch(pkg):
         res = m.solve_jacobian_system()
         m.update(None, 1.0)
         m.synchronize()
-        counts.append(({k: v[0] for k, v in m.profile().items()}, res.it, m.get_state()[0]))
+        counts.append((H.launch_counts(m), res.it, m.get_state()[0]))
     (a, ita, sa), (b, itb, sb) = counts
     assert a == b and ita == itb and np.array_equal(sa, sb) and a["assemble"] >= 1 and a["spmv"] >= 1
     # ... and the counts do show the new launches: with a list set the same calls book the wells alone, the controls, the equations

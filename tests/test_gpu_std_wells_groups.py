@@ -10,88 +10,24 @@ import pytest
 
 import groups_cases as GC
 import limits_cases as LC
+import std_wells_harness as H
 import thp_cases
+from std_wells_harness import moved
 
 pytestmark = pytest.mark.gpu
 DAY = 86400.0
 
 
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
+def constructor_kw(case, groups, nupcol=3, vfp=None, matrix_add=False):
+    """the constructors' keywords of this file: the tables (None: none), the groups and NUPCOL to both sides, the switch to the device's, the
+    device's property functions and the case's PVT regions (None: one) to the host's"""
+    return dict(vfp=vfp, groups=groups, nupcol=nupcol, matrix_add=matrix_add, props="always", pvtnum=case.get("pvtnum"))
 
 
-def pair(pkg, case, make, groups, nupcol=3, vfp=None, matrix_add=False):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state; make(): a fresh list of Well objects;
-    groups(): a fresh list of Group objects"""
-    props = pkg.capi.HipFluid(case["fluid"])
-    out = []
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case)
-        m.set_state(case["pv"], case["meaning"])
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(make(), case["depth"], m, vfp=vfp, groups=groups(), nupcol=nupcol, matrix_add=matrix_add)
-        else:
-            w = pkg.wells.StandardWells(make(), case["depth"], arithmetic="stated", props=props, vfp=vfp, pvtnum=case.get("pvtnum"), groups=groups(), nupcol=nupcol)
-        out.append((m, w))
-    return out
-
-
-def host_begin_and_assemble(m, w, iteration):
-    iq = w.records(m)
-    if iteration == 0:
-        w.calculate_explicit_quantities(iq)
-        w.solve_well_equations(iq)
-    w.update_well_controls(iteration)
-    wa = w.assemble(iq)
-    m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
-
-
-def compare_groups(md, wh, what):
-    got, want = md.std_wells_groups(), wh.group_rates()
-    for k in ("mode", "rates", "voidage", "reduction", "guide_sum"):
-        assert np.array_equal(got[k], want[k]), (what, k, got[k], want[k])
-    assert np.array_equal(got["nupcol_rates"], wh.nupcol_rates), (what, "nupcol_rates")
-
-
-def compare_wells(pkg, md, wa, wh, what, mh):
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    D = wh._assemble_wells(wh.records(mh))[1]
-    rates = wh._perf_rates(wh.records(mh), wh.x[:, 3])
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), ctl=[pkg.wells.control_code(w.control) for w in wh.wells], D=D, rates=rates)
-    got = dict(x=x, head=blk["head"], rw=rw, Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], ctl=list(ctl), D=blk["D"], rates=blk["rates"])
-    for k in want:
-        assert np.array_equal(got[k], want[k]), (what, k, np.abs(np.asarray(got[k], float) - np.asarray(want[k], float)).max())
-    compare_groups(md, wh, what)
-    r = md.std_wells_resv()
-    assert np.array_equal(r["coeff"], wh.resv_coeff), (what, "coeff")
-    if wh.has_resv:
-        assert np.array_equal(r["averages"], wh.resv_averages), what
-    assert np.all(np.isfinite(blk["Dinv"])) and np.all(np.isfinite(x))
-    return x, blk
-
-
-def lockstep(pkg, case, make, groups, states, dt=5.0 * DAY, **kw):
-    """iteration 0 at the case's state, then one more iteration per further state: the wells, the groups and the reservoir's J, r equal on
-    both sides"""
-    (md, wd), (mh, wh) = pair(pkg, case, make, groups, **kw)
-    for it, state in enumerate([None] + list(states)):
-        if state is not None:
-            for m in (md, mh):
-                m.set_state(state, case["meaning"])
-        wa = host_begin_and_assemble(mh, wh, it)
-        jh, rh = mh.assemble(dt, it)
-        wd.begin_iteration(it)
-        jd, rd = md.assemble(dt, it)
-        x, blk = compare_wells(pkg, md, wa, wh, it, mh)
-        assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it
+def lockstep(pkg, case, make, groups, states, **kw):
+    """the harness's, with the controls told the iteration and the groups compared -> the two pairs, the device's arrays of the last
+    comparison; then what is this file's own: the controls and the convergence check of both sides"""
+    (md, wd), (mh, wh), wa, blk = H.lockstep(pkg, case, make, states, extra=("D", "rates", "groups", "resv"), pass_iteration=True, **constructor_kw(case, groups, **kw))
     wd.fetch()
     assert [w.control for w in wd.wells] == [w.control for w in wh.wells]
     # getWellConvergence decides alike on both sides: the read-back carries the groups' modes in force, which tell a GRUP well's rate row
@@ -99,7 +35,7 @@ def lockstep(pkg, case, make, groups, states, dt=5.0 * DAY, **kw):
     assert wd.group_mode == wh.group_mode and any(wh.group_mode)
     for tol_rate, tol_bhp in ((1e-7, 1.0), (1e30, 0.0), (1e30, 1.0)):
         assert wd.converged(tol_rate=tol_rate, tol_bhp=tol_bhp) == wh.converged(wa["res_well"], tol_rate=tol_rate, tol_bhp=tol_bhp), (tol_rate, tol_bhp)
-    return (md, wd), (mh, wh), x, blk
+    return (md, wd), (mh, wh), blk
 
 
 # ---- 1. the SPE9-shaped list in three groups ---------------------------------------------------------------------------------------------------
@@ -111,7 +47,7 @@ def spe9(pkg):
 
 def test_spe9_shaped_list_in_three_groups(pkg):
     case, make, groups = spe9(pkg)
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, groups, [moved(case, 3)])
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, make, groups, [moved(case, 3)])
     modes = wh.group_mode
     print("group modes", modes, "controls", [w.control[0] for w in wh.wells])
     assert sorted(modes) == [1, 4, 5]                       # ORAT, LRAT and RESV: the three groups left NONE for different modes
@@ -131,7 +67,7 @@ def seventy(pkg):
 
 def test_seventy_producers_in_five_groups(pkg):
     case, make, groups = seventy(pkg)
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, groups, [moved(case, 5, 1e5)])
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, make, groups, [moved(case, 5, 1e5)])
     assert wh.nw == 70 and all(min(g) < 63 and max(g) > 64 for g in wh.group_wells)
     late = [k for k in range(64, 70) if wh.wells[k].control == ("grup",)]
     print("wells 64 .. 69 under GRUP", late, "modes", wh.group_mode)
@@ -153,7 +89,7 @@ def test_groups_beside_thp_lrat_and_crossflow(pkg):
         p2.group, p2.guide_rate = 0, np.full(5, 1.0)
         return [p, i, p2]
     groups = lambda: [pkg.wells.Group("G", {"resv": 1.5 / DAY, "orat": 1e9})]
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, groups, [moved(case, 3), moved(case, 4, 4e5)], vfp=tabs)
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, make, groups, [moved(case, 3), moved(case, 4, 4e5)], vfp=tabs)
     print("controls", [w.control[0] for w in wh.wells], "mode", wh.group_mode)
     t = md.std_wells_thp()
     assert np.array_equal(t["thp"], wh.thp_current) and np.array_equal(t["dp"], wh.thp_dp) and np.array_equal(t["bhp_from_thp"], wh.bhp_from_thp)
@@ -172,7 +108,7 @@ def test_groups_with_the_matrix_add_form(pkg):
             w.group, w.guide_rate = n % 2, np.full(5, 1.0 + n)
         return wells
     groups = lambda: [pkg.wells.Group("GA", {"orat": 2.5 / DAY}), pkg.wells.Group("GB", {"lrat": 1.0 / DAY})]
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, groups, [moved(case, 7, 1e5)], matrix_add=True)
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, make, groups, [moved(case, 7, 1e5)], matrix_add=True)
     assert any(w.control == ("grup",) for w in wh.wells)
     md.std_wells_apply_residual()
     md.std_wells_add_to_matrix()
@@ -184,7 +120,7 @@ def test_groups_with_the_matrix_add_form(pkg):
 # ---- 4. a time step given up ---------------------------------------------------------------------------------------------------------------------
 def test_a_given_up_time_step_restores_the_groups(pkg):
     case, make, groups = spe9(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case, make, groups, nupcol=2)
+    (md, wd), (mh, wh) = H.pair(pkg, case, make, **constructor_kw(case, groups, nupcol=2))
     dt = 2.0 * DAY
 
     def change(seed, dp):
@@ -200,13 +136,13 @@ def test_a_given_up_time_step_restores_the_groups(pkg):
             if dx is not None:
                 for m in (md, mh):
                     m.update(dx)
-            wa = host_begin_and_assemble(mh, wh, it)
+            wa = H.host_begin_and_assemble(mh, wh, it, pass_iteration=True)
             mh.assemble(dt, it, fetch=False)
             wd.begin_iteration(it)
             md.assemble(dt, it, fetch=False)
-            x, blk = compare_wells(pkg, md, wa, wh, (what, it), mh)
+            blk = H.compare_wells(pkg, md, wh, wa, (what, it), extra=("D", "rates", "groups", "resv"), mh=mh)
             if it == 0:
-                first = (x.copy(), blk["Dinv"].copy(), md.std_wells_groups())
+                first = (blk["x"].copy(), blk["Dinv"].copy(), md.std_wells_groups())
         return first
     for m in (md, mh):
         m.advance_time_level()

@@ -6,84 +6,24 @@ import numpy as np
 import pytest
 
 import limits_cases as LC
+import std_wells_harness as H
 import thp_cases
+from std_wells_harness import moved
 
 pytestmark = pytest.mark.gpu
 DAY = 86400.0
 
 
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
+def constructor_kw(case, head_model="cell_oil", vfp=None):
+    """the constructors' keywords of this file: the head model and the tables (None: none) to both sides, the device's property functions
+    and the case's PVT regions (None: one) to the host's"""
+    return dict(head_model=head_model, vfp=vfp, props="always", pvtnum=case.get("pvtnum"))
 
 
-def pair(pkg, case, make, head_model="cell_oil", vfp=None, model_kw=None):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state; make(): a fresh list of Well objects"""
-    props = pkg.capi.HipFluid(case["fluid"])
-    out = []
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(make(), case["depth"], m, head_model=head_model, vfp=vfp)
-        else:
-            w = pkg.wells.StandardWells(make(), case["depth"], arithmetic="stated", head_model=head_model, props=props, vfp=vfp, pvtnum=case.get("pvtnum"))
-        out.append((m, w))
-    return out
-
-
-def host_begin(m, w, iteration):
-    iq = w.records(m)
-    if iteration == 0:
-        w.calculate_explicit_quantities(iq)
-        w.solve_well_equations(iq)
-    w.update_well_controls()
-    return iq
-
-
-def host_begin_and_assemble(m, w, iteration):
-    iq = host_begin(m, w, iteration)
-    wa = w.assemble(iq)
-    m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
-
-
-def compare_wells(pkg, md, wa, wh, what, mh):
-    code = pkg.wells.CONTROL_CODE
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    D = wh._assemble_wells(wh.records(mh))[1]
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), ctl=[code[w.control[0]] for w in wh.wells], D=D)
-    got = dict(x=x, head=blk["head"], rw=rw, Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], ctl=list(ctl), D=blk["D"])
-    for k in want:
-        assert np.array_equal(got[k], want[k]), (what, k, np.abs(np.asarray(got[k], float) - np.asarray(want[k], float)).max())
-    r = md.std_wells_resv()
-    assert np.array_equal(r["coeff"], wh.resv_coeff) and np.array_equal(r["resv_current"], wh.resv_current), (what, r, wh.resv_coeff, wh.resv_current)
-    if wh.has_resv:
-        assert np.array_equal(r["averages"], wh.resv_averages), what
-    assert np.all(np.isfinite(blk["Dinv"])) and np.all(np.isfinite(x))
-    return x, blk
-
-
-def lockstep(pkg, case, make, states, dt=5.0 * DAY, **kw):
-    """iteration 0 at the case's state, then one more iteration per further state: the wells and the reservoir's J, r equal on both sides"""
-    (md, wd), (mh, wh) = pair(pkg, case, make, **kw)
-    for it, state in enumerate([None] + list(states)):
-        if state is not None:
-            for m in (md, mh):
-                m.set_state(state, case["meaning"])
-        wa = host_begin_and_assemble(mh, wh, it)
-        jh, rh = mh.assemble(dt, it)
-        wd.begin_iteration(it)
-        jd, rd = md.assemble(dt, it)
-        x, blk = compare_wells(pkg, md, wa, wh, it, mh)
-        assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it
-    return (md, wd), (mh, wh), x, blk
+def lockstep(pkg, case, make, states, **kw):
+    """the harness's, with this file's keywords and compared keys -> the two pairs, the device's arrays of the last comparison"""
+    (md, wd), (mh, wh), wa, blk = H.lockstep(pkg, case, make, states, extra=("D", "resv", "resv_current"), **constructor_kw(case, **kw))
+    return (md, wd), (mh, wh), blk
 
 
 # ---- 1. one producer per mode, an injector under RESV, a well of 65 completions ----------------------------------------------------------------
@@ -101,7 +41,7 @@ def per_mode_wells(pkg, case):
 def test_one_producer_per_mode_and_an_injector_under_resv(pkg):
     case = thp_cases.make_case(pkg)
     lockstep(pkg, case, lambda: per_mode_wells(pkg, case), [moved(case, 3), moved(case, 4, 0.5e5)])     # (against the moved reservoir some wells stop flowing: the guard's row)
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, lambda: per_mode_wells(pkg, case), [])
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, lambda: per_mode_wells(pkg, case), [])
     modes = [w.control[0] for w in wh.wells]
     assert modes == ["resv", "orat", "wrat", "grat", "lrat", "resv"] and [w.control for w in wd.wells] == [w.control for w in wh.wells]
     assert list(np.diff(wh.vp)) == [65, 3, 3, 3, 2, 3]
@@ -114,8 +54,8 @@ def test_one_producer_per_mode_and_an_injector_under_resv(pkg):
 
 def test_the_wells_alone_reach_their_limits_on_the_device(pkg):
     case = thp_cases.make_case(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case, lambda: per_mode_wells(pkg, case))
-    host_begin(mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: per_mode_wells(pkg, case), **constructor_kw(case))
+    H.host_begin(mh, wh, 0)
     wd.begin_iteration(0)
     x = wd.fetch()
     assert np.array_equal(x, wh.x)
@@ -153,7 +93,7 @@ def test_two_pvt_regions_the_first_perforation_in_the_second(pkg):
         return [LC.producer(pkg, case, ("resv", 3.0 / DAY), {"resv": 3.0 / DAY}, use_list_target=False, cells=thp_cases.column(1, 1, [31, 32, 33]), name="B", scale=1.0),
                 LC.producer(pkg, case, ("resv", 3.0 / DAY), {"resv": 3.0 / DAY}, use_list_target=False, cells=thp_cases.column(0, 1, [30, 31, 32]), name="A", scale=1.0),
                 LC.injector(pkg, case, ("resv", 55.0 / DAY), {"resv": 55.0 / DAY}, use_list_target=False)]
-    (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, [])
+    (md, wd), (mh, wh), blk = lockstep(pkg, case, make, [])
     assert list(case["pvtnum"][[w.cells[0] for w in wh.wells]]) == [1, 0, 0] and list(wh.pvt_of_well) == [1, 0, 0]
     c = md.std_wells_resv()["coeff"]
     assert c[0, 1] != c[1, 1] and c[0, 0] == c[1, 0]                                 # the second region's water, the same oil tables
@@ -169,7 +109,7 @@ def test_limits_beside_crossflow_and_a_thp_limit(pkg):
         i = LC.injector(pkg, case, None, {"resv": 70.0 / DAY}, thp_limit=thp_cases.INJ_LIMIT)
         return [p, i, LC.producer(pkg, case, None, {}, cells=thp_cases.column(1, 1, [30, 31]), name="P2", scale=1.0, own=("rate", pkg.wells.OIL, 2.0 / DAY))]
     for hm in ("cell_oil", "wellbore"):
-        (md, wd), (mh, wh), x, blk = lockstep(pkg, case, make, [moved(case, 3), moved(case, 4, 4e5)], vfp=tabs, head_model=hm)
+        (md, wd), (mh, wh), blk = lockstep(pkg, case, make, [moved(case, 3), moved(case, 4, 4e5)], vfp=tabs, head_model=hm)
         print(hm, "controls", [w.control[0] for w in wh.wells])
         t = md.std_wells_thp()
         assert np.array_equal(t["thp"], wh.thp_current) and np.array_equal(t["dp"], wh.thp_dp) and np.array_equal(t["bhp_from_thp"], wh.bhp_from_thp)
@@ -196,8 +136,8 @@ def test_of_two_violated_limits_the_earlier_wins(pkg, order, first, second):
         made = [LC.ordered_pair_well(pkg, case, order, first, second, in_force) for _ in range(2)]
         bhp = made[0][1]
         it = iter(made)
-        (md, wd), (mh, wh) = pair(pkg, case, lambda: [next(it)[0]], vfp=tabs)
-        host_begin(mh, wh, 0)
+        (md, wd), (mh, wh) = H.pair(pkg, case, lambda: [next(it)[0]], **constructor_kw(case, vfp=tabs))
+        H.host_begin(mh, wh, 0)
         wd.begin_iteration(0)                      # dp, the averages and the coefficients of this time step on both sides
         x = x_flow.copy()
         x[3] = bhp
@@ -283,7 +223,7 @@ def test_two_time_steps_with_a_given_up_one(pkg):
     """device and host in lock step over the wells' part of two time steps (begin_iteration(0), a second iteration after a reservoir change);
     the first attempt at step 2 is given up: opmhip_update_failed restores the controls and the retry forms the same averages"""
     case, make = spe9(pkg, True)
-    (md, wd), (mh, wh) = pair(pkg, case, make)
+    (md, wd), (mh, wh) = H.pair(pkg, case, make, **constructor_kw(case))
     dt = 2.0 * DAY
 
     def change(seed, dp):
@@ -299,11 +239,11 @@ def test_two_time_steps_with_a_given_up_one(pkg):
             if dx is not None:
                 for m in (md, mh):
                     m.update(dx)
-            wa = host_begin_and_assemble(mh, wh, it)
+            wa = H.host_begin_and_assemble(mh, wh, it)
             mh.assemble(dt, it, fetch=False)
             wd.begin_iteration(it)
             md.assemble(dt, it, fetch=False)
-            compare_wells(pkg, md, wa, wh, (what, it), mh)
+            H.compare_wells(pkg, md, wh, wa, (what, it), extra=("D", "resv", "resv_current"), mh=mh)
     for m in (md, mh):
         m.advance_time_level()
     both_iterations([None, change(1, 1e5)], "step 1")

@@ -7,6 +7,8 @@ injector; a producer with allow_crossflow and an LRAT limit (another instantiati
 import numpy as np
 import pytest
 
+from std_wells_harness import launch_counts, minus
+
 pytestmark = pytest.mark.gpu
 
 DAY = 86400.0
@@ -208,11 +210,7 @@ def test_a_short_schedule_in_both_forms(pkg, cases):
 # ---- 4. bookkeeping ------------------------------------------------------------------------------------------------------------------------------------
 def counts(m):
     m.synchronize()
-    return {k: v[0] for k, v in m.profile().items()}
-
-
-def minus(a, b):
-    return {k: a[k] - b[k] for k in a}
+    return launch_counts(m)
 
 
 def test_launch_counts(pkg, cases):

@@ -4,54 +4,14 @@ wells.StandardWells(arithmetic="stated", vfp=...) on the same HipModel state, bi
 import numpy as np
 import pytest
 
+import std_wells_harness as H
 import thp_cases
+from std_wells_harness import moved
 
 pytestmark = pytest.mark.gpu
 
 DAY = thp_cases.DAY
 CODE = {"rate": 0, "bhp": 1, "thp": 2}
-
-
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
-
-
-def pair(pkg, case, head_model="cell_oil", limits=True, model_kw=None):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state"""
-    tabs = thp_cases.tables(pkg)
-    props = pkg.capi.HipFluid(case["fluid"]) if head_model == "wellbore" else None
-    out = []
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        wl = thp_cases.make_wells(pkg, case, limits=limits)
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(wl, case["depth"], m, head_model=head_model, vfp=tabs)
-        else:
-            w = pkg.wells.StandardWells(wl, case["depth"], arithmetic="stated", head_model=head_model, props=props, vfp=tabs)
-        out.append((m, w))
-    return out
-
-
-def host_begin(m, w, iteration):
-    iq = w.records(m)
-    if iteration == 0:
-        w.calculate_explicit_quantities(iq)
-        w.solve_well_equations(iq)
-    w.update_well_controls()
-    return iq
-
-
-def host_begin_and_assemble(m, w, iteration):
-    """newton.py's host branch: records down, the wells, rates up -> the assembled dict"""
-    iq = host_begin(m, w, iteration)
-    wa = w.assemble(iq)
-    m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
 
 
 def force(wd, wh, controls, x=None):
@@ -63,30 +23,11 @@ def force(wd, wh, controls, x=None):
     wd.m.set_std_wells_state(x, [CODE[c] for c in controls], None)
 
 
-def compare_wells(md, wa, wh, what, mh=None):
-    """mh: the host model - then D itself is compared too (formed once more on the host: a pure function of the state)"""
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    D = wh._assemble_wells(wh.records(mh))[1] if mh is not None else None
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), ctl=[CODE[w.control[0]] for w in wh.wells])
-    got = dict(x=x, head=blk["head"], rw=rw, Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], ctl=list(ctl))
-    if D is not None:
-        want["D"], got["D"] = D, blk["D"]
-    for k in want:
-        assert np.array_equal(got[k], want[k]), (what, k, np.abs(np.asarray(got[k], float) - np.asarray(want[k], float)).max())
-    t = md.std_wells_thp()
-    assert np.array_equal(t["thp"], wh.thp_current) and np.array_equal(t["dp"], wh.thp_dp) and np.array_equal(t["bhp_from_thp"], wh.bhp_from_thp), what
-    assert np.all(np.isfinite(blk["Dinv"])) and np.all(np.isfinite(x))
-    return x, blk
-
-
 # ---- 1. one assembly and the wells alone under forced control 2 -------------------------------------------------------------------------------
 @pytest.mark.parametrize("ext", [False, True])
 def test_one_assembly_and_the_wells_alone_under_thp(pkg, ext):
     case = thp_cases.make_case(pkg, ext)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: thp_cases.make_wells(pkg, case), head_model="cell_oil", vfp=thp_cases.tables(pkg), props="wellbore")
     assert md.iq().shape[1] == (19 if ext else 17) and list(np.diff(wh.vp)) == [65, 3, 2]
     force(wd, wh, ["thp", "thp", "rate"])
     dt = 5.0 * DAY
@@ -94,11 +35,12 @@ def test_one_assembly_and_the_wells_alone_under_thp(pkg, ext):
         if state is not None:
             for m in (md, mh):
                 m.set_state(state, case["meaning"])
-        wa = host_begin_and_assemble(mh, wh, it)
+        wa = H.host_begin_and_assemble(mh, wh, it)
         jh, rh = mh.assemble(dt, it)
         wd.begin_iteration(it)
         jd, rd = md.assemble(dt, it)
-        x, blk = compare_wells(md, wa, wh, it, mh)
+        blk = H.compare_wells(pkg, md, wh, wa, it, extra=("D", "thp"), mh=mh)
+        x = blk["x"]
         assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it              # the reservoir's J and r equal the host path's
         assert [w.control[0] for w in wh.wells] == ["thp", "thp", "rate"]
         assert np.all(blk["D"][0, 3, [0, 2]] != 0.0) and blk["D"][1, 3, 1] != 0.0 and np.all(blk["D"][:2, 3, 3] == 1.0)
@@ -113,7 +55,7 @@ def test_one_assembly_and_the_wells_alone_under_thp(pkg, ext):
 # ---- 2. the switching table ----------------------------------------------------------------------------------------------------------------------
 def test_switching_table(pkg):
     case = thp_cases.make_case(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: thp_cases.make_wells(pkg, case), head_model="cell_oil", vfp=thp_cases.tables(pkg), props="wellbore")
     iq = wh.records(mh)
     wh.calculate_explicit_quantities(iq)
     wh.solve_well_equations(iq)
@@ -145,13 +87,13 @@ def test_dp_under_both_head_models(pkg):
     case = thp_cases.make_case(pkg)
     dps = {}
     for hm in ("cell_oil", "wellbore"):
-        (md, wd), (mh, wh) = pair(pkg, case, head_model=hm)
+        (md, wd), (mh, wh) = H.pair(pkg, case, lambda: thp_cases.make_wells(pkg, case), head_model=hm, vfp=thp_cases.tables(pkg), props="wellbore")
         for it in (0, 1):
-            wa = host_begin_and_assemble(mh, wh, it)
+            wa = H.host_begin_and_assemble(mh, wh, it)
             mh.assemble(DAY, it, fetch=False)
             wd.begin_iteration(it)
             md.assemble(DAY, it, fetch=False)
-            compare_wells(md, wa, wh, (hm, it), mh)
+            H.compare_wells(pkg, md, wh, wa, (hm, it), extra=("D", "thp"), mh=mh)
         assert [w.control[0] for w in wh.wells] == ["thp", "thp", "rate"]
         dps[hm] = md.std_wells_thp()["dp"]
         W = pkg.wells
@@ -181,7 +123,8 @@ def run_step(pkg, m, wells, length, dt0):
 def test_report_step_device_wells_against_host_wells(pkg):
     case = thp_cases.make_case(pkg)
     runs = []
-    for (m, w) in pair(pkg, case, model_kw=dict(tolerance=1e-2, maxit=200, ilu_relaxation=0.9)):
+    for (m, w) in H.pair(pkg, case, lambda: thp_cases.make_wells(pkg, case), head_model="cell_oil", vfp=thp_cases.tables(pkg), props="wellbore",
+                         model_kw=dict(tolerance=1e-2, maxit=200, ilu_relaxation=0.9)):
         ts, trail, steps = run_step(pkg, m, w, 2.0 * DAY, 0.5 * DAY)
         x = w.fetch().copy() if getattr(w, "on_device", False) else w.x.copy()
         runs.append(dict(ts=ts, trail=trail, steps=steps, x=x, m=m, w=w))
@@ -201,11 +144,11 @@ def test_report_step_device_wells_against_host_wells(pkg):
 # ---- 5. update_failed --------------------------------------------------------------------------------------------------------------------------------
 def test_update_failed_after_a_switch_to_thp(pkg):
     case = thp_cases.make_case(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: thp_cases.make_wells(pkg, case), head_model="cell_oil", vfp=thp_cases.tables(pkg), props="wellbore")
     dt = 5.0 * DAY
     # an accepted first step's start: solved wells under their rate targets (the controls forced back), saved as the time level
     wd.begin_iteration(0)
-    host_begin(mh, wh, 0)
+    H.host_begin(mh, wh, 0)
     x0 = wd.fetch().copy()
     assert np.array_equal(x0, wh.x)
     x0[:, 3] = [236e5, 255e5, 253e5]
@@ -221,7 +164,7 @@ def test_update_failed_after_a_switch_to_thp(pkg):
     assert np.array_equal(wd.fetch(), x0) and [w.control for w in wd.wells] == [w.rate_control for w in wd.wells]
     # the retry: dp is formed anew, the same switch, the host's numbers
     wh.set_state(saved)
-    host_begin(mh, wh, 0)
+    H.host_begin(mh, wh, 0)
     wd.begin_iteration(0)
     assert np.array_equal(wd.fetch(), wh.x) and np.array_equal(wd.x, x1) and [w.control for w in wd.wells] == [w.control for w in wh.wells]
     assert np.array_equal(md.std_wells_thp()["dp"], wh.thp_dp)
@@ -308,8 +251,7 @@ def test_launch_counts_do_not_grow(pkg):
         m.std_wells_update(1.0)
         m.update(None, 1.0)
         m.synchronize()
-        counts = {k: v[0] for k, v in m.profile().items()}
-        runs.append((counts, res.it, m.get_std_wells(), m.get_state()[0]))
+        runs.append((H.launch_counts(m), res.it, m.get_std_wells(), m.get_state()[0]))
     (a, ita, wa, sa), (b, itb, wb, sb), (c, itc, wc, sc) = runs
     assert a == b and ita == itb and np.array_equal(sa, sb) and all(np.array_equal(p, q) for p, q in zip(wa, wb))
     assert a["assemble"] == c["assemble"] and a["assemble"] >= 5         # the wells alone, the controls, the equations, the source rows, the assembly, the restore

@@ -9,72 +9,31 @@ import numpy as np
 import pytest
 
 import helpers
+import std_wells_harness as H
 import thp_cases
+from std_wells_harness import same
 
 pytestmark = pytest.mark.gpu
 
 DAY = 86400.0
-CONTROL_CODE = {"rate": 0, "bhp": 1, "thp": 2, "orat": 3, "wrat": 4, "grat": 5, "lrat": 6, "resv": 7}      # wells.CONTROL_CODE
 
 
 def make_case(pkg, rocktab=None):
     return helpers.wetgas_case(pkg, 3, 3, 70, rocktab=rocktab, heterogeneous=True, dz=1.0)
 
 
-def pair(pkg, case, vaporised_oil=True, model_kw=None, vfp=None, **wells_kw):
-    """(device model, its wells), (host model, stated wells): two contexts in the same state"""
-    out = []
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        wl = pkg.decks.gas_condensate_wells(case, **wells_kw)
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(wl, case["depth"], m, vfp=vfp, vaporised_oil=vaporised_oil)
-        else:
-            w = pkg.wells.StandardWells(wl, case["depth"], arithmetic="stated", vfp=vfp, vaporised_oil=vaporised_oil)
-        out.append((m, w))
-    return out
-
-
-def begin(md, wd, mh, wh, iteration):
-    """beginIteration on both sides; -> the host's records"""
-    iq = wh.records(mh)
-    if iteration == 0:
-        wh.calculate_explicit_quantities(iq)
-        wh.solve_well_equations(iq)
-    wh.update_well_controls()
-    wd.begin_iteration(iteration)
-    return iq
-
-
-def same(got, want, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.flatnonzero((got != want).reshape(-1))
-    assert bad.size == 0 and np.all(np.isfinite(got)), (what, bad[:8], got.reshape(-1)[bad[:8]], want.reshape(-1)[bad[:8]])
-
-
-def assemble_and_compare(md, wd, mh, wh, iq, dt, it, what):
-    """one assembly on both sides: the wells' arrays, the perforated cells' source rows, the reservoir's J and r -> the device's arrays"""
-    W = wh.wells
-    wa = wh.assemble(iq)
-    mh.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
+def assemble_and_compare(pkg, md, wd, mh, wh, iq, dt, it, what):
+    """one assembly on both sides: the wells' arrays, the perforated cells' source rows, the reservoir's J and r -> the device's arrays.
+    (Local: the solution rates and the source rows are this feature's own)"""
+    wa = H.host_assemble(mh, wh, iq)
     jh, rh = mh.assemble(dt, it)
     jd, rd = md.assemble(dt, it)
-    x, ctl, rw = md.get_std_wells()
-    blk = md.std_wells_blocks()
-    nperf = len(wh.cells)
-    r, D, B, C, src, dsrc = wh._assemble_wells(iq)                       # (the same state: the same bits as inside assemble)
-    want = dict(x=wh.x, head=wh.head, rw=wa["res_well"].reshape(-1, 4), D=D, Dinv=wa["wells"]["Dnnzs"].reshape(-1, 4, 4), B=wa["wells"]["Bnnzs"].reshape(nperf, 4, 3),
-                C=wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), rates=wh._perf_rates(iq, wh.x[:, 3]), dq=wh.rate_dq,
-                ctl=[CONTROL_CODE[w.control[0]] for w in W],
-                dissolved_gas=wh.solution_rates()[0], vaporised_oil=wh.solution_rates()[1])
-    dis, vap = wd.solution_rates()
-    got = dict(x=x, head=blk["head"], rw=rw, D=blk["D"], Dinv=blk["Dinv"], B=blk["B"], C=blk["C"], rates=blk["rates"], dq=md.std_wells_rate_dq(), ctl=list(ctl),
-               dissolved_gas=dis, vaporised_oil=vap)
-    assert np.array_equal(want["rw"], r) and np.array_equal(want["C"], C)
-    for k in want:
-        same(got[k], want[k], (what, k))
+    r, _, _, C, _, _ = wh._assemble_wells(iq)                            # (the same state: the same bits as inside assemble)
+    assert np.array_equal(wa["res_well"].reshape(-1, 4), r) and np.array_equal(wa["wells"]["Cnnzs"].reshape(len(wh.cells), 4, 3), C)
+    got = H.compare_wells(pkg, md, wh, wa, what, extra=("D", "rates", "dq"), iq=iq, all_finite=True)
+    got["dissolved_gas"], got["vaporised_oil"] = wd.solution_rates()
+    same(got["dissolved_gas"], wh.solution_rates()[0], (what, "dissolved_gas"))
+    same(got["vaporised_oil"], wh.solution_rates()[1], (what, "vaporised_oil"))
     # the perforated cells' source and dsource rows (every cell has one perforation here), then the reservoir's J and r, which hold them
     order = [list(wh.cells).index(c) for c in wa["cells"]]
     same(got["rates"][order, :, 0], wa["source_cells"].reshape(-1, 3), (what, "source"))
@@ -94,11 +53,11 @@ def test_one_assembly(pkg, rocktab):
     """the wells alone at iteration 0, then one assembly.  Without crossflow PLONG's reversed perforations are closed"""
     W = pkg.wells
     case = make_case(pkg, rocktab)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case), vfp=None, vaporised_oil=True)
     assert md.iq().shape[1] == 19 and list(np.diff(wh.vp)) == [70, 1, 5]
-    iq = begin(md, wd, mh, wh, 0)
+    iq = H.begin(wd, mh, wh, 0)
     same(md.get_std_wells()[0], wh.x, "the wells alone")
-    got = assemble_and_compare(md, wd, mh, wh, iq, 5.0 * DAY, 0, "a")
+    got = assemble_and_compare(pkg, md, wd, mh, wh, iq, 5.0 * DAY, 0, "a")
     assert [w.control[0] for w in wh.wells] == ["rate", "orat", "rate"]           # PCAP's vaporised oil exceeds its ORAT limit
     assert got["rates"][70, W.OIL, 0] < 0.0 and got["vaporised_oil"][1] == got["rates"][70, W.OIL, 0]     # ... and is all its oil
     assert np.all(got["dissolved_gas"][[0]] < 0.0) and np.all(got["vaporised_oil"][:2] < 0.0)
@@ -111,10 +70,10 @@ def test_one_assembly(pkg, rocktab):
 def test_one_assembly_with_crossflow(pkg, rocktab):
     """allow_crossflow on PLONG: the device's own well solve leaves reversed perforations, in the d = 1 - rv rs branch"""
     case = make_case(pkg, rocktab)
-    (md, wd), (mh, wh) = pair(pkg, case, allow_crossflow=True)
-    iq = begin(md, wd, mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case, allow_crossflow=True), vfp=None, vaporised_oil=True)
+    iq = H.begin(wd, mh, wh, 0)
     same(md.get_std_wells()[0], wh.x, "the wells alone")
-    got = assemble_and_compare(md, wd, mh, wh, iq, 5.0 * DAY, 0, "b")
+    got = assemble_and_compare(pkg, md, wd, mh, wh, iq, 5.0 * DAY, 0, "b")
     reversed_ = (got["rates"][:70, :, 0] > 0.0).any(axis=1)
     assert reversed_.sum() >= 1 and np.any(got["dq"][:70][reversed_] != 0.0)
     print("reversed perforations of PLONG after the device's own solve:", np.flatnonzero(reversed_))
@@ -128,23 +87,23 @@ def test_lrat_and_thp_limit_in_force(pkg):
     W = pkg.wells
     case = make_case(pkg)
     kw = dict(allow_crossflow=True, limits={"lrat": 30.0 / DAY}, thp_limit=97e5, vfp_table=5)
-    (md, wd), (mh, wh) = pair(pkg, case, vfp=thp_cases.tables(pkg), **kw)
-    iq = begin(md, wd, mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case, **kw), vfp=thp_cases.tables(pkg), vaporised_oil=True)
+    iq = H.begin(wd, mh, wh, 0)
     assert wh.wells[0].control == ("lrat", 30.0 / DAY)
-    assemble_and_compare(md, wd, mh, wh, iq, 5.0 * DAY, 0, "lrat")
+    assemble_and_compare(pkg, md, wd, mh, wh, iq, 5.0 * DAY, 0, "lrat")
     t = wd.thp()
     same(t["dp"], wh.thp_dp, "thp dp")
     same(t["bhp_from_thp"], wh.bhp_from_thp, "bhp from thp")
     wh.wells[0].control = ("thp", 97e5)
     md.set_std_wells_state(control=[W.CONTROL_CODE[w.control[0]] for w in wh.wells])
-    got = assemble_and_compare(md, wd, mh, wh, iq, 5.0 * DAY, 0, "thp")
+    got = assemble_and_compare(pkg, md, wd, mh, wh, iq, 5.0 * DAY, 0, "thp")
     assert got["ctl"][0] == 2 and np.any(got["D"][0, 3, :3] != 0.0) and got["D"][0, 3, 3] == 1.0
 
 
 # ---- d. two Newton iterations and a round trip through advance_time_level / update_failed ----------------------------------------------------------
 def test_newton_iterations_and_a_given_up_step(pkg):
     case = make_case(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case, model_kw=dict(tolerance=1e-4), allow_crossflow=True)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case, allow_crossflow=True), vfp=None, vaporised_oil=True, model_kw=dict(tolerance=1e-4))
     dt = 0.2 * DAY
 
     def same_everything(what):
@@ -155,16 +114,15 @@ def test_newton_iterations_and_a_given_up_step(pkg):
         same(x, wh.x, (what, "x"))
         assert list(ctl) == [pkg.wells.CONTROL_CODE[w.control[0]] for w in wh.wells], what
 
-    begin(md, wd, mh, wh, 0)                         # a time level whose wells have flowed: what a given-up step goes back to
+    H.begin(wd, mh, wh, 0)                         # a time level whose wells have flowed: what a given-up step goes back to
     for m in (md, mh):
         m.advance_time_level()
     saved = wh.state()
     x_saved = md.get_std_wells()[0]
     same(x_saved, wh.x, "x at the time level")
     for it in range(2):
-        iq = begin(md, wd, mh, wh, it)
-        wa = wh.assemble(iq)
-        mh.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
+        iq = H.begin(wd, mh, wh, it)
+        wa = H.host_assemble(mh, wh, iq)
         mh.assemble(dt, it, fetch=False)
         md.assemble(dt, it, fetch=False)
         mh.wells_apply_residual(wa["wells"], wa["res_well"])
@@ -184,8 +142,8 @@ def test_newton_iterations_and_a_given_up_step(pkg):
     wh.set_state(saved)
     same_everything("given up")
     same(md.get_std_wells()[0], x_saved, "x restored")
-    iq = begin(md, wd, mh, wh, 0)                    # ... and the retry starts as the first attempt did
-    assemble_and_compare(md, wd, mh, wh, iq, 0.5 * dt, 0, "retry")
+    iq = H.begin(wd, mh, wh, 0)                    # ... and the retry starts as the first attempt did
+    assemble_and_compare(pkg, md, wd, mh, wh, iq, 0.5 * dt, 0, "retry")
 
 
 # ---- e. the switch off ---------------------------------------------------------------------------------------------------------------------------
@@ -194,10 +152,10 @@ def test_switch_off_computes_and_launches_what_it_did(pkg):
     a context that had the switch on and off again gives the bits of one that never saw the call; profile_get's launch counts per scope are
     the same with the switch on and off"""
     case = make_case(pkg)
-    (md, wd), (mh, wh) = pair(pkg, case, vaporised_oil=False, allow_crossflow=True)
-    iq = begin(md, wd, mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case, allow_crossflow=True), vfp=None, vaporised_oil=False)
+    iq = H.begin(wd, mh, wh, 0)
     same(md.get_std_wells()[0], wh.x, "the wells alone")
-    got = assemble_and_compare(md, wd, mh, wh, iq, DAY, 0, "off")
+    got = assemble_and_compare(pkg, md, wd, mh, wh, iq, DAY, 0, "off")
     assert np.all(got["dissolved_gas"] == 0.0) and np.all(got["vaporised_oil"] == 0.0) and np.all(got["rates"][70, pkg.wells.OIL] == 0.0)
     seen = []
     for switch in ("never", "off", "on"):
@@ -212,13 +170,13 @@ def test_switch_off_computes_and_launches_what_it_did(pkg):
         w.begin_iteration(0)
         j, r = m.assemble(DAY, 0)
         m.synchronize()
-        formed = {k: v[0] for k, v in m.profile().items()}      # the wells alone, the controls, the assembly: no linear solve yet
+        formed = H.launch_counts(m)                             # the wells alone, the controls, the assembly: no linear solve yet
         blk = m.std_wells_blocks()
         res = m.solve_jacobian_system()
         w.update(1.0)
         m.update(None, 1.0)
         m.synchronize()
-        seen.append(dict(formed=formed, counts={k: v[0] for k, v in m.profile().items()}, j=j, r=r, blk=blk, it=res.it, x=m.get_std_wells()[0],
+        seen.append(dict(formed=formed, counts=H.launch_counts(m), j=j, r=r, blk=blk, it=res.it, x=m.get_std_wells()[0],
                          state=m.get_state()[0]))
     never, off, on = seen
     assert never["formed"] == off["formed"] == on["formed"] and never["formed"]["assemble"] >= 5
@@ -241,8 +199,8 @@ def test_refusals_and_list_replacement(pkg):
     assert rc == C.NOT_READY and "no resident list" in msg                  # before a list
     dis, vap = m.std_wells_solution_rates()
     assert dis.size == 0 and vap.size == 0
-    (md, wd), (mh, wh) = pair(pkg, case, allow_crossflow=True)
-    iq = begin(md, wd, mh, wh, 0)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: pkg.decks.gas_condensate_wells(case, allow_crossflow=True), vfp=None, vaporised_oil=True)
+    iq = H.begin(wd, mh, wh, 0)
     md.assemble(DAY, 0, fetch=False)
     blk0, sol0 = md.std_wells_blocks(), wd.solution_rates()
     assert np.all(sol0[1][:2] < 0.0)

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import helpers
+import std_wells_harness as H
+from std_wells_harness import moved, same
 
 pytestmark = pytest.mark.gpu
 
@@ -24,8 +26,7 @@ def make_case(pkg, wet):
     return pkg.decks.cartesian_case(2, 2, 70, state="mixed", heterogeneous=True, dz=1.0)
 
 
-def column(i, j, ks):
-    return [i + 2 * (j + 2 * k) for k in ks]
+column = H.column(2, 2)
 
 
 def make_wells(pkg, case, shared=True):
@@ -50,51 +51,9 @@ def make_wells(pkg, case, shared=True):
     return out
 
 
-def moved(case, seed, dp=2.0e5):
-    rng = np.random.default_rng(seed)
-    pv = case["pv"].reshape(-1, 3).copy()
-    pv[:, 1] -= dp * rng.uniform(0.0, 1.0, len(pv))
-    pv[:, 0] += rng.uniform(-0.01, 0.01, len(pv))
-    return pv.reshape(-1)
-
-
-def pair(pkg, case, wells=None, head_model="wellbore", model_kw=None):
-    """(device model, its wells), (host model, stated wells over the device's probes): two contexts in the same state"""
-    out = []
-    props = pkg.capi.HipFluid(case["fluid"])
-    for form in ("device", "host"):
-        m = pkg.capi.HipModel(case, **(model_kw or {}))
-        m.set_state(case["pv"], case["meaning"])
-        wl = wells() if wells is not None else make_wells(pkg, case)
-        if form == "device":
-            w = pkg.wells.DeviceStandardWells(wl, case["depth"], m, head_model=head_model)
-        else:
-            w = pkg.wells.StandardWells(wl, case["depth"], arithmetic="stated", head_model=head_model, props=props if head_model == "wellbore" else None)
-        out.append((m, w))
-    return out
-
-
-def host_begin_and_assemble(m, w, iteration):
-    """newton.py's host branch: records down, the wells, rates up -> the assembled dict"""
-    iq = w.records(m)
-    if iteration == 0:
-        w.calculate_explicit_quantities(iq)
-        w.solve_well_equations(iq)
-    w.update_well_controls()
-    wa = w.assemble(iq)
-    m.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
-    return wa
-
-
-def same(got, want, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.flatnonzero((got != want).reshape(-1))
-    assert bad.size == 0, (what, bad[:8], got.reshape(-1)[bad[:8]], want.reshape(-1)[bad[:8]])
-
-
 def compare_heads(md, wh, what):
-    """after begin_iteration(0): density, p_avg, mixture, head"""
+    """after begin_iteration(0): density, p_avg, mixture, head.  (Local: there is no assembly yet, and the harness's compare_wells always
+    compares what an assembly leaves)"""
     wb, blk = md.std_wells_wellbore(), md.std_wells_blocks()
     for k in WB:
         same(wb[k], wh.wellbore[k], (what, k))
@@ -103,44 +62,11 @@ def compare_heads(md, wh, what):
     return wb, blk
 
 
-def compare_assembly(md, wa, wh, what):
-    """after an assembly: rates, B, C, D, D^-1, r_w, the stored perforation pressures and rates"""
-    x, ctl, rw = md.get_std_wells()
-    blk, wb = md.std_wells_blocks(), md.std_wells_wellbore()
-    nperf = len(wh.cells)
-    r, D, B, C, src, dsrc = wh._assemble_wells(wh.records_last)
-    same(x, wh.x, (what, "x"))
-    same(rw, wa["res_well"].reshape(-1, 4), (what, "rw"))
-    same(blk["rates"][:, :, 0], src, (what, "rates"))
-    same(blk["rates"][:, :, 1:4], dsrc, (what, "d rates"))
-    same(blk["D"], D, (what, "D"))
-    same(blk["Dinv"], wa["wells"]["Dnnzs"].reshape(-1, 4, 4), (what, "Dinv"))
-    same(blk["B"], wa["wells"]["Bnnzs"].reshape(nperf, 4, 3), (what, "B"))
-    same(blk["C"], wa["wells"]["Cnnzs"].reshape(nperf, 4, 3), (what, "C"))
-    same(blk["head"], wh.head, (what, "head"))
-    same(wb["perf_pressure"], wh.perf_pressure, (what, "perf_pressure"))
-    same(wb["perf_rates"], wh.perf_rates, (what, "perf_rates"))
-    assert list(ctl) == [int(w.control[0] == "bhp") for w in wh.wells], what
-    return x, blk, wb
-
-
-def newton_iteration(md, wd, mh, wh, dt, it, what):
-    """one Newton iteration on both sides, compared after the assembly; the reservoir and the wells are then updated"""
-    wh.records_last = wh.records(mh)
-    wa = host_begin_and_assemble(mh, wh, it)
-    jh, rh = mh.assemble(dt, it)
-    wd.begin_iteration(it)
-    jd, rd = md.assemble(dt, it)
-    compare_assembly(md, wa, wh, what)
-    assert np.array_equal(jd, jh) and np.array_equal(rd, rh), what
-    return wa
-
-
 # ---- 1. heads and one assembly, dry and wet gas ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("wet", [False, True])
 def test_heads_and_assembly(pkg, wet):
     case = make_case(pkg, wet)
-    (md, wd), (mh, wh) = pair(pkg, case)
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case), head_model="wellbore", props="wellbore")
     W = pkg.wells
     assert md.iq().shape[1] == (19 if wet else 17) and list(np.diff(wh.vp)) == [70, 65, 3, 3, 1, 3, 3, 5, 3, 2]
     dt = 5.0 * DAY
@@ -177,17 +103,17 @@ def test_heads_and_assembly(pkg, wet):
         if state is not None:
             for m in (md, mh):
                 m.set_state(state, case["meaning"])
-        wh.records_last = wh.records(mh)
+        iq = wh.records(mh)
         wh.update_well_controls()
-        wa = wh.assemble(wh.records_last)
+        wa = wh.assemble(iq)
         mh.set_source_cells(wa["cells"], wa["source_cells"], wa["dsource_cells"])
         jh, rh = mh.assemble(dt, it)
         if it > 0:
             wd.begin_iteration(it)
         jd, rd = md.assemble(dt, it)
-        x, blk, wb = compare_assembly(md, wa, wh, it)
+        blk = H.compare_wells(pkg, md, wh, wa, it, extra=("D", "source", "wellbore"), iq=iq)
         assert np.array_equal(jd, jh) and np.array_equal(rd, rh), it
-    assert np.count_nonzero(wb["perf_rates"]) > 50 and np.all(np.isfinite(blk["Dinv"]))
+    assert np.count_nonzero(blk["perf_rates"]) > 50 and np.all(np.isfinite(blk["Dinv"]))
     # the next time step starts from flowing wells: the general branch - the flow summed from below, the rs / rv corrections
     wh.calculate_explicit_quantities(wh.records(mh))
     md.std_wells_begin_iteration(0)
@@ -205,11 +131,11 @@ def test_heads_and_assembly(pkg, wet):
     else:
         assert np.all(b_["rvmax"] == 0.0)
     wh.solve_well_equations(wh.records(mh))
-    wh.records_last = wh.records(mh)
+    iq = wh.records(mh)
     wh.update_well_controls()
-    wa = wh.assemble(wh.records_last)
+    wa = wh.assemble(iq)
     md.assemble(dt, 0, fetch=False)
-    compare_assembly(md, wa, wh, "second step")
+    H.compare_wells(pkg, md, wh, wa, "second step", extra=("D", "source", "wellbore"), iq=iq)
 
 
 # ---- 2. the perforation state handed in ------------------------------------------------------------------------------------------------------
@@ -238,7 +164,7 @@ def handed_in_state(pkg, wh):
 def test_perf_state_handed_in(pkg):
     """wet gas; opmhip_set_std_wells_perf_state and the read-back; the rv min() binds in some perforations and not in others"""
     case = make_case(pkg, True)
-    (md, wd), (mh, wh) = pair(pkg, case, wells=lambda: make_wells(pkg, case, shared=False))
+    (md, wd), (mh, wh) = H.pair(pkg, case, lambda: make_wells(pkg, case, shared=False), head_model="wellbore", props="wellbore")
     W = pkg.wells
     x, pp, rates = handed_in_state(pkg, wh)
     st_none = wd.state()
@@ -433,10 +359,7 @@ def test_first_step_given_up(pkg):
     mh.set_state(case["pv"], case["meaning"])
     wh = pkg.wells.StandardWells(wells(), case["depth"], arithmetic="stated", head_model="wellbore", props=props)
     saved = wh.state()
-    iq = wh.records(mh)
-    wh.calculate_explicit_quantities(iq)
-    wh.solve_well_equations(iq)
-    wh.update_well_controls()
+    iq = H.host_begin(mh, wh, 0)
     wh.assemble(iq)
     assert wh.initialised and np.any(wh.perf_rates != 0.0)
     wh.set_state(saved)
@@ -487,11 +410,11 @@ def test_two_pvt_regions(pkg):
     assert odd.any() and (~odd).any() and np.all(wb["density"][s][odd] != one.wellbore["density"][s][odd]) and np.array_equal(wb["density"][s][~odd], one.wellbore["density"][s][~odd])
     # flowing wells
     wh.solve_well_equations(wh.records(mh))
-    wh.records_last = wh.records(mh)
+    iq = wh.records(mh)
     wh.update_well_controls()
-    wa = wh.assemble(wh.records_last)
+    wa = wh.assemble(iq)
     md.assemble(DAY, 0, fetch=False)
-    compare_assembly(md, wa, wh, "two regions")
+    H.compare_wells(pkg, md, wh, wa, "two regions", extra=("D", "source", "wellbore"), iq=iq)
     wh.calculate_explicit_quantities(wh.records(mh))
     md.std_wells_begin_iteration(0)
     compare_heads(md, wh, "flowing, two regions")
@@ -582,7 +505,7 @@ def test_default_model_launches_and_computes_what_it_did(pkg):
         m.update(None, 1.0)
         m.std_wells_update(1.0)
         m.synchronize()
-        seen.append(({k: v[0] for k, v in m.profile().items()}, res.it, jr, m.get_std_wells(), m.std_wells_blocks(), m.get_state()[0]))
+        seen.append((H.launch_counts(m), res.it, jr, m.get_std_wells(), m.std_wells_blocks(), m.get_state()[0]))
     (ca, ita, jra, wa, ba, sa), (cb, itb, jrb, wb_, bb, sb) = seen
     assert ca == cb and ita == itb
     same(jra[0], jrb[0], "J")
